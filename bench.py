@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: CPTV frames/s end-to-end (track + classify) at 160x120.
 
-    python bench.py --gpus N --steps K --warmup W [--clips B] [--frames T] [--stage e2e|track]
+    python bench.py --gpus N --steps K --warmup W [--clips B] [--frames T] [--stage e2e|track] [--full]
+                    [--dump-outputs DIR]
 
 Workload (BASELINE.json metric; configs[1] + [2] chained as in configs[3]): B synthetic 160x120
 uint16 clips of T = 270 frames (30 s at 9 fps) per GPU, lepton3 thresholds, resident in HBM when
@@ -10,7 +11,12 @@ the timed region starts.  One *step* = one pass of the whole hot path over the b
   -> association (region filter, matching, Kalman) -> end-of-clip filtering -> segment plan
   -> crop / resize / normalise / 5x5 tile -> WR-ResNet-22-4 forward (float32, 17 labels, seeded
   random weights: no checkpoint can be downloaded) -> per-track aggregation.
-value = N * B * T * K / max-over-ranks time (barrier + device sync on both sides).
+value = N * B * T * K / max-over-ranks time (barrier + device sync on both sides); ms_per_step = that time / K.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what the headline does not need:
+the CPU baselines, the measurements after the timed region (other math modes, default_config, fs64, from_files; for
+N > 1 config4) and, for --stage ir, the kernel-alone timings.  --dump-outputs DIR writes what the last timed step
+computed as DIR/<name>.npy (dump_outputs: seeded samples of the per-frame outputs, the classifier's results whole).
 
 N > 1: the driver launches one rank per GPU (torch.distributed.run); clips shard across ranks with
 no data-path collective; the per-track result records are all-gathered once per step over RCCL.
@@ -27,7 +33,7 @@ Extra objects on the JSON line:
                 dense peak with --cnn-math f32.  --stage track: cpx_frame_kernel, 614,400 algorithmic bytes per frame.
   roofline_conv the largest convolution kernel of the step, the same object as its entry under roofline.kernels.
   roofline_track  (e2e) the same HBM accounting for cpx_frame_kernel inside the same run.
-  cpu_baseline  the oracle chain ("port": NumPy tracker + NumPy crop/tile + PyTorch-CPU forward, 1 core)
+  cpu_baseline  (--full) the oracle chain ("port": NumPy tracker + NumPy crop/tile + PyTorch-CPU forward, 1 core)
                 timed on a bounded sample of the same workload on this host (rank 0, N = 1 only);
   cpu_baseline_all_cores  the same chain on one worker process per CPU this process may use (the scheduler affinity,
                 capped by the cgroup's CPU quota: 16 on the GPU boxes of this pool although 256 are visible).  Both run
@@ -35,10 +41,10 @@ Extra objects on the JSON line:
 
 --gpus N > 1 without WORLD_SIZE in the environment: bench.py starts the N ranks itself (a child
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py ...`, before anything touches the GPU) and
-relays rank 0's line; WORLD_SIZE set and != N is an error.  For N > 1 the line also carries "config4": the strong-scaling
-workload below at a reduced size, in the same processes.
+relays rank 0's line; WORLD_SIZE set and != N is an error.  For N > 1 and --full the line also carries "config4": the
+strong-scaling workload below at a reduced size, in the same processes.
 
-  from_files    (default run, N = 1) the file-fed form of the same path: synthetic CPTV byte strings in host memory ->
+  from_files    (--full) the file-fed form of the same path: synthetic CPTV byte strings in host memory ->
                 upload -> gzip inflate + section index + frame decode on the device -> track -> segments -> crop/tile +
                 network -> thumbnails -> metadata JSON text per recording (cpx.track.bulk.run_files_bulk); frames/s and
                 the split of the wall time.
@@ -220,7 +226,8 @@ def dry_launch(args, numa=None):
     """--dry-launch: the ranks rendezvous over gloo and run the HOST side of a multi-GPU bench run -- the NUMA pinning,
     the LPT partition of configs[3], one gather_records exchange of records of its width, the per-rank from_files
     aggregation (all_gather_object), the per-rank timing summary -- with the device work left out; rank 0 prints the line
-    skeleton.  The launch path of --gpus N checked without a GPU (tests/test_bench_launch_cpu.py spawns 2 and 8 ranks)."""
+    skeleton (config4 / from_files with --full, as in a real run).  The launch path of --gpus N checked without a GPU
+    (tests/test_bench_launch_cpu.py spawns 2 and 8 ranks)."""
     import torch
     import torch.distributed as dist
 
@@ -267,7 +274,7 @@ def dry_launch(args, numa=None):
                      "scaling": "weak", "data": "synthetic", "dry_launch": True, "ranks": seen,
                      "config": {"workload": "dry launch: host logic only", "frames_per_clip": T},
                      "per_rank": per_rank_summary(times, 1, [4096 * T] * world)})
-        if world > 1:
+        if world > 1 and args.full:
             line["config4"] = {"scaling": "strong", "clips": 10000, "frames_total": int(lengths.sum()),
                                "frames_per_rank": loads, "imbalance": round(max(loads) / (sum(loads) / len(loads)), 4),
                                "records_gathered": int(gathered.shape[0]), "record_width": int(gathered.shape[1])}
@@ -527,20 +534,21 @@ def bench_ir(args, torch, np, dist, device, rank, world, local_rank):
     torch.cuda.synchronize(device)
     for _ in range(max(args.warmup, 1)):
         step()
-    # the MOG2 kernel alone, timed on the handle's stream by wall clock around back-to-back launches
-    eng.synchronize()
-    t0 = time.perf_counter()
-    reps = 4 * T
-    for r in range(reps):
-        eng.lib.cpx_mog2_apply(bg._m, C.c_void_p(video[r % T].data_ptr()), -1.0, C.c_void_p(mask.data_ptr()))
-    eng.synchronize()
-    mog2_s = (time.perf_counter() - t0) / reps
-    front_step()
-    eng.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(max(args.steps, 1)):
+    if args.full:
+        # the MOG2 kernel alone, timed on the handle's stream by wall clock around back-to-back launches
+        eng.synchronize()
+        t0 = time.perf_counter()
+        reps = 4 * T
+        for r in range(reps):
+            eng.lib.cpx_mog2_apply(bg._m, C.c_void_p(video[r % T].data_ptr()), -1.0, C.c_void_p(mask.data_ptr()))
+        eng.synchronize()
+        mog2_s = (time.perf_counter() - t0) / reps
         front_step()
-    front_s = (time.perf_counter() - t0) / max(args.steps, 1)
+        eng.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(max(args.steps, 1)):
+            front_step()
+        front_s = (time.perf_counter() - t0) / max(args.steps, 1)
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -551,10 +559,9 @@ def bench_ir(args, torch, np, dist, device, rank, world, local_rank):
         tt = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
-    assert int(status.max().item()) == 0 and int(counts[T // 2:].max().item()) >= 1
+    if args.full:  # (status / counts are written by front_step)
+        assert int(status.max().item()) == 0 and int(counts[T // 2:].max().item()) >= 1
     if rank == 0:
-        algo = S * H * W * 124.0
-        gbs = algo / mog2_s / 1e9
         line = {"metric": "IR 640x480 frames/s through the IR tracker (background model, detection, merge, association, "
                           "tracks: the IR half of configs[4])",
                 "value": round(world * S * T * args.steps / elapsed, 1), "unit": "frames/s", "n_gpus": world,
@@ -565,12 +572,16 @@ def bench_ir(args, torch, np, dist, device, rank, world, local_rank):
                 "config": {"workload": "synthetic 640x480 uint8 videos: IRTrackExtractor.parse_frames_batch, "
                                        "streams in lockstep", "streams_per_gpu": S, "frames_per_stream": T,
                            "tracks_found": n_tracks[0]},
-                "detect_stage": {"frames_per_s": round(S * T / front_s, 1), "ms_per_step": round(front_s * 1e3, 3),
-                                 "what": "cpx_mog2_apply + cpx_ir_detect alone (rank 0)"},
-                "roofline": {"kernel": "cpx_mog2_apply_kernel", "bound": "hbm", "achieved": round(gbs, 1),
-                             "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4), "traffic": None,
-                             "avg_launch_us": round(mog2_s * 1e6, 2), "algorithmic_bytes_per_launch": algo}}
-        if world == 1 and args.cpu_clips != 0:
+                "roofline": None}
+        if args.full:
+            algo = S * H * W * 124.0
+            gbs = algo / mog2_s / 1e9
+            line["detect_stage"] = {"frames_per_s": round(S * T / front_s, 1), "ms_per_step": round(front_s * 1e3, 3),
+                                    "what": "cpx_mog2_apply + cpx_ir_detect alone (rank 0)"}
+            line["roofline"] = {"kernel": "cpx_mog2_apply_kernel", "bound": "hbm", "achieved": round(gbs, 1),
+                                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4), "traffic": None,
+                                "avg_launch_us": round(mog2_s * 1e6, 2), "algorithmic_bytes_per_launch": algo}
+        if args.full and world == 1 and args.cpu_clips != 0:
             import ir_oracle as iro
             import mog2_oracle as mo
 
@@ -905,6 +916,89 @@ def bench_config4(args, torch, np, dist, device, rank, world, local_rank, cpu, a
         dist.destroy_process_group()
 
 
+DUMP_SEED = 20240611      # the one seed every sample of --dump-outputs is drawn from
+DUMP_INFO_FRAMES = 4096   # frames whose frame record and components are written
+DUMP_IMAGE_FRAMES = 64    # of those, frames whose whole images are written
+DUMP_CLIPS = 64           # clips whose track-summary slots are written
+DUMP_MAX_ROWS = 65536     # per-track / per-sample rows written whole up to this many
+
+
+def dump_outputs(out_dir, torch, np, track, batch, B, T):
+    """--dump-outputs: what the last timed step handed its caller, as out_dir/<name>.npy, integers widened exactly to
+    float64 (labels to float32).  Per-frame outputs of one step are tens of GB: they are written at frames / clips drawn
+    once from DUMP_SEED, the same for every run of the same arguments.
+      frames_sampled [F]           the frame indices (of B * T) below
+      frame_info     [F, 17]       cpx_frame_info fields in FRAME_INFO_DTYPE order, without `reserved`
+      components     [n, 9]        (sampled frame index, x, y, width, height, area, sum_x, sum_y, pixel_variance), the
+                                   n_components slots of each sampled frame
+      filtered       [G, H, W]     the filtered image of a seeded subset of G of those frames (frames_imaged: their indices)
+      labels         [G, H, W]     --stage track: the label image of the same frames
+    e2e, the classifier's results (batch):
+      counts [B, 4]; track_summaries [DUMP_CLIPS * max_tracks, 22] (TRACK_SUMMARY_DTYPE order, every slot of the
+      clips in clips_sampled); track_clip [n_tracks, 2], scores [n_tracks, 17], best [n_tracks]; logits / probs
+      [n_samples, 17] -- rows beyond DUMP_MAX_ROWS drawn from DUMP_SEED (track_rows / sample_rows then list them)."""
+    from cpx._lib import COMPONENT_DTYPE
+    from cpx.tracking import TRACK_SUMMARY_DTYPE
+
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    total = B * T
+    dev = track.info_dev.device
+    out = {}
+    fr = np.sort(rng.choice(total, size=min(DUMP_INFO_FRAMES, total), replace=False))
+    img = fr[np.sort(rng.choice(fr.size, size=min(DUMP_IMAGE_FRAMES, fr.size), replace=False))]
+    out["frames_sampled"] = fr.astype(np.float64)
+    out["frames_imaged"] = img.astype(np.float64)
+    info = track.info[fr]
+    names = [n for n in info.dtype.names if n != "reserved"]
+    out["frame_info"] = np.stack([info[n].astype(np.float64) for n in names], axis=1)
+    fr_dev = torch.from_numpy(fr.astype(np.int64)).to(dev)
+    comps = (track.comps_dev.view(-1)[: total * track.cap * 8].view(total, track.cap, 8).index_select(0, fr_dev)
+             .cpu().numpy().view(COMPONENT_DTYPE).reshape(fr.size, track.cap))
+    rows = []
+    for i, f in enumerate(fr):
+        c = comps[i, : max(0, min(int(info["n_components"][i]), track.cap))]
+        rows.append(np.stack([np.full(len(c), f, np.float64)] + [c[n].astype(np.float64) for n in COMPONENT_DTYPE.names],
+                             axis=1))
+    out["components"] = np.concatenate(rows) if rows else np.zeros((0, 9))
+    img_dev = torch.from_numpy(img.astype(np.int64)).to(dev)
+    out["filtered"] = track.filtered_dev.index_select(0, img_dev).float().cpu().numpy()
+    if track.labels_dev is not None:
+        out["labels"] = track.labels_dev.index_select(0, img_dev).cpu().numpy().astype(np.float32)
+    if batch is not None:
+        if batch.counts is not None:
+            out["counts"] = np.asarray(batch.counts, dtype=np.float64)
+        if batch.summaries_dev is not None:
+            clips = np.sort(rng.choice(B, size=min(DUMP_CLIPS, B), replace=False))
+            per_clip = batch.summaries_dev.numel() // B
+            s = (batch.summaries_dev.view(B, per_clip).index_select(0, torch.from_numpy(clips.astype(np.int64)).to(dev))
+                 .cpu().numpy().view(TRACK_SUMMARY_DTYPE).reshape(-1))
+            out["clips_sampled"] = clips.astype(np.float64)
+            out["track_summaries"] = np.stack([s[n].astype(np.float64) for n in TRACK_SUMMARY_DTYPE.names], axis=1)
+
+        def rows_of(n, name):
+            if n <= DUMP_MAX_ROWS:
+                return None
+            pick = np.sort(rng.choice(n, size=DUMP_MAX_ROWS, replace=False))
+            out[name] = pick.astype(np.float64)
+            return torch.from_numpy(pick.astype(np.int64)).to(dev)
+
+        def put(name, v, pick, dtype):
+            if v is not None:
+                out[name] = (v if pick is None else v.index_select(0, pick)).cpu().numpy().astype(dtype)
+
+        pt = rows_of(int(batch.n_tracks), "track_rows")
+        put("track_clip", batch.track_clip, pt, np.float64)
+        put("scores", batch.scores, pt, np.float32)
+        put("best", batch.best, pt, np.float64)
+        ps = rows_of(int(batch.n_samples), "sample_rows")
+        put("logits", getattr(batch, "logits", None), ps, np.float32)
+        put("probs", batch.probs, ps, np.float32)
+    for name, v in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(v))
+    return sum(v.nbytes for v in out.values())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None,
@@ -916,7 +1010,7 @@ def main():
     ap.add_argument("--stage", choices=("e2e", "track", "ir"), default="e2e",
                     help="e2e: track + classify (the BASELINE metric); track: configs[1] kernels only; ir: the 640x480 "
                          "IR front half of configs[4] (MOG2 background model + detection stage, SURVEY section 8 f4)")
-    ap.add_argument("--cpu-clips", type=int, default=-1, help="clips in the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--cpu-clips", type=int, default=-1, help="--full: clips in the CPU-baseline sample (0 = skip)")
     ap.add_argument("--cnn-chunk", type=int, default=0,
                     help="samples per CNN forward (default 2048 at frame size 32 = 54 GB of activations, 512 at 64)")
     ap.add_argument("--frame-size", type=int, default=32, choices=(32, 64),
@@ -929,7 +1023,15 @@ def main():
     ap.add_argument("--denoise", action="store_true",
                     help="tracking.denoise = true (the reference's default: NLM kernel between normalise and blur)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the default_config (denoise on) and fs64 measurements taken after the timed region")
+                    help="--full: skip the measurements taken after the timed region (other math modes, default_config "
+                         "(denoise on), fs64, from_files, config4 for N > 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the CPU baselines, the measurements after the timed region (see "
+                         "--no-extras) and --stage ir's kernel-alone timings; without it a run sets up, warms up, times "
+                         "--steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64; "
+                         "fixed seeded samples of the per-frame outputs): --stage e2e or track, rank 0")
     ap.add_argument("--config4", action="store_true",
                     help="BASELINE configs[3]: --clips (default 10000) seeded clips of 90-540 frames, LPT-sharded over the "
                          "ranks, processed in device batches, all_gather of [clip_id, track_id, 17 x f32] (strong scaling)")
@@ -941,8 +1043,10 @@ def main():
                     help="metadata worker processes of the from_files leg (cpx.track.bulk.MetaPool: what a directory run "
                          "of this size starts; 0 = the stage stays in the process)")
     ap.add_argument("--from-files", type=int, default=8192,
-                    help="recordings of the from_files measurement of the default run (0 = skip)")
+                    help="recordings of the from_files measurement of --full (0 = skip)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.stage == "ir" or args.config4 or args.sub_batches > 1):
+        ap.error("--dump-outputs: only --stage e2e or track, without --config4 or --sub-batches")
 
     # ---- --gpus N: this process becomes the launcher of N ranks unless a launcher already started us ----
     # A launcher (torch.distributed.run) exports RANK and WORLD_SIZE together; a stray WORLD_SIZE alone is not one.
@@ -977,9 +1081,9 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.cnn_chunk <= 0:
         args.cnn_chunk = 2048 if args.frame_size == 32 else 512
-    # ---- CPU baselines first: worker processes are spawned while this process has not touched the GPU yet ----
+    # ---- CPU baselines first (--full): worker processes are spawned while this process has not touched the GPU yet ----
     cpu = {}
-    if world == 1 and rank == 0 and args.cpu_clips != 0 and args.stage != "ir":
+    if args.full and world == 1 and rank == 0 and args.cpu_clips != 0 and args.stage != "ir":
         from cpx.ml_tools import wrresnet as wr0
 
         w0 = wr0.random_weights(N_LABELS, seed=0)
@@ -998,8 +1102,8 @@ def main():
     # the file-fed leg formats its metadata text in worker processes (cpx.track.bulk.MetaPool: spawned children that
     # never touch the GPU): started here, ahead of this process's first call that initialises it
     meta_pool = None
-    if args.meta_workers > 0 and args.stage == "e2e" and args.from_files > 0 and not args.no_extras and not args.denoise \
-            and args.frame_size == 32 and not args.config4 and torch.cuda.device_count() > 0:
+    if args.full and args.meta_workers > 0 and args.stage == "e2e" and args.from_files > 0 and not args.no_extras \
+            and not args.denoise and args.frame_size == 32 and not args.config4 and torch.cuda.device_count() > 0:
         from cpx.track.bulk import MetaPool
 
         meta_pool = MetaPool.make(args.meta_workers)
@@ -1027,6 +1131,7 @@ def main():
     if args.config4:
         return bench_config4(args, torch, np, dist, device, rank, world, local_rank, cpu)
     e2e = args.stage == "e2e"
+    extras = args.full and e2e and not args.no_extras and not args.denoise and args.frame_size == 32
     H, W, T = 120, 160, args.frames
     P = H * W
     B = args.clips or 4096
@@ -1108,6 +1213,8 @@ def main():
         rank_times = [float(v.item()) for v in every]  # each rank's own time: what a < N-fold result is attributed with
         elapsed = max(rank_times)
     res.check()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch, np, res, state["res"] if e2e else None, B, T)
 
     if rank == 0:
         frames_done = world * B * T * args.steps
@@ -1300,7 +1407,7 @@ def main():
             line["config"]["outputs"] = "components + label image + filtered image"
             line["roofline"] = track_roof
         line.update(cpu)  # measured before the GPU was initialised (top of main)
-        if e2e and world == 1 and not args.no_extras and not args.denoise and args.frame_size == 32:
+        if extras and world == 1:
             # ---- the same run, after the timed region: the two configurations the headline does not cover ----
             # (a) the reference's DEFAULT tracking configuration (denoise = true: NLM between normalise and blur,
             #     SURVEY F7), track stage over a slice of the resident clips
@@ -1458,8 +1565,7 @@ def main():
                 f64["math"] = args.cnn_math
             line["fs64"] = f64
             net64.close()
-    # ---- after the timed region, in the same process(es): what the headline does not cover ----
-    extras = e2e and not args.no_extras and not args.denoise and args.frame_size == 32
+    # ---- after the timed region, in the same process(es) (--full): what the headline does not cover ----
     if extras and (world > 1 or args.from_files > 0):
         # the resident workload makes room first
         if net is not None:

@@ -27,11 +27,12 @@ def test_gpus_2_spawns_two_ranks():
 def test_gpus_8_spawns_eight_ranks_and_assembles_the_line():
     """The first real 8-GPU run must not be the first time eight ranks meet: --gpus 8 --dry-launch runs the host side of
     the multi-GPU bench on gloo -- LPT partition of configs[3], one gather_records exchange, the per-rank from_files
-    aggregation, per-rank timings -- and rank 0's line has the keys of the real one."""
+    aggregation, per-rank timings -- and rank 0's line has the keys of the real one (--full: the multi-rank objects)."""
     sys.path.insert(0, REPO)
     import bench
 
-    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "8", "--dry-launch", "--steps", "2"],
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "8", "--dry-launch", "--steps", "2",
+                          "--full"],
                          env=_env(), capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     (line,) = [json.loads(l) for l in out.stdout.splitlines() if l.startswith("{")]
