@@ -486,6 +486,18 @@ static int track_run(cpx_handle* h, const uint16_t* frames_dev, const int32_t* c
   h->state_packed = false;
   h->stream_filt_state = need_filt;
   h->last_B = B;
+  // from here on the workspace no longer holds the previous call's state: a return before the end leaves no state at all
+  // (KEEP_BACKGROUND, the *_frame calls and cpx_get_background refuse), never one read in the wrong layout or batch size
+  struct StateGuard {
+    cpx_handle* h;
+    bool armed = true;
+    ~StateGuard() {
+      if (armed) {
+        h->last_B = 0;
+        h->state_packed = false;
+      }
+    }
+  } guard{h};
   if (l.total > h->ws_bytes) {
     if (h->ws) hipFree(h->ws);
     h->ws = nullptr;
@@ -610,6 +622,7 @@ static int track_run(cpx_handle* h, const uint16_t* frames_dev, const int32_t* c
   h->timing_valid = true;
   if (background_dev) cpx::launch_export_background(a, B, background_dev, h->stream);
   CPX_HIP(h, hipGetLastError());
+  guard.armed = false;
   return CPX_OK;
 }
 

@@ -212,7 +212,10 @@ int cpx_track_frame_ex(cpx_handle* h, const uint16_t* frames_dev, const cpx_fram
  * background, a weight that is not an accumulation of the handle's weight_add) -> CPX_ERR_UNSUPPORTED.  A track call
  * that is refused over the staged states (one staged for a clip index it does not have, or CPX_TRACK_KEEP_BACKGROUND
  * without a state for every clip) fails with CPX_ERR_INVALID and drops all staged states.
- * cpx_get_background reads the state the last track call left for clip `clip` (synchronises the handle's stream). */
+ * cpx_get_background reads the state the last track call left for clip `clip` (synchronises the handle's stream).  A
+ * track call that fails after it has begun to overwrite that state (workspace allocation, a HIP error, a batch too large
+ * for one launch) leaves none: cpx_get_background and CPX_TRACK_KEEP_BACKGROUND without staged states are refused with
+ * CPX_ERR_INVALID until the next successful call; a call refused before (bad flag, staged states) keeps the previous one. */
 int cpx_set_background(cpx_handle* h, int clip, const float* background, const double* weights, double average);
 int cpx_get_background(cpx_handle* h, int clip, float* background, double* weights, double* average);
 int cpx_associate_frame(cpx_handle* h, const cpx_track_params* params, const cpx_frame_meta* meta, int n_prev,

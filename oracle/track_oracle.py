@@ -12,6 +12,7 @@ Each function cites the reference file:line (relative to /root/reference/src)
 it follows.  The OpenCV operators come from oracle/cv2_shim.py.
 """
 
+import copy
 import math
 
 import numpy as np
@@ -639,16 +640,25 @@ def filter_tracks(state):
 
 
 def track_clip(frames, time_on=None, last_ffc=None, background_flags=None, cfg=None,
-               keep=False, do_tracking=True, apply_filter=True):
+               keep=False, do_tracking=True, apply_filter=True, background=None):
     """frames: uint16 [N,H,W] -- every frame of the file in order (the first one
     initialises the background even when it is a background frame,
-    cliptrackextractor.py:129-139).  Returns a dict of per-frame results."""
+    cliptrackextractor.py:129-139).  Returns a dict of per-frame results.
+
+    background: a WeightedBackground to continue from (copied, the caller's object is not changed).  Frame 0 then
+    does not seed the model: every frame goes through process_frame's update of an existing model
+    (motiondetector.py:197-237, the branch after `self._background is None`), and the window of the last
+    cfg.window frames starts empty -- as when a caller hands its own model on to a new extractor (cpx.h:
+    CPX_TRACK_KEEP_BACKGROUND)."""
     cfg = cfg or OracleConfig()
     n, H, W = frames.shape
     e = cfg.edge_pixels
     crop = (e, e, W - 2 * e, H - 2 * e)
-    bg = WeightedBackground(W, H, cfg.weight_add, e)
-    bg.process_frame(frames[0])
+    if background is None:
+        bg = WeightedBackground(W, H, cfg.weight_add, e)
+        bg.process_frame(frames[0])
+    else:
+        bg = copy.deepcopy(background)
     out = dict(init_bg=bg.background.copy(), init_avg=bg.average, frames=[])
     state = dict(cfg=cfg, crop=crop, active=[], tracks=[], next_id=1, filtered=[])
     window = []
