@@ -47,10 +47,8 @@ struct cpx_handle {
   int last_launches = 0;
   bool timing_valid = false;
   // incremental (one clip, frame by frame) tracking: frames consumed so far, -1 = no stream open
-  // pipelined split of the frame step: back halves run on stream2 one step behind the front halves
+  // second stream: the deferred medians (CPX_TRACK_DEFER_MEDIANS)
   hipStream_t stream2 = nullptr;
-  hipEvent_t ev_front[2] = {nullptr, nullptr}, ev_back[2] = {nullptr, nullptr};
-  int split_min_clips = 0;  // 0 = never split
   // the last track call kept the per-pixel kept-frame counts in the window sums' top ten bits (cpx_frame_kernel<true>): whatever
   // continues from that state, or exports it, unpacks it first (unpack_state)
   bool state_packed = false;
@@ -78,7 +76,6 @@ struct cpx_handle {
   float* cnn_arena = nullptr;
   size_t cnn_arena_floats = 0;
   int* cnn_ovf = nullptr;                // CPX_CNN_MATH_FP16X2: the overflow word of the forward (or bare convolution) in flight
-  bool planes_handover = true;           // CPX_CNN_PLANES_HANDOVER=0: fp16x2 keeps `mid` float32 (every layer splits its own input)
   int block_fusion = 2;                  // CPX_CNN_BLOCK_FUSION: fp16x2 runs as ONE launch (conv_block32_kernel) 2 = every stage-2 block, 1 = all but the stage's first, 0 = none
   unsigned char* ir_scratch = nullptr;  // cpx_ir_detect: slots for frames whose run / component tables outgrow LDS
   size_t ir_scratch_bytes = 0;
@@ -245,10 +242,6 @@ int cpx_create(int device_id, const cpx_config* cfg, cpx_handle** out) {
   h->cfg = *cfg;
   if (hipSetDevice(device_id) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
       hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&h->ev_front[0], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&h->ev_front[1], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&h->ev_back[0], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&h->ev_back[1], hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&h->ev_median, hipEventDisableTiming) != hipSuccess ||
       hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) {
     cpx_destroy(h);
@@ -311,12 +304,10 @@ int cpx_create(int device_id, const cpx_config* cfg, cpx_handle** out) {
     cpx_destroy(h);
     return CPX_ERR_HIP;
   }
-  if (const char* env = std::getenv("CPX_TRACK_SPLIT_MIN_CLIPS")) h->split_min_clips = std::atoi(env);
   if (const char* env = std::getenv("CPX_TRACK_PACKED_STATE")) h->packed_state_ok = std::atoi(env) != 0;
   if (const char* env = std::getenv("CPX_CNN_FUSE_CONV1")) h->fuse_conv1 = std::atoi(env) != 0;
   if (const char* env = std::getenv("CPX_TRACK_PER_STEP")) h->track_per_step = std::atoi(env) != 0;
   if (const char* env = std::getenv("CPX_CNN_FUSE_SHORTCUT")) h->fuse_shortcut = std::atoi(env) != 0;
-  if (const char* env = std::getenv("CPX_CNN_PLANES_HANDOVER")) h->planes_handover = std::atoi(env) != 0;
   if (const char* env = std::getenv("CPX_CNN_BLOCK_FUSION")) h->block_fusion = std::min(std::max(std::atoi(env), 0), 2);
   if (const char* env = std::getenv("CPX_CNN_MATH")) {
     if (!std::strcmp(env, "f32")) h->cnn_math = CPX_CNN_MATH_F32;
@@ -350,10 +341,6 @@ void cpx_destroy(cpx_handle* h) {
   for (auto& e : h->conv_events) {
     hipEventDestroy(e.e0);
     hipEventDestroy(e.e1);
-  }
-  for (int i = 0; i < 2; ++i) {
-    if (h->ev_front[i]) hipEventDestroy(h->ev_front[i]);
-    if (h->ev_back[i]) hipEventDestroy(h->ev_back[i]);
   }
   if (h->stream2) {
     hipStreamSynchronize(h->stream2);
@@ -577,26 +564,14 @@ static int track_run(cpx_handle* h, const uint16_t* frames_dev, const int32_t* c
   // CPX_TRACK_DEFER_MEDIANS: behind the frame kernel on the second stream instead (below), beside the caller's next stages
   if (!defer_medians) cpx::launch_median(a, B, t_begin, max_proc, h->stream);
   CPX_HIP(h, hipEventRecord(h->ev0, h->stream));  // (ev0 .. ev1 bracket the frame / NLM kernels)
-  // (with the internal ping-pong of filtered frames the back half of step t would read what the front half of
-  // step t+1 overwrites: split only when the caller keeps every filtered frame)
-  const bool split = !c.denoise && !need_filt && h->split_min_clips > 0 && B >= h->split_min_clips &&
-                     max_proc - t_begin > 2;
   int launches = 0;
-  if (!split && !c.denoise && !h->track_per_step) {
+  if (!c.denoise && !h->track_per_step) {
     // one workgroup per clip walks its frames: a single launch, no phase lockstep between the clips (cpx_track.hip)
     cpx::launch_frame(a, B, t_begin, max_proc, 0, h->stream);
     launches = 1;
   } else {
     for (int t = t_begin; t < max_proc; ++t) {
-      if (split) {
-        // front(t) reuses the hand-over slot that back(t - 2) read
-        if (t - t_begin >= 2) CPX_HIP(h, hipStreamWaitEvent(h->stream, h->ev_back[t & 1], 0));
-        cpx::launch_frame(a, B, t, t + 1, 1, h->stream);
-        CPX_HIP(h, hipEventRecord(h->ev_front[t & 1], h->stream));
-        CPX_HIP(h, hipStreamWaitEvent(h->stream2, h->ev_front[t & 1], 0));
-        cpx::launch_frame(a, B, t, t + 1, 2, h->stream2);
-        CPX_HIP(h, hipEventRecord(h->ev_back[t & 1], h->stream2));
-      } else if (!c.denoise) {
+      if (!c.denoise) {
         cpx::launch_frame(a, B, t, t + 1, 0, h->stream);
       } else {  // front (normalise) -> non-local means -> back (blur / threshold / label / statistics)
         cpx::launch_frame(a, B, t, t + 1, 1, h->stream);
@@ -605,10 +580,6 @@ static int track_run(cpx_handle* h, const uint16_t* frames_dev, const int32_t* c
       }
       ++launches;
     }
-  }
-  if (split) {  // everything enqueued later on the handle's stream sees the last back halves
-    CPX_HIP(h, hipStreamWaitEvent(h->stream, h->ev_back[(max_proc - 1) & 1], 0));
-    if (max_proc - t_begin >= 2) CPX_HIP(h, hipStreamWaitEvent(h->stream, h->ev_back[(max_proc - 2) & 1], 0));
   }
   CPX_HIP(h, hipEventRecord(h->ev1, h->stream));
   if (defer_medians) {
@@ -1641,7 +1612,7 @@ int cpx_cnn_forward(cpx_cnn* cnn, const float* in_dev, int N, int H, int W, floa
       // fp16x2: where the first convolution's kernel can store fp16 planes and the second one's can stage them, `mid`
       // travels as the second convolution's scaled planes (same bytes as float32) and its staging is a copy
       bool planes_pair = false;
-      if (h->cnn_math == CPX_CNN_MATH_FP16X2 && h->planes_handover) {
+      if (h->cnn_math == CPX_CNN_MATH_FP16X2) {
         cpx::ConvArgs pa{}, pb{};
         pa.N = N; pa.H = hh; pa.W = ww; pa.Ho = ho; pa.Wo = wo; pa.Cin = c_in; pa.Cout = f; pa.groups = p.groups; pa.ksize = 3;
         pa.stride = s; pa.pad_top = pa.pad_left = 1;

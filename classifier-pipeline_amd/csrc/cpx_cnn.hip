@@ -87,11 +87,9 @@ __global__ __launch_bounds__(CT) void conv_mfma_kernel(ConvArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int tiles_x = (a.Wo + TW - 1) / TW, tiles_y = (a.Ho + TH - 1) / TH;
   int bid = blockIdx.x;
-#ifndef CPX_CONV_NO_XCD_REMAP
   // workgroups are dealt round-robin to the 8 XCDs (each with its own L2): give every XCD a contiguous run of
   // tiles so that neighbouring tiles, which share their halo rows / columns, hit the same L2
   if ((gridDim.x & 7) == 0) bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);
-#endif
   const int txi = bid % tiles_x;
   bid /= tiles_x;
   const int tyi = bid % tiles_y;

@@ -850,25 +850,17 @@ __global__ __launch_bounds__(CT) void conv_bf3flat_kernel(ConvArgs a, const uint
 // one 16-byte access per accumulator tile straight from the registers -- no transpose through LDS, no epilogue barrier.
 // A wave owns two tile rows (2 x 16 pixels) x 32 columns = 2 x 2 accumulator tiles; 12 ds_read_b128 feed 24 MFMAs.
 constexpr int KW = 32;
-#ifndef CPX_BF3W_RUN
-#define CPX_BF3W_RUN 1  // tiles a workgroup walks along x (launch_bf3w)
-#endif
-#ifndef CPX_BF3W_LDSBN
-#define CPX_BF3W_LDSBN 0
-#endif
 constexpr int W_TW = 16, W_TH = 16, W_PW = 18, W_NPX = 18 * 18;
 constexpr int W_NPXP = 326;  // pixels per (plane, quarter pair) region: 326 * 32 B = 64 mod 128, the two regions' ds_write_b64 lanes then use different banks
 constexpr int w_patch_entries(int planes) { return planes * 2 * W_NPXP * 2; }
 constexpr int w_rows_resident(int planes) { return planes == 2 ? 3 : 1; }
 constexpr int w_wsub_entries(int planes) { return w_rows_resident(planes) * planes * 3 * 4 * 32; }  // a weight sub-chunk
-// WALK: the workgroup walks a run of td.run tiles along x (else exactly one tile: the loop and the per-use
+// WALK: the workgroup walks a run of td.run tiles along x (launched false: exactly one tile, the loop and the per-use
 // laundering of the staging bases fold away); LDSBN: BatchNorm scale / shift read back from LDS at each patch commit
 // instead of living in eight registers; NH: 32-column slices of the group's output channels the workgroup computes from
 // ONE staged patch (NH = 2 for 64 columns per group: the patch of a tile is loaded, normalised and split once instead
 // of once per slice -- the slices' weights alternate through the same 18 KB, twice the accumulators)
-// NG: GROUPS the workgroup walks on its tile, one after the other (experiment, -DCPX_BF3W_NG=2: the second group's patch
-// and first weights are in flight under the first group's products, as the next chunk's are in a layer with 64
-// channels per group, and the tile's index arithmetic is paid once for both -- 171 vs 183 TFLOP/s on stage 2: not shipped)
+// NG: GROUPS the workgroup walks on its tile, one after the other (launched 1; 2 ran 171 vs 183 TFLOP/s on stage 2)
 // PL: bf16 planes per operand.  3 = the exact split (six products per K step: every term down to 2^-24 of the float32
 // product); 2 = CPX_CNN_MATH_BF16X2: both operands as hi + lo rounded to nearest (16 significand bits, relative error
 // <= 2^-16 each), three products w0 x1 + w1 x0 + w0 x0 -- half the matrix work, two thirds of the staging and LDS.
@@ -910,11 +902,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   bid = qd;
   qd = div_magic(bid, td.m_ty);
   const int tyi = bid - qd * td.tiles_y;
-#ifdef CPX_BF3W_ALIAS_N  // experiment (scratch/patches/README.md): every sample reads and writes the first CPX_BF3W_ALIAS_N ones -- same work, no HBM traffic
-  const int n = qd & (CPX_BF3W_ALIAS_N - 1);
-#else
   const int n = qd;
-#endif
   const int g0 = blockIdx.y * NG;
   const int oy0 = tyi * W_TH;
   const int iy0 = oy0 - a.pad_top;
@@ -1169,15 +1157,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 #pragma unroll
           for (int i = 0; i < NP; ++i) {
             if (i * CT + CT <= NITEM || tid < NITEM - i * CT) {
-#ifdef CPX_BF3W_FAKE_SPLIT  // experiment (scratch/patches/README.md): the staged pieces go to LDS as they are -- wrong results, the cost of BatchNorm + split gone
-              {
-                uint2* sp2 = reinterpret_cast<uint2*>(s_patch) + st_e2 + i * (64 * 4);
-                sp2[(0 * 2 * W_NPXP) * 4] = make_uint2(pre_p[i][0], pre_p[i][1]);
-                sp2[(1 * 2 * W_NPXP) * 4] = make_uint2(pre_p[i][2], pre_p[i][3]);
-                if (PL == 3) sp2[(2 * 2 * W_NPXP) * 4] = make_uint2(pre_p[i][1], pre_p[i][2]);
-                continue;
-              }
-#endif
               if (H && a.in_planes) {  // (uniform) the producer stored this layer's planes: [hi 0..3 | lo 0..3] per piece
                 asm volatile("");
                 u32x4 pv = pre_p[i];
@@ -1588,17 +1567,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       for (int i = 0; i < NP; ++i) convert_item(i, oy0 - 2, ox0 - 2, interior);
     }
   }
-#ifdef CPX_B32_STAMPS  // (experiment, scratch/build_conv_variant.sh: where a tile's time goes -- cycle stamps of waves 0 and 7 of one workgroup)
-  long long st_last = clock64(), st_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  int st_tiles = 0;
-  const bool st_on = blockIdx.x == 8 && blockIdx.y == 0 && (tid == 0 || tid == 448);
-#define B32_STAMP(i_) if (st_on) { const long long now_ = clock64(); st_acc[i_] += now_ - st_last; st_last = now_; }
-#else
-#define B32_STAMP(i_)
-#endif
   for (;;) {
     commit_patch();
-    B32_STAMP(0)
     const int n_cur = n, oy_cur = oy0, ox_cur = ox0;
     const bool interior_cur = tile_interior();
     // ---- what goes in flight under the first convolution, in pieces BETWEEN its K steps (address arithmetic and load issue
@@ -1637,9 +1607,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       if (more) decode(tile_of(t));
       interior_next = tile_interior();
     };
-    B32_STAMP(1)
     __syncthreads();
-    B32_STAMP(2)
     // ---- first convolution: 21 groups of 16 mid pixels x two 16-column tiles.  Waves 0-3 take groups w, w + 8, w + 16; waves
     //      4-7 groups w, w + 8; the 21st group (4 valid pixels) is split by column tile between waves 4 and 5 -- waves w and
     //      w + 4 share a SIMD, so the SIMDs carry 11, 11, 10, 10 (group, tile) units (with three whole groups on wave 4
@@ -1738,11 +1706,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
     static_assert(C8 || NP == 7, "the patch items ride on K steps 2..8 of the first convolution");
     }
-    B32_STAMP(3)
     // every wave has read its patch fragments: the region becomes mid (C8: the patch has a region of its own -- a wave
     // writes its share of mid as soon as its own products are done)
     if (!C8) __syncthreads();
-    B32_STAMP(4)
     // ---- mid = relu(acc * a_scale + a_shift), times the second convolution's range scale, as its fp16 planes in LDS;
     //      pixels outside the image are that convolution's zero padding ----
 #pragma unroll
@@ -1774,9 +1740,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
       for (int pt = 0; pt < 2; ++pt)
         if (!C8) acc[ct][pt] *= rs_b[ct];  // the accumulators hold act_scale * w_scale[channel] times the sum: so must the residual
-    B32_STAMP(5)
     __syncthreads();
-    B32_STAMP(6)
     // ---- second convolution: conv_bf3w_kernel's loop on the mid image; between its taps the next tile's patch (landed
     //      during the first convolution) takes its prologue and split, one item per tap: vector work under the products ----
     {
@@ -1807,13 +1771,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             acc[ct][pt] = mfma16<true>(wv[bf][ct][0], xv[bf][pt][1], acc[ct][pt]);
             acc[ct][pt] = mfma16<true>(wv[bf][ct][0], xv[bf][pt][0], acc[ct][pt]);
           }
-#ifndef CPX_B32_NO_CONVERT
         if constexpr (C1) {
           if (tp < 3 && more) convert_c1(tp, oy0 - 2, ox0 - 2, interior_next, cbuf ^ 1);  // (in one lump on the first tap: 24,641 against 24,691 samples/s)
         } else {
           if (tp < NP && more) convert_item(tp, oy0 - 2, ox0 - 2, interior_next);
         }
-#endif
       }
     }
     if constexpr (C8) {
@@ -1837,7 +1799,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
           for (int pt = 0; pt < 2; ++pt) acc[ct][pt] = __builtin_amdgcn_mfma_f32_16x16x4f32(ws[ct], xs[pt], acc[ct][pt], 0, 0, 0);
       }
     }
-    B32_STAMP(7)
     // ---- epilogue: unscale, bias, ReLU, one 16-byte store per accumulator tile ----
     {
       float* out_n = b.out + (size_t)n_cur * a.H * a.W * C;
@@ -1852,23 +1813,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
       }
     }
-    B32_STAMP(8)
-#ifdef CPX_B32_STAMPS
-    ++st_tiles;
-#endif
     if (!more) break;
     cbuf ^= 1;
     // every wave has read its mid fragments: the region takes the next patch (C8: the patch goes to its own region, and the
     // barrier behind the commit is passed only by waves that are through with this tile's mid)
     if (!C8) __syncthreads();
-    B32_STAMP(9)
   }
-#ifdef CPX_B32_STAMPS
-  if (st_on)
-    printf("b32 stamps C8 %d wave %d tiles %d: commit %lld issue %lld bar1 %lld phaseA %lld bar2 %lld midepi %lld bar3 %lld phaseB %lld outepi %lld bar4 %lld\n",
-           (int)C8, wave, st_tiles, st_acc[0], st_acc[1], st_acc[2], st_acc[3], st_acc[4], st_acc[5], st_acc[6], st_acc[7], st_acc[8], st_acc[9]);
-#endif
-#undef B32_STAMP
   if ((hmax & 0xFFFFu) >= 0x7C00u || (hmax >> 16) >= 0x7C00u) atomicOr(a.ovf, 1);  // (infinity or NaN)
 }
 
@@ -1908,9 +1858,6 @@ static bool flat_pays(const ConvArgs& a, int TW, int TH, int npx_cap, int band =
   const double flat = (double)M / ((double)((M + band - 1) / band) * band);
   return flat > rect + 0.08;
 }
-#ifndef CPX_BF3FLAT_WIDE
-#define CPX_BF3FLAT_WIDE 0  // fp16x2: 256-position bands (512 threads) where the staged rows fit 384 pixels -- measured SLOWER on stage 4 (36.5 vs 31.4 ms per 15 launches of 1,536 samples, profiles/r06_conv_rw_experiments.md): not shipped
-#endif
 
 // packed float32 weights [g][tap][cin_g][cout_g] -> bf16 plane image [g][chunk][3][9][2][cout_g] of 16-byte entries
 // cin_g == 8: [g][3][5][2][cout_g], the entry of (step s, k half h) = the 8 channels of tap 2 s + h (zeros for tap 9)
@@ -2077,22 +2024,16 @@ __global__ __launch_bounds__(256) void split_weights32_kernel(const float* __res
   }
 }
 
-template <int NH, int NG, int PL, bool H = false>
+template <int NH, int PL, bool H = false>
 static int launch_bf3w_t(const ConvArgs& a, const uint4* wimg, hipStream_t s) {
   const size_t lds = (size_t)(w_patch_entries(PL) + w_wsub_entries(PL)) * 16 + (size_t)(a.Cin / a.groups) * 8;  // + BatchNorm scale / shift
   static bool lds_ready[64], lds_ready_p[64];
   // (NH = 2 carries 16 more accumulator registers: the BatchNorm parameters go to LDS there)
-  constexpr bool WALK = CPX_BF3W_RUN > 1, LDSBN = CPX_BF3W_LDSBN != 0 || NH > 1 || PL == 2;
-  if (!cpx_dyn_lds_ready(reinterpret_cast<const void*>(conv_bf3w_kernel<WALK, LDSBN, NH, NG, PL, H>), lds_ready, 160 * 1024 - 1024)) return -1;
+  constexpr bool LDSBN = NH > 1 || PL == 2;
+  if (!cpx_dyn_lds_ready(reinterpret_cast<const void*>(conv_bf3w_kernel<false, LDSBN, NH, 1, PL, H>), lds_ready, 160 * 1024 - 1024)) return -1;
   TileDiv td;
-  const int tx = (a.Wo + W_TW - 1) / W_TW;
-  // tiles per workgroup: the largest of CPX_BF3W_RUN .. 2 that divides the tiles of a row, else the whole row if it is short
-  int run = 1;
-  for (int r = CPX_BF3W_RUN; r >= 2; --r)  // (never entered at CPX_BF3W_RUN = 1)
-    if (tx % r == 0) { run = r; break; }
-  if (run == 1 && tx <= CPX_BF3W_RUN) run = tx;
-  td.run = run;
-  td.tiles_x = (tx + run - 1) / run;
+  td.run = 1;
+  td.tiles_x = (a.Wo + W_TW - 1) / W_TW;
   td.tiles_y = (a.Ho + W_TH - 1) / W_TH;
   td.nsplit = (a.Cout / a.groups) / (32 * NH);
   const long long blocks = (long long)td.tiles_x * td.tiles_y * a.N * td.nsplit;
@@ -2102,22 +2043,17 @@ static int launch_bf3w_t(const ConvArgs& a, const uint4* wimg, hipStream_t s) {
   td.m_ty = (1ull << 42) / td.tiles_y + 1;
   td.total = (int)blocks;
   if constexpr (PL == 3 && !H) if (a.guard != nullptr) {  // the guarded rerun of a fp16x2 layer: a small grid that walks the tiles (PERSIST)
-    if (!cpx_dyn_lds_ready(reinterpret_cast<const void*>(conv_bf3w_kernel<WALK, LDSBN, NH, NG, PL, false, true>), lds_ready_p, 160 * 1024 - 1024)) return -1;
-    hipLaunchKernelGGL((conv_bf3w_kernel<WALK, LDSBN, NH, NG, PL, false, true>), dim3((unsigned)std::min<long long>(blocks, RERUN_GRID), a.groups / NG), dim3(512), lds, s, a, wimg, td);
+    if (!cpx_dyn_lds_ready(reinterpret_cast<const void*>(conv_bf3w_kernel<false, LDSBN, NH, 1, PL, false, true>), lds_ready_p, 160 * 1024 - 1024)) return -1;
+    hipLaunchKernelGGL((conv_bf3w_kernel<false, LDSBN, NH, 1, PL, false, true>), dim3((unsigned)std::min<long long>(blocks, RERUN_GRID), a.groups), dim3(512), lds, s, a, wimg, td);
     return 0;
   }
-  hipLaunchKernelGGL((conv_bf3w_kernel<WALK, LDSBN, NH, NG, PL, H>), dim3((unsigned)blocks, a.groups / NG), dim3(512), lds, s, a, wimg, td);
+  hipLaunchKernelGGL((conv_bf3w_kernel<false, LDSBN, NH, 1, PL, H>), dim3((unsigned)blocks, a.groups), dim3(512), lds, s, a, wimg, td);
   return 0;
 }
-#ifndef CPX_BF3W_NH
-#define CPX_BF3W_NH 2  // 32-column slices per workgroup where the group has 64 columns (1: one slice, two workgroups per tile)
-#endif
-#ifndef CPX_BF3W_NG
-#define CPX_BF3W_NG 1  // groups a workgroup walks on its tile in the one-slice form (2: measured 6.5 % slower on stage 2, scratch/patches/README.md)
-#endif
 // the three-plane image of a layer, then (these layers only) the two-plane one
 static size_t bf3w_image3_bytes(const ConvArgs& a) { return (size_t)a.groups * (a.Cin / a.groups / KW) * 3 * 36 * (a.Cout / a.groups) * 16; }
 static size_t bf3w_image2_bytes(const ConvArgs& a) { return (size_t)a.groups * (a.Cin / a.groups / KW) * 3 * 24 * (a.Cout / a.groups) * 16; }
+// (groups with 64 columns: both 32-column slices in one workgroup, NH = 2)
 static int launch_bf3w(const ConvArgs& a, const uint4* wimg, hipStream_t s) {
   if (a.planes == 2 && a.half) {  // the fp16 image lies behind the two bf16 ones
     const uint4* wh = wimg + (bf3w_image3_bytes(a) + bf3w_image2_bytes(a)) / 16;
@@ -2128,18 +2064,16 @@ static int launch_bf3w(const ConvArgs& a, const uint4* wimg, hipStream_t s) {
       const int rc = launch_conv_rw(a, wh, s);
       if (rc != -2) return rc;
     }
-    if (CPX_BF3W_NH == 2 && a.Cout / a.groups == 64) return launch_bf3w_t<2, 1, 2, true>(a, wh, s);
-    return launch_bf3w_t<1, 1, 2, true>(a, wh, s);
+    if (a.Cout / a.groups == 64) return launch_bf3w_t<2, 2, true>(a, wh, s);
+    return launch_bf3w_t<1, 2, true>(a, wh, s);
   }
   if (a.planes == 2) {
     const uint4* w2 = wimg + bf3w_image3_bytes(a) / 16;
-    if (CPX_BF3W_NH == 2 && a.Cout / a.groups == 64) return launch_bf3w_t<2, 1, 2>(a, w2, s);
-    return launch_bf3w_t<1, 1, 2>(a, w2, s);
+    if (a.Cout / a.groups == 64) return launch_bf3w_t<2, 2>(a, w2, s);
+    return launch_bf3w_t<1, 2>(a, w2, s);
   }
-  if (CPX_BF3W_NH == 2 && a.Cout / a.groups == 64) return launch_bf3w_t<2, 1, 3>(a, wimg, s);
-  constexpr int NG = (CPX_BF3W_NG == 2 && CPX_BF3W_RUN <= 1 && CPX_BF3W_LDSBN == 0) ? 2 : 1;
-  if (NG == 2 && (a.groups & 1) == 0) return launch_bf3w_t<1, NG, 3>(a, wimg, s);
-  return launch_bf3w_t<1, 1, 3>(a, wimg, s);
+  if (a.Cout / a.groups == 64) return launch_bf3w_t<2, 3>(a, wimg, s);
+  return launch_bf3w_t<1, 3>(a, wimg, s);
 }
 
 template <int NTN, int S, int NB, int TW, int CT, bool C8 = false, int PL = 3, bool H = false>
@@ -2188,9 +2122,6 @@ int launch_bf3_t(const ConvArgs& a, const uint4* wimg, hipStream_t s) {
 #ifndef CPX_BF3_NTN_S4
 #define CPX_BF3_NTN_S4 2
 #endif
-#ifndef CPX_BF3_NTN_ST3
-#define CPX_BF3_NTN_ST3 1
-#endif
 #ifndef CPX_BF3_NB_S2
 #define CPX_BF3_NB_S2 2
 #endif
@@ -2215,27 +2146,20 @@ static bool bf3_c8(const ConvArgs& a) { return a.Cin / a.groups == 8 && a.Cout /
 // the strided first convolution of a stage (wr_resnet.py:27-30: stride = stage index): the same kernel with a strided
 // patch -- the MFMA loop is unchanged, only the A-fragment addresses carry the stride.  S = 2 (res3b0_branch2a): 33 x 33
 // staged pixels for 16 x 16 outputs and both 32-column tiles of a group in one workgroup (160 KB, one workgroup per CU):
-// 123 TFLOP/s against 95 on the float32 MFMA.  S = 3 (res4b0_branch2a, -DCPX_BF3_STRIDED=3): 24 x 48 staged pixels for
-// 8 x 16 outputs, 138 KB, four waves per CU and the patch split once per 32-column slice: 40 TFLOP/s against 78 on the
-// float32 MFMA (windows of a stride-3 3 x 3 kernel do not overlap: nothing is reused) -- measured, not shipped.
-#ifndef CPX_BF3_STRIDED
-#define CPX_BF3_STRIDED 1
-#endif
+// 123 TFLOP/s against 95 on the float32 MFMA.  (S = 3, res4b0_branch2a: 24 x 48 staged pixels for 8 x 16 outputs, 138 KB,
+// four waves per CU and the patch split once per 32-column slice: 40 TFLOP/s against 78 on the float32 MFMA -- windows of
+// a stride-3 3 x 3 kernel do not overlap, nothing is reused.  Measured, not shipped.)
 static bool bf3_strided(const ConvArgs& a) {
   const int cin_g = a.Cin / a.groups, cout_g = a.Cout / a.groups;
-  if (!CPX_BF3_STRIDED || a.ksize != 3 || cin_g < KC || (cin_g % KC) != 0) return false;
-  return (a.stride == 2 && cout_g == 64) || (CPX_BF3_STRIDED >= 3 && a.stride == 3 && cout_g == 128);
+  if (a.ksize != 3 || cin_g < KC || (cin_g % KC) != 0) return false;
+  return a.stride == 2 && cout_g == 64;
 }
 // stride-1 layers with 32 or 64 channels per group (stages 2 and 3): the 16x16x32 form (conv_bf3w_kernel) and its
 // weight image; a property of the layer shape alone, so that the image built at cpx_cnn_create is the one every
 // launch of the layer reads (with or without a fused shortcut)
-#ifndef CPX_BF3W
-#define CPX_BF3W 1
-#endif
-
 static bool bf3w_layer(const ConvArgs& a) {
   const int cin_g = a.Cin / a.groups, cout_g = a.Cout / a.groups;
-  return CPX_BF3W && a.ksize == 3 && a.stride == 1 && cin_g >= KW && (cin_g % KW) == 0 && (cout_g == 32 || cout_g == 64) && cin_g <= 64;
+  return a.ksize == 3 && a.stride == 1 && cin_g >= KW && (cin_g % KW) == 0 && (cout_g == 32 || cout_g == 64) && cin_g <= 64;
 }
 // the strided first convolutions conv_rw_kernel takes in fp16x2 (cpx_cnn_rw.hip): the stride-2 one has this file's kernels for
 // the other modes and the rerun; the stride-3 one has none here -- every launch of it that is not conv_rw_kernel's goes to the
@@ -2383,7 +2307,6 @@ int launch_conv_bf3(const ConvArgs& a_in, const void* wimg, hipStream_t s) {
     // guarded twin behind finds the overflow word clear)
     return rc == -2 ? launch_conv(a, s) : rc;
   }
-  if (a.stride == 3) return bf3_strided(a) ? launch_bf3_t<CPX_BF3_NTN_ST3, 3, 1, 16, 256>(a, w, s) : -2;
   if (a.stride != 1) return -2;
   if (bf3w_layer(a)) {
     if (a.sc_in && ((a.sc_cin / a.groups) & 3)) return -2;  // the fused shortcut walks K in fours
@@ -2395,8 +2318,6 @@ int launch_conv_bf3(const ConvArgs& a_in, const void* wimg, hipStream_t s) {
   // need 384 staged pixels and then fit only one N tile per workgroup: measured slower than the rectangular bands,
   // 399 vs 371 ms, the patch being activated and split by four column slices instead of two.)
   if (cout_g == 128 && flat_pays(a, 32, 4 * CPX_BF3_NB_S4, 256)) {
-    if (a.planes == 2 && a.half && CPX_BF3FLAT_WIDE && flat_pays(a, 32, 4 * CPX_BF3_NB_S4, 384, 256))
-      return launch_bf3flat_t<2, 384, 2, true, 512>(a, w + half_image_offset(a) / 16, s);
     if (a.planes == 2 && a.half) return launch_bf3flat_t<2, 256, 2, true>(a, w + half_image_offset(a) / 16, s);
     if (a.planes == 2 && flat_layer(a)) return launch_bf3flat_t<2, 256, 2>(a, w + image3_bytes(a) / 16, s);
     return launch_bf3flat_t<2, 256, 3>(a, w, s);

@@ -33,7 +33,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 
 #include "cpx_kernels.h"
@@ -269,10 +268,7 @@ __global__ __launch_bounds__(RW_CT) __attribute__((amdgpu_waves_per_eu(1, 1))) v
   //      staging work that rides along.  Fragments are requested RW_AHEAD steps before their products (one wave per SIMD:
   //      distance instead of a partner) ----
   const int a_base = ((q >> 1) * NPXP + S * i16) * 2 + (q & 1);
-#ifndef CPX_RW_AHEAD
-#define CPX_RW_AHEAD 3
-#endif
-  constexpr int RW_AHEAD = CPX_RW_AHEAD, RW_RING = CPX_RW_AHEAD + 1;
+  constexpr int RW_AHEAD = 3, RW_RING = RW_AHEAD + 1;
   auto compute = [&](auto cc, auto bc, auto&& between) __attribute__((always_inline)) {
     constexpr int C = decltype(cc)::value, B = decltype(bc)::value;
     const uint4* sb = s_buf + B * BUF + a_base;
@@ -451,19 +447,14 @@ __global__ __launch_bounds__(RW_CT) __attribute__((amdgpu_waves_per_eu(1, 1))) v
 //   1  stride 1, 64 -> 64   (stage 3 of WR-ResNet-22-4: the convolutions of its blocks but the strided first one)
 //   2  stride 2, 32 -> 64   (that strided first one)
 //   3  stride 3, 64 -> 128  (stage 4's)
-// CPX_CNN_RW: bit k - 1 enables kind k (default: all; 0 = none)
 int conv_rw_kind(const ConvArgs& a) {
-  static const int enabled = [] {
-    const char* e = std::getenv("CPX_CNN_RW");
-    return e == nullptr ? 7 : std::atoi(e);
-  }();
   if (a.ksize != 3 || a.groups < 1 || a.Cin % a.groups || a.Cout % a.groups) return 0;
   const int cin_g = a.Cin / a.groups, cout_g = a.Cout / a.groups;
   int kind = 0;
   if (a.stride == 1 && cin_g == 64 && cout_g == 64) kind = 1;
   else if (a.stride == 2 && cin_g == 32 && cout_g == 64) kind = 2;
   else if (a.stride == 3 && cin_g == 64 && cout_g == 128) kind = 3;
-  return (kind && ((enabled >> (kind - 1)) & 1)) ? kind : 0;
+  return kind;
 }
 bool conv_rw_layer(const ConvArgs& a) { return conv_rw_kind(a) == 1; }
 
@@ -495,7 +486,6 @@ int launch_rw_t(const ConvArgs& a, const uint4* wimg, hipStream_t s) {
   }
   const int ny = a.groups * ((a.Cout / a.groups) / RW_WC);
   int gx = std::max(8, cus_of[dev] / ny / 8 * 8);
-  if (const char* e = std::getenv("CPX_RW_GRID")) gx = std::max(8, std::atoi(e) / 8 * 8);
   gx = (int)std::min<long long>(gx, (tiles + 7) / 8 * 8);
   hipLaunchKernelGGL((conv_rw_kernel<S, NCH, ROWS, BN, RES>), dim3((unsigned)gx, (unsigned)ny), dim3(RW_CT), G::LDS, s, a, wimg, td);
   return 0;

@@ -572,9 +572,6 @@ struct GlobalBytes {
 
 __global__ __launch_bounds__(64 * WAVES_PER_WG, 6) void cpx_cptv_inflate_kernel(CptvInflateArgs a) {
   __shared__ WaveLds s_lds[WAVES_PER_WG];
-#ifdef CPX_INFLATE_CLOCK_PROBE
-  const unsigned long probe_c0 = __builtin_amdgcn_s_memtime(), probe_r0 = __builtin_amdgcn_s_memrealtime();
-#endif
   const int lane = threadIdx.x & 63;
   const int f = rfl((int)(blockIdx.x * WAVES_PER_WG + (threadIdx.x >> 6)));
   if (f >= a.B) return;
@@ -680,12 +677,6 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG, 6) void cpx_cptv_inflate_kernel(
     }
   }
   res.status = status;
-#ifdef CPX_INFLATE_CLOCK_PROBE
-  {  // diagnostic build only: the shader clock this wave ran at, in MHz (s_memrealtime ticks at 100 MHz)
-    const unsigned long c1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-    res.reserved = (int)((c1 - probe_c0) * 100 / (r1 - probe_r0 + 1));
-  }
-#endif
   if (lane == 0) a.results[f] = res;
 }
 

@@ -509,12 +509,7 @@ __device__ __forceinline__ void frame_step(KernArgs& a, const int b, const int p
       u32 xs2[2];
       // |pix - bg| of both pixels + the running sum in one v_sad_u16 on the packed pairs (written per pixel on the unpacked
       // values the compiler spent 11 instructions per two steps on SDWA min / max pairs)
-#ifndef CPX_TRACK_SAD32
       sabs = __builtin_amdgcn_sad_u16(pq, (u32)bgv[0] | ((u32)bgv[1] << 16), sabs);
-#else
-      sabs = __usad((u32)pix[0], (u32)bgv[0], sabs);
-      sabs = __usad((u32)pix[1], (u32)bgv[1], sabs);
-#endif
       // interior test per pixel; with the usual one-pixel border the column tests are the ones the background selects made
       bool colin[2];
       if (edge1) {
@@ -537,11 +532,7 @@ __device__ __forceinline__ void frame_step(KernArgs& a, const int b, const int p
         wsv[j] = wsv[j] + (u32)pix[j] - (u32)oldp[j];
         const int f = (nwin > 1) ? (int)__umulhi(wsv[j], div_magic) : (int)wsv[j];  // == wsv / nwin exactly
         nb[j] = bgv[j];
-#ifndef CPX_TRACK_COLTEST
         if (row_in && colin[j]) {
-#else
-        if (row_in && x0 + j >= e && x0 + j <= W - 1 - e) {
-#endif
           // motiondetector.py:212-223: bg' = bg if bg < f - w else f ; w' = w + add if (same) else 0
           // keep <=> bg < fl64(f - w_k), w_k = k-fold float64 accumulation of weight_add.  For integers bg, f that is
           // d = f - bg >= hi_k with hi_k = floor(w_k) + 1 from a table (csrc/cpx_api.cpp:weight_thresholds) -- unless
@@ -680,11 +671,7 @@ __device__ __forceinline__ void frame_step(KernArgs& a, const int b, const int p
       const u32 fill = (mx == 0) ? 0u : 0x01010101u;  // zeros, or data / max == 1
 #pragma unroll 1
       for (int c = tid; c < nchunk; c += NT) *reinterpret_cast<u32*>(s_u8 + (c << 2)) = fill;
-#ifndef CPX_NORM_FLOAT   // (experiment switch: -DCPX_NORM_FLOAT = the float32 expression for every span)
     } else if (mx - mn <= 65793) {
-#else
-    } else if (false) {
-#endif
       const u32 mg = (u32)uni((int)s_mag[0]);
       const int lsh = uni((int)s_mag[1]);
       const u32 cadd = 0u - (u32)mn * 65280u;
@@ -761,7 +748,6 @@ __device__ __forceinline__ void frame_step(KernArgs& a, const int b, const int p
     s_keep[2] = mx;
     s_keep[3] = __float_as_int(thresh);
   }
-#ifndef CPX_BLUR_SCALAR
   // ---- phase 4a: horizontal [1 4 6 4 1], BORDER_REFLECT_101 -----------------------
   // Packed 16-bit arithmetic, two pixels per instruction (sums <= 16 * 255): a group of 8 output pixels reads the 16 bytes
   // around it with three aligned LDS loads (the reflections only exist at the two ends of a row: byte shuffles of the group
@@ -840,57 +826,6 @@ __device__ __forceinline__ void frame_step(KernArgs& a, const int b, const int p
     }
   }
   __syncthreads();
-#else
-  // ---- phase 4a: horizontal [1 4 6 4 1], BORDER_REFLECT_101 -----------------------
-  const int ngroup = P >> 3;
-  const int gpr = W >> 3;  // 8-pixel groups per row
-  for (int g = tid; g < ngroup; g += NT) {
-    const int y = g / gpr, x0 = (g - y * gpr) << 3;
-    const unsigned char* row = s_u8 + y * W;
-    int pv[12];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) {
-      int x = x0 - 2 + k;
-      x = x < 0 ? -x : (x >= W ? 2 * W - 2 - x : x);
-      pv[k] = row[x];
-    }
-    uint16_t o[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) o[k] = (uint16_t)(pv[k] + 4 * pv[k + 1] + 6 * pv[k + 2] + 4 * pv[k + 3] + pv[k + 4]);
-    uint4 pk;
-    pk.x = o[0] | ((u32)o[1] << 16);
-    pk.y = o[2] | ((u32)o[3] << 16);
-    pk.z = o[4] | ((u32)o[5] << 16);
-    pk.w = o[6] | ((u32)o[7] << 16);
-    *reinterpret_cast<uint4*>(s_tmp + y * W + x0) = pk;
-  }
-  __syncthreads();
-  // ---- phase 4b: vertical pass, (S + 128) >> 8, floor-threshold -> bit rows ---------
-  for (int g = tid; g < ngroup; g += NT) {
-    const int y = g / gpr, x0 = (g - y * gpr) << 3;
-    int acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-      int yy = y - 2 + k;
-      yy = yy < 0 ? -yy : (yy >= H ? 2 * H - 2 - yy : yy);
-      const int wgt = (k == 0 || k == 4) ? 1 : ((k == 2) ? 6 : 4);
-      const uint4 q = *reinterpret_cast<const uint4*>(s_tmp + yy * W + x0);
-      acc[0] += wgt * (int)(q.x & 0xFFFF);
-      acc[1] += wgt * (int)(q.x >> 16);
-      acc[2] += wgt * (int)(q.y & 0xFFFF);
-      acc[3] += wgt * (int)(q.y >> 16);
-      acc[4] += wgt * (int)(q.z & 0xFFFF);
-      acc[5] += wgt * (int)(q.z >> 16);
-      acc[6] += wgt * (int)(q.w & 0xFFFF);
-      acc[7] += wgt * (int)(q.w >> 16);
-    }
-    u32 bits = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) bits |= (u32)((((acc[k] + 128) >> 8) > ithr) ? 1 : 0) << k;
-    reinterpret_cast<unsigned char*>(s_rowI)[y * (RW * 8) + (x0 >> 3)] = (unsigned char)bits;
-  }
-  __syncthreads();
-#endif
   // ---- phase 5: MORPH_CLOSE with the 1x2 element ----------------------
   for (int i = tid; i < H * RW; i += NT) {
     const int y = i / RW;
@@ -1089,7 +1024,6 @@ __device__ __forceinline__ void frame_step(KernArgs& a, const int b, const int p
     o.pixel_variance = var;
     Cout[rnk[cidx]] = o;
   };
-#ifndef CPX_VAR_PER_WAVE
   // The components of a frame share the workgroup's waves: with nc components in a round (at most NWAVE), NWAVE / nc waves sum
   // each one's box, partials meet in LDS, the first lane of a group combines them in wave order.  (One wave per component left
   // eleven of twelve waves waiting on the usual one or two boxes, seven trips to L2 long: the phase was 9 % of the step.)
@@ -1164,60 +1098,6 @@ __device__ __forceinline__ void frame_step(KernArgs& a, const int b, const int p
       par ^= 1;
     }
   }
-#else
-  constexpr int BIG = 512;  // pixels: above this a box is summed by the whole workgroup
-  int par = 0;
-  for (int cidx = 0; cidx < ncomp; ++cidx) {
-    const int bx = (int)stat[1 * SC + cidx], by = (int)stat[3 * SC + cidx];
-    const int bw = (int)stat[2 * SC + cidx] - bx + 1, bh = (int)stat[4 * SC + cidx] - by + 1;
-    const int n = bw * bh;
-    if (n > BIG && has_prev) {
-      double s1 = 0.0, s2 = 0.0;
-      for (int k = tid; k < n; k += NT) {
-        const int yy = k / bw;
-        const double d = delta_at((by + yy) * W + bx + (k - yy * bw));
-        s1 += d;
-        s2 += d * d;
-      }
-      s1 = wave_sum(s1);
-      s2 = wave_sum(s2);
-      if (lane == 0) {
-        s_part[(par * NWAVE + wave) * 2] = s1;
-        s_part[(par * NWAVE + wave) * 2 + 1] = s2;
-      }
-      phase_sync();
-      if (tid == 0) {
-        double t1 = 0.0, t2 = 0.0;
-        for (int w = 0; w < NWAVE; ++w) {
-          t1 += s_part[(par * NWAVE + w) * 2];
-          t2 += s_part[(par * NWAVE + w) * 2 + 1];
-        }
-        const double mean = t1 / (double)n;
-        double var = t2 / (double)n - mean * mean;
-        emit(cidx, bx, by, bw, bh, (float)(var < 0.0 ? 0.0 : var));
-      }
-      par ^= 1;
-    } else if ((cidx % NWAVE) == wave) {
-      float var = 0.0f;
-      if (has_prev) {
-        double s1 = 0.0, s2 = 0.0;
-        for (int k = lane; k < n; k += 64) {
-          const int yy = k / bw;
-          const double d = delta_at((by + yy) * W + bx + (k - yy * bw));
-          s1 += d;
-          s2 += d * d;
-        }
-        s1 = wave_sum(s1);
-        s2 = wave_sum(s2);
-        const double mean = s1 / (double)n;
-        const double v = s2 / (double)n - mean * mean;
-        var = (float)(v < 0.0 ? 0.0 : v);
-      }
-      if (lane == 0) emit(cidx, bx, by, bw, bh, var);
-    }
-  }
-
-#endif
   };
   if (big) label_phases(a.big_stat + (size_t)b * 9 * a.cap_out, a.big_stat + (size_t)b * 9 * a.cap_out + (size_t)8 * a.cap_out, a.cap_out, true);
   else label_phases(s_stat, s_rank, CAP, false);
@@ -1393,11 +1273,7 @@ __global__ __launch_bounds__(NT_MED) void cpx_median_kernel(TrackArgs a, int t0,
   // found by galloping away from it (steps of 2, 8, 32, ...) before it is bisected -- 4-6 rounds where bisecting [min, max]
   // takes log2(max - min) = 10-14.  Every probe keeps the invariant (rank k1 lies in [lo, hi]); the order of the probes does not
   // change what is found.
-#ifdef CPX_MED_PLAIN_BISECT   // (experiment switch: bisect [min, max] as rounds 2-5 did)
-  int phase = 3;
-#else
   int phase = 0;   // 0: probe the mean; 1 / 2: galloping down from hi / up from lo; 3: bisection
-#endif
   u32 gstep = 2;
   while (lo < hi) {  // uniform: every thread sees the same block totals
     if (phase != 0 && hi - lo <= gstep) phase = 3;   // the bracket is narrower than the next step: bisect it (the step stops growing:
@@ -1488,14 +1364,7 @@ __global__ __launch_bounds__(NT_MED) void cpx_median_kernel(TrackArgs a, int t0,
 // ---------------------------------------------------------------------------------------------
 namespace {
 // double-buffered row sums (one barrier per offset pair, the row pass of pair q + 1 beside the column pass of pair q):
-// 4.53 vs 4.56 us per frame in round 3, 3.80 vs 4.04 after the round-4 instruction trims (-DCPX_NLM_SINGLE: one buffer)
-#if !defined(CPX_NLM_SINGLE) && !defined(CPX_NLM_DB)
-#define CPX_NLM_DB 1
-#endif
-#ifndef CPX_NLM_ASM   // experiment switch: 0 = compiler-scheduled LDS reads, 1 = row sums by hand, 2 = the row loop too
-#define CPX_NLM_ASM 1
-#endif
-constexpr bool NLM_ASM_HV = (CPX_NLM_ASM & 1) != 0, NLM_ASM_ROWS = (CPX_NLM_ASM & 2) != 0;
+// 4.53 vs 4.56 us per frame in round 3, 3.80 vs 4.04 after the round-4 instruction trims (against one buffer)
 constexpr int NLM_R = 13;      // border = template radius 3 + search radius 10
 constexpr int NT_NLM = 1024;  // threads of an NLM workgroup (independent of the frame kernel's)
 __device__ __forceinline__ int refl101(int v, int n) { return v < 0 ? -v : (v >= n ? 2 * n - 2 - v : v); }
@@ -1534,23 +1403,8 @@ __device__ __forceinline__ void lds_read8_b32(u32 addr, u32* v) {
                : "v"(addr), "n"(BASE), "n"(BASE + STRIDE), "n"(BASE + 2 * STRIDE), "n"(BASE + 3 * STRIDE), "n"(BASE + 4 * STRIDE),
                  "n"(BASE + 5 * STRIDE), "n"(BASE + 6 * STRIDE), "n"(BASE + 7 * STRIDE));
 }
-template <int STRIDE, int BASE>
-__device__ __forceinline__ void lds_read5_u16(u32 addr, u32* v) {
-  asm volatile("ds_read_u16 %0, %5 offset:%6\n\tds_read_u16 %1, %5 offset:%7\n\tds_read_u16 %2, %5 offset:%8\n\t"
-               "ds_read_u16 %3, %5 offset:%9\n\tds_read_u16 %4, %5 offset:%10"
-               : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4])
-               : "v"(addr), "n"(BASE), "n"(BASE + STRIDE), "n"(BASE + 2 * STRIDE), "n"(BASE + 3 * STRIDE), "n"(BASE + 4 * STRIDE));
-}
-__device__ __forceinline__ void lds_gather5_b32(const u32* addr, u32* v) {
-  asm volatile("ds_read_b32 %0, %5\n\tds_read_b32 %1, %6\n\tds_read_b32 %2, %7\n\tds_read_b32 %3, %8\n\tds_read_b32 %4, %9"
-               : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4])
-               : "v"(addr[0]), "v"(addr[1]), "v"(addr[2]), "v"(addr[3]), "v"(addr[4]));
-}
 __device__ __forceinline__ void lds_wait8(u32* v) {
   asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]));
-}
-__device__ __forceinline__ void lds_wait5(u32* v) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]));
 }
 // the LDS byte address of a pointer into the workgroup's shared memory
 __device__ __forceinline__ u32 lds_addr(const void* p) { return (u32)reinterpret_cast<size_t>(p); }
@@ -1558,11 +1412,8 @@ __device__ __forceinline__ u32 lds_addr(const void* p) { return (u32)reinterpret
 
 // WC = the frame width when it is known at compile time (160: row strides fold into instruction offsets and the
 // pass-B row loads pair up as ds_read2_b32), 0 = any supported width.
-#ifndef CPX_NLM_WPE5   // experiment switch: waves per SIMD the BH <= 5 forms are compiled for (8 = two workgroups per CU)
-#define CPX_NLM_WPE5 4
-#endif
 template <int BH, int WC>
-__global__ __launch_bounds__(NT_NLM) __attribute__((amdgpu_waves_per_eu(BH <= 5 ? CPX_NLM_WPE5 : 4, BH <= 5 ? CPX_NLM_WPE5 : 4)))
+__global__ __launch_bounds__(NT_NLM) __attribute__((amdgpu_waves_per_eu(4, 4)))
 void cpx_nlm_kernel(TrackArgs a, int t) {
   const int b = blockIdx.x;
   const int nproc = a.proc_off[b + 1] - a.proc_off[b];
@@ -1584,14 +1435,10 @@ void cpx_nlm_kernel(TrackArgs a, int t) {
   const int RBa = RB < H ? RB : H;   // rows the launch sized the LDS for
   uint16_t* Hh = reinterpret_cast<uint16_t*>(smem + (((size_t)(RBa + 2 * NLM_R) * ES + 32 + 15) & ~(size_t)15));  // [RBa+16+BH][HS]
   // weights of a PAIR of distances in one 4-byte entry (two uint16): [min(d0 >> 6, 48)][min(d1 >> 6, 48)] (entry 48 = weight 0)
-#ifdef CPX_NLM_DB
   // double-buffered row sums: the row pass of pair q + 1 and the column pass of pair q run between the same two
   // barriers (one barrier per pair, and waves drift between an LDS-heavy and a VALU-heavy phase)
   uint16_t* const Hh1 = Hh + (size_t)(RBa + 16 + BH) * HS;
   u32* s_lut2 = reinterpret_cast<u32*>(Hh1 + (size_t)(RBa + 16 + BH) * HS);  // [49][49]
-#else
-  u32* s_lut2 = reinterpret_cast<u32*>(Hh + (size_t)(RBa + 16 + BH) * HS);  // [49][49]
-#endif
   const unsigned char* img = a.u8_state + ((size_t)b * 2 + (t & 1)) * P;
   unsigned char* out = a.u8_state + ((size_t)b * 2 + ((t + 1) & 1)) * P;
 
@@ -1723,7 +1570,7 @@ void cpx_nlm_kernel(TrackArgs a, int t) {
     const int cc = bx + coff;
     // (rows past the band's last one feed only outputs that are never stored; the array has BH spare rows for them)
     const uint16_t* hr0 = Hh + (cc & ~1) + __umul24((u32)rbase, (u32)HS);
-    if constexpr (WC == 160 && BH == 10 && NLM_ASM_HV) {  // sixteen rows off one address register (row stride 2 HS = 368 bytes: HS = W + 24 uint16 entries)
+    if constexpr (WC == 160 && BH == 10) {  // sixteen rows off one address register (row stride 2 HS = 368 bytes: HS = W + 24 uint16 entries)
       constexpr int RS = 2 * ((160 + 24 + 7) & ~7);
       const u32 ad = lds_addr(hr0);
       if (coff & 1) {  // the pair straddles two aligned words (bx is even: the parity is the offset's)
@@ -1782,53 +1629,6 @@ void cpx_nlm_kernel(TrackArgs a, int t) {
       const u16x2 ones = {1, 1};
       auto rows = [&](auto podd_c) __attribute__((always_inline)) {
         constexpr bool PODD = decltype(podd_c)::value;
-        if constexpr (WC == 160 && BH == 10 && NLM_ASM_ROWS) {
-          // three phases instead of ten dependent chains: all table addresses (the sliding sums are cheap), then all
-          // LDS reads in flight at once, then the accumulation
-          constexpr int ESC = (160 + 2 * NLM_R + 8 + 7) & ~7;   // row stride of the padded image (bytes)
-          const u32 lut_ad = lds_addr(s_lut2);
-          u32 T0[BH], T1[BH];
-#pragma unroll
-          for (int i = 0; i < BH; ++i) {
-            const u16x2 cap48 = {48, 48};
-            T0[i] = __builtin_amdgcn_udot2(__builtin_elementwise_min(V0 >> 6, cap48), lut_k, lut_ad, false);
-            T1[i] = __builtin_amdgcn_udot2(__builtin_elementwise_min(V1 >> 6, cap48), lut_k, lut_ad, false);
-            if (i + 1 < BH) {
-              V0 = V0 + as_pk(hv0[i + 7]) - as_pk(hv0[i]);
-              V1 = V1 + as_pk(hv1[i + 7]) - as_pk(hv1[i]);
-            }
-          }
-          u32 W0[BH], W1[BH], A0[BH], B0[BH], A1[BH], B1[BH];
-          const u32 pa0 = lds_addr(px0), pa1 = lds_addr(px1);
-          lds_gather5_b32(T0, W0); lds_gather5_b32(T0 + 5, W0 + 5);
-          lds_gather5_b32(T1, W1); lds_gather5_b32(T1 + 5, W1 + 5);
-          lds_read5_u16<ESC, 0>(pa0, A0); lds_read5_u16<ESC, 5 * ESC>(pa0, A0 + 5);
-          lds_read5_u16<ESC, 0>(pa1, B0); lds_read5_u16<ESC, 5 * ESC>(pa1, B0 + 5);
-          if (PODD) {
-            lds_read5_u16<ESC, 2>(pa0, A1); lds_read5_u16<ESC, 5 * ESC + 2>(pa0, A1 + 5);
-            lds_read5_u16<ESC, 2>(pa1, B1); lds_read5_u16<ESC, 5 * ESC + 2>(pa1, B1 + 5);
-            lds_wait5(A1); lds_wait5(A1 + 5); lds_wait5(B1); lds_wait5(B1 + 5);
-          }
-          lds_wait5(W0); lds_wait5(W0 + 5); lds_wait5(W1); lds_wait5(W1 + 5);
-          lds_wait5(A0); lds_wait5(A0 + 5); lds_wait5(B0); lds_wait5(B0 + 5);
-#pragma unroll
-          for (int i = 0; i < BH; ++i) {
-            const u32 WA = __builtin_amdgcn_perm(W1[i], W0[i], 0x05040100u), WB = __builtin_amdgcn_perm(W1[i], W0[i], 0x07060302u);
-            u32 PA, PB;
-            if (PODD) {
-              PA = __builtin_amdgcn_perm(B0[i], A0[i], 0x0c050c01u);
-              PB = __builtin_amdgcn_perm(B1[i], A1[i], 0x0c040c00u);
-            } else {
-              PA = __builtin_amdgcn_perm(B0[i], A0[i], 0x0c040c00u);
-              PB = __builtin_amdgcn_perm(B0[i], A0[i], 0x0c050c01u);
-            }
-            est[2 * i] = (int)__builtin_amdgcn_udot2(as_pk(WA), as_pk(PA), (u32)est[2 * i], false);
-            est[2 * i + 1] = (int)__builtin_amdgcn_udot2(as_pk(WB), as_pk(PB), (u32)est[2 * i + 1], false);
-            wsum[2 * i] = (int)__builtin_amdgcn_udot2(as_pk(WA), ones, (u32)wsum[2 * i], false);
-            wsum[2 * i + 1] = (int)__builtin_amdgcn_udot2(as_pk(WB), ones, (u32)wsum[2 * i + 1], false);
-          }
-          return;
-        }
 #pragma unroll
         for (int i = 0; i < BH; ++i) {
           const u16x2 cap48 = {48, 48};
@@ -1863,36 +1663,13 @@ void cpx_nlm_kernel(TrackArgs a, int t) {
       else rows(std::false_type{});
     }
   };
-#ifdef CPX_NLM_DB
   pass_a(0, Hh);
   __syncthreads();
-#ifdef CPX_NLM_STAGGER   // experiment: half of the waves take the two passes of an interval in the other order
-  const bool b_first = ((tid >> 6) & CPX_NLM_STAGGER) != 0;
-  for (int q = 0; q < 220; ++q) {
-    if (b_first) {
-      pass_b(q, (q & 1) ? Hh1 : Hh);
-      if (q + 1 < 220) pass_a(q + 1, ((q + 1) & 1) ? Hh1 : Hh);
-    } else {
-      if (q + 1 < 220) pass_a(q + 1, ((q + 1) & 1) ? Hh1 : Hh);
-      pass_b(q, (q & 1) ? Hh1 : Hh);
-    }
-    __syncthreads();
-  }
-#else
   for (int q = 0; q < 220; ++q) {
     if (q + 1 < 220) pass_a(q + 1, ((q + 1) & 1) ? Hh1 : Hh);
     pass_b(q, (q & 1) ? Hh1 : Hh);
     __syncthreads();
   }
-#endif
-#else
-  for (int q = 0; q < 220; ++q) {
-    pass_a(q, Hh);
-    __syncthreads();
-    pass_b(q, Hh);
-    __syncthreads();
-  }
-#endif
   if (active_b) {
 #pragma unroll
     for (int i = 0; i < BH; ++i) {
@@ -1913,11 +1690,7 @@ namespace {
 size_t nlm_lds_rows(int W, int rows, int bh) {
   const size_t ES = ((size_t)W + 2 * NLM_R + 8 + 7) & ~(size_t)7;
   const size_t HS = ((size_t)W + 24 + 7) & ~(size_t)7;
-#ifdef CPX_NLM_DB
   const size_t nbuf = 2;
-#else
-  const size_t nbuf = 1;
-#endif
   return ((((size_t)rows + 2 * NLM_R) * ES + 32 + 15) & ~(size_t)15) + nbuf * ((size_t)rows + 16 + bh) * HS * 2 + NLM_LUT2 * NLM_LUT2 * 4 + 64;
 }
 template <int BH, int WC>
@@ -1948,11 +1721,7 @@ void launch_nlm(const TrackArgs& a, int B, int t, hipStream_t s) {
   // enough workgroups to fill the chip: whole frames per workgroup for big batches, bands of a frame for small
   // ones (a single clip is one frame per launch)
   const int nsub = NT_NLM / (a.W / 2);
-#ifdef CPX_NLM_BANDS   // experiment switch: bands per frame for big batches (scratch/build_variant.sh)
-  const int want = (B >= 384) ? CPX_NLM_BANDS : (512 + B - 1) / B;
-#else
   const int want = (B >= 384) ? 1 : (512 + B - 1) / B;  // bands per frame that would give ~2 workgroups per CU
-#endif
   const int rows = (a.H + want - 1) / want;              // rows per band for that
   if (rows > 5 * nsub) launch_nlm_t<10>(a, B, t, s);
   else if (rows > 2 * nsub) launch_nlm_t<5>(a, B, t, s);

@@ -1,8 +1,8 @@
-"""cpx_nlm_kernel issues its LDS reads in inline asm (`lds_read8_b32`, `lds_read5_u16`, `lds_gather5_b32`: many loads off
-one address register) and waits for them in a SEPARATE asm statement (`lds_wait*`), so that the loads of a block are all in
-flight before one wait.  Between the two the compiler believes the destination registers hold their values: a copy, a
-spill or any other instruction it places there would read registers whose data has not landed, and SIInsertWaitcnts does
-not look inside inline asm.  This test compiles csrc/cpx_track.hip to gfx950 assembly (no GPU) and checks the
+"""cpx_nlm_kernel issues its LDS reads in inline asm (`lds_read8_b32`: many loads off one address register) and waits
+for them in a SEPARATE asm statement (`lds_wait8`), so that the loads of a block are all in flight before one wait.
+Between the two the compiler believes the destination registers hold their values: a copy, a spill or any other
+instruction it places there would read registers whose data has not landed, and SIInsertWaitcnts does not look inside
+inline asm.  This test compiles csrc/cpx_track.hip to gfx950 assembly (no GPU) and checks the
 property on the generated code: from an asm block that contains ds_read instructions to the next `s_waitcnt lgkmcnt(0)`,
 no instruction outside asm blocks mentions one of the registers being loaded."""
 import os

@@ -18,7 +18,7 @@ from helpers import crc
 pytestmark = pytest.mark.gpu
 
 H, W, E = 120, 160, 1
-ENV = ("CPX_TRACK_PACKED_STATE", "CPX_TRACK_PER_STEP", "CPX_TRACK_SPLIT_MIN_CLIPS")
+ENV = ("CPX_TRACK_PACKED_STATE", "CPX_TRACK_PER_STEP")
 INFO_FIELDS = ("frame_number", "n_components", "status", "ffc_affected", "avg_change", "norm_min", "norm_max",
                "threshold", "filt_min", "filt_max", "thermal_min", "thermal_max", "thermal_sum", "thermal_median",
                "filtered_abs_sum", "background_average", "background_changed")
@@ -130,11 +130,11 @@ def check_state(got, want, what=""):
     assert avg == float(wavg), ("average", what, avg, wavg)
 
 
-def make_engine(monkeypatch, packed=None, per_step=None, split=None, **kw):
+def make_engine(monkeypatch, packed=None, per_step=None, **kw):
     """A TrackEngine whose handle reads the given launch / state switches (read at cpx_create)."""
     from cpx.engine import TrackEngine
 
-    for name, v in zip(ENV, (packed, per_step, split)):
+    for name, v in zip(ENV, (packed, per_step)):
         if v is None:
             monkeypatch.delenv(name, raising=False)
         else:
@@ -193,7 +193,7 @@ def _flags():
 # 1. packed == two arrays, under every launch form
 # ---------------------------------------------------------------------------------------------------------------------
 FORMS = [("fused", "none"), ("fused", "freeze_ffc"), ("fused", "freeze_bg"), ("fused", "defer"), ("per_step", "none"),
-         ("split", "none"), ("denoise", "none")]
+         ("denoise", "none")]
 
 
 @pytest.mark.parametrize("form,flag", FORMS)
@@ -206,8 +206,7 @@ def test_packed_equals_two_array_state(monkeypatch, form, flag):
     want_filtered = form != "per_step"   # (per step: the workspace layout with the filtered ping-pong inside)
     outs = []
     for packed in (0, 1):
-        eng = make_engine(monkeypatch, packed=packed, per_step=1 if form == "per_step" else None,
-                          split=1 if form == "split" else None, denoise=form == "denoise")
+        eng = make_engine(monkeypatch, packed=packed, per_step=1 if form == "per_step" else None, denoise=form == "denoise")
         dev, offs, meta = batch(clips, eng)
         res = eng.track_batch(dev, offs, meta, want_labels=True, want_filtered=want_filtered, want_background=True,
                               flags=_flags()[flag])
