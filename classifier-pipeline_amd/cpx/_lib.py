@@ -124,7 +124,7 @@ EXPORTS = [
     "cpx_mog2_create", "cpx_mog2_apply", "cpx_mog2_background", "cpx_mog2_destroy",
     "cpx_track_batch_ex", "cpx_track_frame_ex", "cpx_set_background", "cpx_get_background", "cpx_track_limits_batch_ex",
     "cpx_cnn_head_ex", "cpx_ir_delta_variance", "cpx_cptv_inflate", "cpx_cptv_gather_index", "cpx_format_regions", "cpx_json_indent", "cpx_ir_merge", "cpx_ir_resize_area",
-    "cpx_ir_frame_statistics", "cpx_cnn_last_overflow", "cpx_cnn_set_activation_bounds", "cpx_cnn_overflow_forwards",
+    "cpx_ir_frame_statistics", "cpx_cnn_last_overflow", "cpx_cnn_set_activation_bounds", "cpx_cnn_overflow_forwards", "cpx_cnn_forward_taps",
 ]
 
 IR_FRAME_STATS_DTYPE = np.dtype([("min", "<i4"), ("max", "<i4"), ("sum", "<i8"), ("median_x2", "<i4"), ("reserved", "<i4"),
@@ -231,6 +231,8 @@ def load():
     lib.cpx_cnn_destroy.restype = None
     lib.cpx_cnn_forward.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
     lib.cpx_cnn_forward.restype = C.c_int
+    lib.cpx_cnn_forward_taps.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.POINTER(vp), C.c_int, vp]
+    lib.cpx_cnn_forward_taps.restype = C.c_int
     lib.cpx_track_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     lib.cpx_track_frame.restype = C.c_int
     lib.cpx_track_batch_ex.argtypes = [vp, vp, i32p, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int]

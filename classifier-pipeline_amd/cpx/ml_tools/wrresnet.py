@@ -283,19 +283,36 @@ class WRResNetDevice:
         if rc != 0:
             raise CpxError(rc, self.eng._err())
 
-    def forward(self, x, want_probs=True):
-        """x: device float32 [N, S, S, 2] (values 0..255, no input scaling) -> (logits, probs) [N, n_labels]."""
+    def forward(self, x, want_probs=True, taps=False):
+        """x: device float32 [N, H, W, 2] (values 0..255, no input scaling) -> (logits, probs) [N, n_labels].
+        taps=True (cpx_cnn_forward_taps): -> (logits, probs, blocks, overflow), blocks = every residual block's output in
+        launch order (device NHWC float32), overflow = int numpy [3 * BLOCKS], nonzero where an fp16x2 block was rerun."""
         t = self.torch
         N, H, W, cin = x.shape
         assert cin == 2 and x.dtype == t.float32 and x.is_contiguous()
         t.cuda.current_stream(self.eng.device).synchronize()
-        logits = t.empty((N, self.n_labels), dtype=t.float32, device=self.eng.device)
-        probs = t.empty((N, self.n_labels), dtype=t.float32, device=self.eng.device) if want_probs else None
-        rc = self.lib.cpx_cnn_forward(self._cnn, C.c_void_p(x.data_ptr()), N, H, W, C.c_void_p(logits.data_ptr()),
-                                      C.c_void_p(probs.data_ptr()) if probs is not None else None)
+        dev = self.eng.device
+        logits = t.empty((N, self.n_labels), dtype=t.float32, device=dev)
+        probs = t.empty((N, self.n_labels), dtype=t.float32, device=dev) if want_probs else None
+        args = (self._cnn, C.c_void_p(x.data_ptr()), N, H, W, C.c_void_p(logits.data_ptr()),
+                C.c_void_p(probs.data_ptr()) if probs is not None else None)
+        if not taps:
+            rc = self.lib.cpx_cnn_forward(*args)
+        else:
+            blocks, h, w_ = [], H, W
+            for si in range(3):
+                for d in range(BLOCKS):
+                    s = si + 1 if d == 0 else 1
+                    h, w_ = -(-h // s), -(-w_ // s)
+                    blocks.append(t.full((N, h, w_, FILTERS[si + 1]), float("nan"), dtype=t.float32, device=dev))
+            ovf = t.full((len(blocks),), -1, dtype=t.int32, device=dev)
+            ptrs = (C.c_void_p * len(blocks))(*[b.data_ptr() for b in blocks])
+            rc = self.lib.cpx_cnn_forward_taps(*args, ptrs, len(blocks), C.c_void_p(ovf.data_ptr()))
         if rc != 0:
             raise CpxError(rc, self.eng._err())
         self.eng.synchronize()
+        if taps:
+            return logits, probs, blocks, ovf.cpu().numpy()
         return logits, probs
 
     def forward_async(self, x, logits, probs=None):

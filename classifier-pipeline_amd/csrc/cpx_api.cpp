@@ -1538,10 +1538,11 @@ int cpx_cnn_set_activation_bounds(cpx_cnn* cnn, const float* bounds, int n) {
   return CPX_OK;
 }
 
-int cpx_cnn_forward(cpx_cnn* cnn, const float* in_dev, int N, int H, int W, float* logits_dev, float* probs_dev) {
-  if (!cnn) return CPX_ERR_INVALID;
+// cpx_cnn_forward and cpx_cnn_forward_taps: the same launches; with taps != nullptr each residual block's final output is
+// also copied to taps[stage * blocks_per_stage + d] and, when ovf_out != nullptr, the blocks' overflow words to ovf_out
+static int cnn_forward(cpx_cnn* cnn, const float* in_dev, int N, int H, int W, float* logits_dev, float* probs_dev,
+                       float* const* taps, int* ovf_out) {
   cpx_handle* h = cnn->h;
-  if (!in_dev || !logits_dev || N < 1 || H < 1 || W < 1) return fail(h, CPX_ERR_INVALID, "cpx_cnn_forward: bad argument");
   CPX_ENTER(h);
   const cpx_wrresnet_params& p = cnn->p;
   if (h->cnn_math == CPX_CNN_MATH_FP16X2) {  // the blocks' overflow words start clear
@@ -1731,6 +1732,9 @@ int cpx_cnn_forward(cpx_cnn* cnn, const float* in_dev, int N, int H, int W, floa
       }
       if (rc != CPX_OK) return rc;
       cur = act[flip];
+      if (taps)  // (behind the block's guarded rerun launches: what the next block reads)
+        CPX_HIP(h, hipMemcpyAsync(taps[st * p.blocks_per_stage + d], cur, (size_t)N * ho * wo * f * sizeof(float),
+                                  hipMemcpyDeviceToDevice, h->stream));
       hh = ho;
       ww = wo;
       c_in = f;
@@ -1750,6 +1754,13 @@ int cpx_cnn_forward(cpx_cnn* cnn, const float* in_dev, int N, int H, int W, floa
   rc = cpx_cnn_head_ex(h, &hd);
   if (rc == CPX_OK && h->cnn_math == CPX_CNN_MATH_FP16X2)
     cpx::launch_count_overflow(h->cnn_ovf, 3 * p.blocks_per_stage, h->stream);
+  if (rc == CPX_OK && ovf_out) {
+    const size_t bytes = (size_t)3 * p.blocks_per_stage * sizeof(int);
+    if (h->cnn_math == CPX_CNN_MATH_FP16X2)
+      CPX_HIP(h, hipMemcpyAsync(ovf_out, h->cnn_ovf + 2, bytes, hipMemcpyDeviceToDevice, h->stream));
+    else  // (no fp16 launch: no block was rerun)
+      CPX_HIP(h, hipMemsetAsync(ovf_out, 0, bytes, h->stream));
+  }
   if (rc == CPX_OK && h->cnn_math == CPX_CNN_MATH_FP16X2 && std::getenv("CPX_CNN_DEBUG_OVF")) {
     // diagnostic (synchronises): which blocks of this forward left fp16's range
     int words[OVF_WORDS];
@@ -1762,6 +1773,26 @@ int cpx_cnn_forward(cpx_cnn* cnn, const float* in_dev, int N, int H, int W, floa
     }
   }
   return rc;
+}
+
+int cpx_cnn_forward(cpx_cnn* cnn, const float* in_dev, int N, int H, int W, float* logits_dev, float* probs_dev) {
+  if (!cnn) return CPX_ERR_INVALID;
+  if (!in_dev || !logits_dev || N < 1 || H < 1 || W < 1)
+    return fail(cnn->h, CPX_ERR_INVALID, "cpx_cnn_forward: bad argument");
+  return cnn_forward(cnn, in_dev, N, H, W, logits_dev, probs_dev, nullptr, nullptr);
+}
+
+int cpx_cnn_forward_taps(cpx_cnn* cnn, const float* in_dev, int N, int H, int W, float* logits_dev, float* probs_dev,
+                         float* const* block_out_dev, int n_blocks, int* block_overflow_dev) {
+  if (!cnn) return CPX_ERR_INVALID;
+  cpx_handle* h = cnn->h;
+  if (!in_dev || !logits_dev || N < 1 || H < 1 || W < 1 || !block_out_dev)
+    return fail(h, CPX_ERR_INVALID, "cpx_cnn_forward_taps: bad argument");
+  if (n_blocks != 3 * cnn->p.blocks_per_stage)
+    return fail(h, CPX_ERR_INVALID, "cpx_cnn_forward_taps: expected n_blocks = 3 * blocks_per_stage");
+  for (int k = 0; k < n_blocks; ++k)
+    if (!block_out_dev[k]) return fail(h, CPX_ERR_INVALID, "cpx_cnn_forward_taps: null block output");
+  return cnn_forward(cnn, in_dev, N, H, W, logits_dev, probs_dev, block_out_dev, block_overflow_dev);
 }
 
 int cpx_ir_delta_variance(cpx_handle* h, const uint8_t* cur_dev, const uint8_t* prev_dev, int width, int height,

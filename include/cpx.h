@@ -744,6 +744,15 @@ int cpx_cnn_set_activation_bounds(cpx_cnn* cnn, const float* bounds, int n);
 /* in_dev float32 [N, H, W, in_channels] (NHWC, values 0..255) -> logits_dev [N, n_labels] and, when not NULL,
  * probs_dev (sigmoid). */
 int cpx_cnn_forward(cpx_cnn* cnn, const float* in_dev, int N, int H, int W, float* logits_dev, float* probs_dev);
+/* The same forward (the same launches, in the same order) that also hands out what it computes below the logits, for
+ * tests: behind each residual block's last launch -- its guarded rerun included -- a device-to-device copy on the handle's
+ * stream of the block's output into block_out_dev[stage * blocks_per_stage + d], NHWC float32 [N, h, w, filters[stage + 1]]
+ * (h, w: H, W divided by the strides so far, rounded up).  n_blocks must be 3 * blocks_per_stage.  block_overflow_dev
+ * (int [n_blocks], or NULL) receives the blocks' overflow words: nonzero where a block of a CPX_CNN_MATH_FP16X2 forward
+ * left fp16's range and was rerun, zero in the other modes.  conv1 has no tap (fused into the first block, its output
+ * never reaches memory).  Without this call nothing is copied. */
+int cpx_cnn_forward_taps(cpx_cnn* cnn, const float* in_dev, int N, int H, int W, float* logits_dev, float* probs_dev,
+                         float* const* block_out_dev, int n_blocks, int* block_overflow_dev);
 
 /* Per-kernel timing of cpx_conv2d launches with HIP events on the handle's stream (bench.py's roofline).
  * cpx_conv_timing_enable(h, 1) starts collecting (and clears); cpx_conv_timing_report synchronises and
