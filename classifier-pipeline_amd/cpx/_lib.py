@@ -109,7 +109,26 @@ class HeadDesc(C.Structure):  # struct cpx_head_desc
                 ("logits_dev", C.c_void_p), ("probs_dev", C.c_void_p)]
 
 
+class GraphTensor(C.Structure):  # struct cpx_graph_tensor
+    _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("c_offset", C.c_int32), ("c_stride", C.c_int32),
+                ("reserved", C.c_int32), ("arena_offset", C.c_int64)]
+
+
+class GraphOp(C.Structure):  # struct cpx_graph_op
+    _fields_ = [("kind", C.c_int32), ("in0", C.c_int32), ("in1", C.c_int32), ("out", C.c_int32),
+                ("kh", C.c_int32), ("kw", C.c_int32), ("stride_h", C.c_int32), ("stride_w", C.c_int32),
+                ("pad_top", C.c_int32), ("pad_left", C.c_int32), ("pad_bottom", C.c_int32), ("pad_right", C.c_int32),
+                ("activation", C.c_int32), ("out_c_offset", C.c_int32), ("out_c_stride", C.c_int32),
+                ("n_map", C.c_int32), ("channel_map", C.c_int32 * 4), ("param", C.c_float),
+                ("weights", C.c_void_p), ("scale", C.c_void_p), ("shift", C.c_void_p)]
+
+
 assert C.sizeof(WRResNetParams) == 1560
+assert C.sizeof(GraphTensor) == 32 and C.sizeof(GraphOp) == 112
+# enum CPX_GRAPH_* (include/cpx.h)
+GRAPH_CONV, GRAPH_MAX_POOL, GRAPH_AVG_POOL, GRAPH_ADD, GRAPH_AFFINE, GRAPH_MEAN, GRAPH_FC, GRAPH_LOGISTIC, GRAPH_SOFTMAX, \
+    GRAPH_PAD, GRAPH_CHANNEL_MAP = range(1, 12)
+GRAPH_CONV_KC, GRAPH_CONV_CO = 16, 32   # CONV weights: Cin / Cout rounded up to these (csrc/cpx_kernels.h)
 HEAD_SIGMOID, HEAD_SOFTMAX = 0, 1
 
 
@@ -125,6 +144,7 @@ EXPORTS = [
     "cpx_track_batch_ex", "cpx_track_frame_ex", "cpx_set_background", "cpx_get_background", "cpx_track_limits_batch_ex",
     "cpx_cnn_head_ex", "cpx_ir_delta_variance", "cpx_cptv_inflate", "cpx_cptv_gather_index", "cpx_format_regions", "cpx_json_indent", "cpx_ir_merge", "cpx_ir_resize_area",
     "cpx_ir_frame_statistics", "cpx_cnn_last_overflow", "cpx_cnn_set_activation_bounds", "cpx_cnn_overflow_forwards", "cpx_cnn_forward_taps",
+    "cpx_graph_create", "cpx_graph_forward", "cpx_graph_arena_bytes", "cpx_graph_arena_allocated", "cpx_graph_destroy",
 ]
 
 IR_FRAME_STATS_DTYPE = np.dtype([("min", "<i4"), ("max", "<i4"), ("sum", "<i8"), ("median_x2", "<i4"), ("reserved", "<i4"),
@@ -229,6 +249,17 @@ def load():
     lib.cpx_cnn_create.restype = C.c_int
     lib.cpx_cnn_destroy.argtypes = [vp]
     lib.cpx_cnn_destroy.restype = None
+    lib.cpx_graph_create.argtypes = [vp, C.POINTER(GraphOp), C.c_int, C.POINTER(GraphTensor), C.c_int, C.c_int, C.c_int,
+                                     C.POINTER(vp)]
+    lib.cpx_graph_create.restype = C.c_int
+    lib.cpx_graph_forward.argtypes = [vp, vp, C.c_int, vp]
+    lib.cpx_graph_forward.restype = C.c_int
+    lib.cpx_graph_arena_bytes.argtypes = [vp, C.c_int, C.POINTER(C.c_size_t)]
+    lib.cpx_graph_arena_bytes.restype = C.c_int
+    lib.cpx_graph_arena_allocated.argtypes = [vp, C.POINTER(C.c_size_t)]
+    lib.cpx_graph_arena_allocated.restype = C.c_int
+    lib.cpx_graph_destroy.argtypes = [vp]
+    lib.cpx_graph_destroy.restype = None
     lib.cpx_cnn_forward.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
     lib.cpx_cnn_forward.restype = C.c_int
     lib.cpx_cnn_forward_taps.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.POINTER(vp), C.c_int, vp]

@@ -351,11 +351,121 @@ class WRResNetInterpreter(Interpreter):
         return probs.cpu().numpy()
 
 
+class LiteInterpreter(Interpreter):
+    """Any float32 `.tflite` graph of the operator set cpx/ml_tools/tflite_reader.py reads (the reference's inceptionv3
+    family, ml_tools/kerasmodel.py:171-180,259-350) on the device graph executor (cpx_graph_*): the reference's
+    LiteInterpreter (interpreter.py:520-560) with the TFLite runtime replaced.  model = <name>.tflite + <name>.json.
+    predict runs the whole batch in one forward (the reference loops sample by sample because its runtime must)."""
+
+    TYPE = "TFLite"
+
+    def __init__(self, model_file, run_over_network=False, load_model=True, engine=None):
+        super().__init__(model_file, run_over_network)
+        self._engine = engine
+        self._graph = None
+        self._plans = {}
+        self._devices = {}
+        if load_model and not self.run_over_network:
+            self.load_model()
+
+    def load_model(self):
+        from .tflite_graph import build_plan
+        from .tflite_reader import Graph
+
+        logging.info("Reading TFLite graph %s", self.model_file)
+        with open(str(self.model_file), "rb") as fh:
+            self._graph = Graph(fh.read())
+        plan = build_plan(self._graph)   # refuses, by operator, what the executor does not run
+        self._plans[(plan.graph_input_shape, None)] = plan
+        if plan.output_shape[:2] != (1, 1) or plan.output_shape[2] != len(self.labels):
+            raise ValueError("model output %s but %d labels" % (plan.output_shape, len(self.labels)))
+
+    def shape(self):
+        """interpreter.py:557-559: (number of inputs, the input tensor's shape as the file states it)."""
+        if self._graph is None:
+            return 1, (None,) + tuple(self.params.output_dim)
+        return 1, tuple(self._graph.tensors[self._graph.inputs[0]]["shape"])
+
+    def channel_map(self):
+        """The graph's input channels as indices into the [thermal, filtered] sample the crop kernel writes; the
+        reference repeats a channel it has built to fill three (ml_tools/preprocess.py:169-189)."""
+        channels = [str(getattr(c, "name", c)) for c in self.params.channels]
+        if not channels or len(channels) > 4 or any(c not in ("thermal", "filtered") for c in channels):
+            raise NotImplementedError("channels %s: the crop kernel builds thermal and filtered; a graph's input takes up to "
+                                      "four of them, in any order, repeated" % (channels,))
+        return [0 if c == "thermal" else 1 for c in channels]
+
+    def limits_flags(self, single=False):
+        from .._lib import LIMITS_ALWAYS_CLIP, LIMITS_NO_DIFF_NORM, LIMITS_TF_SCALING, LIMITS_THERMAL_DIFF_NORM
+
+        self.channel_map()   # the sample stays [thermal, filtered]; the graph's channel map orders and repeats them
+        flags = 0
+        if self.params.thermal_diff_norm:
+            flags |= LIMITS_THERMAL_DIFF_NORM
+        if not self.params.diff_norm:
+            flags |= LIMITS_NO_DIFF_NORM
+        if single:
+            flags |= LIMITS_ALWAYS_CLIP
+        if self.preprocess_fn is not None:
+            flags |= LIMITS_TF_SCALING
+        return flags
+
+    def _device(self, engine, hwc):
+        """One device graph per engine and input shape; hwc: the sample as it arrives."""
+        from .tflite_graph import GraphDevice, build_plan
+
+        cin = self._plans[next(iter(self._plans))].graph_input_shape[2]
+        cmap = None
+        if hwc[2] != cin or (hwc[2] == 2 and self.channel_map() != [0, 1]):
+            cmap = self.channel_map()
+            if hwc[2] != 2 or len(cmap) != cin:
+                raise ValueError("samples of %d channels, channels %s, for a graph of %d input channels"
+                                 % (hwc[2], list(self.params.channels), cin))
+        key = ((hwc[0], hwc[1], cin), None if cmap is None else tuple(cmap))
+        plan = self._plans.get(key)
+        if plan is None:
+            plan = self._plans[key] = build_plan(self._graph, input_shape=key[0], channel_map=cmap)
+        dev = self._devices.get((id(engine), key))
+        if dev is None or dev.eng is not engine or not engine.h:
+            dev = self._devices[(id(engine), key)] = GraphDevice(engine, plan)
+        return dev
+
+    def predict(self, frames):
+        """frames: device tensor (from preprocess_segments) or host float32 [N, H, W, C] -> numpy [N, n_labels]."""
+        import torch
+
+        from ..track.cliptrackextractor import default_engine
+
+        if self.run_over_network:
+            host = frames.cpu().numpy() if isinstance(frames, torch.Tensor) else np.asarray(frames, dtype=np.float32)
+            return self.predict_over_network(host)
+        if self._graph is None:
+            self.load_model()
+        if isinstance(frames, torch.Tensor) and frames.is_cuda:
+            engine = self._engine or default_engine(frames.device.index or 0)
+            x = frames
+        else:
+            engine = self._engine or default_engine(0)
+            x = torch.from_numpy(np.array(frames, dtype=np.float32, copy=True)).to(engine.device)
+        x = x.contiguous()
+        return self._device(engine, tuple(int(v) for v in x.shape[1:])).forward(x).cpu().numpy()
+
+
 def inc3_preprocess(x):
     """interpreter.py:563-566 (= tf.keras.applications' 'tf' mode), in place on a float32 array."""
     x /= 127.5
     x -= 1.0
     return x
+
+
+def _sidecar_model_name(model_file):
+    try:
+        with open(Path(model_file).with_suffix(".json"), "r") as fh:
+            hp = HyperParams()
+            hp.update(json.load(fh).get("hyperparams", {}))
+            return hp.model_name
+    except OSError:
+        return "wr-resnet"   # no sidecar: the WR-ResNet route reports it
 
 
 def get_interpreter(model, run_over_network=False, load_model=True, seed=None):
@@ -367,11 +477,15 @@ def get_interpreter(model, run_over_network=False, load_model=True, seed=None):
         raise NotImplementedError(
             "%s: convert the Keras model once with `python tools/keras_to_npz.py %s <name>` (runs where TensorFlow is "
             "installed) and pass <name>.npz; a released .tflite model is read directly" % (model.model_file, model.model_file))
-    if model.type not in (None, WRResNetInterpreter.TYPE, "tflite", "keras") or suffix not in (".npz", ".json", "", ".tflite"):
+    if model.type not in (None, WRResNetInterpreter.TYPE, "tflite", "keras", LiteInterpreter.TYPE) or suffix not in (".npz", ".json", "", ".tflite"):
         raise NotImplementedError(
             "model type %r (%s): cpx runs WR-ResNet models as <name>.npz + <name>.json or as a released <name>.tflite "
             "(TensorFlow / RandomForest runtimes are not part of this build)" % (model.type, model.model_file))
-    classifier = WRResNetInterpreter(model.model_file, run_over_network, load_model)
+    if suffix == ".tflite" and not run_over_network and _sidecar_model_name(model.model_file) != "wr-resnet":
+        # the reference's route for every .tflite (interpreter.py:597-628): the graph executor takes the file as it is
+        classifier = LiteInterpreter(model.model_file, run_over_network, load_model)
+    else:
+        classifier = WRResNetInterpreter(model.model_file, run_over_network, load_model)
     classifier.id = model.id
     classifier.port = model.port
     if seed is not None:

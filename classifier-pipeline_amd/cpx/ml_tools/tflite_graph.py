@@ -1,0 +1,505 @@
+"""A float32 TFLite graph (cpx/ml_tools/tflite_reader.py: Graph) turned into a plan the device executor runs
+(cpx_graph_create / cpx_graph_forward, include/cpx.h) -- what the reference's LiteInterpreter hands to the TFLite runtime
+(src/ml_tools/interpreter.py:520-560).  build_plan is host work and needs no GPU:
+
+* shapes are inferred operator by operator for a given [H, W, C] input with TensorFlow's SAME / VALID arithmetic (SAME's
+  surplus padding goes bottom and right);
+* MUL / ADD / SUB by a per-channel constant behind a convolution (or behind another such operator) that nothing else
+  reads are folded into its scale and shift; elsewhere they are one element-wise AFFINE operator;
+* a CONCATENATION along the channels runs no kernel: every producer of one of its inputs writes straight into its channel
+  slice of the concatenated tensor (channel offset + row stride).  Only an input that cannot be placed -- it feeds two
+  concatenations, it is the graph's input, it is a view of another tensor -- is copied (a COPY entry: an AFFINE operator
+  without constants);
+* tensors get offsets in one arena by lifetime (first write to last read, in operator order); the offsets are per
+  sample, the arena of a forward over N samples is N times as large;
+* CONV_2D filters are transposed from TFLite's OHWI to the kernel's [tap][Cin][Cout], Cin padded to 16 and Cout to 32.
+
+GraphDevice uploads a plan's constants to an engine's device and runs it."""
+import ctypes as C
+
+import numpy as np
+
+from .. import _lib
+from .tflite_reader import ACT_NONE, ACT_RELU, ACT_RELU6, PADDING_SAME
+
+ALIGN = 64   # floats: every tensor of the arena starts on a 256-byte boundary
+
+
+class PlanOp:
+    def __init__(self, kind, name, in0, out, in1=-1, **kw):
+        self.kind, self.name, self.in0, self.in1, self.out = kind, name, in0, in1, out
+        self.kh = self.kw = self.stride_h = self.stride_w = 1
+        self.pads = (0, 0, 0, 0)   # top, left, bottom, right
+        self.act = ACT_NONE
+        self.param = 0.0
+        self.channel_map = None
+        self.weights = self.scale = self.shift = None   # numpy float32, host
+        self.copy = False
+        self.source = None   # index of the flatbuffer's operator
+        self.__dict__.update(kw)
+
+
+class PlanTensor:
+    def __init__(self, tid, H, W, C):
+        self.id, self.H, self.W, self.C = tid, H, W, C
+        self.root = tid       # the tensor whose storage this one lives in
+        self.c_offset = 0
+        self.c_stride = C
+        self.arena_offset = -1
+        self.alias = False    # a RESHAPE's view of its input
+
+
+class Plan:
+    """ops: [PlanOp] in launch order; tensors: {flatbuffer tensor id: PlanTensor}; input / output: tensor ids;
+    arena_floats: per sample."""
+
+    def __init__(self):
+        self.ops, self.tensors = [], {}
+        self.input = self.output = -1
+        self.input_shape = self.output_shape = None
+        self.arena_floats = 0
+        self.lifetimes = {}   # root tensor id -> (first op, last op) of the plan
+
+    @property
+    def arena_bytes_per_sample(self):
+        return 4 * self.arena_floats
+
+    def copies(self):
+        return [o for o in self.ops if o.copy]
+
+    def census(self):
+        out = {}
+        for o in self.ops:
+            out[o.name] = out.get(o.name, 0) + 1
+        return out
+
+
+def same_pads(size, k, s):
+    out = -(-size // s)
+    total = max((out - 1) * s + k - size, 0)
+    return out, total // 2, total - total // 2
+
+
+def window(size, k, s, padding):
+    if padding == PADDING_SAME:
+        return same_pads(size, k, s)
+    return (size - k) // s + 1, 0, 0
+
+
+def _channel_const(g, tid, channels, what):
+    c = g.const(tid)
+    v = np.asarray(c, np.float32).reshape(-1)
+    if v.size == 1:
+        v = np.full(channels, v[0], np.float32)
+    if v.size != channels or (c.ndim > 1 and c.shape[-1] != v.size and c.size != 1):
+        raise NotImplementedError("%s: a constant of shape %s against %d channels" % (what, list(c.shape), channels))
+    return v.astype(np.float32)
+
+
+def build_plan(g, input_shape=None, output=None, channel_map=None):
+    """g: tflite_reader.Graph.  input_shape: (H, W, C) of a sample, default: the flatbuffer's.  output: the tensor the
+    forward hands out, default the graph's output; the operators it does not need are dropped.  channel_map: up to 4
+    indices into the channels of the sample the CALLER brings ([N, H, W, max(map) + 1 or more]): the graph's input
+    channel c is the caller's channel channel_map[c]."""
+    g.check_executable()
+    if len(g.inputs) != 1 or len(g.outputs) < 1:
+        raise NotImplementedError("graphs with %d inputs" % len(g.inputs))
+    gin = g.inputs[0]
+    gout = g.outputs[0] if output is None else int(output)
+    if input_shape is None:
+        input_shape = tuple(g.tensors[gin]["shape"][1:])
+    if len(input_shape) != 3 or min(input_shape) < 1:
+        raise NotImplementedError("operator 0: the input has the dynamic shape %s: pass input_shape" % (list(input_shape),))
+    plan = Plan()
+    T = plan.tensors
+    T[gin] = PlanTensor(gin, *[int(v) for v in input_shape])
+    producer = {}     # tensor id -> PlanOp that writes it
+    consumers = {}
+    for i, op in enumerate(g.ops):
+        for t in op["inputs"]:
+            if t >= 0 and g.const(t) is None:
+                consumers.setdefault(t, []).append(i)
+    ops = []
+
+    def emit(o, src):
+        o.source = src
+        ops.append(o)
+        producer[o.out] = o
+        return o
+
+    for i, op in enumerate(g.ops):
+        name = op["name"]
+        what = "operator %d (%s)" % (i, name)
+        ins = [t for t in op["inputs"] if t >= 0]
+        act_ins = [t for t in ins if g.const(t) is None]
+        for t in act_ins:
+            if t not in T:
+                raise NotImplementedError("%s reads tensor %d, which no earlier operator wrote" % (what, t))
+        y = op["outputs"][0]
+        x = T[act_ins[0]] if act_ins else None
+        if op.get("act", 0) not in (ACT_NONE, ACT_RELU, ACT_RELU6):
+            raise NotImplementedError("%s: fused activation %d" % (what, op["act"]))
+        if name == "CONV_2D":
+            w = g.const(ins[1])
+            co, kh, kw, ci = w.shape
+            if ci != x.C:
+                raise NotImplementedError("%s: grouped convolution (filter depth %d, input depth %d)" % (what, ci, x.C))
+            sh, sw = op.get("stride_h", 1), op.get("stride_w", 1)
+            if not (1 <= kh <= 7 and 1 <= kw <= 7 and sh in (1, 2) and sw in (1, 2)):
+                raise NotImplementedError("%s: %d x %d kernel with strides %d, %d" % (what, kh, kw, sh, sw))
+            ho, pt, pb = window(x.H, kh, sh, op.get("padding", 0))
+            wo, pl, pr = window(x.W, kw, sw, op.get("padding", 0))
+            if ho < 1 or wo < 1:
+                raise NotImplementedError("%s: the %d x %d input is smaller than the kernel" % (what, x.H, x.W))
+            T[y] = PlanTensor(y, ho, wo, co)
+            bias = g.const(ins[2]) if len(ins) > 2 else None
+            emit(PlanOp(_lib.GRAPH_CONV, name, x.id, y, kh=kh, kw=kw, stride_h=sh, stride_w=sw, pads=(pt, pl, pb, pr),
+                        act=op.get("act", 0), filter=w, scale=None,
+                        shift=np.zeros(co, np.float32) if bias is None else np.asarray(bias, np.float32).reshape(-1)), i)
+        elif name in ("MAX_POOL_2D", "AVERAGE_POOL_2D"):
+            kh, kw = op["filter_height"], op["filter_width"]
+            sh, sw = op["stride_h"], op["stride_w"]
+            if not (1 <= kh <= 7 and 1 <= kw <= 7 and 1 <= sh <= 7 and 1 <= sw <= 7):
+                raise NotImplementedError("%s: %d x %d window with strides %d, %d" % (what, kh, kw, sh, sw))
+            ho, pt, pb = window(x.H, kh, sh, op["padding"])
+            wo, pl, pr = window(x.W, kw, sw, op["padding"])
+            if ho < 1 or wo < 1:
+                raise NotImplementedError("%s: the %d x %d input is smaller than the window" % (what, x.H, x.W))
+            T[y] = PlanTensor(y, ho, wo, x.C)
+            emit(PlanOp(_lib.GRAPH_MAX_POOL if name[0] == "M" else _lib.GRAPH_AVG_POOL, name, x.id, y, kh=kh, kw=kw,
+                        stride_h=sh, stride_w=sw, pads=(pt, pl, pb, pr), act=op["act"]), i)
+        elif name in ("ADD", "SUB", "MUL"):
+            if len(act_ins) == 2:
+                b = T[act_ins[1]]
+                if name == "MUL" or (x.H, x.W, x.C) != (b.H, b.W, b.C):
+                    raise NotImplementedError("%s of two tensors of shapes %s, %s" % (what, (x.H, x.W, x.C), (b.H, b.W, b.C)))
+                T[y] = PlanTensor(y, x.H, x.W, x.C)
+                emit(PlanOp(_lib.GRAPH_ADD, name, x.id, y, in1=b.id, act=op["act"], param=1.0 if name == "ADD" else -1.0), i)
+            else:
+                cid = next(t for t in ins if g.const(t) is not None)
+                c = _channel_const(g, cid, x.C, what)
+                one, zero = np.ones(x.C, np.float32), np.zeros(x.C, np.float32)
+                if name == "MUL":
+                    sc, sf = c, zero
+                elif name == "ADD":
+                    sc, sf = one, c
+                elif ins[0] == cid:    # c - x
+                    sc, sf = -one, c
+                else:
+                    sc, sf = one, -c
+                T[y] = PlanTensor(y, x.H, x.W, x.C)
+                p = producer.get(x.id)
+                if p is not None and p.kind in (_lib.GRAPH_CONV, _lib.GRAPH_AFFINE) and p.act == ACT_NONE and not p.copy \
+                        and len(consumers.get(x.id, [])) == 1 and x.id != gout:
+                    # fold: (v * s0 + h0) * sc + sf; the producer now writes this operator's output
+                    s0 = one if p.scale is None else p.scale
+                    h0 = zero if p.shift is None else p.shift
+                    p.scale, p.shift, p.act = (s0 * sc).astype(np.float32), (h0 * sc + sf).astype(np.float32), op["act"]
+                    p.out = y
+                    p.name = p.name + "+" + name
+                    producer[y] = p
+                    del T[x.id]
+                else:
+                    emit(PlanOp(_lib.GRAPH_AFFINE, name, x.id, y, scale=sc, shift=sf, act=op["act"]), i)
+        elif name in ("RELU", "RELU6"):
+            T[y] = PlanTensor(y, x.H, x.W, x.C)
+            emit(PlanOp(_lib.GRAPH_AFFINE, name, x.id, y, act=ACT_RELU if name == "RELU" else ACT_RELU6), i)
+        elif name == "CONCATENATION":
+            rank = len(g.tensors[act_ins[0]]["shape"]) or 4
+            axis = op.get("axis", 0)
+            if axis not in (-1, rank - 1) or len(act_ins) != len(ins):
+                raise NotImplementedError("%s along axis %d: only the channel axis of activations is concatenated" % (what, axis))
+            parts = [T[t] for t in act_ins]
+            if any((p.H, p.W) != (x.H, x.W) for p in parts):
+                raise NotImplementedError("%s of different spatial sizes" % what)
+            T[y] = PlanTensor(y, x.H, x.W, sum(p.C for p in parts))
+            off = 0
+            seen = set()
+            for p in parts:
+                must_copy = p.root != p.id or p.alias or p.id in seen or p.id == gin or p.id == gout or \
+                    any(T[t].alias and T[t].root == p.id for t in T)
+                if must_copy:
+                    # a slice of the output that an AFFINE operator without constants fills
+                    s = PlanTensor((y, off), x.H, x.W, p.C)
+                    s.root, s.c_offset = y, off
+                    T[s.id] = s
+                    o = emit(PlanOp(_lib.GRAPH_AFFINE, "COPY", p.id, s.id, copy=True), i)
+                    producer.pop(s.id, None)
+                    o.out = s.id
+                else:
+                    p.root, p.c_offset = y, off
+                seen.add(p.id)
+                off += p.C
+            if op.get("act", 0) != ACT_NONE:
+                emit(PlanOp(_lib.GRAPH_AFFINE, "CONCATENATION_ACT", y, y, act=op["act"]), i)
+        elif name == "MEAN":
+            axes = sorted(a % 4 for a in op["axes"])
+            if axes != [1, 2]:
+                raise NotImplementedError("%s over axes %s: only H and W (global average pooling)" % (what, op["axes"]))
+            T[y] = PlanTensor(y, 1, 1, x.C)
+            emit(PlanOp(_lib.GRAPH_MEAN, name, x.id, y), i)
+        elif name == "FULLY_CONNECTED":
+            w = g.const(ins[1])
+            if w is None or x.H != 1 or x.W != 1 or w.shape[1] != x.C:
+                raise NotImplementedError("%s: weights %s on a %d x %d x %d input" % (what, None if w is None else list(w.shape), x.H, x.W, x.C))
+            bias = g.const(ins[2]) if len(ins) > 2 else None
+            T[y] = PlanTensor(y, 1, 1, w.shape[0])
+            emit(PlanOp(_lib.GRAPH_FC, name, x.id, y, act=op["act"], weights=np.ascontiguousarray(w, np.float32),
+                        shift=None if bias is None else np.asarray(bias, np.float32).reshape(-1)), i)
+        elif name in ("LOGISTIC", "SOFTMAX"):
+            T[y] = PlanTensor(y, x.H, x.W, x.C)
+            emit(PlanOp(_lib.GRAPH_LOGISTIC if name == "LOGISTIC" else _lib.GRAPH_SOFTMAX, name, x.id, y,
+                        param=float(op.get("beta", 1.0))), i)
+        elif name == "PAD":
+            pd = op["paddings"]
+            if len(pd) != 4 or pd[0] != [0, 0] or pd[3] != [0, 0] or min(min(p) for p in pd) < 0:
+                raise NotImplementedError("%s with paddings %s: only H and W are padded" % (what, pd))
+            T[y] = PlanTensor(y, x.H + pd[1][0] + pd[1][1], x.W + pd[2][0] + pd[2][1], x.C)
+            emit(PlanOp(_lib.GRAPH_PAD, name, x.id, y, pads=(pd[1][0], pd[2][0], pd[1][1], pd[2][1])), i)
+        elif name == "RESHAPE":
+            shp = g.const(ins[1]) if len(ins) > 1 else None
+            shp = [int(v) for v in (shp.reshape(-1) if shp is not None else (op.get("new_shape") or g.tensors[y]["shape"]))]
+            dims = shp[1:]
+            n_el = x.H * x.W * x.C
+            if -1 in dims:
+                known = int(np.prod([d for d in dims if d != -1])) if len(dims) > 1 else 1
+                dims[dims.index(-1)] = n_el // max(known, 1)
+            if len(dims) not in (1, 3) or int(np.prod(dims)) != n_el or min(dims) < 1:
+                raise NotImplementedError("%s to shape %s from %d x %d x %d" % (what, shp, x.H, x.W, x.C))
+            hwc = (1, 1, dims[0]) if len(dims) == 1 else tuple(dims)
+            v = PlanTensor(y, *hwc)
+            v.root, v.alias = x.id, True
+            v.src_shape = (x.H, x.W, x.C)
+            T[y] = v
+            producer[y] = producer.get(x.id)
+        else:
+            raise NotImplementedError("%s is not run by the graph executor" % what)
+
+    if gout not in T:
+        raise NotImplementedError("tensor %d is not an activation of the graph" % gout)
+
+    # ---- views: follow the chains (a concatenation inside a concatenation; a reshape of a tensor) to the storage ----
+    def resolve(t):
+        off = 0
+        r = t
+        while r.root != r.id:
+            if r.alias:
+                # a view with another shape needs the storage to be dense in its own right
+                parent = T[r.root]
+                if parent.root != parent.id and not parent.alias:
+                    raise NotImplementedError("RESHAPE of tensor %s, which lives inside a concatenation" % (parent.id,))
+            off += r.c_offset
+            r = T[r.root]
+        return r, off
+
+    for t in list(T.values()):
+        r, off = resolve(t)
+        t.storage = r.id
+        if t.alias:
+            if off != 0:
+                raise NotImplementedError("RESHAPE of a channel slice")
+            t.c_offset, t.c_stride = 0, t.C
+        else:
+            t.c_offset, t.c_stride = off, r.C
+    for t in T.values():
+        if t.alias and T[t.storage].H * T[t.storage].W * T[t.storage].C != t.H * t.W * t.C:
+            raise NotImplementedError("RESHAPE changes the element count")
+
+    # ---- the input: as the caller brings it, or through the channel map ----
+    if channel_map is not None:
+        cmap = [int(c) for c in channel_map]
+        if len(cmap) != T[gin].C or not 1 <= len(cmap) <= 4 or min(cmap) < 0:
+            raise ValueError("channel map %s for a graph of %d input channels" % (cmap, T[gin].C))
+        ext = PlanTensor("input", T[gin].H, T[gin].W, max(max(cmap) + 1, 2))
+        ext.storage = ext.id
+        T[ext.id] = ext
+        o = PlanOp(_lib.GRAPH_CHANNEL_MAP, "CHANNEL_MAP", ext.id, gin, channel_map=cmap)
+        o.source = -1
+        ops.insert(0, o)
+        plan.input = ext.id
+    else:
+        plan.input = gin
+    plan.output = gout
+    if T[gout].storage != gout and not T[gout].alias:
+        raise NotImplementedError("the output tensor %d lives inside a concatenation" % gout)
+    out_storage = T[gout].storage
+    if T[plan.input].storage != plan.input:
+        raise NotImplementedError("the input tensor lives inside another tensor")
+
+    # ---- drop what the output does not need ----
+    needed = {out_storage}
+    kept = []
+    for o in reversed(ops):
+        if T[o.out].storage in needed:
+            kept.append(o)
+            needed.add(T[o.in0].storage)
+            if o.in1 != -1:
+                needed.add(T[o.in1].storage)
+    ops = kept[::-1]
+    used = set()
+    for o in ops:
+        used.update((o.in0, o.out) + ((o.in1,) if o.in1 != -1 else ()))
+    if plan.input not in used:
+        raise NotImplementedError("the output does not depend on the input")
+    plan.ops = ops
+    live = set(T[k].storage for k in used)
+    plan.tensors = {k: t for k, t in T.items() if t.storage in live}
+    for k, t in plan.tensors.items():
+        # the native graph knows ONE tensor as its input and one as its output: no second view of either
+        if (t.storage == plan.input and k != plan.input) or (t.storage == out_storage and k != gout):
+            raise NotImplementedError("tensor %s is a view of the graph's input or output" % (k,))
+
+    # ---- arena: storage lifetimes in operator order, greedy by size ----
+    life = {}
+    for k, o in enumerate(ops):
+        for tid in (o.in0, o.in1, o.out):
+            if tid == -1:
+                continue
+            s = T[tid].storage
+            a, b = life.get(s, (k, k))
+            life[s] = (min(a, k), max(b, k))
+    plan.lifetimes = life
+    external = {plan.input, out_storage}
+    sizes = {s: -(-(T[s].H * T[s].W * T[s].C) // ALIGN) * ALIGN for s in life if s not in external}
+    placed = []   # (offset, size, first, last)
+    offsets = {}
+    for s in sorted(sizes, key=lambda k: (-sizes[k], life[k][0])):
+        a, b = life[s]
+        busy = sorted((o, z) for o, z, fa, fb in placed if not (fb < a or b < fa))
+        off = 0
+        for o, z in busy:
+            if off + sizes[s] <= o:
+                break
+            off = max(off, o + z)
+        offsets[s] = off
+        placed.append((off, sizes[s], a, b))
+    plan.arena_floats = max([offsets[k] + T[k].H * T[k].W * T[k].C for k in offsets] or [0])   # (the last tensor unpadded)
+    for t in plan.tensors.values():
+        t.arena_offset = offsets.get(t.storage, 0)
+        t.external = t.storage in external
+    plan.out_storage = out_storage
+    plan.input_shape = (T[plan.input].H, T[plan.input].W, T[plan.input].C)
+    plan.graph_input_shape = (T[gin].H, T[gin].W, T[gin].C)
+    plan.output_shape = (T[gout].H, T[gout].W, T[gout].C)
+
+    # ---- weights in the kernel's layout ----
+    for o in ops:
+        if o.kind == _lib.GRAPH_CONV:
+            o.weights = pack_conv_filter(o.filter)
+    return plan
+
+
+def pack_conv_filter(w_ohwi):
+    """TFLite OHWI [Cout, kh, kw, Cin] -> [kh * kw][Cin rounded up to 16][Cout rounded up to 32], zeros beyond."""
+    co, kh, kw, ci = w_ohwi.shape
+    cip = -(-ci // _lib.GRAPH_CONV_KC) * _lib.GRAPH_CONV_KC
+    cop = -(-co // _lib.GRAPH_CONV_CO) * _lib.GRAPH_CONV_CO
+    out = np.zeros((kh * kw, cip, cop), np.float32)
+    out[:, :ci, :co] = np.transpose(np.asarray(w_ohwi, np.float32), (1, 2, 3, 0)).reshape(kh * kw, ci, co)
+    return out
+
+
+def load_plan(path, input_shape=None, channel_map=None):
+    from .tflite_reader import Graph
+
+    with open(str(path), "rb") as fh:
+        g = Graph(fh.read())
+    return g, build_plan(g, input_shape=input_shape, channel_map=channel_map)
+
+
+class GraphDevice:
+    """A plan resident on one engine's GPU: constants uploaded once, one native graph (cpx_graph_create) on the
+    engine's handle; forward() is one cpx_graph_forward call = one launch per planned operator on the engine's stream."""
+
+    def __init__(self, engine, plan, out_slice=None):
+        """out_slice = (c_offset, c_stride): the output goes into that channel slice of the caller's [N, H, W, c_stride]
+        buffer (forward's `out`), whose other channels are left alone."""
+        self.eng, self.lib, self.torch, self.plan = engine, engine.lib, engine.torch, plan
+        self.out_slice = out_slice
+        t = self.torch
+        self._const = []   # device tensors the native graph points into
+
+        def up(a):
+            if a is None:
+                return None
+            d = t.from_numpy(np.array(a, dtype=np.float32, order="C")).to(engine.device)
+            self._const.append(d)
+            return d.data_ptr()
+
+        ids = {tid: k for k, tid in enumerate(plan.tensors)}
+        tens = (_lib.GraphTensor * len(ids))()
+        for tid, k in ids.items():
+            p = plan.tensors[tid]
+            tens[k].H, tens[k].W, tens[k].C = p.H, p.W, p.C
+            tens[k].c_offset, tens[k].c_stride, tens[k].arena_offset = p.c_offset, p.c_stride, p.arena_offset
+            if out_slice is not None and tid == plan.output:
+                tens[k].c_offset, tens[k].c_stride = out_slice
+        out_id = plan.output
+        ops = (_lib.GraphOp * len(plan.ops))()
+        for k, o in enumerate(plan.ops):
+            n = ops[k]
+            n.kind, n.in0, n.in1, n.out = o.kind, ids[o.in0], (ids[o.in1] if o.in1 != -1 else -1), ids[o.out]
+            n.kh, n.kw, n.stride_h, n.stride_w = o.kh, o.kw, o.stride_h, o.stride_w
+            n.pad_top, n.pad_left, n.pad_bottom, n.pad_right = o.pads
+            n.activation = o.act
+            n.out_c_offset, n.out_c_stride = tens[ids[o.out]].c_offset, tens[ids[o.out]].c_stride
+            n.param = o.param
+            if o.channel_map is not None:
+                n.n_map = len(o.channel_map)
+                for c, v in enumerate(o.channel_map):
+                    n.channel_map[c] = v
+            n.weights, n.scale, n.shift = up(o.weights), up(o.scale), up(o.shift)
+        self._graph = C.c_void_p()
+        rc = self.lib.cpx_graph_create(engine.h, ops, len(plan.ops), tens, len(ids), ids[plan.input], ids[out_id],
+                                       C.byref(self._graph))
+        if rc != 0:
+            self._graph = None
+            raise _lib.CpxError(rc, engine._err())
+
+    def arena_bytes(self, N):
+        v = C.c_size_t()
+        rc = self.lib.cpx_graph_arena_bytes(self._graph, int(N), C.byref(v))
+        if rc != 0:
+            raise _lib.CpxError(rc, self.eng._err())
+        return int(v.value)
+
+    def arena_allocated(self):
+        v = C.c_size_t()
+        self.lib.cpx_graph_arena_allocated(self.eng.h, C.byref(v))
+        return int(v.value)
+
+    def forward(self, x, out=None):
+        """x: device float32 [N, H, W, C] of plan.input_shape -> device float32 [N, C_out] (or [N, H, W, C_out])."""
+        t = self.torch
+        H, W, Cin = self.plan.input_shape
+        assert x.dtype == t.float32 and x.is_contiguous() and tuple(x.shape[1:]) == (H, W, Cin), (tuple(x.shape), self.plan.input_shape)
+        N = int(x.shape[0])
+        t.cuda.current_stream(self.eng.device).synchronize()
+        oh, ow, oc = self.plan.output_shape
+        if self.out_slice is not None:
+            assert out is not None and out.is_contiguous() and tuple(out.shape) == (N, oh, ow, self.out_slice[1])
+        if out is None:
+            out = t.empty((N, oc) if (oh, ow) == (1, 1) else (N, oh, ow, oc), dtype=t.float32, device=self.eng.device)
+        for attempt in range(2):
+            rc = self.lib.cpx_graph_forward(self._graph, C.c_void_p(x.data_ptr()), N, C.c_void_p(out.data_ptr()))
+            if rc == -6 and attempt == 0:   # CPX_ERR_NOMEM: the arena is a plain hipMalloc; torch's cache is invisible to it
+                self.eng.synchronize()
+                t.cuda.empty_cache()
+                continue
+            break
+        if rc != 0:
+            raise _lib.CpxError(rc, self.eng._err())
+        self.eng.synchronize()
+        return out
+
+    def close(self):
+        if self._graph is not None:
+            if self.eng.h:   # a closed engine has already freed its graphs
+                self.lib.cpx_graph_destroy(self._graph)
+            self._graph = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

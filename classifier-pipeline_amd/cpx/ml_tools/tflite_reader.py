@@ -1,13 +1,18 @@
-"""Pure-Python reader of ONE kind of TFLite model: a float32 WR-ResNet graph (.tflite).  The flatbuffer is parsed here --
-TensorFlow is not needed, only NumPy -- and the graph is walked into the Keras-layout weights of cpx/ml_tools/wrresnet.py.
+"""Pure-Python reader of float32 TFLite models (.tflite).  The flatbuffer is parsed here -- TensorFlow is not needed,
+only NumPy.  Two users:
 
-The reference loads any `.tflite` with LiteInterpreter (src/ml_tools/interpreter.py:520-560), picked by the file's suffix
-(interpreter.py:597-628).  This reader does NOT cover that: the artefact the reference's own CI classifies with
-(.github/workflows/release.yml:46 downloads `inc3-tflite-15122023.tar`) is an Inception-v3, another topology, and is
-REFUSED here with the operator that stopped the walk; get_interpreter then sends such a model to a model server, as it
-does every family but WR-ResNet (cpx/ml_tools/interpreter.py).  Only a WR-ResNet-22-4 exported to float32 TFLite is read:
-get_interpreter on such a path converts on load (load_tflite below); tools/tflite_to_npz.py writes the same arrays to an
-.npz.
+* `Graph` decodes subgraph 0 of any float32 model made of the operators in OPS below, with their options: CONV_2D
+  (dilation 1 only), AVERAGE_POOL_2D, MAX_POOL_2D, CONCATENATION, ADD, SUB, MUL, RELU, RELU6, MEAN, FULLY_CONNECTED,
+  LOGISTIC, SOFTMAX, RESHAPE, PAD.  That is the set the converter writes for the reference's `inceptionv3` family
+  (ml_tools/kerasmodel.py:171-180,259-350; the artefact the reference's CI classifies with, .github/workflows/
+  release.yml:46 `inc3-tflite-15122023.tar`, is one).  cpx/ml_tools/tflite_graph.py plans such a graph for the device
+  executor (cpx_graph_*), the LiteInterpreter of cpx/ml_tools/interpreter.py runs it -- what the reference's
+  LiteInterpreter does with any `.tflite` (src/ml_tools/interpreter.py:520-560,597-628).  check_executable() refuses
+  everything else by operator name and index: DEPTHWISE_CONV_2D, quantised or non-float32 tensors, grouped CONV_2D, a
+  dynamic shape, an operator outside the set.
+* `convert` / `load_tflite` walk ONE topology, a WR-ResNet-22-4, into the Keras-layout weights of
+  cpx/ml_tools/wrresnet.py (the fused MFMA network); get_interpreter on such a path converts on load,
+  tools/tflite_to_npz.py writes the same arrays to an .npz.
 
 What is read: the float32 graph of WR-ResNet-22-4 (src/ml_tools/resnet/wr_resnet.py:5-98) as the TFLite converter
 writes it -- CONV_2D (filter OHWI, bias, fused ReLU: a convolution with the BatchNorm that follows it folded in), MUL +
@@ -21,8 +26,14 @@ import struct
 import numpy as np
 
 BN_EPS = np.float32(1e-3)
-OPS = {0: "ADD", 3: "CONV_2D", 9: "FULLY_CONNECTED", 14: "LOGISTIC", 18: "MUL", 19: "RELU", 25: "SOFTMAX", 40: "MEAN",
-       22: "RESHAPE", 34: "PAD"}
+OPS = {0: "ADD", 1: "AVERAGE_POOL_2D", 2: "CONCATENATION", 3: "CONV_2D", 9: "FULLY_CONNECTED", 14: "LOGISTIC",
+       17: "MAX_POOL_2D", 18: "MUL", 19: "RELU", 21: "RELU6", 25: "SOFTMAX", 40: "MEAN", 41: "SUB", 22: "RESHAPE", 34: "PAD"}
+# operators that are recognised only to be refused by name (check_executable)
+REFUSED_OPS = {4: "DEPTHWISE_CONV_2D", 6: "DEQUANTIZE", 114: "QUANTIZE", 67: "TRANSPOSE_CONV", 23: "RESIZE_BILINEAR",
+               28: "TANH", 39: "TRANSPOSE", 32: "CUSTOM"}
+TENSOR_TYPES = {0: "FLOAT32", 1: "FLOAT16", 2: "INT32", 3: "UINT8", 4: "INT64", 6: "BOOL", 7: "INT16", 9: "INT8"}
+PADDING_SAME, PADDING_VALID = 0, 1
+ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 3
 
 
 # ---- flatbuffer access ---------------------------------------------------------------------------------------
@@ -122,13 +133,71 @@ class Graph:
             if opts is not None:
                 if o["name"] == "CONV_2D":
                     o.update(padding=opts.scalar(0, "b", 0), stride_w=opts.scalar(1, "i", 1), stride_h=opts.scalar(2, "i", 1),
-                             act=opts.scalar(3, "b", 0))
-                elif o["name"] in ("ADD", "MUL", "FULLY_CONNECTED"):
+                             act=opts.scalar(3, "b", 0), dilation_w=opts.scalar(4, "i", 1), dilation_h=opts.scalar(5, "i", 1))
+                    if o["dilation_w"] != 1 or o["dilation_h"] != 1:
+                        raise NotImplementedError("operator %d (CONV_2D): dilation %d x %d, only 1 x 1 is read"
+                                                  % (len(self.ops), o["dilation_h"], o["dilation_w"]))
+                elif o["name"] in ("AVERAGE_POOL_2D", "MAX_POOL_2D"):
+                    o.update(padding=opts.scalar(0, "b", 0), stride_w=opts.scalar(1, "i", 1), stride_h=opts.scalar(2, "i", 1),
+                             filter_width=opts.scalar(3, "i", 1), filter_height=opts.scalar(4, "i", 1),
+                             act=opts.scalar(5, "b", 0))
+                elif o["name"] == "CONCATENATION":
+                    o.update(axis=opts.scalar(0, "i", 0), act=opts.scalar(1, "b", 0))
+                elif o["name"] in ("ADD", "MUL", "SUB", "FULLY_CONNECTED"):
                     o["act"] = opts.scalar(0, "b", 0)
+                elif o["name"] == "SOFTMAX":
+                    o["beta"] = opts.scalar(0, "f", 0.0)
+                elif o["name"] == "MEAN":
+                    o["keep_dims"] = bool(opts.scalar(0, "b", 0))
+                elif o["name"] == "RESHAPE":
+                    o["new_shape"] = opts.vector(0, "i")
+            if o["name"] == "MEAN":
+                o.setdefault("keep_dims", False)
+                ax = self.tensors[o["inputs"][1]]["const"] if len(o["inputs"]) > 1 else None
+                o["axes"] = None if ax is None else [int(v) for v in np.asarray(ax).reshape(-1)]
+            elif o["name"] == "PAD":
+                pd = self.tensors[o["inputs"][1]]["const"] if len(o["inputs"]) > 1 else None
+                o["paddings"] = None if pd is None else [[int(a), int(b)] for a, b in np.asarray(pd).reshape(-1, 2)]
+            elif o["name"] == "SOFTMAX":
+                o.setdefault("beta", 1.0)
+            o["code"] = code
             self.ops.append(o)
 
     def const(self, idx):
         return self.tensors[idx]["const"]
+
+    def check_executable(self):
+        """Raises NotImplementedError, naming the operator and its index, for whatever the graph executor
+        (cpx/ml_tools/tflite_graph.py) does not run: an operator outside OPS, a tensor that is not float32 (int32
+        constants of MEAN / RESHAPE / PAD excepted), grouped CONV_2D, a dynamic shape."""
+        for i, op in enumerate(self.ops):
+            name = op["name"]
+            if op["code"] not in OPS:
+                raise NotImplementedError("operator %d (%s) is not in the set the graph executor runs: %s"
+                                          % (i, REFUSED_OPS.get(op["code"], name), ", ".join(sorted(OPS.values()))))
+            for k, t in enumerate(list(op["inputs"]) + list(op["outputs"])):
+                if t < 0:
+                    continue
+                ten = self.tensors[t]
+                int_const = ten["type"] == 2 and ten["const"] is not None and name in ("MEAN", "RESHAPE", "PAD") and k >= 1
+                if ten["type"] != 0 and not int_const:
+                    raise NotImplementedError("operator %d (%s): tensor %r has type %s, only float32 graphs are run"
+                                              % (i, name, ten["name"], TENSOR_TYPES.get(ten["type"], ten["type"])))
+                if ten["const"] is None and any(d < 0 for d in ten["shape"][1:]):
+                    raise NotImplementedError("operator %d (%s): tensor %r has a dynamic shape %s"
+                                              % (i, name, ten["name"], ten["shape"]))
+            if name == "CONV_2D":
+                w = self.const(op["inputs"][1])
+                if w is None:
+                    raise NotImplementedError("operator %d (CONV_2D): the filter is not a constant" % i)
+                cin = self.tensors[op["inputs"][0]]["shape"]
+                if len(cin) == 4 and cin[3] > 0 and w.shape[3] != cin[3]:
+                    raise NotImplementedError("operator %d (CONV_2D): grouped convolution (filter depth %d, input depth %d)"
+                                              % (i, w.shape[3], cin[3]))
+            if name == "MEAN" and op["axes"] is None:
+                raise NotImplementedError("operator %d (MEAN): the axes are not a constant" % i)
+            if name == "PAD" and op["paddings"] is None:
+                raise NotImplementedError("operator %d (PAD): the paddings are not a constant" % i)
 
 
 # ---- the walk: operators in order -> Keras-layout names -------------------------------------------------------

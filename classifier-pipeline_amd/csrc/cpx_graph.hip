@@ -1,0 +1,337 @@
+// cpx_graph.hip -- the kernels of the float32 TFLite graph executor (cpx_graph_forward, include/cpx.h; what the
+// reference's LiteInterpreter hands to the TFLite runtime, ml_tools/interpreter.py:520-560).  One launch per planned
+// operator; every kernel reads and writes NHWC views with a channel offset and a row stride, so that the producers of a
+// CONCATENATION write straight into their slice of the concatenated tensor.
+//
+// CONV_2D is an implicit GEMM on v_mfma_f32_32x32x2_f32 (exact float32 in, float32 accumulate: a k-ordered fmaf chain
+// per output, the same chain wherever the pixel sits in a tile or a batch):
+//   M = output pixels of the WHOLE batch, flattened (128 per workgroup, 32 per wave): the 8 x 8 and 17 x 17 maps of an
+//       Inception-v3 fill their tiles from the next sample instead of wasting them
+//   N = output channels (32 per MFMA tile, NTN tiles per wave)
+//   K = kh * kw * Cin walked as (tap) x (chunk of 16 input channels) x (pair of channels)
+// Weights arrive [tap][Cin rounded up to 16][Cout rounded up to 32] with zeros beyond, so only the activation side is
+// masked.  Scale / shift (bias, folded MUL / ADD), the activation and the channel-sliced store happen from the accumulators.
+#include <hip/hip_runtime.h>
+
+#include "cpx_kernels.h"
+
+namespace cpx {
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ float activate(float v, int act) {
+  if (act == CPX_GRAPH_ACT_RELU) return fmaxf(v, 0.0f);
+  if (act == CPX_GRAPH_ACT_RELU6) return fminf(fmaxf(v, 0.0f), 6.0f);
+  return v;
+}
+
+constexpr int CT = 256;
+constexpr int BM = 128;            // output pixels of a workgroup
+constexpr int KC = GRAPH_CONV_KC;  // input channels per staged chunk
+constexpr int AP = BM + 4;         // row stride of the k-major patch image: the two 8-channel halves of a pixel land 32 banks apart
+
+struct ConvGeom {
+  long long P;   // N * Ho * Wo
+  int HoWo, cin_pad, cout_pad, vec4;
+};
+
+template <int NTN>
+__global__ __launch_bounds__(CT) void graph_conv_kernel(GraphOpArgs a, ConvGeom g) {
+  constexpr int BN = 32 * NTN;
+  __shared__ __attribute__((aligned(16))) float s_a[KC * AP];   // [k][pixel]
+  __shared__ __attribute__((aligned(16))) float s_b[KC * BN];   // [k][channel]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long p0 = (long long)blockIdx.x * BM;
+  const int cout0 = blockIdx.y * BN;
+  const int Cin = a.in0.C, H = a.in0.H, W = a.in0.W, Wo = a.out.W;
+
+  // staging role: pixel tid / 2 of the tile, channels [8 * half, 8 * half + 8) of the chunk -- the same pixel for the
+  // whole K walk, so its coordinates are worked out once
+  const int spx = tid >> 1, half = tid & 1;
+  const long long sp = p0 + spx;
+  const bool pv = sp < g.P;
+  const long long sn = pv ? sp / g.HoWo : 0;
+  const int srem = pv ? (int)(sp - sn * g.HoWo) : 0;
+  const int soy = srem / Wo, sox = srem - soy * Wo;
+  const int iy0 = soy * a.stride_h - a.pad_top, ix0 = sox * a.stride_w - a.pad_left;
+  const float* in_n = a.in0.p + (size_t)sn * a.in0.sample_stride;   // 64-bit over the batch, 32-bit inside a sample
+  // weight staging: KC rows of BN channels = KC * BN / 4 float4 (one per thread with NTN = 2)
+  constexpr int WQ = BN / 4;
+  const int wk = tid / WQ, wc4 = tid - wk * WQ;
+  const bool wload = tid < KC * WQ;
+
+  const int nchunks = g.cin_pad / KC;
+  const int steps = a.kh * a.kw * nchunks;
+
+  f32x16 acc[NTN];
+#pragma unroll
+  for (int t = 0; t < NTN; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
+
+  float pre[8];
+  f32x4 pre_w = {0.0f, 0.0f, 0.0f, 0.0f};
+
+  // global -> registers of step s (branch-free: a masked element reads the sample's first element and is zeroed)
+  auto fetch = [&](int s) {
+    const int tap = s / nchunks, c0 = (s - tap * nchunks) * KC;
+    const int ky = tap / a.kw, kx = tap - ky * a.kw;
+    const int iy = iy0 + ky, ix = ix0 + kx;
+    const bool inside = pv && iy >= 0 && iy < H && ix >= 0 && ix < W;
+    const int c = c0 + 8 * half;
+    const int pix = inside ? (iy * W + ix) * a.in0.cstride : 0;
+    if (g.vec4) {
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const bool ok = inside && (c + 4 * q) < Cin;   // Cin % 4 == 0: a quad is valid as a whole
+        const f32x4 v = *reinterpret_cast<const f32x4*>(in_n + (ok ? pix + c + 4 * q : 0));
+        pre[4 * q + 0] = ok ? v.x : 0.0f;
+        pre[4 * q + 1] = ok ? v.y : 0.0f;
+        pre[4 * q + 2] = ok ? v.z : 0.0f;
+        pre[4 * q + 3] = ok ? v.w : 0.0f;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const bool ok = inside && (c + j) < Cin;
+        const float v = in_n[ok ? pix + c + j : 0];
+        pre[j] = ok ? v : 0.0f;
+      }
+    }
+    if (wload)
+      pre_w = *reinterpret_cast<const f32x4*>(a.weights + ((size_t)(tap * g.cin_pad + c0 + wk) * g.cout_pad + cout0 + 4 * wc4));
+  };
+
+  fetch(0);
+  for (int s = 0; s < steps; ++s) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s_a[(8 * half + j) * AP + spx] = pre[j];
+    if (wload) *reinterpret_cast<f32x4*>(s_b + wk * BN + 4 * wc4) = pre_w;
+    __syncthreads();
+    if (s + 1 < steps) fetch(s + 1);   // in flight while the matrix cores work on step s
+    const float* ap = s_a + (lane >> 5) * AP + 32 * wave + (lane & 31);
+    const float* bp = s_b + (lane >> 5) * BN + (lane & 31);
+#pragma unroll
+    for (int k2 = 0; k2 < KC / 2; ++k2) {
+      const float av = ap[2 * k2 * AP];
+#pragma unroll
+      for (int t = 0; t < NTN; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bp[2 * k2 * BN + 32 * t], acc[t], 0, 0, 0);
+    }
+    __syncthreads();
+  }
+
+  // epilogue: accumulator register r of a lane is pixel (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5) of the wave's 32,
+  // channel lane & 31 of the tile: 32 lanes store 128 contiguous bytes of one pixel
+  const long long pb = p0 + 32 * wave;
+  if (pb >= g.P) return;
+  const long long nb = pb / g.HoWo;
+  const int remb = (int)(pb - nb * g.HoWo);
+#pragma unroll
+  for (int t = 0; t < NTN; ++t) {
+    const int ch = cout0 + 32 * t + (lane & 31);
+    if (ch >= a.out.C) continue;
+    const float sc = a.scale ? a.scale[ch] : 1.0f;
+    const float sh = a.shift ? a.shift[ch] : 0.0f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int i = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+      if (pb + i >= g.P) continue;
+      long long n = nb;
+      int rem = remb + i;
+      while (rem >= g.HoWo) {
+        rem -= g.HoWo;
+        ++n;
+      }
+      a.out.p[(size_t)n * a.out.sample_stride + (unsigned)(rem * a.out.cstride + ch)] = activate(acc[t][r] * sc + sh, a.act);
+    }
+  }
+}
+
+// one thread per output element, channel fastest
+__device__ __forceinline__ bool out_coords(const GraphOpArgs& a, size_t idx, size_t* n, int* y, int* x, int* c) {
+  const size_t total = (size_t)a.N * a.out.H * a.out.W * a.out.C;
+  if (idx >= total) return false;
+  *c = (int)(idx % a.out.C);
+  size_t p = idx / a.out.C;
+  *x = (int)(p % a.out.W);
+  p /= a.out.W;
+  *y = (int)(p % a.out.H);
+  *n = p / a.out.H;
+  return true;
+}
+
+__device__ __forceinline__ float* at(const GraphView& v, size_t n, int y, int x, int c) {
+  return v.p + n * v.sample_stride + (unsigned)((y * v.W + x) * v.cstride + c);
+}
+
+template <bool MAX>
+__global__ __launch_bounds__(CT) void graph_pool_kernel(GraphOpArgs a) {
+  size_t n;
+  int oy, ox, c;
+  if (!out_coords(a, (size_t)blockIdx.x * CT + threadIdx.x, &n, &oy, &ox, &c)) return;
+  const int iy0 = oy * a.stride_h - a.pad_top, ix0 = ox * a.stride_w - a.pad_left;
+  float v = MAX ? -INFINITY : 0.0f;
+  int count = 0;
+  for (int ky = 0; ky < a.kh; ++ky) {
+    const int iy = iy0 + ky;
+    if (iy < 0 || iy >= a.in0.H) continue;
+    for (int kx = 0; kx < a.kw; ++kx) {
+      const int ix = ix0 + kx;
+      if (ix < 0 || ix >= a.in0.W) continue;
+      const float e = *at(a.in0, n, iy, ix, c);
+      v = MAX ? fmaxf(v, e) : v + e;
+      ++count;
+    }
+  }
+  if (!MAX) v = v / (float)max(count, 1);   // the divisor leaves the padding out, as TFLite's AVERAGE_POOL_2D
+  *at(a.out, n, oy, ox, c) = activate(v, a.act);
+}
+
+__global__ __launch_bounds__(CT) void graph_add_kernel(GraphOpArgs a) {
+  size_t n;
+  int y, x, c;
+  if (!out_coords(a, (size_t)blockIdx.x * CT + threadIdx.x, &n, &y, &x, &c)) return;
+  *at(a.out, n, y, x, c) = activate(*at(a.in0, n, y, x, c) + a.param * *at(a.in1, n, y, x, c), a.act);
+}
+
+__global__ __launch_bounds__(CT) void graph_affine_kernel(GraphOpArgs a) {
+  size_t n;
+  int y, x, c;
+  if (!out_coords(a, (size_t)blockIdx.x * CT + threadIdx.x, &n, &y, &x, &c)) return;
+  float v = *at(a.in0, n, y, x, c);
+  if (a.scale) v *= a.scale[c];
+  if (a.shift) v += a.shift[c];
+  *at(a.out, n, y, x, c) = activate(v, a.act);
+}
+
+__global__ __launch_bounds__(CT) void graph_pad_kernel(GraphOpArgs a) {
+  size_t n;
+  int y, x, c;
+  if (!out_coords(a, (size_t)blockIdx.x * CT + threadIdx.x, &n, &y, &x, &c)) return;
+  const int iy = y - a.pad_top, ix = x - a.pad_left;
+  const bool inside = iy >= 0 && iy < a.in0.H && ix >= 0 && ix < a.in0.W;
+  *at(a.out, n, y, x, c) = inside ? *at(a.in0, n, iy, ix, c) : 0.0f;
+}
+
+__global__ __launch_bounds__(CT) void graph_channel_map_kernel(GraphOpArgs a) {
+  size_t n;
+  int y, x, c;
+  if (!out_coords(a, (size_t)blockIdx.x * CT + threadIdx.x, &n, &y, &x, &c)) return;
+  *at(a.out, n, y, x, c) = *at(a.in0, n, y, x, a.map[c]);
+}
+
+// MEAN over H and W: one thread per (sample, channel), pixels in order (channel-contiguous loads across the wave)
+__global__ __launch_bounds__(CT) void graph_mean_kernel(GraphOpArgs a) {
+  const size_t idx = (size_t)blockIdx.x * CT + threadIdx.x;
+  if (idx >= (size_t)a.N * a.in0.C) return;
+  const int c = (int)(idx % a.in0.C);
+  const size_t n = idx / a.in0.C;
+  const float* src = a.in0.p + n * a.in0.sample_stride + c;
+  const int hw = a.in0.H * a.in0.W;
+  float sum = 0.0f;
+  for (int i = 0; i < hw; ++i) sum += src[(unsigned)(i * a.in0.cstride)];
+  a.out.p[n * a.out.sample_stride + c] = sum / (float)hw;
+}
+
+// FULLY_CONNECTED: one wave per (sample, output); lanes stride over the inputs, a fixed butterfly sums them
+__global__ __launch_bounds__(CT) void graph_fc_kernel(GraphOpArgs a) {
+  const int lane = threadIdx.x & 63;
+  const size_t wid = (size_t)blockIdx.x * (CT / 64) + (threadIdx.x >> 6);
+  if (wid >= (size_t)a.N * a.out.C) return;
+  const int o = (int)(wid % a.out.C);
+  const size_t n = wid / a.out.C;
+  const float* x = a.in0.p + n * a.in0.sample_stride;
+  const float* w = a.weights + (size_t)o * a.in0.C;
+  float sum = 0.0f;
+  for (int k = lane; k < a.in0.C; k += 64) sum += x[k] * w[k];
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
+  if (lane == 0) a.out.p[n * a.out.sample_stride + o] = activate(sum + (a.shift ? a.shift[o] : 0.0f), a.act);
+}
+
+__global__ __launch_bounds__(CT) void graph_logistic_kernel(GraphOpArgs a) {
+  size_t n;
+  int y, x, c;
+  if (!out_coords(a, (size_t)blockIdx.x * CT + threadIdx.x, &n, &y, &x, &c)) return;
+  *at(a.out, n, y, x, c) = 1.0f / (1.0f + expf(-*at(a.in0, n, y, x, c)));
+}
+
+// SOFTMAX over the channels of every pixel: one thread per pixel (the heads this runs have tens of labels)
+__global__ __launch_bounds__(CT) void graph_softmax_kernel(GraphOpArgs a) {
+  const size_t idx = (size_t)blockIdx.x * CT + threadIdx.x;
+  const size_t hw = (size_t)a.in0.H * a.in0.W;
+  if (idx >= (size_t)a.N * hw) return;
+  const size_t n = idx / hw;
+  const unsigned pix = (unsigned)(idx - n * hw);
+  const float* src = a.in0.p + n * a.in0.sample_stride + pix * a.in0.cstride;
+  float* dst = a.out.p + n * a.out.sample_stride + pix * a.out.cstride;
+  float m = -INFINITY;
+  for (int c = 0; c < a.in0.C; ++c) m = fmaxf(m, src[c]);
+  float sum = 0.0f;
+  for (int c = 0; c < a.in0.C; ++c) sum += expf(a.param * (src[c] - m));
+  for (int c = 0; c < a.in0.C; ++c) dst[c] = expf(a.param * (src[c] - m)) / sum;
+}
+
+unsigned blocks_for(size_t items) { return (unsigned)((items + CT - 1) / CT); }
+
+}  // namespace
+
+void launch_graph_op(const GraphOpArgs& a, hipStream_t s) {
+  const size_t out_elems = (size_t)a.N * a.out.H * a.out.W * a.out.C;
+  switch (a.kind) {
+    case CPX_GRAPH_CONV: {
+      ConvGeom g;
+      g.HoWo = a.out.H * a.out.W;
+      g.P = (long long)a.N * g.HoWo;
+      g.cin_pad = (a.in0.C + GRAPH_CONV_KC - 1) / GRAPH_CONV_KC * GRAPH_CONV_KC;
+      g.cout_pad = (a.out.C + GRAPH_CONV_CO - 1) / GRAPH_CONV_CO * GRAPH_CONV_CO;
+      g.vec4 = (a.in0.C % 4 == 0 && a.in0.cstride % 4 == 0 && a.in0.sample_stride % 4 == 0 &&
+                (reinterpret_cast<uintptr_t>(a.in0.p) & 15) == 0)
+                   ? 1
+                   : 0;
+      const unsigned gx = (unsigned)((g.P + BM - 1) / BM);
+      if (g.cout_pad % 64 == 0)
+        hipLaunchKernelGGL(graph_conv_kernel<2>, dim3(gx, g.cout_pad / 64), dim3(CT), 0, s, a, g);
+      else
+        hipLaunchKernelGGL(graph_conv_kernel<1>, dim3(gx, g.cout_pad / 32), dim3(CT), 0, s, a, g);
+      break;
+    }
+    case CPX_GRAPH_MAX_POOL:
+      hipLaunchKernelGGL(graph_pool_kernel<true>, dim3(blocks_for(out_elems)), dim3(CT), 0, s, a);
+      break;
+    case CPX_GRAPH_AVG_POOL:
+      hipLaunchKernelGGL(graph_pool_kernel<false>, dim3(blocks_for(out_elems)), dim3(CT), 0, s, a);
+      break;
+    case CPX_GRAPH_ADD:
+      hipLaunchKernelGGL(graph_add_kernel, dim3(blocks_for(out_elems)), dim3(CT), 0, s, a);
+      break;
+    case CPX_GRAPH_AFFINE:
+      hipLaunchKernelGGL(graph_affine_kernel, dim3(blocks_for(out_elems)), dim3(CT), 0, s, a);
+      break;
+    case CPX_GRAPH_PAD:
+      hipLaunchKernelGGL(graph_pad_kernel, dim3(blocks_for(out_elems)), dim3(CT), 0, s, a);
+      break;
+    case CPX_GRAPH_CHANNEL_MAP:
+      hipLaunchKernelGGL(graph_channel_map_kernel, dim3(blocks_for(out_elems)), dim3(CT), 0, s, a);
+      break;
+    case CPX_GRAPH_MEAN:
+      hipLaunchKernelGGL(graph_mean_kernel, dim3(blocks_for((size_t)a.N * a.in0.C)), dim3(CT), 0, s, a);
+      break;
+    case CPX_GRAPH_FC:
+      hipLaunchKernelGGL(graph_fc_kernel, dim3((unsigned)(((size_t)a.N * a.out.C + 3) / 4)), dim3(CT), 0, s, a);
+      break;
+    case CPX_GRAPH_LOGISTIC:
+      hipLaunchKernelGGL(graph_logistic_kernel, dim3(blocks_for(out_elems)), dim3(CT), 0, s, a);
+      break;
+    case CPX_GRAPH_SOFTMAX:
+      hipLaunchKernelGGL(graph_softmax_kernel, dim3(blocks_for((size_t)a.N * a.in0.H * a.in0.W)), dim3(CT), 0, s, a);
+      break;
+    default:
+      break;
+  }
+}
+
+}  // namespace cpx

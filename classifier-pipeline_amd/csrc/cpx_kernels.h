@@ -369,6 +369,30 @@ struct Mog2Args {
 void launch_mog2_apply(const Mog2Args& a, hipStream_t s);
 void launch_mog2_background(const Mog2Args& a, unsigned char* out, hipStream_t s);
 
+// ---- float32 TFLite graph executor (cpx_graph.hip) ----
+// A view of an NHWC tensor of N samples: sample n at p + n * sample_stride, pixel (y, x) channel c at
+// ((y * W + x) * cstride + c).  `p` already points at the view's first channel (the channel offset is added by the caller).
+struct GraphView {
+  float* p;
+  int H, W, C, cstride;
+  size_t sample_stride;  // floats
+};
+struct GraphOpArgs {
+  int kind;  // CPX_GRAPH_*
+  int N;
+  GraphView in0, in1, out;
+  int kh, kw, stride_h, stride_w, pad_top, pad_left;
+  int act;
+  int n_map, map[4];
+  float param;
+  const float* weights;
+  const float* scale;
+  const float* shift;
+};
+void launch_graph_op(const GraphOpArgs& a, hipStream_t s);
+constexpr int GRAPH_CONV_KC = 16;  // CONV weights: Cin padded to this ...
+constexpr int GRAPH_CONV_CO = 32;  // ... and Cout to this
+
 // Kernels that use more than 64 KB of dynamic LDS need hipFuncAttributeMaxDynamicSharedMemorySize raised once per
 // (kernel, device): `done` is a per-kernel array indexed by the current device ordinal.
 inline bool cpx_dyn_lds_ready(const void* fn, bool* done, int bytes) {

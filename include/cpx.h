@@ -765,6 +765,72 @@ typedef struct cpx_conv_timing {
 int cpx_conv_timing_enable(cpx_handle* h, int enable);
 int cpx_conv_timing_report(cpx_handle* h, cpx_conv_timing* out, int cap, int* n_out);
 
+/* ---- float32 TFLite graph executor ----------------------------------------------------------------------------
+ * LiteInterpreter.predict (ml_tools/interpreter.py:520-560) runs any `.tflite` graph sample by sample through the
+ * TFLite runtime; here a planned float32 graph (cpx/ml_tools/tflite_graph.py: shapes inferred, constants folded,
+ * concatenations resolved by placement, tensors placed in one arena) runs for a whole batch in one call.  Tensors are
+ * NHWC float32 views: H x W pixels of C channels that sit at channel c_offset of rows of c_stride channels (a
+ * CONCATENATION input lives inside the concatenated tensor), `arena_offset` floats PER SAMPLE from the arena's start:
+ * the tensor of a forward over N samples starts at arena + arena_offset * N, sample n at + n * H * W * c_stride.  The
+ * tensors `input_tensor` / `output_tensor` of cpx_graph_create are in_dev / out_dev of cpx_graph_forward and have no
+ * place in the arena; the input is dense (c_offset 0, c_stride C), the output may be a channel slice of the caller's
+ * rows of c_stride channels (the other channels of out_dev are left as they are). */
+enum {
+  CPX_GRAPH_CONV = 1,        /* CONV_2D: weights [kh * kw][Cin rounded up to 16][Cout rounded up to 32] (zeros beyond),
+                                out = act(acc * scale + shift); scale may be NULL (1), shift NULL (0) */
+  CPX_GRAPH_MAX_POOL = 2,    /* kh x kw window, strides, explicit pads; padding never wins */
+  CPX_GRAPH_AVG_POOL = 3,    /* ... divided by the number of in-bounds elements */
+  CPX_GRAPH_ADD = 4,         /* out = act(in0 + param * in1): param 1 (ADD) or -1 (SUB) */
+  CPX_GRAPH_AFFINE = 5,      /* out = act(in0 * scale[c] + shift[c]); NULL scale / shift: 1 / 0 (a bare RELU, a copy) */
+  CPX_GRAPH_MEAN = 6,        /* over H and W -> 1 x 1 x C */
+  CPX_GRAPH_FC = 7,          /* FULLY_CONNECTED on a 1 x 1 x C input: weights [Cout][Cin], shift = bias */
+  CPX_GRAPH_LOGISTIC = 8,
+  CPX_GRAPH_SOFTMAX = 9,     /* over C, param = beta */
+  CPX_GRAPH_PAD = 10,        /* zeros around H and W (the four pads) */
+  CPX_GRAPH_CHANNEL_MAP = 11 /* out channel c = in0 channel channel_map[c], c < n_map (n_map = out C <= 4): a
+                                [N, H, W, 2] sample of cpx_crop_tile feeds a 3-channel graph, a channel repeated as
+                                the reference's preprocess_movement repeats one (ml_tools/preprocess.py:169-189) */
+};
+enum { CPX_GRAPH_ACT_NONE = 0, CPX_GRAPH_ACT_RELU = 1, CPX_GRAPH_ACT_RELU6 = 3 }; /* TFLite's ActivationFunctionType */
+
+typedef struct cpx_graph_tensor {
+  int32_t H, W, C;
+  int32_t c_offset, c_stride;
+  int32_t reserved;
+  int64_t arena_offset; /* floats per sample; ignored for the input and output tensors */
+} cpx_graph_tensor;
+
+typedef struct cpx_graph_op {
+  int32_t kind;
+  int32_t in0, in1, out; /* tensor ids; in1 = -1 where there is one input */
+  int32_t kh, kw, stride_h, stride_w;
+  int32_t pad_top, pad_left, pad_bottom, pad_right;
+  int32_t activation;
+  int32_t out_c_offset, out_c_stride; /* where the output goes: the channel slice of tensors[out] */
+  int32_t n_map, channel_map[4];
+  float param;
+  const float* weights; /* device pointers, owned by the caller, alive as long as the graph */
+  const float* scale;
+  const float* shift;
+} cpx_graph_op;
+
+/* A graph belongs to the handle it was created on: cpx_destroy(h) frees the graphs still alive, after which their
+ * pointers are invalid (do not call cpx_graph_destroy on them).  cpx_graph_create checks every operator against its
+ * tensors (ids, channel slices, output sizes against kernel / stride / pads, arena extents) and copies the arrays. */
+typedef struct cpx_graph cpx_graph;
+int cpx_graph_create(cpx_handle* h, const cpx_graph_op* ops, int n_ops, const cpx_graph_tensor* tensors, int n_tensors,
+                     int input_tensor, int output_tensor, cpx_graph** out);
+/* in_dev [N, H, W, C] of the input tensor -> out_dev [N, H, W, C] of the output tensor: one launch per operator,
+ * enqueued on the handle's stream, no host synchronisation (unless the arena has to grow).  The arena belongs to the
+ * handle, is shared by its graphs, grows to the largest call seen and is released by cpx_release_memory. */
+int cpx_graph_forward(cpx_graph* g, const float* in_dev, int N, float* out_dev);
+/* bytes of arena a forward over N samples needs (linear in N) */
+int cpx_graph_arena_bytes(const cpx_graph* g, int N, size_t* bytes);
+/* Diagnostic and test surface, not needed to run a graph: bytes of graph arena the handle holds now (0 after
+ * cpx_release_memory). */
+int cpx_graph_arena_allocated(const cpx_handle* h, size_t* bytes);
+void cpx_graph_destroy(cpx_graph* g);
+
 /* Bytes of device workspace cpx_track_batch needs for B clips / total frames
  * (allocated lazily inside the handle and reused). */
 size_t cpx_track_workspace_bytes(const cpx_handle* h, int B, int total_frames);

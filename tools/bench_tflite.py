@@ -1,0 +1,201 @@
+#!/usr/bin/env python3
+"""Times the TFLite graph executor (cpx_graph_forward) on a width-1.0 Inception-v3 at 160 x 160 x 3 (the synthetic
+flatbuffer of tests/tflite_build.py: the converter's layout, seeded weights) with HIP events after warm-up, for a few
+batch sizes, and -- the yardstick, on the same card in the same run -- PyTorch-ROCm evaluating the same graph in float32
+with its reduced-precision convolution paths disabled.  Prints one JSON line.
+
+    python tools/bench_tflite.py [--batches 1,8,32,128] [--steps 10] [--warmup 3]
+
+The per-kernel-kind split of the time comes from the device's own timestamps: run the script (one batch size, --skip-torch)
+under `rocprofv3 --kernel-trace --output-format csv -d DIR -- python tools/bench_tflite.py ...`, then hand the trace back:
+
+    python tools/bench_tflite.py --kernel-trace DIR/.../*_kernel_trace.csv --batches 128
+
+which needs no GPU: it maps the last forward's launches, in order, onto the plan's operators and prints the time per kind,
+the GPU-busy share of the forward and, for the convolution shape that takes the most time, its algorithmic TFLOP/s and
+the share of the float32 matrix-pipe peak (157.3 TFLOP/s) that is."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (os.path.join(REPO, "classifier-pipeline_amd"), os.path.join(REPO, "tests")):
+    sys.path.insert(0, p)
+
+KIND_NAMES = {1: "conv", 2: "max_pool", 3: "avg_pool", 4: "add", 5: "affine", 6: "mean", 7: "fc", 8: "logistic", 9: "softmax",
+              10: "pad", 11: "channel_map"}
+
+
+def torch_model(g, device):
+    """The graph as PyTorch modules' functional calls, float32, weights on the device."""
+    import torch
+    import torch.nn.functional as F
+
+    from tflite_eval import _act, _pads
+
+    const = {i: torch.from_numpy(np.array(t["const"])).to(device) for i, t in enumerate(g.tensors)
+             if t["const"] is not None and t["type"] == 0}
+    wts = {i: c.permute(0, 3, 1, 2).contiguous() for i, c in const.items() if c.ndim == 4}
+
+    def forward(x_nchw):
+        val = {g.inputs[0]: x_nchw}
+        for op in g.ops:
+            name, ins = op["name"], op["inputs"]
+            a = val[ins[0]]
+            if name == "CONV_2D":
+                kh, kw = wts[ins[1]].shape[2:]
+                pt, pb = _pads(a.shape[2], kh, op["stride_h"], op["padding"])
+                pl, pr = _pads(a.shape[3], kw, op["stride_w"], op["padding"])
+                if pt or pb or pl or pr:
+                    a = F.pad(a, (pl, pr, pt, pb))
+                r = _act(F.conv2d(a, wts[ins[1]], const[ins[2]], stride=(op["stride_h"], op["stride_w"])), op["act"])
+            elif name in ("MAX_POOL_2D", "AVERAGE_POOL_2D"):
+                k, st = (op["filter_height"], op["filter_width"]), (op["stride_h"], op["stride_w"])
+                pt, pb = _pads(a.shape[2], k[0], st[0], op["padding"])
+                pl, pr = _pads(a.shape[3], k[1], st[1], op["padding"])
+                assert pt == pb and pl == pr and op["act"] == 0, "the yardstick takes symmetric pool padding only"
+                if name == "MAX_POOL_2D":
+                    r = F.max_pool2d(a, k, st, (pt, pl))
+                else:
+                    r = F.avg_pool2d(a, k, st, (pt, pl), count_include_pad=False)
+            elif name == "CONCATENATION":
+                r = torch.cat([val[t] for t in ins], dim=1)
+            elif name == "MEAN":
+                r = a.mean(dim=(2, 3))
+            elif name == "FULLY_CONNECTED":
+                r = _act(F.linear(a, const[ins[1]], const[ins[2]]), op["act"])
+            elif name == "LOGISTIC":
+                r = torch.sigmoid(a)
+            else:
+                raise NotImplementedError(name)
+            val[op["outputs"][0]] = r
+        return val[g.outputs[0]]
+
+    return forward
+
+
+def timed(torch, fn, steps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    times = []
+    for _ in range(steps):
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        times.append(e0.elapsed_time(e1))
+    return float(np.median(times))
+
+
+F32_MFMA_PEAK_TFLOPS = 157.3
+
+
+def split_from_trace(path, plan, n):
+    """The last forward of a rocprofv3 kernel trace: its launches are the plan's operators in order."""
+    import csv
+
+    with open(path) as fh:
+        rows = [r for r in csv.DictReader(fh) if "graph_" in r["Kernel_Name"]]
+    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
+    rows = rows[-len(plan.ops):]
+    assert len(rows) == len(plan.ops), "the trace holds no whole forward"
+    by_kind, shapes = {}, {}
+    for r, o in zip(rows, plan.ops):
+        ns = int(r["End_Timestamp"]) - int(r["Start_Timestamp"])
+        assert ("conv" in r["Kernel_Name"]) == (o.kind == 1), (r["Kernel_Name"], o.name)
+        k = by_kind.setdefault(KIND_NAMES[o.kind], {"launches": 0, "ms": 0.0})
+        k["launches"] += 1
+        k["ms"] += ns / 1e6
+        if o.kind == 1:
+            t, i = plan.tensors[o.out], plan.tensors[o.in0]
+            key = "%dx%d s%d %d->%d at %dx%d" % (o.kh, o.kw, o.stride_h, i.C, t.C, t.H, t.W)
+            s = shapes.setdefault(key, {"launches": 0, "ms": 0.0, "gflop": 0.0})
+            s["launches"] += 1
+            s["ms"] += ns / 1e6
+            s["gflop"] += 2.0 * n * t.H * t.W * t.C * o.kh * o.kw * i.C / 1e9
+    wall = (int(rows[-1]["End_Timestamp"]) - int(rows[0]["Start_Timestamp"])) / 1e6
+    busy = sum(k["ms"] for k in by_kind.values())
+    top = max(shapes, key=lambda k: shapes[k]["ms"])
+    conv = by_kind["conv"]
+    conv_gflop = sum(s["gflop"] for s in shapes.values())
+    tf = shapes[top]["gflop"] / shapes[top]["ms"]
+    return {"N": n, "forward_ms_first_start_to_last_end": wall, "kernel_ms_sum": busy, "gpu_busy_share": busy / wall,
+            "ms_by_kind": by_kind, "conv_tflops_while_running": conv_gflop / conv["ms"],
+            "conv_matrix_pipe_share": conv_gflop / conv["ms"] / F32_MFMA_PEAK_TFLOPS,
+            "dominant_conv": dict(shapes[top], shape=top, tflops=tf, matrix_pipe_share=tf / F32_MFMA_PEAK_TFLOPS)}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--batches", default="1,8,32,128")
+    ap.add_argument("--skip-torch", action="store_true", help="time the executor only (for a run under a profiler)")
+    ap.add_argument("--kernel-trace", default=None, help="a rocprofv3 kernel trace CSV of a run of this script: print the split")
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--width", type=float, default=1.0)
+    args = ap.parse_args()
+    import ctypes as C
+
+    import tflite_build as tb
+    from cpx.ml_tools.tflite_graph import GraphDevice, build_plan
+    from cpx.ml_tools.tflite_reader import Graph
+    g = Graph(tb.inception_v3(17, (), seed=7, width=args.width))
+    plan = build_plan(g)
+    if args.kernel_trace:
+        print(json.dumps(split_from_trace(args.kernel_trace, plan, int(args.batches.split(",")[-1]))))
+        return
+    flops = 0.0   # algorithmic, per sample
+    for o in plan.ops:
+        if o.kind == 1:
+            t, i = plan.tensors[o.out], plan.tensors[o.in0]
+            flops += 2.0 * t.H * t.W * t.C * o.kh * o.kw * i.C
+    import torch
+
+    from cpx.engine import TrackEngine
+
+    torch.backends.cudnn.allow_tf32 = False
+    torch.backends.cuda.matmul.allow_tf32 = False
+    eng = TrackEngine(model="lepton3", device=0)
+    dev = GraphDevice(eng, plan)
+    ref = torch_model(g, eng.device)
+    stream = torch.cuda.ExternalStream(eng.lib.cpx_stream(eng.h), device=eng.device)
+    out = {"model": "inception_v3 width %.2f 160x160x3" % args.width, "gflop_per_sample": flops / 1e9,
+           "arena_bytes_per_sample": plan.arena_bytes_per_sample, "batches": []}
+    rng = np.random.default_rng(0)
+    for n in [int(v) for v in args.batches.split(",")]:
+        x = torch.from_numpy(rng.uniform(-1, 1, size=(n, 160, 160, 3)).astype(np.float32)).to(eng.device)
+        y = torch.empty((n, 17), dtype=torch.float32, device=eng.device)
+        x_nchw = x.permute(0, 3, 1, 2).contiguous()
+        torch.cuda.synchronize()
+
+        def ours():
+            rc = eng.lib.cpx_graph_forward(dev._graph, C.c_void_p(x.data_ptr()), n, C.c_void_p(y.data_ptr()))
+            assert rc == 0, eng._err()
+
+        with torch.cuda.stream(stream):
+            ms = timed(torch, ours, args.steps, args.warmup)
+        rec = {"N": n, "ms": ms, "samples_per_s": n / ms * 1e3, "tflops": flops * n / ms / 1e9}
+        if not args.skip_torch:
+            with torch.no_grad():
+                ms_ref = timed(torch, lambda: ref(x_nchw), args.steps, args.warmup)
+                err = float((ref(x_nchw) - y).abs().max())
+            rec.update({"torch_ms": ms_ref, "torch_samples_per_s": n / ms_ref * 1e3, "ratio_vs_torch": ms_ref / ms,
+                        "max_abs_diff_vs_torch": err})
+        out["batches"].append(rec)
+    # (the per-kernel-kind split of the TIME: --kernel-trace, from a run under rocprofv3)
+    kinds = {}
+    for o in plan.ops:
+        kinds[KIND_NAMES[o.kind]] = kinds.get(KIND_NAMES[o.kind], 0) + 1
+    out["launches_by_kind"] = kinds
+    dev.close()
+    eng.close()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

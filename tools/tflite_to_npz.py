@@ -3,6 +3,11 @@
 flatbuffer is parsed here, TensorFlow is not needed (only NumPy).
 
     python tools/tflite_to_npz.py model.tflite /tmp/wr [--sidecar model.json]
+    python tools/tflite_to_npz.py --describe model.tflite
+
+--describe converts nothing: it prints the operator census, the input and output shapes and the arena bytes per sample
+of ANY graph the device executor runs (cpx/ml_tools/tflite_graph.py: an Inception-v3, say), or the refusal -- the
+operator and its index -- of one it does not.
 
 The reference loads this artefact with LiteInterpreter (/root/reference/src/ml_tools/interpreter.py:520-560); its CI
 downloads it (.github/workflows/release.yml:46) and tests/clips/possum.txt's prediction came from one.  Anyone holding
@@ -30,14 +35,37 @@ from cpx.ml_tools.tflite_reader import (BN_EPS, OPS, Graph, Table, bn_params, co
                                         identity_variance)
 
 
+def describe(g):
+    from cpx.ml_tools.tflite_graph import build_plan
+
+    census = {}
+    for op in g.ops:
+        census[op["name"]] = census.get(op["name"], 0) + 1
+    print("operators: " + ", ".join("%s: %d" % kv for kv in sorted(census.items())))
+    try:
+        plan = build_plan(g)
+    except NotImplementedError as e:
+        print("refused: %s" % e)
+        return 1
+    print("input shape %s, output shape %s" % (list(plan.input_shape), list(plan.output_shape)))
+    print("launches: " + ", ".join("%s: %d" % kv for kv in sorted(plan.census().items())))
+    print("arena bytes per sample: %d" % plan.arena_bytes_per_sample)
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("model", help="the .tflite file")
-    ap.add_argument("out_base", help="writes <out_base>.npz (and copies the sidecar to <out_base>.json)")
+    ap.add_argument("out_base", nargs="?", help="writes <out_base>.npz (and copies the sidecar to <out_base>.json)")
+    ap.add_argument("--describe", action="store_true", help="print what the graph executor makes of the file; writes nothing")
     ap.add_argument("--sidecar", default=None, help="the model's JSON sidecar (default: <model>.json next to it)")
     args = ap.parse_args()
     with open(args.model, "rb") as fh:
         g = Graph(fh.read())
+    if args.describe:
+        return describe(g)
+    if args.out_base is None:
+        ap.error("out_base is required unless --describe is given")
     weights = convert(g)
     np.savez(args.out_base + ".npz", **weights)
     sidecar = args.sidecar or os.path.splitext(args.model)[0] + ".json"
@@ -49,4 +77,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())
