@@ -430,6 +430,22 @@ class LiteInterpreter(Interpreter):
             dev = self._devices[(id(engine), key)] = GraphDevice(engine, plan)
         return dev
 
+    def _network(self, engine):
+        """The network of the batched pipeline (cpx/pipeline.py) on `engine`: the device graph for the crop kernel's
+        [n, side, side, 2] sample -- the channel map orders and repeats its two channels into the graph's, the crop
+        kernel has applied the input scaling (limits_flags) -- one per engine, as _device keeps them."""
+        from .tflite_graph import GraphNetwork
+
+        if self._graph is None:
+            self.load_model()
+        side = self.params.square_width * self.params.frame_size
+        dev = self._device(engine, (side, side, 2))
+        nets = self.__dict__.setdefault("_nets", {})
+        net = nets.get(id(engine))
+        if net is None or net.dev is not dev:
+            net = nets[id(engine)] = GraphNetwork(dev)
+        return net
+
     def predict(self, frames):
         """frames: device tensor (from preprocess_segments) or host float32 [N, H, W, C] -> numpy [N, n_labels]."""
         import torch

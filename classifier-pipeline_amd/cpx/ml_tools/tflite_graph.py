@@ -492,6 +492,25 @@ class GraphDevice:
         self.eng.synchronize()
         return out
 
+    def forward_async(self, x, out):
+        """forward() for a caller that orders its work by the engine's stream (the batched pipeline): the launches are
+        enqueued behind what that stream holds, straight into the caller's `out` ([N, C_out], or a view of its rows);
+        no host synchronisation before or after and no allocation -- unless the handle's arena has to grow."""
+        H, W, Cin = self.plan.input_shape
+        assert x.dtype == self.torch.float32 and x.is_contiguous() and tuple(x.shape[1:]) == (H, W, Cin), (tuple(x.shape), self.plan.input_shape)
+        N = int(x.shape[0])
+        assert self.out_slice is None and out.dtype == self.torch.float32 and out.is_contiguous() and \
+            out.numel() == N * int(np.prod(self.plan.output_shape)), tuple(out.shape)
+        for attempt in range(2):
+            rc = self.lib.cpx_graph_forward(self._graph, C.c_void_p(x.data_ptr()), N, C.c_void_p(out.data_ptr()))
+            if rc == -6 and attempt == 0:   # CPX_ERR_NOMEM: as forward()
+                self.eng.synchronize()
+                self.torch.cuda.empty_cache()
+                continue
+            break
+        if rc != 0:
+            raise _lib.CpxError(rc, self.eng._err())
+
     def close(self):
         if self._graph is not None:
             if self.eng.h:   # a closed engine has already freed its graphs
@@ -503,3 +522,20 @@ class GraphDevice:
             self.close()
         except Exception:
             pass
+
+
+class GraphNetwork:
+    """A GraphDevice behind the batched pipeline's network protocol (WRResNetDevice's: `.eng` and
+    forward_async(x, logits, probs) on the engine's stream).  A graph hands out one tensor -- the probabilities -- so
+    there are no logits (has_logits: the pipeline allocates none and reports None)."""
+
+    has_logits = False
+
+    def __init__(self, dev):
+        self.dev, self.eng = dev, dev.eng
+        # a forward over N samples holds N times this much arena: the pipeline clamps its chunk to its memory budget
+        self.arena_bytes_per_sample = dev.plan.arena_bytes_per_sample
+
+    def forward_async(self, x, logits, probs):
+        assert logits is None
+        self.dev.forward_async(x, probs)

@@ -40,7 +40,8 @@ class BatchResult:
 
 class BatchPipeline:
     def __init__(self, engine, network=None, n_labels=17, fp_index=-1, frame_size=32, square_width=5,
-                 track_params=None, filter_params=None, cnn_chunk=512, want_regions=False, limits_flags=0):
+                 track_params=None, filter_params=None, cnn_chunk=512, want_regions=False, limits_flags=0,
+                 network_bytes=None):
         self.want_regions = want_regions  # per-frame region lists from the association (the trackless thumbnail)
         self.limits_flags = limits_flags  # _lib.LIMITS_*: the model's normalisation variant (cpx_track_limits_batch_ex)
         self.eng = engine
@@ -52,11 +53,23 @@ class BatchPipeline:
         self.fp = filter_params or make_filter_params(max_active_tracks=self.tp.max_active_tracks,
                                                       max_tracks_per_clip=self.tp.max_tracks)
         self.cnn_chunk = cnn_chunk
+        # a network whose working memory grows with the samples of a forward (a TFLite graph's arena: N x
+        # arena_bytes_per_sample) gets chunks that keep it inside this many bytes; None: cnn_chunk alone decides
+        self.network_bytes = network_bytes
         self._sample_buf = None
 
     def _check(self, rc):
         if rc != 0:
             raise CpxError(rc, self.eng._err())
+
+    def sample_chunk(self):
+        """Samples per network call at the most: cnn_chunk, clamped by network_bytes for a network that states its
+        arena_bytes_per_sample."""
+        chunk = max(1, int(self.cnn_chunk))
+        per = getattr(self.net, "arena_bytes_per_sample", 0)
+        if self.network_bytes is not None and per:
+            chunk = max(1, min(chunk, int(self.network_bytes) // int(per)))
+        return chunk
 
     def run(self, frames_dev, clip_offsets, meta, outputs=None, classify=True, keep_samples=False, sub_batches=1):
         """All stages for the clips of one batch.  Everything -- the cpx kernels and the few torch ops between them --
@@ -66,6 +79,9 @@ class BatchPipeline:
         stream): the batch is cut into that many groups of clips and the HBM-bound track stage of group k+1 runs
         while the MFMA-bound network works on group k."""
         if sub_batches > 1 and classify and self.net is not None and not keep_samples:
+            if not getattr(self.net, "has_logits", True):
+                raise NotImplementedError("sub_batches > 1 (BatchPipeline._run_overlapped) takes the WR-ResNet network only: "
+                                          "a TFLite graph network runs through run(sub_batches=1) / classify_front")
             return self._run_overlapped(frames_dev, clip_offsets, meta, outputs, sub_batches)
         eng, t = self.eng, self.eng.torch
         t.cuda.current_stream(eng.device).synchronize()  # the caller's inputs (made on its stream) are complete
@@ -102,7 +118,8 @@ class BatchPipeline:
             fp_k.max_active_tracks, fp_k.max_tracks_per_clip = tp_k.max_active_tracks, tp_k.max_tracks
             sub = BatchPipeline(eng_k, self.net, n_labels=self.n_labels, fp_index=self.fp_index, frame_size=self.fs,
                                 square_width=self.sq, track_params=tp_k, filter_params=fp_k, cnn_chunk=self.cnn_chunk,
-                                want_regions=self.want_regions, limits_flags=self.limits_flags)
+                                want_regions=self.want_regions, limits_flags=self.limits_flags,
+                                network_bytes=self.network_bytes)
             with t.cuda.stream(eng_k.torch_stream()):
                 part = sub._front(fr, np.array([0, f1 - f0], np.int32), meta[f0:f1], None, classify, pre=(res_k, assoc_k))
                 if classify and part.n_tracks and part.n_samples:
@@ -139,10 +156,12 @@ class BatchPipeline:
         reqs, limits, per = out.reqs_dev, out.limits_dev, self.sq * self.sq
         side = self.sq * self.fs
         probs = t.empty((n_samples, self.n_labels), dtype=t.float32, device=dev)
-        logits = t.empty((n_samples, self.n_labels), dtype=t.float32, device=dev)
+        # (a TFLite graph network hands out probabilities only: no logits buffer, out.logits is None)
+        has_logits = getattr(self.net, "has_logits", True)
+        logits = t.empty((n_samples, self.n_labels), dtype=t.float32, device=dev) if has_logits else None
         # equal chunks of at most cnn_chunk samples: a short last chunk runs the network's persistent kernels on a sliver of
         # the chip (92 samples behind three chunks of 2048 cost 4.3 ms of a 388 ms step, profiles/r06_step_timeline.txt)
-        n_chunks = -(-n_samples // max(1, self.cnn_chunk))
+        n_chunks = -(-n_samples // self.sample_chunk())
         chunk = -(-n_samples // n_chunks)
         if keep_samples:
             out.samples_dev = t.empty((n_samples, side, side, 2), dtype=t.float32, device=dev)
@@ -169,8 +188,8 @@ class BatchPipeline:
                     ev = t.cuda.Event()
                     ev.record(s_eng)
                     s_net.wait_event(ev)
-                self.net.forward_async(buf, logits[s0:s1], probs[s0:s1])
-                if os.environ.get("CPX_CNN_DEBUG_OVF") and self.net.eng.cnn_last_overflow():
+                self.net.forward_async(buf, logits[s0:s1] if has_logits else None, probs[s0:s1])
+                if has_logits and os.environ.get("CPX_CNN_DEBUG_OVF") and self.net.eng.cnn_last_overflow():
                     per = buf.reshape(buf.shape[0], -1)
                     mx = per.abs().amax(dim=1)
                     print("overflow forward: samples %d..%d, input max %.1f min %.1f nan %d; per-sample max: top %s; "

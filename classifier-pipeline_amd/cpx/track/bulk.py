@@ -347,6 +347,25 @@ def frame_meta_from_slots(slots, process_background=False):
     return m
 
 
+NETWORK_BYTES = 4 << 30   # run_files_bulk's default budget for a graph network's arena
+
+
+def has_device_network(interp):
+    """Whether the batched forward can drive this interpreter: it builds a device network (_network(engine): the
+    WR-ResNet's, or a TFLite graph's) and its model is not served by another process."""
+    if interp.run_over_network or not callable(getattr(interp, "_network", None)):
+        return False
+    # (a WR-ResNet interpreter of another family holds no weights: its samples go to a model server)
+    return getattr(interp, "_weights", True) is not None
+
+
+def require_device_network(interp):
+    if not has_device_network(interp):
+        raise NotImplementedError("only the WR-ResNet network runs in the batched forward: a TFLite graph model "
+                                  "(LiteInterpreter) or a model served over the network is classified by the "
+                                  "one-file path (ClipClassifier.process_file / process_files)")
+
+
 class BulkTracker:
     """Tracks decoded groups and writes the metadata; one instance per TrackExtractor.extract call."""
 
@@ -362,6 +381,10 @@ class BulkTracker:
         self.lib = None
         self.decode_engine = None   # a handle (= HIP stream) of its own for the decode stage of run_files_bulk
         self.cnn_chunk = 2048
+        # device memory a network call may take for working memory that grows with its samples (a TFLite graph's arena,
+        # N x arena_bytes_per_sample: 2,048 samples of a 160 x 160 Inception-v3 would hold several times this): such a
+        # network's chunks are cut to fit (run_files_bulk's network_bytes, shared between its device lanes)
+        self.network_bytes = NETWORK_BYTES
         self._algorithm_text = {}
         self.timings = {"decode_s": 0.0, "device_s": 0.0, "host_s": 0.0, "write_s": 0.0, "files": 0, "frames": 0}
 
@@ -437,14 +460,11 @@ class BulkTracker:
             for model, interp in classifiers:
                 if interp.params.square_width != sq:
                     raise NotImplementedError("models with different square_width in one run")
-                if interp.run_over_network or getattr(interp, "_weights", None) is None:
-                    raise NotImplementedError("only the WR-ResNet network runs in the batched forward: a TFLite graph model "
-                                              "(LiteInterpreter) or a model served over the network is classified by the "
-                                              "one-file path (ClipClassifier.process_file / process_files)")
+                require_device_network(interp)
                 fpi = interp.labels.index("false-positive") if "false-positive" in interp.labels else -1
                 mp = BatchPipeline(eng, interp._network(eng), n_labels=len(interp.labels), fp_index=fpi,
                                    frame_size=interp.params.frame_size, square_width=sq, track_params=tp,
-                                   filter_params=fp, cnn_chunk=self.cnn_chunk)
+                                   filter_params=fp, cnn_chunk=self.cnn_chunk, network_bytes=self.network_bytes)
                 t0 = time.time()
                 probs = None
                 if front.n_tracks and front.n_samples:
@@ -978,14 +998,15 @@ def auto_batch_files(n_files):
 
 def run_files_bulk(filenames, config, to_stdout=False, save_meta=True, device=0, batch_files=None, want_text=False,
                    stager=None, tracker=None, clip_classifier=None, blobs=None, track_files=1024,
-                   decode_bytes=8 << 30, track_frames=400000, meta_pool=None, device_lanes=2):
+                   decode_bytes=8 << 30, track_frames=400000, meta_pool=None, device_lanes=2, network_bytes=None):
     """extract_file -- or, with a ClipClassifier, process_file(track=True) -- for many recordings at device speed.
     Writes <file>.txt (or prints with to_stdout) and returns ({filename: metadata text (want_text) or True, or an
     "error: ..." string for a skipped file}, tracker with timings).  Files that cannot take the batched path are
     retried through the one-file path.  blobs: the recordings as byte strings already in memory (names in
     `filenames`; nothing is read from disk; one the batch refuses is retried from its bytes by the host reader).
     batch_files: recordings per decode launch (and per read-ahead batch; None: auto_batch_files); track_files: recordings
-    per tracking group."""
+    per tracking group; network_bytes: device memory for the arena of a TFLite graph network's forwards (None:
+    NETWORK_BYTES) -- its sample chunks are cut to fit, which changes no result."""
     import torch
 
     from .cliptrackextractor import default_engine
@@ -998,6 +1019,9 @@ def run_files_bulk(filenames, config, to_stdout=False, save_meta=True, device=0,
     if blobs is None:
         stager = stager or FileStager(torch)
     tracker = tracker or BulkTracker(config, device)
+    # (from the constant, as cnn_chunk below: a tracker reused by a later call does not hand on a lane's share)
+    base_network_bytes = NETWORK_BYTES if network_bytes is None else int(network_bytes)
+    tracker.network_bytes = base_network_bytes
     eng0 = default_engine(device)
     indent = None if (to_stdout or (clip_classifier is not None and config.classify.meta_to_stdout)) else 4
     classifiers, models = [], []
@@ -1299,6 +1323,7 @@ def run_files_bulk(filenames, config, to_stdout=False, save_meta=True, device=0,
             k = lanes_now[0]
             track_files, track_frames = max(64, base_track_files // k), max(20000, base_track_frames // k)
             tracker.cnn_chunk = max(256, 2048 // k)
+            tracker.network_bytes = base_network_bytes // k
             groups = [sub for g in decoded.groups for sub in g.split(track_files, track_frames)]
             ctx = dict(paths=paths, base=order[bi], texts={}, retry=dict(decoded.errors), t0=t0, open=len(groups), submitted=False,
                        n_ok=sum(len(g.files) for g in decoded.groups), futures=[],
