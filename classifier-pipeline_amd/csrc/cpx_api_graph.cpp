@@ -1,0 +1,203 @@
+// cpx_api_graph.cpp -- the float32 TFLite graph executor's entry points (include/cpx.h: cpx_graph_*).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "cpx_internal.h"
+
+static_assert(sizeof(cpx_graph_tensor) == 32 && sizeof(cpx_graph_op) == 112, "graph layouts are part of the ABI");
+
+// ---- float32 TFLite graph executor (LiteInterpreter.predict, ml_tools/interpreter.py:520-560) ------------------------
+struct cpx_graph {
+  cpx_handle* h = nullptr;
+  std::vector<cpx_graph_op> ops;
+  std::vector<cpx_graph_tensor> tensors;
+  int input = 0, output = 0;
+  size_t arena_floats = 0;  // per sample
+};
+
+void graph_free(cpx_graph* g) { delete g; }
+
+extern "C" {
+
+// what one operator asks of its tensors; every kernel masks by these sizes, so a graph that passes cannot reach outside
+// the views it names (the weights' extents are the caller's: device pointers cannot be measured)
+static const char* graph_check_op(const cpx_graph_op& o, const std::vector<cpx_graph_tensor>& t, int input, int output) {
+  const int nt = (int)t.size();
+  if (o.in0 < 0 || o.in0 >= nt || o.out < 0 || o.out >= nt || o.in1 >= nt) return "tensor id out of range";
+  if (o.out == input || o.in0 == output || o.in1 == output) return "the input is written or the output read";
+  const cpx_graph_tensor &a = t[o.in0], &y = t[o.out];
+  if (o.out_c_offset != y.c_offset || o.out_c_stride != y.c_stride) return "output slice differs from the tensor's";
+  if (o.activation != CPX_GRAPH_ACT_NONE && o.activation != CPX_GRAPH_ACT_RELU && o.activation != CPX_GRAPH_ACT_RELU6)
+    return "unknown activation";
+  const bool same_hw = a.H == y.H && a.W == y.W;
+  switch (o.kind) {
+    case CPX_GRAPH_CONV:
+    case CPX_GRAPH_MAX_POOL:
+    case CPX_GRAPH_AVG_POOL: {
+      const bool conv = o.kind == CPX_GRAPH_CONV;
+      if (o.kh < 1 || o.kw < 1 || o.kh > 7 || o.kw > 7) return "kernel sides are 1 to 7";
+      if (o.stride_h < 1 || o.stride_w < 1 || o.stride_h > (conv ? 2 : 7) || o.stride_w > (conv ? 2 : 7)) return "bad stride";
+      if (o.pad_top < 0 || o.pad_left < 0 || o.pad_bottom < 0 || o.pad_right < 0 || o.pad_top >= o.kh || o.pad_bottom >= o.kh ||
+          o.pad_left >= o.kw || o.pad_right >= o.kw)
+        return "bad padding";
+      const int hh = a.H + o.pad_top + o.pad_bottom - o.kh, ww = a.W + o.pad_left + o.pad_right - o.kw;
+      if (hh < 0 || ww < 0 || y.H != hh / o.stride_h + 1 || y.W != ww / o.stride_w + 1) return "output size does not follow from kernel, stride and pads";
+      if (conv && !o.weights) return "CONV without weights";
+      if (!conv && a.C != y.C) return "pool changes the channel count";
+      break;
+    }
+    case CPX_GRAPH_ADD:
+      if (o.in1 < 0) return "ADD needs two inputs";
+      if (!same_hw || a.C != y.C || t[o.in1].H != y.H || t[o.in1].W != y.W || t[o.in1].C != y.C) return "ADD of different shapes";
+      break;
+    case CPX_GRAPH_AFFINE:
+    case CPX_GRAPH_LOGISTIC:
+    case CPX_GRAPH_SOFTMAX:
+      if (!same_hw || a.C != y.C) return "element-wise operator changes the shape";
+      break;
+    case CPX_GRAPH_MEAN:
+      if (y.H != 1 || y.W != 1 || a.C != y.C) return "MEAN gives 1 x 1 x C";
+      break;
+    case CPX_GRAPH_FC:
+      if (a.H != 1 || a.W != 1 || y.H != 1 || y.W != 1 || !o.weights) return "FULLY_CONNECTED takes and gives 1 x 1 x C";
+      break;
+    case CPX_GRAPH_PAD:
+      if (o.pad_top < 0 || o.pad_left < 0 || o.pad_bottom < 0 || o.pad_right < 0 || a.C != y.C ||
+          y.H != a.H + o.pad_top + o.pad_bottom || y.W != a.W + o.pad_left + o.pad_right)
+        return "PAD sizes do not add up";
+      break;
+    case CPX_GRAPH_CHANNEL_MAP:
+      if (!same_hw || o.n_map != y.C || o.n_map < 1 || o.n_map > 4) return "channel map of 1 to 4 output channels";
+      for (int c = 0; c < o.n_map; ++c)
+        if (o.channel_map[c] < 0 || o.channel_map[c] >= a.C) return "channel map index out of range";
+      break;
+    default:
+      return "unknown operator kind";
+  }
+  return nullptr;
+}
+
+int cpx_graph_create(cpx_handle* h, const cpx_graph_op* ops, int n_ops, const cpx_graph_tensor* tensors, int n_tensors,
+                     int input_tensor, int output_tensor, cpx_graph** out) {
+  if (!h) return CPX_ERR_INVALID;
+  if (!ops || !tensors || !out || n_ops < 1 || n_tensors < 2 || input_tensor < 0 || input_tensor >= n_tensors ||
+      output_tensor < 0 || output_tensor >= n_tensors || input_tensor == output_tensor)
+    return fail(h, CPX_ERR_INVALID, "cpx_graph_create: bad argument");
+  *out = nullptr;
+  cpx_graph* g = new (std::nothrow) cpx_graph();
+  if (!g) return fail(h, CPX_ERR_NOMEM, "cpx_graph_create: out of memory");
+  g->h = h;
+  g->ops.assign(ops, ops + n_ops);
+  g->tensors.assign(tensors, tensors + n_tensors);
+  g->input = input_tensor;
+  g->output = output_tensor;
+  for (int i = 0; i < n_tensors; ++i) {
+    const cpx_graph_tensor& t = g->tensors[i];
+    const bool ext = i == input_tensor || i == output_tensor;
+    // a sample is indexed in 32 bits
+    if (t.H < 1 || t.W < 1 || t.C < 1 || t.c_offset < 0 || t.c_stride < t.c_offset + t.C ||
+        (double)t.H * t.W * t.c_stride >= 2147483648.0 || (!ext && t.arena_offset < 0) ||
+        (i == input_tensor && (t.c_offset != 0 || t.c_stride != t.C))) {
+      delete g;
+      return fail(h, CPX_ERR_INVALID, "cpx_graph_create: bad tensor");
+    }
+    if (!ext) g->arena_floats = std::max(g->arena_floats, (size_t)t.arena_offset + (size_t)t.H * t.W * t.c_stride);
+  }
+  for (int i = 0; i < n_ops; ++i) {
+    if (const char* why = graph_check_op(g->ops[i], g->tensors, input_tensor, output_tensor)) {
+      delete g;
+      h->err = "cpx_graph_create: operator " + std::to_string(i) + ": " + why;
+      return CPX_ERR_INVALID;
+    }
+  }
+  h->graphs.push_back(g);
+  *out = g;
+  return CPX_OK;
+}
+
+void cpx_graph_destroy(cpx_graph* g) {
+  if (!g) return;
+  cpx_handle* h = g->h;
+  hipSetDevice(h->device);
+  hipStreamSynchronize(h->stream);
+  h->graphs.erase(std::remove(h->graphs.begin(), h->graphs.end(), g), h->graphs.end());
+  graph_free(g);
+}
+
+int cpx_graph_arena_bytes(const cpx_graph* g, int N, size_t* bytes) {
+  if (!g || !bytes || N < 0) return CPX_ERR_INVALID;
+  *bytes = g->arena_floats * (size_t)N * sizeof(float);
+  return CPX_OK;
+}
+
+int cpx_graph_arena_allocated(const cpx_handle* h, size_t* bytes) {
+  if (!h || !bytes) return CPX_ERR_INVALID;
+  *bytes = h->graph_arena_floats * sizeof(float);
+  return CPX_OK;
+}
+
+int cpx_graph_forward(cpx_graph* g, const float* in_dev, int N, float* out_dev) {
+  if (!g) return CPX_ERR_INVALID;
+  cpx_handle* h = g->h;
+  if (!in_dev || !out_dev || N < 1) return fail(h, CPX_ERR_INVALID, "cpx_graph_forward: bad argument");
+  CPX_ENTER(h);
+  const size_t need = g->arena_floats * (size_t)N;
+  if (need > h->graph_arena_floats) {
+    if (h->graph_arena) {
+      CPX_HIP(h, hipStreamSynchronize(h->stream));  // an earlier forward may still be using it
+      hipFree(h->graph_arena);
+    }
+    h->graph_arena = nullptr;
+    h->graph_arena_floats = 0;
+    hipError_t e = hipMalloc((void**)&h->graph_arena, need * sizeof(float));
+    if (e != hipSuccess) return fail(h, CPX_ERR_NOMEM, "cpx_graph_forward: arena hipMalloc", e);
+    h->graph_arena_floats = need;
+  }
+  auto view = [&](int id) {
+    const cpx_graph_tensor& t = g->tensors[id];
+    cpx::GraphView v{};
+    v.H = t.H;
+    v.W = t.W;
+    v.C = t.C;
+    v.cstride = t.c_stride;
+    v.sample_stride = (size_t)t.H * t.W * t.c_stride;
+    if (id == g->input)
+      v.p = const_cast<float*>(in_dev);
+    else if (id == g->output)
+      v.p = out_dev + t.c_offset;
+    else
+      v.p = h->graph_arena + (size_t)t.arena_offset * N + t.c_offset;
+    return v;
+  };
+  for (const cpx_graph_op& o : g->ops) {
+    cpx::GraphOpArgs a{};
+    a.kind = o.kind;
+    a.N = N;
+    a.in0 = view(o.in0);
+    if (o.in1 >= 0) a.in1 = view(o.in1);
+    a.out = view(o.out);
+    a.kh = o.kh;
+    a.kw = o.kw;
+    a.stride_h = o.stride_h;
+    a.stride_w = o.stride_w;
+    a.pad_top = o.pad_top;
+    a.pad_left = o.pad_left;
+    a.act = o.activation;
+    a.n_map = o.n_map;
+    for (int c = 0; c < 4; ++c) a.map[c] = o.channel_map[c];
+    a.param = o.param;
+    a.weights = o.weights;
+    a.scale = o.scale;
+    a.shift = o.shift;
+    cpx::launch_graph_op(a, h->stream);
+  }
+  CPX_HIP(h, hipGetLastError());
+  return CPX_OK;
+}
+
+}  // extern "C"

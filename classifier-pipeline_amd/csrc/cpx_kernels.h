@@ -1,5 +1,5 @@
 // cpx_kernels.h -- internal interface between the C-ABI translation unit
-// (cpx_api.cpp) and the HIP kernels.  Not part of the public ABI.
+// (cpx_api*.cpp) and the HIP kernels.  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

@@ -258,6 +258,77 @@ def test_fp16x2_forms_are_f32_accurate_per_block(monkeypatch, env, value, want):
     _assert_f32_accurate((env, value), "fp16x2", errs, herr)
 
 
+def _launch_table(eng, mode):
+    """One forward with taps of the 17-label random model on 2 x 48 x 48 x 2 -> {key: (launches, flops)}, the complete
+    conv_timing table of that forward."""
+    from cpx.ml_tools import wrresnet as wr
+
+    x = _input(2, 48, 48, 1)
+    w = _model(2, x)
+    eng.set_cnn_math(mode)
+    net = wr.WRResNetDevice(eng, w, 17)
+    eng.conv_timing(True)
+    _run(net, eng, x)
+    table = eng.conv_timing()
+    eng.conv_timing(False)
+    net.close()
+    return {key: (launches, flops) for key, (launches, _, flops) in table.items()}
+
+
+# The complete conv_timing table of one forward, {key: (launches, FLOPs)}, per (math mode, fusion form); recorded on an
+# MI355X from the build BEFORE the forward was split into a plan and an executor, so it pins the dispatch that build
+# had.  Keys: (Cin / groups) * 10000 + (Cout / groups) * 10 + stride (+ 5 for a 1x1 layer); "stride 4" = a fused block.
+# The FLOP totals are exact doubles the host computes from the shapes (2 N Ho Wo Cout Cin/groups k^2 per launch).
+LAUNCH_TABLES = {
+    'f32': {10081: (1, 1327104.0), 80321: (1, 42467328.0), 80326: (1, 4718592.0), 320321: (5, 849346560.0),
+        320642: (1, 84934656.0), 320647: (1, 9437184.0), 640641: (5, 849346560.0), 641283: (1, 37748736.0),
+        641288: (1, 4194304.0), 1281281: (5, 377487360.0)},
+    'bf16x3': {10081: (1, 1327104.0), 80321: (1, 42467328.0), 320321: (5, 849346560.0), 320642: (1, 84934656.0),
+        640641: (5, 849346560.0), 641283: (1, 37748736.0), 1281281: (5, 377487360.0)},
+    'bf16x2': {10081: (1, 1327104.0), 80321: (1, 42467328.0), 320321: (5, 849346560.0), 320642: (1, 84934656.0),
+        640641: (5, 849346560.0), 641283: (1, 37748736.0), 1281281: (5, 377487360.0)},
+    'fp16x2': {80324: (1, 213663744.0), 320324: (2, 679477248.0), 320642: (1, 84934656.0),
+        640641: (5, 849346560.0), 641283: (1, 37748736.0), 1281281: (5, 377487360.0)},
+    'fp16x2 CPX_CNN_BLOCK_FUSION=0': {10081: (1, 1327104.0), 80321: (1, 42467328.0), 320321: (5, 849346560.0),
+        320642: (1, 84934656.0), 640641: (5, 849346560.0), 641283: (1, 37748736.0), 1281281: (5, 377487360.0)},
+    'fp16x2 CPX_CNN_BLOCK_FUSION=1': {10081: (1, 1327104.0), 80321: (1, 42467328.0), 320321: (1, 169869312.0),
+        320324: (2, 679477248.0), 320642: (1, 84934656.0), 640641: (5, 849346560.0), 641283: (1, 37748736.0),
+        1281281: (5, 377487360.0)},
+    'fp16x2 CPX_CNN_FUSE_SHORTCUT=0': {10081: (1, 1327104.0), 80321: (1, 42467328.0), 80326: (1, 4718592.0),
+        320321: (1, 169869312.0), 320324: (2, 679477248.0), 320642: (1, 84934656.0), 320647: (1, 9437184.0),
+        640641: (5, 849346560.0), 641283: (1, 37748736.0), 641288: (1, 4194304.0), 1281281: (5, 377487360.0)},
+    'fp16x2 CPX_CNN_FUSE_CONV1=0': {10081: (1, 1327104.0), 80324: (1, 212336640.0), 320324: (2, 679477248.0),
+        320642: (1, 84934656.0), 640641: (5, 849346560.0), 641283: (1, 37748736.0), 1281281: (5, 377487360.0)},
+}
+
+
+@pytest.mark.parametrize("case", ["f32", "bf16x3", "bf16x2", "fp16x2"] + ["fp16x2 %s=%s" % (e, v) for e, v, _ in FORMS])
+def test_forward_launch_table(engine, monkeypatch, case):
+    """Which launches a forward is made of: every conv_timing key, its launch count and its FLOP total, and no key
+    beyond them, for each math mode on a default handle and for fp16x2 under each switch of FORMS (a fresh engine
+    created under the switch).  2 x 48 x 48: stage 2 at 48 x 48 takes the fused first block with conv1_1 inside and
+    the two later fused blocks, stage 3 runs at 24 x 24, stage 4 at 8 x 8 (the strided layers, the plane hand-off and
+    the flattened stage-4 route)."""
+    from cpx.engine import TrackEngine
+
+    mode, _, form = case.partition(" ")
+    if not form:
+        got = _launch_table(engine, mode)
+        engine.set_cnn_math(engine.DEFAULT_CNN_MATH)
+    else:
+        env, value = form.split("=")
+        assert (env, value) in [(e, v) for e, v, _ in FORMS]
+        monkeypatch.setenv(env, value)
+        eng = TrackEngine(model="lepton3")
+        monkeypatch.delenv(env)
+        try:
+            got = _launch_table(eng, mode)
+        finally:
+            eng.close()
+    print("launch table %-36s %r" % (case, got))
+    assert got == LAUNCH_TABLES[case], (case, got)
+
+
 def test_fp16x2_unsplit_block_kernel_is_f32_accurate_per_block():
     """CPX_BLOCK32_SPLIT=0 (conv_block32_kernel instead of the split-role conv_block32s_kernel) is read once per process:
     this form runs in a child."""
