@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "cpx_internal.h"
+#include "cpx_schedule_core.h"
 
 static_assert(sizeof(cpx_component) == 32, "cpx_component layout is part of the ABI");
 static_assert(sizeof(cpx_frame_info) == 80, "cpx_frame_info layout is part of the ABI");
@@ -63,63 +64,21 @@ WsLayout ws_layout(const cpx_config& c, int B, bool need_filt_state) {
   return l;
 }
 
-struct Schedule {
-  std::vector<int> clip_first, proc_off, proc_idx, proc_ffc, order;
-  int total = 0, max_proc = 0;
-};
-
-// which frames are processed (background frames only initialise, cliptrackextractor.py:167-168)
-// and their FFC flags (cptvmotiondetector.py:211-223 with int milliseconds)
-int build_schedule(cpx_handle* h, const int32_t* clip_offsets, const cpx_frame_meta* meta, int B, Schedule* sc) {
-  sc->total = clip_offsets[B];
-  sc->clip_first.resize(B);
-  sc->proc_off.assign(B + 1, 0);
-  sc->proc_idx.reserve(sc->total);
-  sc->proc_ffc.reserve(sc->total);
-  for (int b = 0; b < B; ++b) {
-    const int f0 = clip_offsets[b], f1 = clip_offsets[b + 1];
-    if (f1 <= f0) return fail(h, CPX_ERR_INVALID, "empty clip in batch");
-    sc->clip_first[b] = f0;
-    for (int f = f0; f < f1; ++f) {
-      if (meta[f].background_frame) continue;
-      sc->proc_idx.push_back(f);
-      int ffc = 0;
-      if (meta[f].has_times) ffc = (meta[f].time_on_ms - meta[f].last_ffc_ms) < 9 ? 1 : 0;
-      sc->proc_ffc.push_back(ffc);
-    }
-    sc->proc_off[b + 1] = (int)sc->proc_idx.size();
-    const int np = sc->proc_off[b + 1] - sc->proc_off[b];
-    if (np > h->cfg.max_frames) return fail(h, CPX_ERR_INVALID, "clip longer than max_frames");
-    sc->max_proc = std::max(sc->max_proc, np);
+int build_schedule(cpx_handle* h, const int32_t* clip_offsets, const cpx_frame_meta* meta, int B, cpx::Schedule* sc) {
+  switch (cpx::schedule_build(clip_offsets, meta, B, h->cfg.max_frames, sc)) {
+    case cpx::SchedError::EmptyClip: return fail(h, CPX_ERR_INVALID, "empty clip in batch");
+    case cpx::SchedError::TooLong: return fail(h, CPX_ERR_INVALID, "clip longer than max_frames");
+    case cpx::SchedError::Ok: break;
   }
-  // longest clips first: one workgroup walks a whole clip, and the dispatcher hands out workgroups in index order
-  sc->order.resize(B);
-  for (int b = 0; b < B; ++b) sc->order[b] = b;
-  std::stable_sort(sc->order.begin(), sc->order.end(), [&](int x, int y) {
-    return sc->proc_off[x + 1] - sc->proc_off[x] > sc->proc_off[y + 1] - sc->proc_off[y];
-  });
   return CPX_OK;
 }
 
-// layout in sched_dev: clip_first[B] | proc_off[B+1] | proc_idx[n] | proc_ffc[n] | order[B]
-int upload_schedule(cpx_handle* h, const Schedule& sc, int B) {
-  const int n = std::max((int)sc.proc_idx.size(), 1);
-  const size_t ints = (size_t)B + (B + 1) + 2 * (size_t)n + (size_t)B;
-  if (ints > h->sched_ints) {
-    if (h->sched_dev) hipFree(h->sched_dev);
-    h->sched_dev = nullptr;
-    h->sched_ints = 0;
-    hipError_t e = hipMalloc((void**)&h->sched_dev, ints * sizeof(int));
-    if (e != hipSuccess) return fail(h, CPX_ERR_NOMEM, "schedule hipMalloc", e);
-    h->sched_ints = ints;
-  }
-  std::vector<int> flat(ints, 0);
-  std::copy(sc.clip_first.begin(), sc.clip_first.end(), flat.begin());
-  std::copy(sc.proc_off.begin(), sc.proc_off.end(), flat.begin() + B);
-  std::copy(sc.proc_idx.begin(), sc.proc_idx.end(), flat.begin() + B + (B + 1));
-  std::copy(sc.proc_ffc.begin(), sc.proc_ffc.end(), flat.begin() + B + (B + 1) + n);
-  std::copy(sc.order.begin(), sc.order.end(), flat.begin() + B + (B + 1) + 2 * (size_t)n);
-  CPX_HIP(h, hipMemcpyAsync(h->sched_dev, flat.data(), ints * sizeof(int), hipMemcpyHostToDevice, h->stream));
+// the schedule in h->sched; *sl says where its arrays lie there
+int upload_schedule(cpx_handle* h, const cpx::Schedule& sc, int B, cpx::SchedLayout* sl) {
+  const std::vector<int> flat = cpx::schedule_flatten(sc, B);
+  *sl = cpx::SchedLayout::of(B, (int)sc.proc_idx.size());
+  if (int rc = h->sched.grow(h, flat.size() * sizeof(int), "schedule hipMalloc")) return rc;
+  CPX_HIP(h, hipMemcpyAsync(h->sched.p, flat.data(), flat.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
   CPX_HIP(h, hipStreamSynchronize(h->stream));  // `flat` dies with this scope
   return CPX_OK;
 }
@@ -179,8 +138,8 @@ int cpx_create(int device_id, const cpx_config* cfg, cpx_handle** out) {
       const double wr = std::nearbyint((double)fixed_point_mult * wv);
       lut[a2] = (wr < 0.001 * fixed_point_mult) ? 0 : (int)wr;
     }
-    if (lut[63] != 0 || hipMalloc((void**)&h->nlm_lut_dev, 64 * sizeof(int)) != hipSuccess ||
-        hipMemcpy(h->nlm_lut_dev, lut.data(), 64 * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
+    if (lut[63] != 0 || h->nlm_lut_dev.grow(h, 64 * sizeof(int), "NLM weight table allocation") ||
+        hipMemcpy(h->nlm_lut_dev.p, lut.data(), 64 * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
       cpx_destroy(h);
       return CPX_ERR_HIP;
     }
@@ -199,13 +158,13 @@ int cpx_create(int device_id, const cpx_config* cfg, cpx_handle** out) {
     if (hi > 536870912.0) hi = 536870912.0;        // beyond any f - bg: never kept (and 2 hi a positive int32)
     thr[k] = 2u * (uint32_t)hi - (near ? 1u : 0u);
   }
-  if (hipMalloc((void**)&h->wthr_dev, thr.size() * sizeof(uint32_t)) != hipSuccess ||
-      hipMemcpy(h->wthr_dev, thr.data(), thr.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+  if (h->wthr_dev.grow(h, thr.size() * sizeof(uint32_t), "threshold table allocation") ||
+      hipMemcpy(h->wthr_dev.p, thr.data(), thr.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
     cpx_destroy(h);
     return CPX_ERR_HIP;
   }
-  if (hipMalloc(&h->wtab_dev, wt.size() * sizeof(double)) != hipSuccess ||
-      hipMemcpy(h->wtab_dev, wt.data(), wt.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+  if (h->wtab_dev.grow(h, wt.size() * sizeof(double), "weight table allocation") ||
+      hipMemcpy(h->wtab_dev.p, wt.data(), wt.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
       cpx::frame_kernel_attr_setup() != 0) {
     cpx_destroy(h);
     return CPX_ERR_HIP;
@@ -225,6 +184,14 @@ int cpx_create(int device_id, const cpx_config* cfg, cpx_handle** out) {
   return CPX_OK;
 }
 
+// The one place that names the handle's device buffers.  cpx_release_memory gives back the first list, the ones that
+// grow with the calls; cpx_destroy the small tables of the second as well.
+static void release_buffers(cpx_handle* h, bool all) {
+  for (DeviceBuffer* b : {&h->ws, &h->ws_assoc, &h->bf3_scratch, &h->cnn_arena, &h->graph_arena, &h->ir_scratch}) b->release();
+  if (!all) return;
+  for (DeviceBuffer* b : {&h->sched, &h->wtab_dev, &h->wthr_dev, &h->nlm_lut_dev, &h->cnn_ovf, &h->ir_bitmap}) b->release();
+}
+
 void cpx_destroy(cpx_handle* h) {
   if (!h) return;
   hipSetDevice(h->device);
@@ -235,18 +202,7 @@ void cpx_destroy(cpx_handle* h) {
   h->mog2s.clear();
   for (cpx_graph* g : h->graphs) graph_free(g);
   h->graphs.clear();
-  if (h->graph_arena) hipFree(h->graph_arena);
-  if (h->ws) hipFree(h->ws);
-  if (h->wtab_dev) hipFree(h->wtab_dev);
-  if (h->wthr_dev) hipFree(h->wthr_dev);
-  if (h->nlm_lut_dev) hipFree(h->nlm_lut_dev);
-  if (h->sched_dev) hipFree(h->sched_dev);
-  if (h->ws_assoc) hipFree(h->ws_assoc);
-  if (h->ir_scratch) hipFree(h->ir_scratch);
-  if (h->bf3_scratch) hipFree(h->bf3_scratch);
-  if (h->cnn_ovf) hipFree(h->cnn_ovf);
-  if (h->cnn_arena) hipFree(h->cnn_arena);
-  if (h->ir_bitmap) hipFree(h->ir_bitmap);
+  release_buffers(h, true);
   for (auto& e : h->conv_events) {
     hipEventDestroy(e.e0);
     hipEventDestroy(e.e1);
@@ -288,26 +244,9 @@ int cpx_release_memory(cpx_handle* h) {
   if (int rc = join_medians(h)) return rc;
   CPX_HIP(h, hipStreamSynchronize(h->stream));
   CPX_HIP(h, hipStreamSynchronize(h->stream2));
-  if (h->cnn_arena) hipFree(h->cnn_arena);
-  h->cnn_arena = nullptr;
-  h->cnn_arena_floats = 0;
-  if (h->graph_arena) hipFree(h->graph_arena);
-  h->graph_arena = nullptr;
-  h->graph_arena_floats = 0;
-  if (h->bf3_scratch) hipFree(h->bf3_scratch);
-  h->bf3_scratch = nullptr;
-  h->bf3_scratch_bytes = 0;
-  if (h->ws) hipFree(h->ws);
-  h->ws = nullptr;
-  h->ws_bytes = 0;
-  h->last_B = 0;
+  release_buffers(h, false);
+  h->last_B = 0;  // (the track state went with the workspace)
   h->state_packed = false;
-  if (h->ws_assoc) hipFree(h->ws_assoc);
-  h->ws_assoc = nullptr;
-  h->ws_assoc_bytes = 0;
-  if (h->ir_scratch) hipFree(h->ir_scratch);
-  h->ir_scratch = nullptr;
-  h->ir_scratch_bytes = 0;
   return CPX_OK;
 }
 
@@ -329,9 +268,9 @@ size_t cpx_track_workspace_bytes(const cpx_handle* h, int B, int total_frames) {
 // [n_prev, clip_offsets[1]) are processed (cpx_track_frame).
 // the state of the last track call in the layout every path but cpx_frame_kernel<true> reads (see cpx_handle::state_packed)
 static int unpack_state(cpx_handle* h) {
-  if (h->state_packed && h->ws && h->last_B > 0) {
+  if (h->state_packed && h->ws.p && h->last_B > 0) {
     const WsLayout lp = ws_layout(h->cfg, h->last_B, h->stream_filt_state);
-    char* base = (char*)h->ws;
+    char* base = h->ws.as<char>();
     cpx::launch_unpack_state((uint32_t*)(base + lp.wsum), (uint16_t*)(base + lp.kcnt),
                              (size_t)h->last_B * h->cfg.width * h->cfg.height, h->stream);
     CPX_HIP(h, hipGetLastError());
@@ -350,23 +289,21 @@ static int track_run(cpx_handle* h, const uint16_t* frames_dev, const int32_t* c
   if (int jrc = join_medians(h)) return jrc;  // (a previous call's medians read the frames / write the records this one may reuse)
   const bool defer_medians = (flags & CPX_TRACK_DEFER_MEDIANS) != 0;
   const cpx_config& c = h->cfg;
-  Schedule sc;
+  cpx::Schedule sc;
   int rc = build_schedule(h, clip_offsets, meta, B, &sc);
   if (rc != CPX_OK) return rc;
   const int total = sc.total, max_proc = sc.max_proc;
   const bool resume = n_prev > 0;
-  int t_begin = 0;
-  if (resume)
-    for (int f = 0; f < n_prev; ++f) t_begin += meta[f].background_frame ? 0 : 1;
+  const int t_begin = cpx::processed_before(meta, n_prev);
   // ---- device workspace ----
   const bool need_filt = (filtered_dev == nullptr);
   const WsLayout l = ws_layout(c, B, need_filt);
-  if (resume && (l.total > h->ws_bytes || need_filt != h->stream_filt_state))
+  if (resume && (l.total > h->ws.bytes || need_filt != h->stream_filt_state))
     return fail(h, CPX_ERR_INVALID, "cpx_track_frame: the stream's workspace is gone (optional outputs changed?)");
   const bool keep = !resume && (flags & CPX_TRACK_KEEP_BACKGROUND);
   if (keep) {
     // every clip needs a state to continue from: the previous call's (same layout) or a staged one
-    const bool have_prev = h->ws && h->last_B == B && need_filt == h->stream_filt_state && l.total <= h->ws_bytes;
+    const bool have_prev = h->ws.p && h->last_B == B && need_filt == h->stream_filt_state && l.total <= h->ws.bytes;
     for (int b = 0; b < B && !have_prev; ++b)
       if (!h->staged_bg.count(b)) {
         h->staged_bg.clear();  // staged for THIS call: a refused call does not leave them behind for the one after
@@ -397,17 +334,10 @@ static int track_run(cpx_handle* h, const uint16_t* frames_dev, const int32_t* c
       }
     }
   } guard{h};
-  if (l.total > h->ws_bytes) {
-    if (h->ws) hipFree(h->ws);
-    h->ws = nullptr;
-    h->ws_bytes = 0;
-    hipError_t e = hipMalloc(&h->ws, l.total);
-    if (e != hipSuccess) return fail(h, CPX_ERR_NOMEM, "workspace hipMalloc", e);
-    h->ws_bytes = l.total;
-  }
-  rc = upload_schedule(h, sc, B);
+  if ((rc = h->ws.grow(h, l.total, "workspace hipMalloc"))) return rc;
+  cpx::SchedLayout sl;
+  rc = upload_schedule(h, sc, B, &sl);
   if (rc != CPX_OK) return rc;
-  const int nproc_total = (int)sc.proc_idx.size();
 
   cpx::TrackArgs a{};
   a.W = c.width;
@@ -419,15 +349,12 @@ static int track_run(cpx_handle* h, const uint16_t* frames_dev, const int32_t* c
   a.background_thresh = c.background_thresh;
   a.weight_add = c.weight_add;
   a.frames = frames_dev;
-  a.clip_first = h->sched_dev;
-  a.proc_off = h->sched_dev + B;
-  a.proc_idx = h->sched_dev + B + (B + 1);
-  a.proc_ffc = h->sched_dev + B + (B + 1) + std::max(nproc_total, 1);
-  a.order = h->sched_dev + B + (B + 1) + 2 * (size_t)std::max(nproc_total, 1);
-  a.wtab = h->wtab_dev;
+  cpx::schedule_point(a, h->sched.as<int>(), sl);
+  a.order = h->sched.as<int>() + sl.order;
+  a.wtab = h->wtab_dev.as<double>();
   a.wtab_len = h->wtab_len;
-  a.wthr = h->wthr_dev;
-  char* base = (char*)h->ws;
+  a.wthr = h->wthr_dev.as<uint32_t>();
+  char* base = h->ws.as<char>();
   a.bg = (uint16_t*)(base + l.bg);
   a.wsum = (uint32_t*)(base + l.wsum);
   a.kcnt = (uint16_t*)(base + l.kcnt);
@@ -440,7 +367,7 @@ static int track_run(cpx_handle* h, const uint16_t* frames_dev, const int32_t* c
   a.bgavg = (double*)(base + l.bgavg);
   a.big_stat = c.max_components > cpx::track_lds_components() ? (uint32_t*)(base + l.big) : nullptr;
   a.nlm_flip = c.denoise ? 1 : 0;
-  a.nlm_lut = h->nlm_lut_dev;
+  a.nlm_lut = h->nlm_lut_dev.as<int>();
   a.comps_out = comps_dev;
   a.info_out = info_dev;
   a.labels_out = labels_dev;
@@ -593,13 +520,13 @@ int cpx_set_background(cpx_handle* h, int clip, const float* background, const d
 
 int cpx_get_background(cpx_handle* h, int clip, float* background, double* weights, double* average) {
   if (!h) return CPX_ERR_INVALID;
-  if (clip < 0 || clip >= h->last_B || !h->ws) return fail(h, CPX_ERR_INVALID, "cpx_get_background: no such clip in the last track call");
+  if (clip < 0 || clip >= h->last_B || !h->ws.p) return fail(h, CPX_ERR_INVALID, "cpx_get_background: no such clip in the last track call");
   CPX_ENTER(h);
   const cpx_config& c = h->cfg;
   const int W = c.width, H = c.height, e = c.edge_pixels;
   const size_t P = (size_t)W * H;
   const WsLayout l = ws_layout(c, h->last_B, h->stream_filt_state);
-  char* base = (char*)h->ws;
+  char* base = h->ws.as<char>();
   if (int urc = unpack_state(h)) return urc;
   CPX_HIP(h, hipStreamSynchronize(h->stream));
   cpx::ClipState st;
@@ -639,15 +566,13 @@ static int assoc_run(cpx_handle* h, const cpx_track_params* params, const int32_
     return fail(h, CPX_ERR_INVALID, "association: capacities must be positive");
   CPX_ENTER(h);
   const bool resume = n_prev > 0 && !fresh;
-  int t_begin = 0;
-  if (n_prev > 0)
-    for (int f = 0; f < n_prev; ++f) t_begin += meta[f].background_frame ? 0 : 1;
-  Schedule sc;
+  const int t_begin = cpx::processed_before(meta, n_prev);
+  cpx::Schedule sc;
+  cpx::SchedLayout sl;
   int rc = build_schedule(h, clip_offsets, meta, B, &sc);
   if (rc != CPX_OK) return rc;
-  rc = upload_schedule(h, sc, B);
+  rc = upload_schedule(h, sc, B, &sl);
   if (rc != CPX_OK) return rc;
-  const int n = std::max((int)sc.proc_idx.size(), 1);
   const int cap = h->cfg.max_components, ma = params->max_active_tracks;
   size_t off = 0;
   const size_t o_active = off;
@@ -660,25 +585,15 @@ static int assoc_run(cpx_handle* h, const cpx_track_params* params, const int32_
   off = align_up(off + (size_t)B * cap, 256);
   const size_t o_resume = off;
   off = align_up(off + (size_t)B * sizeof(cpx::AssocResume), 256);
-  if (resume && off > h->ws_assoc_bytes)
+  if (resume && off > h->ws_assoc.bytes)
     return fail(h, CPX_ERR_INVALID, "cpx_associate_frame: the stream's association state is gone");
-  if (off > h->ws_assoc_bytes) {
-    if (h->ws_assoc) hipFree(h->ws_assoc);
-    h->ws_assoc = nullptr;
-    h->ws_assoc_bytes = 0;
-    hipError_t e = hipMalloc(&h->ws_assoc, off);
-    if (e != hipSuccess) return fail(h, CPX_ERR_NOMEM, "association workspace hipMalloc", e);
-    h->ws_assoc_bytes = off;
-  }
-  char* base = (char*)h->ws_assoc;
+  if ((rc = h->ws_assoc.grow(h, off, "association workspace hipMalloc"))) return rc;
+  char* base = h->ws_assoc.as<char>();
   cpx::AssocArgs a{};
   a.B = B;
   a.cap = cap;
   a.params = *params;
-  a.clip_first = h->sched_dev;
-  a.proc_off = h->sched_dev + B;
-  a.proc_idx = h->sched_dev + B + (B + 1);
-  a.proc_ffc = h->sched_dev + B + (B + 1) + n;
+  cpx::schedule_point(a, h->sched.as<int>(), sl);
   a.comps = comps_dev;
   a.info = info_dev;
   a.pool = pool_dev;
@@ -801,41 +716,28 @@ int cpx_crop_tile(cpx_handle* h, const uint16_t* frames_dev, const float* filter
   return CPX_OK;
 }
 
-static int final_common(cpx_handle* h, const cpx_filter_params* params, const int32_t* clip_offsets,
-                        const cpx_frame_meta* meta, int B, cpx::FinalArgs* a) {
+// what cpx_finalize_tracks and cpx_plan_segments share: the schedule, and the per-clip scalar scratch of the end-of-clip
+// kernels, double [B][2 * max_frames] + float [B][max_frames]
+static int final_args(cpx_handle* h, const cpx_filter_params* params, const int32_t* clip_offsets,
+                      const cpx_frame_meta* meta, int B, cpx::FinalArgs* a) {
   if (params->max_active_tracks < 1 || params->max_tracks_per_clip < 1)
     return fail(h, CPX_ERR_INVALID, "filter params: capacities must be positive");
   CPX_ENTER(h);
-  Schedule sc;
+  cpx::Schedule sc;
+  cpx::SchedLayout sl;
   int rc = build_schedule(h, clip_offsets, meta, B, &sc);
   if (rc != CPX_OK) return rc;
-  rc = upload_schedule(h, sc, B);
+  rc = upload_schedule(h, sc, B, &sl);
   if (rc != CPX_OK) return rc;
-  const int n = std::max((int)sc.proc_idx.size(), 1);
   a->B = B;
   a->params = *params;
   a->max_frames = h->cfg.max_frames;
-  a->clip_first = h->sched_dev;
-  a->proc_off = h->sched_dev + B;
-  a->proc_idx = h->sched_dev + B + (B + 1);
-  a->proc_ffc = h->sched_dev + B + (B + 1) + n;
-  return CPX_OK;
-}
-
-// per-clip scalar scratch of the end-of-clip kernels: double [B][2 * max_frames] + float [B][max_frames]
-static int final_scratch(cpx_handle* h, int B, cpx::FinalArgs* a) {
-  const size_t need = (size_t)B * h->cfg.max_frames * (2 * sizeof(double) + sizeof(float)) + 512;
-  if (need > h->ws_assoc_bytes) {
-    CPX_HIP(h, hipStreamSynchronize(h->stream));
-    if (h->ws_assoc) hipFree(h->ws_assoc);
-    h->ws_assoc = nullptr;
-    h->ws_assoc_bytes = 0;
-    hipError_t e = hipMalloc(&h->ws_assoc, need);
-    if (e != hipSuccess) return fail(h, CPX_ERR_NOMEM, "finalize workspace hipMalloc", e);
-    h->ws_assoc_bytes = need;
-  }
-  a->scratch_d = (double*)h->ws_assoc;
-  a->scratch_f = (float*)((char*)h->ws_assoc + align_up((size_t)B * h->cfg.max_frames * 2 * sizeof(double), 256));
+  cpx::schedule_point(*a, h->sched.as<int>(), sl);
+  const size_t doubles = (size_t)B * h->cfg.max_frames * 2 * sizeof(double);
+  rc = h->ws_assoc.grow(h, doubles + (size_t)B * h->cfg.max_frames * sizeof(float) + 512, "finalize workspace hipMalloc");
+  if (rc != CPX_OK) return rc;
+  a->scratch_d = h->ws_assoc.as<double>();
+  a->scratch_f = (float*)(h->ws_assoc.as<char>() + align_up(doubles, 256));
   return CPX_OK;
 }
 
@@ -848,9 +750,7 @@ int cpx_finalize_tracks(cpx_handle* h, const cpx_filter_params* params, const in
       !counts_dev)
     return fail(h, CPX_ERR_INVALID, "cpx_finalize_tracks: null argument");
   cpx::FinalArgs a{};
-  int rc = final_common(h, params, clip_offsets, meta, B, &a);
-  if (rc != CPX_OK) return rc;
-  rc = final_scratch(h, B, &a);
+  const int rc = final_args(h, params, clip_offsets, meta, B, &a);
   if (rc != CPX_OK) return rc;
   a.square_width = 5;
   a.pool = pool_dev;
@@ -875,9 +775,7 @@ int cpx_plan_segments(cpx_handle* h, const cpx_filter_params* params, const int3
     return fail(h, CPX_ERR_INVALID, "cpx_plan_segments: null argument");
   if (square_width != 5) return fail(h, CPX_ERR_UNSUPPORTED, "cpx_plan_segments: square_width must be 5");
   cpx::FinalArgs a{};
-  int rc = final_common(h, params, clip_offsets, meta, B, &a);
-  if (rc != CPX_OK) return rc;
-  rc = final_scratch(h, B, &a);
+  const int rc = final_args(h, params, clip_offsets, meta, B, &a);
   if (rc != CPX_OK) return rc;
   a.square_width = square_width;
   a.pool = pool_dev;

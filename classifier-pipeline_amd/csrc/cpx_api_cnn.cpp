@@ -67,12 +67,9 @@ struct conv_half {
 // back on the fp16 ones
 constexpr int OVF_WORDS = 2 + 3 * CPX_WRRESNET_MAX_BLOCKS;
 static int ensure_ovf_word(cpx_handle* h) {
-  if (h->cnn_ovf) return CPX_OK;
-  if (hipMalloc((void**)&h->cnn_ovf, OVF_WORDS * sizeof(int)) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(h, CPX_ERR_NOMEM, "cpx_conv2d: overflow word allocation failed");
-  }
-  CPX_HIP(h, hipMemsetAsync(h->cnn_ovf, 0, OVF_WORDS * sizeof(int), h->stream));
+  if (h->cnn_ovf.p) return CPX_OK;
+  if (int rc = h->cnn_ovf.grow(h, OVF_WORDS * sizeof(int), "cpx_conv2d: overflow word allocation failed")) return rc;
+  CPX_HIP(h, hipMemsetAsync(h->cnn_ovf.p, 0, OVF_WORDS * sizeof(int), h->stream));
   return CPX_OK;
 }
 // One convolution's geometry from its shape: TensorFlow SAME (out = ceil(in / stride), surplus padding goes to the bottom /
@@ -183,24 +180,14 @@ static int conv_run(cpx_handle* h, const cpx_conv_desc* d, const void* split_wei
   int* word = nullptr;
   if (route == ConvRoute::Fp16Pair || route == ConvRoute::RerunOnly) {
     if (int rc = ensure_ovf_word(h)) return rc;
-    if (!k.keep_flag) CPX_HIP(h, hipMemsetAsync(h->cnn_ovf, 0, sizeof(int), h->stream));
-    word = h->cnn_ovf + k.word;
+    if (!k.keep_flag) CPX_HIP(h, hipMemsetAsync(h->cnn_ovf.p, 0, sizeof(int), h->stream));
+    word = h->cnn_ovf.as<int>() + k.word;
   }
   if (split && !split_weights) {
-    const size_t need = cpx::conv_bf3_weight_bytes(a);
-    if (need > h->bf3_scratch_bytes) {
-      CPX_HIP(h, hipStreamSynchronize(h->stream));
-      if (h->bf3_scratch) hipFree(h->bf3_scratch);
-      h->bf3_scratch = nullptr;
-      h->bf3_scratch_bytes = 0;
-      if (hipMalloc(&h->bf3_scratch, need) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(h, CPX_ERR_NOMEM, "cpx_conv2d: weight scratch allocation failed");
-      }
-      h->bf3_scratch_bytes = need;
-    }
-    cpx::launch_split_weights(a, h->bf3_scratch, h->stream);
-    split_weights = h->bf3_scratch;
+    if (int rc = h->bf3_scratch.grow(h, cpx::conv_bf3_weight_bytes(a), "cpx_conv2d: weight scratch allocation failed"))
+      return rc;
+    cpx::launch_split_weights(a, h->bf3_scratch.p, h->stream);
+    split_weights = h->bf3_scratch.p;
   }
   // ---- launch
   int rc = 0;
@@ -325,7 +312,7 @@ static void block32_args(const Forward& fw, const BlockPlan& bp, cpx::ConvArgs* 
   for (int i = 0; i < 2; ++i) {
     both[i]->planes = 2;
     both[i]->half = 1;
-    both[i]->ovf = fw.h->cnn_ovf + bp.word;
+    both[i]->ovf = fw.h->cnn_ovf.as<int>() + bp.word;
     both[i]->act_scale = fw.cnn->act_scale[bp.st][bp.d][i];
     both[i]->act_unscale = 1.0f / both[i]->act_scale;
   }
@@ -478,7 +465,7 @@ static int cnn_forward(cpx_cnn* cnn, const float* in_dev, int N, int H, int W, f
   if (h->cnn_math == CPX_CNN_MATH_FP16X2) {  // the blocks' overflow words start clear
     const int rco = ensure_ovf_word(h);
     if (rco != CPX_OK) return rco;
-    CPX_HIP(h, hipMemsetAsync(h->cnn_ovf + 2, 0, (OVF_WORDS - 2) * sizeof(int), h->stream));
+    CPX_HIP(h, hipMemsetAsync(h->cnn_ovf.as<int>() + 2, 0, (OVF_WORDS - 2) * sizeof(int), h->stream));
   }
   // largest activation: conv1 output (and the stage-2 tensors at stride 1)
   size_t biggest = 0;
@@ -493,19 +480,9 @@ static int cnn_forward(cpx_cnn* cnn, const float* in_dev, int N, int H, int W, f
     }
   }
   biggest = align_up(biggest, 64);
-  if (4 * biggest > h->cnn_arena_floats) {
-    if (h->cnn_arena) {
-      CPX_HIP(h, hipStreamSynchronize(h->stream));
-      hipFree(h->cnn_arena);
-    }
-    h->cnn_arena = nullptr;
-    h->cnn_arena_floats = 0;
-    hipError_t e = hipMalloc((void**)&h->cnn_arena, 4 * biggest * sizeof(float));
-    if (e != hipSuccess) return fail(h, CPX_ERR_NOMEM, "cpx_cnn_forward: activation hipMalloc", e);
-    h->cnn_arena_floats = 4 * biggest;
-  }
-  const Forward fw{cnn, h, in_dev, N, H, W, {h->cnn_arena, h->cnn_arena + biggest}, h->cnn_arena + 2 * biggest,
-                   h->cnn_arena + 3 * biggest};
+  if (int rc = h->cnn_arena.grow(h, 4 * biggest * sizeof(float), "cpx_cnn_forward: activation hipMalloc")) return rc;
+  float* const arena = h->cnn_arena.as<float>();
+  const Forward fw{cnn, h, in_dev, N, H, W, {arena, arena + biggest}, arena + 2 * biggest, arena + 3 * biggest};
   // decide ...
   const int n_blocks = 3 * p.blocks_per_stage;
   BlockPlan plan[3 * CPX_WRRESNET_MAX_BLOCKS];
@@ -537,11 +514,11 @@ static int cnn_forward(cpx_cnn* cnn, const float* in_dev, int N, int H, int W, f
   hd.dense_w_dev = p.dense_w; hd.dense_b_dev = p.dense_b; hd.logits_dev = logits_dev; hd.probs_dev = probs_dev;
   int rc = cpx_cnn_head_ex(h, &hd);
   if (rc == CPX_OK && h->cnn_math == CPX_CNN_MATH_FP16X2)
-    cpx::launch_count_overflow(h->cnn_ovf, 3 * p.blocks_per_stage, h->stream);
+    cpx::launch_count_overflow(h->cnn_ovf.as<int>(), 3 * p.blocks_per_stage, h->stream);
   if (rc == CPX_OK && ovf_out) {
     const size_t bytes = (size_t)3 * p.blocks_per_stage * sizeof(int);
     if (h->cnn_math == CPX_CNN_MATH_FP16X2)
-      CPX_HIP(h, hipMemcpyAsync(ovf_out, h->cnn_ovf + 2, bytes, hipMemcpyDeviceToDevice, h->stream));
+      CPX_HIP(h, hipMemcpyAsync(ovf_out, h->cnn_ovf.as<int>() + 2, bytes, hipMemcpyDeviceToDevice, h->stream));
     else  // (no fp16 launch: no block was rerun)
       CPX_HIP(h, hipMemsetAsync(ovf_out, 0, bytes, h->stream));
   }
@@ -549,7 +526,7 @@ static int cnn_forward(cpx_cnn* cnn, const float* in_dev, int N, int H, int W, f
     // diagnostic (synchronises): which blocks of this forward left fp16's range
     int words[OVF_WORDS];
     if (hipStreamSynchronize(h->stream) == hipSuccess &&
-        hipMemcpy(words, h->cnn_ovf, sizeof(words), hipMemcpyDeviceToHost) == hipSuccess && words[0]) {
+        hipMemcpy(words, h->cnn_ovf.p, sizeof(words), hipMemcpyDeviceToHost) == hipSuccess && words[0]) {
       std::fprintf(stderr, "cpx_cnn_forward: N = %d, fp16 overflow in blocks", N);
       for (int k = 0; k < 3 * p.blocks_per_stage; ++k)
         if (words[2 + k]) std::fprintf(stderr, " %d.%d", k / p.blocks_per_stage + 2, k % p.blocks_per_stage);
@@ -577,10 +554,10 @@ int cpx_cnn_overflow_forwards(cpx_handle* h, int* count, int reset) {
   if (!count) return fail(h, CPX_ERR_INVALID, "cpx_cnn_overflow_forwards: null argument");
   CPX_ENTER(h);
   *count = 0;
-  if (!h->cnn_ovf) return CPX_OK;
+  if (!h->cnn_ovf.p) return CPX_OK;
   CPX_HIP(h, hipStreamSynchronize(h->stream));
-  CPX_HIP(h, hipMemcpy(count, h->cnn_ovf + 1, sizeof(int), hipMemcpyDeviceToHost));
-  if (reset) CPX_HIP(h, hipMemset(h->cnn_ovf + 1, 0, sizeof(int)));
+  CPX_HIP(h, hipMemcpy(count, h->cnn_ovf.as<int>() + 1, sizeof(int), hipMemcpyDeviceToHost));
+  if (reset) CPX_HIP(h, hipMemset(h->cnn_ovf.as<int>() + 1, 0, sizeof(int)));
   return CPX_OK;
 }
 
@@ -589,9 +566,9 @@ int cpx_cnn_last_overflow(cpx_handle* h, int* overflowed) {
   if (!overflowed) return fail(h, CPX_ERR_INVALID, "cpx_cnn_last_overflow: null argument");
   CPX_ENTER(h);
   *overflowed = 0;
-  if (!h->cnn_ovf) return CPX_OK;
+  if (!h->cnn_ovf.p) return CPX_OK;
   CPX_HIP(h, hipStreamSynchronize(h->stream));
-  CPX_HIP(h, hipMemcpy(overflowed, h->cnn_ovf, sizeof(int), hipMemcpyDeviceToHost));
+  CPX_HIP(h, hipMemcpy(overflowed, h->cnn_ovf.p, sizeof(int), hipMemcpyDeviceToHost));
   return CPX_OK;
 }
 

@@ -137,7 +137,7 @@ int cpx_graph_arena_bytes(const cpx_graph* g, int N, size_t* bytes) {
 
 int cpx_graph_arena_allocated(const cpx_handle* h, size_t* bytes) {
   if (!h || !bytes) return CPX_ERR_INVALID;
-  *bytes = h->graph_arena_floats * sizeof(float);
+  *bytes = h->graph_arena.bytes;
   return CPX_OK;
 }
 
@@ -146,18 +146,8 @@ int cpx_graph_forward(cpx_graph* g, const float* in_dev, int N, float* out_dev) 
   cpx_handle* h = g->h;
   if (!in_dev || !out_dev || N < 1) return fail(h, CPX_ERR_INVALID, "cpx_graph_forward: bad argument");
   CPX_ENTER(h);
-  const size_t need = g->arena_floats * (size_t)N;
-  if (need > h->graph_arena_floats) {
-    if (h->graph_arena) {
-      CPX_HIP(h, hipStreamSynchronize(h->stream));  // an earlier forward may still be using it
-      hipFree(h->graph_arena);
-    }
-    h->graph_arena = nullptr;
-    h->graph_arena_floats = 0;
-    hipError_t e = hipMalloc((void**)&h->graph_arena, need * sizeof(float));
-    if (e != hipSuccess) return fail(h, CPX_ERR_NOMEM, "cpx_graph_forward: arena hipMalloc", e);
-    h->graph_arena_floats = need;
-  }
+  if (int rc = h->graph_arena.grow(h, g->arena_floats * (size_t)N * sizeof(float), "cpx_graph_forward: arena hipMalloc"))
+    return rc;
   auto view = [&](int id) {
     const cpx_graph_tensor& t = g->tensors[id];
     cpx::GraphView v{};
@@ -171,7 +161,7 @@ int cpx_graph_forward(cpx_graph* g, const float* in_dev, int N, float* out_dev) 
     else if (id == g->output)
       v.p = out_dev + t.c_offset;
     else
-      v.p = h->graph_arena + (size_t)t.arena_offset * N + t.c_offset;
+      v.p = h->graph_arena.as<float>() + (size_t)t.arena_offset * N + t.c_offset;
     return v;
   };
   for (const cpx_graph_op& o : g->ops) {

@@ -15,13 +15,13 @@ struct cpx_mog2 {
   int n_streams = 0, width = 0, height = 0, history = 0, nframes = 0;
   float var_threshold = 16.0f;
   size_t n = 0;
-  float* state = nullptr;        // weight | var | mean, each [5][n]
-  unsigned char* modes = nullptr;
+  DeviceBuffer state;            // float: weight | var | mean, each [5][n]
+  DeviceBuffer modes;            // unsigned char [n]
 };
 
 void mog2_free(cpx_mog2* m) {
-  if (m->state) hipFree(m->state);
-  if (m->modes) hipFree(m->modes);
+  m->state.release();
+  m->modes.release();
   delete m;
 }
 
@@ -109,14 +109,13 @@ int cpx_mog2_create(cpx_handle* h, int n_streams, int width, int height, int his
   m->history = history > 0 ? history : 500;
   m->var_threshold = var_threshold;
   m->n = (size_t)n_streams * width * height;
-  if (hipMalloc(reinterpret_cast<void**>(&m->state), 15 * m->n * sizeof(float)) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&m->modes), m->n) != hipSuccess) {
-    (void)hipGetLastError();
+  if (m->state.grow(h, 15 * m->n * sizeof(float), "cpx_mog2_create: state allocation failed") ||
+      m->modes.grow(h, m->n, "cpx_mog2_create: state allocation failed")) {
     mog2_free(m);
-    return fail(h, CPX_ERR_NOMEM, "cpx_mog2_create: state allocation failed");
+    return CPX_ERR_NOMEM;
   }
-  CPX_HIP(h, hipMemsetAsync(m->state, 0, 15 * m->n * sizeof(float), h->stream));
-  CPX_HIP(h, hipMemsetAsync(m->modes, 0, m->n, h->stream));
+  CPX_HIP(h, hipMemsetAsync(m->state.p, 0, m->state.bytes, h->stream));
+  CPX_HIP(h, hipMemsetAsync(m->modes.p, 0, m->modes.bytes, h->stream));
   h->mog2s.push_back(m);
   *out = m;
   return CPX_OK;
@@ -140,10 +139,10 @@ static cpx::Mog2Args mog2_args(const cpx_mog2* m) {
   a.var_init = 15.0f;
   a.var_min = 4.0f;
   a.var_max = 75.0f;
-  a.weight = m->state;
-  a.var = m->state + 5 * m->n;
-  a.mean = m->state + 10 * m->n;
-  a.modes = m->modes;
+  a.weight = m->state.as<float>();
+  a.var = a.weight + 5 * m->n;
+  a.mean = a.weight + 10 * m->n;
+  a.modes = m->modes.as<unsigned char>();
   return a;
 }
 
@@ -199,25 +198,11 @@ int cpx_ir_detect(cpx_handle* h, const uint8_t* images_dev, int n_frames, int wi
   // one slot per frame that can be resident at once (at most one workgroup of this LDS size per CU pair)
   a.n_slots = n_frames < 256 ? n_frames : 256;
   a.slot_bytes = cpx::ir_slot_bytes(width, height);
-  const size_t need = a.slot_bytes * (size_t)a.n_slots;
-  if (need > h->ir_scratch_bytes) {
-    CPX_HIP(h, hipStreamSynchronize(h->stream));
-    if (h->ir_scratch) hipFree(h->ir_scratch);
-    h->ir_scratch = nullptr;
-    h->ir_scratch_bytes = 0;
-    if (hipMalloc(reinterpret_cast<void**>(&h->ir_scratch), need) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(h, CPX_ERR_NOMEM, "cpx_ir_detect: scratch allocation failed");
-    }
-    h->ir_scratch_bytes = need;
-  }
-  if (!h->ir_bitmap && hipMalloc(reinterpret_cast<void**>(&h->ir_bitmap), 32) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(h, CPX_ERR_NOMEM, "cpx_ir_detect: scratch allocation failed");
-  }
-  CPX_HIP(h, hipMemsetAsync(h->ir_bitmap, 0, 32, h->stream));
-  a.slots = h->ir_scratch;
-  a.slot_bitmap = h->ir_bitmap;
+  if (int rc = h->ir_scratch.grow(h, a.slot_bytes * (size_t)a.n_slots, "cpx_ir_detect: scratch allocation failed")) return rc;
+  if (int rc = h->ir_bitmap.grow(h, 32, "cpx_ir_detect: scratch allocation failed")) return rc;
+  CPX_HIP(h, hipMemsetAsync(h->ir_bitmap.p, 0, 32, h->stream));
+  a.slots = h->ir_scratch.as<unsigned char>();
+  a.slot_bitmap = h->ir_bitmap.as<uint32_t>();
   if (cpx::launch_ir_detect(a, n_frames, h->stream) != 0)
     return fail(h, CPX_ERR_HIP, "cpx_ir_detect: kernel configuration failed");
   CPX_HIP(h, hipGetLastError());
