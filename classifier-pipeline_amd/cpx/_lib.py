@@ -145,6 +145,7 @@ EXPORTS = [
     "cpx_cnn_head_ex", "cpx_ir_delta_variance", "cpx_cptv_inflate", "cpx_cptv_gather_index", "cpx_format_regions", "cpx_json_indent", "cpx_ir_merge", "cpx_ir_resize_area",
     "cpx_ir_frame_statistics", "cpx_cnn_last_overflow", "cpx_cnn_set_activation_bounds", "cpx_cnn_overflow_forwards", "cpx_cnn_forward_taps",
     "cpx_graph_create", "cpx_graph_forward", "cpx_graph_arena_bytes", "cpx_graph_arena_allocated", "cpx_graph_destroy",
+    "cpx_cnn_set_residual_bounds", "cpx_cnn_shortcut_scale",
 ]
 
 IR_FRAME_STATS_DTYPE = np.dtype([("min", "<i4"), ("max", "<i4"), ("sum", "<i8"), ("median_x2", "<i4"), ("reserved", "<i4"),
@@ -227,6 +228,10 @@ def load():
     lib.cpx_cnn_overflow_forwards.restype = C.c_int
     lib.cpx_cnn_set_activation_bounds.argtypes = [vp, C.POINTER(C.c_float), C.c_int]
     lib.cpx_cnn_set_activation_bounds.restype = C.c_int
+    lib.cpx_cnn_set_residual_bounds.argtypes = [vp, C.POINTER(C.c_float), C.c_int]
+    lib.cpx_cnn_set_residual_bounds.restype = C.c_int
+    lib.cpx_cnn_shortcut_scale.argtypes = [C.c_float, C.c_float, C.POINTER(C.c_float)]
+    lib.cpx_cnn_shortcut_scale.restype = C.c_int
     lib.cpx_mog2_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(vp)]
     lib.cpx_mog2_create.restype = C.c_int
     lib.cpx_mog2_apply.argtypes = [vp, vp, C.c_double, vp]

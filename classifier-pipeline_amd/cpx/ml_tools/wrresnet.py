@@ -123,6 +123,16 @@ def activation_bound(w, name, sigmas=64.0):
     return float(np.max(np.abs(w[name + "/beta"]) + sigmas * np.abs(w[name + "/gamma"])))
 
 
+def residual_bound(w, stage, sigmas=64.0):
+    """Upper bound of |x| of the input of stage `stage`'s first block -- the un-normalised tensor its 1x1 projection shortcut
+    reads -- for the fp16x2 math mode's range scaling (include/cpx.h: cpx_cnn_set_residual_bounds): the block's first
+    BatchNorm normalises that tensor, so its moving statistics bound it as activation_bound bounds the activated input:
+    within |moving_mean| + sigmas standard deviations; an input that is not costs a rerun of the block, never correctness."""
+    name = "bn%db0_branch2a" % stage
+    var = np.asarray(w[name + "/moving_variance"], dtype=np.float64) + BN_EPS
+    return float(np.max(np.abs(np.asarray(w[name + "/moving_mean"], dtype=np.float64)) + sigmas * np.sqrt(var)))
+
+
 def pack_conv(kernel):
     """Keras HWIO [kh,kw,Cin/g,Cout] -> [g][kh*kw][Cin/g][Cout/g] contiguous."""
     kh, kw, ci, co = kernel.shape
@@ -193,13 +203,20 @@ class WRResNetDevice:
         self.act_bounds = [activation_bound(w, n) for n in names]
         folded = [bool(np.allclose(w[n + "/moving_variance"], 1.0 - BN_EPS) and np.all(w[n + "/moving_mean"] == 0))
                   for n in names]
+        # ... and what the input of each stage's first block can reach (the operand of the stage's fused 1x1 shortcut), from
+        # the statistics of the BatchNorm that normalises it, or measured by the same probe where those arrive folded
+        self.res_bounds = [residual_bound(w, stage) for stage in (2, 3, 4)]
+        res_folded = [folded[names.index("bn%db0_branch2a" % stage)] for stage in (2, 3, 4)]
         self._create_native()
         if any(folded):
-            measured = self._measure_activation_bounds()
+            measured, res_measured = self._measure_activation_bounds()
             self.act_bounds = [m if f else b for b, m, f in zip(self.act_bounds, measured, folded)]
+            self.res_bounds = [m if f else b for b, m, f in zip(self.res_bounds, res_measured, res_folded)]
             self._set_activation_bounds()
+            self._set_residual_bounds()
 
-    def _create_native(self):
+    def _native_params(self):
+        """The cpx_wrresnet_params of the uploaded parameters (device pointers into self.p)."""
         ptr = lambda key: self.p[key].data_ptr()
         prm = WRResNetParams()
         prm.n_labels, prm.blocks_per_stage, prm.groups, prm.in_channels = self.n_labels, BLOCKS, GROUPS, 2
@@ -221,12 +238,17 @@ class WRResNetDevice:
         for k, name in enumerate(self.hidden):
             prm.hidden_sizes[k] = int(self.p[name + "/b"].shape[0])
             prm.hidden_w[k], prm.hidden_b[k] = ptr(name + "/w"), ptr(name + "/b")
+        return prm
+
+    def _create_native(self):
+        prm = self._native_params()
         out = C.c_void_p()
         rc = self.lib.cpx_cnn_create(self.eng.h, C.byref(prm), C.byref(out))
         if rc != 0:
             raise CpxError(rc, self.eng._err())
         self._cnn = out
         self._set_activation_bounds()
+        self._set_residual_bounds()
 
     def _set_activation_bounds(self):
         bounds = (C.c_float * len(self.act_bounds))(*self.act_bounds)
@@ -234,21 +256,28 @@ class WRResNetDevice:
         if rc != 0:
             raise CpxError(rc, self.eng._err())
 
+    def _set_residual_bounds(self):
+        bounds = (C.c_float * len(self.res_bounds))(*self.res_bounds)
+        rc = self.lib.cpx_cnn_set_residual_bounds(self._cnn, bounds, len(self.res_bounds))
+        if rc != 0:
+            raise CpxError(rc, self.eng._err())
+
     def _measure_activation_bounds(self, headroom=32.0, n=2, seed=12345):
         """The largest activated input of every 3x3 convolution on a seeded probe batch (uniform 0..255 tiles through the
         network layer by layer, exact-split math), times `headroom`: deterministic for a given model; an input that goes
-        beyond it costs the overflow rerun, never correctness."""
+        beyond it costs the overflow rerun, never correctness.  -> (those, in launch order; the largest |input| of each
+        stage's first block, with the same headroom)."""
         t = self.torch
         rng = np.random.default_rng(seed)
         x = t.from_numpy(rng.uniform(0, 255, size=(n, 160, 160, 2)).astype(np.float32)).to(self.eng.device)
         prev = self.eng.get_cnn_math()
         self.eng.set_cnn_math("bf16x3")
-        seen = []
+        seen, res_seen = [], []
         try:
-            self.forward_layerwise(x, want_probs=False, _probe=seen)
+            self.forward_layerwise(x, want_probs=False, _probe=seen, _probe_res=res_seen)
         finally:
             self.eng.set_cnn_math(prev)
-        return [max(float(v) * headroom, 1e-3) for v in seen]
+        return [max(float(v) * headroom, 1e-3) for v in seen], [max(float(v) * headroom, 1e-3) for v in res_seen]
 
     def close(self):
         if self._cnn is not None:
@@ -332,7 +361,7 @@ class WRResNetDevice:
         if rc != 0:
             raise CpxError(rc, self.eng._err())
 
-    def forward_layerwise(self, x, want_probs=True, _probe=None):
+    def forward_layerwise(self, x, want_probs=True, _probe=None, _probe_res=None):
         """The same network issued layer by layer through cpx_conv2d / cpx_cnn_head (what a caller binding the
         building blocks directly would write); tests compare it with forward()."""
         t = self.torch
@@ -350,6 +379,9 @@ class WRResNetDevice:
                 s = stride if d == 0 else 1
                 Ho, Wo = -(-H // s), -(-W // s)
                 mid = self._buf("mid", (N, Ho, Wo, f))
+                if _probe_res is not None and d == 0:  # the stage's first-block input: the 1x1 shortcut's operand
+                    self.eng.synchronize()
+                    _probe_res.append(cur.abs().max().item())
                 if _probe is not None:  # the activated input of branch2a: relu(BatchNorm 2a(block input))
                     self.eng.synchronize()
                     _probe.append(t.relu(cur * self.p["%s/in_scale" % b] + self.p["%s/in_shift" % b]).max().item())

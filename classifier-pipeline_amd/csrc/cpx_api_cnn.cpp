@@ -22,6 +22,13 @@ struct cpx_cnn {
   // CPX_CNN_MATH_FP16X2: the power of two each 3x3 convolution's activated input is multiplied by before the fp16 split
   // ([stage][block][a / b]; 1 until cpx_cnn_set_activation_bounds says more)
   float act_scale[3][CPX_WRRESNET_MAX_BLOCKS][2];
+  // CPX_CNN_MATH_FP16X2, the fused 1x1 shortcut of a stage's first block as fp16x2 products: the bound of the block's input
+  // (cpx_cnn_set_residual_bounds; 0 = none given), the power of two the host chose for it (0 = this layer keeps the float32
+  // side product) and the fp16 plane image of the shortcut's weights built for that scale and the layer's act_scale
+  float res_bound[3] = {0.0f, 0.0f, 0.0f};
+  float sc_xscale[3] = {0.0f, 0.0f, 0.0f};
+  void* sc_img[3] = {nullptr, nullptr, nullptr};
+  double sc_wmax[3] = {-1.0, -1.0, -1.0};  // max |shortcut weight| w_scale[c] of the stage: read back once (< 0 = not yet)
   cpx_cnn() {
     for (auto& st : act_scale)
       for (auto& b : st) b[0] = b[1] = 1.0f;
@@ -35,6 +42,8 @@ struct cpx_cnn {
 
 void cnn_free(cpx_cnn* c) {
   for (auto& e : c->split) hipFree(e.second);
+  for (void* img : c->sc_img)
+    if (img) hipFree(img);
   delete c;
 }
 
@@ -44,6 +53,8 @@ struct conv_fuse {
   const float* w = nullptr;
   const float* bias = nullptr;
   int H = 0, W = 0, cin = 0, stride = 1;
+  const void* planes = nullptr;  // fp16 plane image of w for the operand scale xscale (ConvArgs::sc_planes), or none
+  float xscale = 0.0f;
 };
 
 // the modes that run the split-operand kernels (16-bit planes on the bf16 / fp16 matrix pipe)
@@ -99,6 +110,7 @@ static cpx::ConvArgs conv_describe(const cpx_conv_desc& d, const conv_fuse* fuse
   if (fuse) {
     a.sc_in = fuse->in; a.sc_w = fuse->w; a.sc_bias = fuse->bias;
     a.sc_H = fuse->H; a.sc_W = fuse->W; a.sc_cin = fuse->cin; a.sc_stride = fuse->stride;
+    a.sc_planes = fuse->planes; a.sc_xscale = fuse->xscale;
   }
   return a;
 }
@@ -260,6 +272,7 @@ struct BlockPlan {
   int word;                              // its overflow word
   BlockForm form;
   Shortcut shortcut;
+  bool shortcut_fp16;                    // FusedIntoSecond: its products on the fp16 matrix pipe (the network has the scaled image)
   Conv1 conv1;
 };
 
@@ -298,6 +311,10 @@ static BlockLayers block_layers(const Forward& fw, const BlockPlan& bp) {
   l.sc.out_shift_dev = p.shortcut_b[bp.st];
   l.fuse.in = cur; l.fuse.w = p.shortcut_w[bp.st]; l.fuse.bias = p.shortcut_b[bp.st];
   l.fuse.H = bp.H; l.fuse.W = bp.W; l.fuse.cin = bp.c_in; l.fuse.stride = bp.stride;
+  if (bp.shortcut_fp16) {
+    l.fuse.planes = fw.cnn->sc_img[bp.st];
+    l.fuse.xscale = fw.cnn->sc_xscale[bp.st];
+  }
   l.b = layer_desc(fw, fw.mid, fw.act[(bp.k + 1) & 1], b.wb, bp.Ho, bp.Wo, bp.f, bp.f, 3, 1, 1, 1);
   l.b.out_shift_dev = b.bb;
   l.b.residual_dev = bp.shortcut == Shortcut::Identity ? cur : bp.shortcut == Shortcut::OwnLaunch ? fw.sc : nullptr;
@@ -347,6 +364,10 @@ static BlockPlan plan_block(const Forward& fw, int k, int H, int W, Fusion most)
   bp.shortcut = bp.d != 0 ? Shortcut::Identity
                 : (h->fuse_shortcut && conv_can_fuse(h, bp.f, g) && (bp.c_in / g) % 4 == 0) ? Shortcut::FusedIntoSecond
                                                                                           : Shortcut::OwnLaunch;
+  // fp16x2: the fused shortcut's products run on fp16 planes where a residual bound was given and the host found scales
+  // for this layer (update_shortcut_images); CPX_CNN_SHORTCUT_FP16=0, or no bound: the float32 side product
+  bp.shortcut_fp16 = bp.shortcut == Shortcut::FusedIntoSecond && fp16 && h->shortcut_fp16 && cnn->sc_xscale[bp.st] > 0.0f &&
+                     cnn->sc_img[bp.st] != nullptr;
   // fp16x2: a block whose two convolutions are stride-1 with 32 channels per group (stage 2 past its first block) is ONE
   // launch; the stage's first block too (8 input channels per group; its 1x1 shortcut inside the second convolution) ...
   const bool first8 = bp.d == 0 && bp.stride == 1 && bp.c_in / g == 8 && h->block_fusion >= 2 && h->fuse_shortcut;
@@ -453,6 +474,53 @@ static int run_block(const Forward& fw, BlockPlan bp) {
     if (int rc = downgrade(fw, &bp, declined)) return rc;
   }
   return run_layers(fw, bp, bp.form == BlockForm::PlanesPair, false);
+}
+
+// The fused shortcuts on the fp16 pipe, decided per layer on the host whenever a bound changes (cpx_cnn_set_residual_bounds,
+// cpx_cnn_set_activation_bounds): for each stage whose first block's second convolution can take the shortcut as fp16x2
+// products (conv_shortcut_planes_layer) and whose input has a bound, the largest scaled shortcut weight is read back, a power
+// of two for the operand is chosen (cpx_cnn_shortcut_scale) and the weights' fp16 plane image is built for it.  A layer
+// without a bound, or for which no power of two fits, keeps sc_xscale = 0: the float32 side product.
+static int update_shortcut_images(cpx_cnn* cnn) {
+  cpx_handle* h = cnn->h;
+  const cpx_wrresnet_params& p = cnn->p;
+  CPX_ENTER(h);
+  for (int st = 0; st < 3; ++st) {
+    cnn->sc_xscale[st] = 0.0f;
+    const int g = p.groups, c_in = p.filters[st], f = p.filters[st + 1];
+    if (!(cnn->res_bound[st] > 0.0f) || c_in % g || f % g) continue;
+    cpx::ConvArgs second = conv_shape(0, 0, 0, f, f, g, 3, 1, 1);
+    second.weights = p.block[st][0].wb;
+    const void* wimg = cnn->split_of(second.weights);
+    if (!wimg || !cpx::conv_shortcut_planes_layer(second, c_in / g)) continue;
+    const int cin_g = c_in / g, cout_g = f / g;
+    const float* w_scale_dev = cpx::conv_bf3_weight_scales(second, wimg);
+    if (cnn->sc_wmax[st] < 0.0) {  // the weights are constant for the life of the network: one read-back per stage
+      std::vector<float> ws((size_t)f), w((size_t)g * cin_g * cout_g);
+      CPX_HIP(h, hipStreamSynchronize(h->stream));  // (the scales were written on the stream when the network was created)
+      CPX_HIP(h, hipMemcpy(ws.data(), w_scale_dev, ws.size() * sizeof(float), hipMemcpyDeviceToHost));
+      CPX_HIP(h, hipMemcpy(w.data(), p.shortcut_w[st], w.size() * sizeof(float), hipMemcpyDeviceToHost));
+      double m = 0.0;
+      for (int gi = 0; gi < g; ++gi)
+        for (int k = 0; k < cin_g; ++k)
+          for (int c = 0; c < cout_g; ++c)
+            m = std::max(m, std::fabs((double)w[((size_t)gi * cin_g + k) * cout_g + c]) * ws[gi * cout_g + c]);
+      cnn->sc_wmax[st] = m;
+    }
+    const float act_scale = cnn->act_scale[st][0][1];
+    const double wmax = cnn->sc_wmax[st] * act_scale;  // the largest shortcut weight as the accumulators are scaled
+    float sx = 0.0f;
+    if (!cpx_cnn_shortcut_scale(cnn->res_bound[st], (float)wmax, &sx)) continue;
+    if (!cnn->sc_img[st] && hipMalloc(&cnn->sc_img[st], cpx::conv_shortcut_image_bytes(g, cin_g, cout_g)) != hipSuccess) {
+      (void)hipGetLastError();
+      cnn->sc_img[st] = nullptr;
+      return fail(h, CPX_ERR_NOMEM, "cpx_cnn_set_residual_bounds: shortcut image allocation failed");
+    }
+    cpx::launch_split_shortcut(p.shortcut_w[st], cnn->sc_img[st], g, cin_g, cout_g, w_scale_dev, act_scale / sx, h->stream);
+    CPX_HIP(h, hipGetLastError());
+    cnn->sc_xscale[st] = sx;
+  }
+  return CPX_OK;
 }
 
 // cpx_cnn_forward and cpx_cnn_forward_taps: the same launches; with taps != nullptr each residual block's final output is
@@ -734,7 +802,37 @@ int cpx_cnn_set_activation_bounds(cpx_cnn* cnn, const float* bounds, int n) {
         }
         cnn->act_scale[st][d][k] = std::ldexp(1.0f, e);
       }
-  return CPX_OK;
+  return update_shortcut_images(cnn);  // (the shortcut images carry act_scale: nothing to do while no residual bound is set)
+}
+
+int cpx_cnn_shortcut_scale(float bound, float wmax, float* sx) {
+  if (!sx) return 0;
+  *sx = 0.0f;
+  if (!(bound > 0.0f) || !(wmax > 0.0f) || !std::isfinite(bound) || !std::isfinite(wmax)) return 0;
+  int eb = 0, ew = 0;
+  (void)std::frexp(bound, &eb);  // bound <= 2^eb
+  (void)std::frexp(wmax, &ew);   // 2^(ew - 1) <= wmax < 2^ew
+  // sx = 2^e.  Inside fp16: bound sx <= 2^15 and wmax / sx < 2^15.  Low planes (they resolve 2^-24 absolute): bound sx > 2^3 --
+  // a bound of 64 standard deviations then has its typical operand above 2^-3 --, and wmax / sx >= 2^-1: weights down to a
+  // quarter of the largest stay above 2^-3
+  const int e_lo = std::max(4 - eb, ew - 15), e_hi = std::min(15 - eb, ew);
+  if (e_lo > e_hi) return 0;
+  // the bound at 2^12 where the window allows: sixteen-fold headroom, as for the activations
+  const int e = std::min(std::max(12 - eb, e_lo), e_hi);
+  if (e < -60 || e > 60) return 0;
+  *sx = std::ldexp(1.0f, e);
+  return 1;
+}
+
+int cpx_cnn_set_residual_bounds(cpx_cnn* cnn, const float* bounds, int n) {
+  if (!cnn) return CPX_ERR_INVALID;
+  cpx_handle* h = cnn->h;
+  if (!bounds || n != 3) return fail(h, CPX_ERR_INVALID, "cpx_cnn_set_residual_bounds: expected 3 bounds, one per stage");
+  for (int st = 0; st < 3; ++st)
+    if (!(bounds[st] >= 0.0f) || !std::isfinite(bounds[st]))
+      return fail(h, CPX_ERR_INVALID, "cpx_cnn_set_residual_bounds: a bound is negative or not finite");
+  for (int st = 0; st < 3; ++st) cnn->res_bound[st] = bounds[st];
+  return update_shortcut_images(cnn);
 }
 
 int cpx_cnn_forward(cpx_cnn* cnn, const float* in_dev, int N, int H, int W, float* logits_dev, float* probs_dev) {

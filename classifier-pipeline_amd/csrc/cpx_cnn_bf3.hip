@@ -566,11 +566,16 @@ __global__ __launch_bounds__(CT) __attribute__((amdgpu_waves_per_eu(S > 1 ? CT /
 // CT: threads = 64 x the 32-position wave tiles of a workgroup's band (256: 128 positions; 512: 256 positions -- a staged
 // weight chunk then feeds twice the products: at 128 positions three workgroups per CU pull 37 KB of weights each per 16-channel
 // chunk, ~50 B per clock and CU out of L2, which is about what an XCD's L2 delivers)
-template <int NTN, int NPXC, int PL, bool H = false, bool PERSIST = false, int CT = 256>
+// SC (H only): the fused 1x1 shortcut of a.sc_in (64 channels per group, stride a.sc_stride) as fp16x2 products from
+// a.sc_planes -- its operand at the band's positions and its weights staged through LDS behind the last chunk, like four more
+// 16-channel chunks with a single tap (see below); without SC the shortcut is a float32 side product
+template <int NTN, int NPXC, int PL, bool H = false, bool PERSIST = false, int CT = 256, bool SC = false>
 __global__ __launch_bounds__(CT) void conv_bf3flat_kernel(ConvArgs a, const uint4* __restrict__ wimg, TileDiv td) {
   constexpr int KS = 3, BAND = CT / 2;
   constexpr int COGW = 32 * NTN;
   static_assert(!H || PL == 2, "fp16 planes come in twos");
+  static_assert(!SC || (H && !PERSIST && CT == 256 && 4 * 2 * 2 * BAND + 4 * 2 * 2 * COGW <= 2 * PL * NPXC + 18 * PL * COGW),
+                "the shortcut's planes reuse the LDS of the patch and the weights");
   extern __shared__ __attribute__((aligned(16))) uint4 lds4[];
   BF3_ENTRY_GUARD(H)
   uint4* s_patch = lds4;                 // [PL][2][NPXC]
@@ -751,7 +756,68 @@ __global__ __launch_bounds__(CT) void conv_bf3flat_kernel(ConvArgs a, const uint
     }
   }
 
-  if (a.sc_in) {  // fused 1x1 shortcut (see conv_bf3_kernel)
+  if constexpr (SC) {
+    // The fused 1x1 shortcut on the fp16 pipe: K = 64 = four 16-channel chunks, one tap.  The LDS is free (the barrier behind
+    // the last chunk's products): thread t stages channel half t & 1 of band position t >> 1 for all four chunks -- the strided
+    // pixel of the block input times sc_xscale, split like an activation, the same overflow test -- and four entries of the
+    // weights' planes (image [g][chunk of 32][plane][quarter][cout_g], split_shortcut_kernel); one barrier; twelve products
+    // per 32-column tile.  LDS: operand [chunk][plane][half][BAND], then weights [chunk][plane][half][COGW]
+    uint4* s_x = lds4;
+    uint4* s_scw = lds4 + 4 * 2 * 2 * BAND;
+    {
+      const int sp = min(p0 + (tid >> 1), M - 1);
+      const int sy = sp / a.Wo, sxp = sp - sy * a.Wo;
+      const float* src = a.sc_in + (((size_t)n * a.sc_H + sy * a.sc_stride) * a.sc_W + sxp * a.sc_stride) * a.sc_cin + g * 64 + 8 * my_h;
+      f32x4 xv[4][2];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        xv[c][0] = *reinterpret_cast<const f32x4*>(src + 16 * c);
+        xv[c][1] = *reinterpret_cast<const f32x4*>(src + 16 * c + 4);
+      }
+      u32x4 wv[4];
+      const u32x4* scw = reinterpret_cast<const u32x4*>(a.sc_planes) + (size_t)g * 16 * cout_g + ns * COGW;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {  // entry tid of chunk c: column tid % COGW, half, plane; 8-channel block j = 2 c + half
+        const int col = tid & (COGW - 1), hh = (tid / COGW) & 1, pp = (tid / (2 * COGW)) & 1, j = 2 * c + hh;
+        wv[c] = scw[(size_t)(((j >> 2) * 2 + pp) * 4 + (j & 3)) * cout_g + col];
+      }
+      float vmax = 0.0f;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = xv[c][j >> 2][j & 3] * a.sc_xscale;
+#pragma unroll
+        for (int j = 0; j < 8; j += 2) vmax = fmaxf(fmaxf(fabsf(v[j]), fabsf(v[j + 1])), vmax);
+        unsigned q0[4], q1[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) split2<true>(v[2 * j], v[2 * j + 1], q0[j], q1[j]);
+        u32x4* sx4 = reinterpret_cast<u32x4*>(s_x);
+        sx4[((c * 2 + 0) * 2 + my_h) * BAND + (tid >> 1)] = u32x4{q0[0], q0[1], q0[2], q0[3]};
+        sx4[((c * 2 + 1) * 2 + my_h) * BAND + (tid >> 1)] = u32x4{q1[0], q1[1], q1[2], q1[3]};
+        reinterpret_cast<u32x4*>(s_scw)[c * (2 * 2 * COGW) + tid] = wv[c];
+      }
+      if (!(vmax <= F16_MAX)) atomicOr(a.ovf, 1);  // (out of fp16's range, or not a number: the rerun computes the layer)
+    }
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      u32x4 av[2], bv[NTN][2];
+#pragma unroll
+      for (int p = 0; p < 2; ++p) {
+        av[p] = __builtin_bit_cast(u32x4, s_x[((c * 2 + p) * 2 + kh) * BAND + wave * 32 + (lane & 31)]);
+#pragma unroll
+        for (int t = 0; t < NTN; ++t) bv[t][p] = __builtin_bit_cast(u32x4, s_scw[((c * 2 + p) * 2 + kh) * COGW + (lane & 31) + t * 32]);
+      }
+#pragma unroll
+      for (int t = 0; t < NTN; ++t) {
+        acc[t] = mfma32<true>(av[0], bv[t][1], acc[t]);
+        acc[t] = mfma32<true>(av[1], bv[t][0], acc[t]);
+        acc[t] = mfma32<true>(av[0], bv[t][0], acc[t]);
+      }
+    }
+    __syncthreads();  // (the epilogue's tiles reuse the same LDS)
+  } else if (a.sc_in) {  // fused 1x1 shortcut (see conv_bf3_kernel)
     const int sc_cg = a.sc_cin / a.groups;
     const float* wsc = a.sc_w + (size_t)g * sc_cg * cout_g + ns * COGW + (lane & 31);
     const float* psc_in = a.sc_in + (((size_t)n * a.sc_H + ly * a.sc_stride) * a.sc_W + lx * a.sc_stride) * a.sc_cin +
@@ -1823,12 +1889,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 }
 
 constexpr long long RERUN_GRID = 1024;  // workgroups along x of a guarded rerun (four per CU and group row)
-template <int NTN, int NPXC, int PL, bool H = false, int CT = 256>
+template <int NTN, int NPXC, int PL, bool H = false, int CT = 256, bool SC = false>
 int launch_bf3flat_t(const ConvArgs& a, const uint4* wimg, hipStream_t s) {
   constexpr int BAND = CT / 2;
   const size_t lds = std::max(((size_t)2 * PL * NPXC + (size_t)18 * PL * 32 * NTN) * 16, (size_t)(CT / 64) * 32 * 32 * sizeof(float));
   static bool lds_ready[64], lds_ready_p[64];
-  if (!cpx_dyn_lds_ready(reinterpret_cast<const void*>(conv_bf3flat_kernel<NTN, NPXC, PL, H, false, CT>), lds_ready, 160 * 1024 - 1024)) return -1;
+  if (!cpx_dyn_lds_ready(reinterpret_cast<const void*>(conv_bf3flat_kernel<NTN, NPXC, PL, H, false, CT, SC>), lds_ready, 160 * 1024 - 1024)) return -1;
   TileDiv td;
   td.tiles_x = (a.Ho * a.Wo + BAND - 1) / BAND;
   td.tiles_y = 1;
@@ -1844,7 +1910,7 @@ int launch_bf3flat_t(const ConvArgs& a, const uint4* wimg, hipStream_t s) {
     hipLaunchKernelGGL((conv_bf3flat_kernel<NTN, NPXC, PL, false, true, CT>), dim3((unsigned)std::min<long long>(blocks, RERUN_GRID), a.groups), dim3(CT), lds, s, a, wimg, td);
     return 0;
   }
-  hipLaunchKernelGGL((conv_bf3flat_kernel<NTN, NPXC, PL, H, false, CT>), dim3((unsigned)blocks, a.groups), dim3(CT), lds, s, a, wimg, td);
+  hipLaunchKernelGGL((conv_bf3flat_kernel<NTN, NPXC, PL, H, false, CT, SC>), dim3((unsigned)blocks, a.groups), dim3(CT), lds, s, a, wimg, td);
   return 0;
 }
 // the flattened tiling applies to stride-1 SAME 3 x 3 layers whose staged rows fit the LDS cap and pays when the
@@ -2057,10 +2123,12 @@ static size_t bf3w_image2_bytes(const ConvArgs& a) { return (size_t)a.groups * (
 static int launch_bf3w(const ConvArgs& a, const uint4* wimg, hipStream_t s) {
   if (a.planes == 2 && a.half) {  // the fp16 image lies behind the two bf16 ones
     const uint4* wh = wimg + (bf3w_image3_bytes(a) + bf3w_image2_bytes(a)) / 16;
-    // 64 -> 64 channels per group: weights in registers (cpx_cnn_rw.hip) -- but for the launch that carries a stage's 1x1
-    // shortcut: that side product (strided float32 operands) stays with this kernel, measured faster than the shortcut as a
-    // launch of its own + conv_rw64_kernel with its output as residual (profiles/r06_conv_rw_experiments.md)
-    if (conv_rw_layer(a) && !a.in_planes && !a.out_planes && !a.sc_in) {
+    // 64 -> 64 channels per group: weights in registers (cpx_cnn_rw.hip).  The launch that carries a stage's 1x1 shortcut goes
+    // there too when the network has fp16 planes of the shortcut's weights (ConvArgs::sc_planes: the shortcut is then three more
+    // fp16 products per output row); as a float32 side product (strided float32 operands) it stays with this kernel, measured
+    // faster than the shortcut as a launch of its own + conv_rw64_kernel with its output as residual
+    // (profiles/r06_conv_rw_experiments.md)
+    if (conv_rw_layer(a) && !a.in_planes && !a.out_planes && (!a.sc_in || a.sc_planes)) {
       const int rc = launch_conv_rw(a, wh, s);
       if (rc != -2) return rc;
     }
@@ -2222,6 +2290,9 @@ static size_t scales_offset(const ConvArgs& a) {
   if (bf3_c8(a)) return c8_image3_bytes(a) + c8_half_bytes(a);
   return bf3w_layer(a) ? bf3w_image3_bytes(a) + 2 * bf3w_image2_bytes(a) : image3_bytes(a) + 2 * (image3_bytes(a) / 3 * 2);
 }
+const float* conv_bf3_weight_scales(const ConvArgs& a, const void* wimg) {
+  return reinterpret_cast<const float*>(reinterpret_cast<const char*>(wimg) + scales_offset(a));
+}
 void launch_split_weights(const ConvArgs& a, void* wimg, hipStream_t s) {
   const int cin_g = a.Cin / a.groups, cout_g = a.Cout / a.groups;
   if (rw_stride3(a)) {
@@ -2318,6 +2389,11 @@ int launch_conv_bf3(const ConvArgs& a_in, const void* wimg, hipStream_t s) {
   // need 384 staged pixels and then fit only one N tile per workgroup: measured slower than the rectangular bands,
   // 399 vs 371 ms, the patch being activated and split by four column slices instead of two.)
   if (cout_g == 128 && flat_pays(a, 32, 4 * CPX_BF3_NB_S4, 256)) {
+    // (the launch that carries stage 4's shortcut with fp16 planes of its weights: ConvArgs::sc_planes)
+    if (a.planes == 2 && a.half && a.sc_in && a.sc_planes && conv_shortcut_planes_layer(a, a.sc_cin / a.groups) && !a.residual &&
+        a.sc_stride >= 1 && a.sc_xscale > 0.0f && (a.sc_H - 1) / a.sc_stride + 1 == a.Ho && (a.sc_W - 1) / a.sc_stride + 1 == a.Wo &&
+        (long long)a.sc_H * a.sc_W * a.sc_cin < (1ll << 31))
+      return launch_bf3flat_t<2, 256, 2, true, 256, true>(a, w + half_image_offset(a) / 16, s);
     if (a.planes == 2 && a.half) return launch_bf3flat_t<2, 256, 2, true>(a, w + half_image_offset(a) / 16, s);
     if (a.planes == 2 && flat_layer(a)) return launch_bf3flat_t<2, 256, 2>(a, w + image3_bytes(a) / 16, s);
     return launch_bf3flat_t<2, 256, 3>(a, w, s);

@@ -26,6 +26,18 @@
 // convolution of stage 3 (32 -> 64 channels per group: one 32-channel chunk per tile, 16 x 8 output tiles from 33 x 17 patches,
 // the two buffers alternate per tile; HBM-bound at 5.05 TB/s), conv_rw_kernel<3, 2, 4> the first convolution of stage 4
 // (64 -> 128: 16 x 4 output tiles from 48 x 12 patches, a workgroup computes 64 of the 128 output channels of its group).
+// The 1x1 projection shortcut of stage 3's first block (K = 32 input channels per group, read from the un-normalised block
+// input at the strided positions of the output pixels) runs inside the same stream (template parameter SC): per tile 256 pixels
+// x 32 channels are requested where the RES form requests its residual rows, scaled, split and stored to an LDS region of their
+// own beside the tile's first chunk, and multiplied beside its last -- three more products per output row from two weight
+// fragments (8 registers), instead of eight v_mfma_f32_16x16x4_f32 at half the rate in the epilogue.  Its scales are DECIDED PER
+// LAYER ON THE HOST when the network's bounds are set (cpx_api_cnn.cpp: update_shortcut_images, cpx_cnn_shortcut_scale): the
+// operand is multiplied by a power of two sx taken from the bound of the block's input, the shortcut's weights by
+// w_scale[c] act_scale / sx (split_shortcut_kernel below), so that the products arrive at the accumulators' scale; a layer for
+// which no power of two keeps both inside fp16 and above their low planes' resolution, or which has no bound, or a handle
+// created under CPX_CNN_SHORTCUT_FP16=0, is launched without SC planes and keeps the float32 side product (on
+// conv_bf3w_kernel).  An operand beyond fp16's range sets the same overflow word as an activation; the rerun is unchanged.
+// Measurements: profiles/shortcut_fp16_experiments.md.
 // Measurements of every step on the way, the forms that lost and what was considered and not built:
 // profiles/r06_conv_rw_experiments.md; counters of the shipped forms: profiles/r06_conv_sq_counters.json, r06_conv_traffic.json.
 // Reference semantics: /root/reference/src/ml_tools/resnet/wr_resnet.py:49-98 (wr_block: BN -> ReLU -> conv3x3 -> BN -> ReLU ->
@@ -103,20 +115,31 @@ struct RwGeo {
   static constexpr int CING = 32 * NCH;
   static constexpr size_t LDS = (size_t)2 * BUF * 16 + (size_t)(2 * CING + 3 * RW_WC) * sizeof(float);
 };
+// the fused shortcut's operand of a 16 x 16 tile (SC): 256 pixels x 32 channels as fp16 planes in a region of its own behind
+// the epilogue parameters, laid out like a chunk buffer ([plane][quarter pair][pixel][2] of 16-byte entries) so that the 16
+// pixels of an output row are one B fragment.  SC_NPXP * 32 B = 64 mod 128, as NPXP
+constexpr int SC_NPXP = 258;
+constexpr int SC_ITEMS = 16 * RW_TW * 8 / RW_CT;   // 16-byte pieces (4 channels) per thread: 8
+constexpr size_t SC_LDS = (size_t)2 * 2 * SC_NPXP * 2 * 16;
 
 // LDS: [chunk buffer 0][chunk buffer 1][BatchNorm scale, shift of the group's input channels][per-channel epilogue parameters: 3 x 64]
 // BN: the layer has a BatchNorm + ReLU prologue (a template parameter, like every other condition inside the product stream:
 // a branch there ends the scheduling region, and with one wave per SIMD nothing else fills the matrix pipe meanwhile)
 // RES: the layer adds a residual tensor (requested into registers beside the tile's last products, added in the epilogue)
-template <int S, int NCH, int ROWS, bool BN, bool RES>
+// SC: the layer adds the 1x1 shortcut of a.sc_in (32 channels per group, stride a.sc_stride) as fp16x2 products from
+// a.sc_planes: three more products per output row, inside the stream of the tile's last chunk (see `unit`).  Without SC a
+// launch that carries a shortcut adds it in the epilogue on the float32 matrix instruction
+template <int S, int NCH, int ROWS, bool BN, bool RES, bool SC = false>
 __global__ __launch_bounds__(RW_CT) __attribute__((amdgpu_waves_per_eu(1, 1))) void conv_rw_kernel(ConvArgs a, const uint4* __restrict__ wimg, RwTiles td) {
   using G = RwGeo<S, NCH, ROWS>;
   constexpr int PW = G::PW, NPX = G::NPX, NP = G::NP, NPXP = G::NPXP, BUF = G::BUF, STEPS = G::STEPS, CING = G::CING, PH = G::PH;
+  static_assert(!SC || (S == 1 && NCH == 2 && ROWS == 16 && !RES), "the fp16 shortcut is built into the stride-1 form's two-chunk stream");
   if (*a.ovf != 0) return;  // (the guarded rerun follows)
   extern __shared__ __attribute__((aligned(16))) uint4 lds4[];
   uint4* s_buf = lds4;
   float* s_bn = reinterpret_cast<float*>(lds4 + 2 * BUF);
   float* s_par = s_bn + 2 * CING;  // [os 64][ob 64][rs 64]
+  uint4* s_sc = reinterpret_cast<uint4*>(s_par + 3 * RW_WC);  // (SC) the shortcut operand's planes
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i16 = lane & 15, q = lane >> 4;
   const int ct = wave;  // the wave's 16-column tile of the workgroup's 64 output channels
   const int cout_g = a.Cout / a.groups, nhalf = cout_g / RW_WC;
@@ -135,6 +158,13 @@ __global__ __launch_bounds__(RW_CT) __attribute__((amdgpu_waves_per_eu(1, 1))) v
         for (int kx = 0; kx < 3; ++kx)
 #pragma unroll
           for (int p = 0; p < 2; ++p) Wr[c][ky * 3 + kx][p] = wg[(size_t)((c * 3 + ky) * 24 + (p * 3 + kx) * 4) * cout_g];
+  }
+  // (SC) the shortcut's weights: image [g][plane][quarter][cout_g] (split_shortcut_kernel), two fragments
+  u32x4 Wsc[2];
+  if constexpr (SC) {
+    const u32x4* ws = reinterpret_cast<const u32x4*>(a.sc_planes) + (size_t)g * 8 * cout_g + (q * cout_g + half * RW_WC + ct * 16 + i16);
+    Wsc[0] = ws[0];
+    Wsc[1] = ws[(size_t)4 * cout_g];
   }
   if (tid < CING) {  // relu(x s + b) 2^k = relu(x (s 2^k) + b 2^k), exactly
     const int ci = g * CING + tid;
@@ -244,6 +274,35 @@ __global__ __launch_bounds__(RW_CT) __attribute__((amdgpu_waves_per_eu(1, 1))) v
     *reinterpret_cast<uint2*>(sp + (bsel * BUF * 16 + 2 * NPXP * 32 + i * (RW_PPI * 32))) = make_uint2(l0, l1);
   };
 
+  // ---- (SC) the shortcut's operand: item i of a thread = piece tid & 7 (4 channels) of the tile's output pixel
+  //      (tid >> 3) + 32 i = row 2 i + (tid >> 7), column (tid >> 3) & 15, read at the strided position of the block input.
+  //      Requested beside the PREVIOUS tile's last chunk, scaled by sc_xscale, split and stored beside this tile's first
+  //      chunk, multiplied beside its last: the barrier between the two chunks publishes the region, the one at the head of
+  //      the next tile frees it.  Rows and columns past the map repeat its last ones (never stored) ----
+  u32x4 pre_s[SC ? SC_ITEMS : 1];
+  u32x4 xsh[2], xsl[2];
+  const unsigned sc_st_base = (unsigned)((((q8 >> 2) * SC_NPXP + (tid >> 3)) * 4 + (q8 & 3)) * 8);
+  const int sc_a_base = ((q >> 1) * SC_NPXP + i16) * 2 + (q & 1);
+  auto issue_sc = [&](const int i, const int n_, const int oy_, const int ox_) __attribute__((always_inline)) {
+    if constexpr (SC) {
+      const float* sc_n = a.sc_in + (size_t)n_ * a.sc_H * a.sc_W * a.sc_cin;  // (uniform)
+      const int oy = min(oy_ + 2 * i + (tid >> 7), a.Ho - 1), ox = min(ox_ + ((tid >> 3) & 15), a.Wo - 1);
+      pre_s[i] = *reinterpret_cast<const u32x4*>(
+          at_off(sc_n, (pix_off(oy * a.sc_stride, ox * a.sc_stride, a.sc_W, a.sc_cin) + (unsigned)(g * 32 + 4 * q8)) << 2));
+    }
+  };
+  auto store_sc = [&](const int i) __attribute__((always_inline)) {
+    if constexpr (SC) {
+      unsigned h0, h1, l0, l1;
+      split_h(__uint_as_float(pre_s[i][0]) * a.sc_xscale, __uint_as_float(pre_s[i][1]) * a.sc_xscale, h0, l0);
+      split_h(__uint_as_float(pre_s[i][2]) * a.sc_xscale, __uint_as_float(pre_s[i][3]) * a.sc_xscale, h1, l1);
+      hmax = pk_max_u16(pk_max_u16(hmax, h0 & 0x7FFF7FFFu), h1 & 0x7FFF7FFFu);  // (the residual stream has both signs)
+      unsigned char* sp = reinterpret_cast<unsigned char*>(s_sc) + sc_st_base;
+      *reinterpret_cast<uint2*>(sp + i * (RW_PPI * 32)) = make_uint2(h0, h1);
+      *reinterpret_cast<uint2*>(sp + (2 * SC_NPXP * 32 + i * (RW_PPI * 32))) = make_uint2(l0, l1);
+    }
+  };
+
   // ---- accumulators: ROWS output rows x (16 pixels x 16 channels); a lane holds channels ct 16 + 4 q .. + 3 of pixel column i16 ----
   f32x4 acc[ROWS];
   const int ch_l = g * cout_g + half * RW_WC + ct * 16 + 4 * q;
@@ -319,6 +378,27 @@ __global__ __launch_bounds__(RW_CT) __attribute__((amdgpu_waves_per_eu(1, 1))) v
         if constexpr (k == 1) store_item(i, B ^ 1);
         if constexpr (k == 2) issue_item(i, CI, ni, oyi, oxi);
       });
+      if constexpr (SC && !LAST) {  // this tile's shortcut operand -> LDS
+        constexpr int klo = (s * SC_ITEMS + STEPS - 1) / STEPS, khi = ((s + 1) * SC_ITEMS + STEPS - 1) / STEPS;
+        static_for<klo, (khi < SC_ITEMS ? khi : SC_ITEMS)>([&](auto kc) __attribute__((always_inline)) { store_sc(decltype(kc)::value); });
+      }
+      if constexpr (SC && LAST) {
+        // the shortcut's products: row o's fragment pair is requested at step 3 o and multiplied at step 3 o + 3, in the
+        // plane order of the taps; then the next tile's operand is requested into the registers the first chunk emptied
+        if constexpr (s % 3 == 0 && s >= 3 && s / 3 - 1 < ROWS) {
+          constexpr int o = s / 3 - 1;
+          acc[o] = mfma_h(Wsc[1], xsh[o & 1], acc[o]);
+          acc[o] = mfma_h(Wsc[0], xsl[o & 1], acc[o]);
+          acc[o] = mfma_h(Wsc[0], xsh[o & 1], acc[o]);
+        }
+        if constexpr (s % 3 == 0 && s / 3 < ROWS) {
+          constexpr int o = s / 3;
+          xsh[o & 1] = __builtin_bit_cast(u32x4, s_sc[sc_a_base + o * 2 * RW_TW]);
+          xsl[o & 1] = __builtin_bit_cast(u32x4, s_sc[sc_a_base + 4 * SC_NPXP + o * 2 * RW_TW]);
+        }
+        constexpr int klo = (s * SC_ITEMS + STEPS - 1) / STEPS, khi = ((s + 1) * SC_ITEMS + STEPS - 1) / STEPS;
+        static_for<klo, (khi < SC_ITEMS ? khi : SC_ITEMS)>([&](auto kc) __attribute__((always_inline)) { issue_sc(decltype(kc)::value, ni, oyi, oxi); });
+      }
       if constexpr (LAST && RES) {
         constexpr int olo = (s * ROWS + STEPS - 1) / STEPS, ohi = ((s + 1) * ROWS + STEPS - 1) / STEPS;
         static_for<olo, (ohi < ROWS ? ohi : ROWS)>([&](auto oc) __attribute__((always_inline)) { issue_res(decltype(oc)::value, n0, oy0, ox0); });
@@ -326,10 +406,10 @@ __global__ __launch_bounds__(RW_CT) __attribute__((amdgpu_waves_per_eu(1, 1))) v
     });
   };
 
-  // ---- epilogue of a tile: fused 1x1 shortcut (float32 MFMA, as conv_bf3w_kernel), affine, residual, ReLU, 16-byte stores ----
+  // ---- epilogue of a tile: fused 1x1 shortcut (without SC: float32 MFMA, as conv_bf3w_kernel), affine, residual, ReLU, 16-byte stores ----
   auto finish = [&](const int n_, const int oy_, const int ox_) __attribute__((always_inline)) {
     const int ox = min(ox_ + i16, a.Wo - 1);
-    if (a.sc_in) {
+    if (!SC && a.sc_in) {
       const int sc_cg = a.sc_cin / a.groups;
       const float* wsc = a.sc_w + ((size_t)g * sc_cg + q) * cout_g + half * RW_WC + ct * 16 + i16;
       const float ss = s_par[2 * RW_WC + ct * 16 + i16];
@@ -396,6 +476,10 @@ __global__ __launch_bounds__(RW_CT) __attribute__((amdgpu_waves_per_eu(1, 1))) v
     // units (tile, chunk 0) from buffer 0, (tile, chunk 1) from buffer 1
 #pragma unroll
     for (int i = 0; i < NP; ++i) issue_item(i, 1, n0, oy0, ox0);
+    if constexpr (SC) {
+#pragma unroll
+      for (int i = 0; i < SC_ITEMS; ++i) issue_sc(i, n0, oy0, ox0);
+    }
     init_acc();
     for (;;) {
       n1 = n0; oy1 = oy0; ox1 = ox0;
@@ -441,7 +525,52 @@ __global__ __launch_bounds__(RW_CT) __attribute__((amdgpu_waves_per_eu(1, 1))) v
   if ((hmax & 0x7FFFu) >= 0x7C00u || ((hmax >> 16) & 0x7FFFu) >= 0x7C00u) atomicOr(a.ovf, 1);  // (infinity or NaN: out of fp16's range)
 }
 
+// The fused shortcut's weights as fp16 planes: packed float32 [g][cin_g][cout_g] -> [g][chunk of 32][plane][quarter][cout_g] of
+// 16-byte entries (the eight channels 8 quarter .. + 7 of a chunk: one A fragment per wave and plane), each weight times
+// wscale[output channel] * factor first -- the accumulators it is added into hold w_scale[c] act_scale times the sum, and the
+// operand arrives multiplied by sc_xscale: factor = act_scale / sc_xscale (powers of two: exact)
+__global__ __launch_bounds__(256) void split_shortcut_kernel(const float* __restrict__ w, uint4* __restrict__ out, int groups, int cin_g,
+                                                             int cout_g, const float* __restrict__ wscale, float factor) {
+  const int nch = cin_g / 32;
+  const int total = groups * nch * 4 * cout_g;
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const int col = idx % cout_g;
+  int r = idx / cout_g;
+  const int qq = r & 3;
+  r >>= 2;
+  const int chunk = r % nch, g = r / nch;
+  const float f = wscale[g * cout_g + col] * factor;
+  float v[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) v[j] = w[((size_t)g * cin_g + chunk * 32 + 8 * qq + j) * cout_g + col] * f;
+  uint4 hi, lo;
+  split_h(v[0], v[1], hi.x, lo.x);
+  split_h(v[2], v[3], hi.y, lo.y);
+  split_h(v[4], v[5], hi.z, lo.z);
+  split_h(v[6], v[7], hi.w, lo.w);
+  const size_t base = (size_t)(g * nch + chunk) * 8 * cout_g + (size_t)qq * cout_g + col;
+  out[base] = hi;
+  out[base + (size_t)4 * cout_g] = lo;
+}
+
 }  // namespace
+
+// second convolutions whose fused 1x1 shortcut can run as fp16x2 products: conv_rw_kernel's stride-1 layer with a shortcut of 32
+// input channels per group (stage 3 of WR-ResNet-22-4: one K = 32 fragment), and the stride-1 layer of 128 -> 128 channels per
+// group with a shortcut of 64 (stage 4: conv_bf3flat_kernel, where the map is small enough for the flattened tiling)
+bool conv_shortcut_planes_layer(const ConvArgs& second, int sc_cin_g) {
+  if (conv_rw_kind(second) == 1) return sc_cin_g == 32;
+  return second.ksize == 3 && second.stride == 1 && second.groups >= 1 && second.Cin == second.Cout &&
+         second.Cout == 128 * second.groups && sc_cin_g == 64;
+}
+size_t conv_shortcut_image_bytes(int groups, int cin_g, int cout_g) { return (size_t)groups * (cin_g / 32) * 8 * cout_g * 16; }
+void launch_split_shortcut(const float* sc_w, void* img, int groups, int cin_g, int cout_g, const float* w_scale, float factor,
+                           hipStream_t s) {
+  const int total = groups * (cin_g / 32) * 4 * cout_g;
+  hipLaunchKernelGGL(split_shortcut_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, sc_w, reinterpret_cast<uint4*>(img),
+                     groups, cin_g, cout_g, w_scale, factor);
+}
 
 // the layers conv_rw_kernel takes (fp16x2, 3x3, SAME padding; channels per group in -> out):
 //   1  stride 1, 64 -> 64   (stage 3 of WR-ResNet-22-4: the convolutions of its blocks but the strided first one)
@@ -459,10 +588,11 @@ int conv_rw_kind(const ConvArgs& a) {
 bool conv_rw_layer(const ConvArgs& a) { return conv_rw_kind(a) == 1; }
 
 namespace {
-template <int S, int NCH, int ROWS, bool BN, bool RES>
+template <int S, int NCH, int ROWS, bool BN, bool RES, bool SC = false>
 int launch_rw_t(const ConvArgs& a, const uint4* wimg, hipStream_t s) {
   using G = RwGeo<S, NCH, ROWS>;
-  static_assert(G::LDS <= 160 * 1024 - 1024, "two chunk buffers must fit the CU's LDS");
+  constexpr size_t LDS = G::LDS + (SC ? SC_LDS : 0);
+  static_assert(LDS <= 160 * 1024 - 1024, "two chunk buffers (and the shortcut's operand) must fit the CU's LDS");
   RwTiles td{};
   td.tiles_x = (a.Wo + RW_TW - 1) / RW_TW;
   td.tiles_y = (a.Ho + ROWS - 1) / ROWS;
@@ -472,7 +602,7 @@ int launch_rw_t(const ConvArgs& a, const uint4* wimg, hipStream_t s) {
   td.m_ty = (1ull << 42) / td.tiles_y + 1;
   td.total = (int)tiles;
   static bool lds_ready[64];
-  if (!cpx_dyn_lds_ready(reinterpret_cast<const void*>(conv_rw_kernel<S, NCH, ROWS, BN, RES>), lds_ready, 160 * 1024 - 1024)) return -1;
+  if (!cpx_dyn_lds_ready(reinterpret_cast<const void*>(conv_rw_kernel<S, NCH, ROWS, BN, RES, SC>), lds_ready, 160 * 1024 - 1024)) return -1;
   // one workgroup per CU (four waves, each with a SIMD's whole register file), shared among the (group, 64-channel half)
   // pairs; a multiple of eight per pair so that blockIdx.x & 7 names the XCD -- the halves of a group then walk the same tiles
   // on the same XCD at the same time and share the patch in its L2
@@ -487,7 +617,7 @@ int launch_rw_t(const ConvArgs& a, const uint4* wimg, hipStream_t s) {
   const int ny = a.groups * ((a.Cout / a.groups) / RW_WC);
   int gx = std::max(8, cus_of[dev] / ny / 8 * 8);
   gx = (int)std::min<long long>(gx, (tiles + 7) / 8 * 8);
-  hipLaunchKernelGGL((conv_rw_kernel<S, NCH, ROWS, BN, RES>), dim3((unsigned)gx, (unsigned)ny), dim3(RW_CT), G::LDS, s, a, wimg, td);
+  hipLaunchKernelGGL((conv_rw_kernel<S, NCH, ROWS, BN, RES, SC>), dim3((unsigned)gx, (unsigned)ny), dim3(RW_CT), LDS, s, a, wimg, td);
   return 0;
 }
 }  // namespace
@@ -503,6 +633,13 @@ int launch_conv_rw(const ConvArgs& a, const void* wimg, hipStream_t s) {
   const bool bn = a.in_scale != nullptr, res = a.residual != nullptr;
   if (kind == 1) {
     if (a.pad_top != 1 || a.pad_left != 1 || a.H != a.Ho || a.W != a.Wo) return -2;
+    if (a.sc_in && a.sc_planes) {  // the shortcut on the fp16 pipe: the form a stage's first block has (no prologue, no residual)
+      if (bn || res || !conv_shortcut_planes_layer(a, a.sc_cin / a.groups) || a.sc_stride < 1 || !(a.sc_xscale > 0.0f) ||
+          (a.sc_H - 1) / a.sc_stride + 1 != a.Ho || (a.sc_W - 1) / a.sc_stride + 1 != a.Wo)
+        return -2;
+      if ((long long)a.sc_H * a.sc_W >= (1 << 24) || (long long)a.sc_H * a.sc_W * a.sc_cin >= (1ll << 30)) return -3;
+      return launch_rw_t<1, 2, 16, false, false, true>(a, wi, s);
+    }
     if (bn && res) return launch_rw_t<1, 2, 16, true, true>(a, wi, s);
     if (bn) return launch_rw_t<1, 2, 16, true, false>(a, wi, s);
     if (res) return launch_rw_t<1, 2, 16, false, true>(a, wi, s);

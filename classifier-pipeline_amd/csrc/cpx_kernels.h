@@ -193,6 +193,11 @@ struct ConvArgs {
   const float* sc_w;     // packed [groups][1][sc_cin / groups][Cout / groups]
   const float* sc_bias;  // [Cout]
   int sc_H, sc_W, sc_cin, sc_stride;
+  // fp16x2, the layers of conv_shortcut_planes_layer(): the shortcut's products on the fp16 matrix pipe too.  sc_planes = the
+  // fp16 plane image of sc_w times w_scale[c] act_scale / sc_xscale (launch_split_shortcut; act_scale as THIS launch has it),
+  // sc_xscale = the power of two sc_in is multiplied by before its split.  nullptr: the float32 side product
+  const void* sc_planes;
+  float sc_xscale;
   // conv_block32_kernel<true, true> only: the network's first convolution computed while the block's patch is staged (`in` is
   // then never read): its raw input [N, H, W, groups], packed weights [groups][9][1][8] and bias [8 groups]
   const float* c1_in;
@@ -256,6 +261,15 @@ int launch_conv_block32s(const ConvArgs& a, const ConvArgs& b, const void* wa, c
 int conv_rw_kind(const ConvArgs& a);
 bool conv_rw_layer(const ConvArgs& a);  // kind 1
 int launch_conv_rw(const ConvArgs& a, const void* wimg, hipStream_t s);
+// the fused 1x1 shortcut as fp16x2 products (ConvArgs::sc_planes): which second convolutions can take it (by layer shape and
+// the shortcut's input channels per group), the bytes of its weight image [g][chunk of 32][plane][quarter][cout_g] of 16-byte
+// entries, and the kernel that builds it: fp16 planes of sc_w[g][k][c] * w_scale[c] * factor
+bool conv_shortcut_planes_layer(const ConvArgs& second, int sc_cin_g);
+size_t conv_shortcut_image_bytes(int groups, int cin_g, int cout_g);
+void launch_split_shortcut(const float* sc_w, void* img, int groups, int cin_g, int cout_g, const float* w_scale, float factor,
+                           hipStream_t s);
+// the per-output-channel weight scales [Cout] (device) inside a two-plane layer's weight images
+const float* conv_bf3_weight_scales(const ConvArgs& a, const void* wimg);
 void launch_head(const HeadArgs& a, hipStream_t s);
 void launch_count_overflow(int* ovf, int n_words, hipStream_t s);
 

@@ -642,6 +642,10 @@ int cpx_conv2d(cpx_handle* h, const cpx_conv_desc* desc);
  *                        Inside cpx_cnn_forward the residual blocks whose convolutions are stride 1 with 32 output
  *                        channels per group (stage 2 of WR-ResNet-22-4) run as ONE launch each, the tensor between
  *                        their two convolutions kept on chip (environment CPX_CNN_BLOCK_FUSION=0|1|2, default 2).
+ *                        The 1x1 projection shortcut of a stage's first block is folded into that block's second
+ *                        convolution: as fp16x2 products of the un-normalised block input at stages 3 and 4 when the network
+ *                        has a bound for it (cpx_cnn_set_residual_bounds, environment CPX_CNN_SHORTCUT_FP16=0|1, default 1),
+ *                        as a float32 side product (v_mfma_f32_*_f32) otherwise and at stage 2.
  *                        Every other layer as BF16X3.
  *                        Two conditions on the 2^-22 figure and on the rerun, both met inside cpx_cnn_forward and the
  *                        caller's to meet for a bare cpx_conv2d (activation scale 1): (1) the low plane is an fp16
@@ -741,6 +745,25 @@ void cpx_cnn_destroy(cpx_cnn* cnn);
  * small activations keep their low plane's bits; a bound that turns out too small costs
  * time (the overflow rerun), never correctness.  Without this call the scale is 1. */
 int cpx_cnn_set_activation_bounds(cpx_cnn* cnn, const float* bounds, int n);
+/* CPX_CNN_MATH_FP16X2: an upper bound of |x| of the INPUT of each stage's first block (n = 3 values: stages 2, 3, 4) -- the
+ * un-normalised tensor the stage's 1x1 projection shortcut reads; e.g. max over channels of |moving_mean| + 64 sqrt(moving_variance
+ * + eps) of the BatchNorm that normalises it.  With a bound the shortcut that is fused into the block's second convolution
+ * runs as fp16x2 products too (stage 3: K = 32 per group, stage 4: K = 64 where the map is small enough for the flattened
+ * kernel; stage 2's K = 8 has nothing to win and keeps the float32 instruction): the operand is multiplied by a power of two sx before its fp16 split, the shortcut's weights by
+ * w_scale[c] act_scale / sx, so that the products arrive at the accumulators' scale.  sx is decided PER LAYER ON THE HOST, when
+ * the bounds are set (and again when cpx_cnn_set_activation_bounds changes act_scale), by cpx_cnn_shortcut_scale below; a
+ * layer for which no power of two fits keeps the float32 side product, as does every layer of a network that never
+ * received a bound (value 0, the state after cpx_cnn_create) and every handle created under CPX_CNN_SHORTCUT_FP16=0.  An operand
+ * beyond fp16's range after scaling raises the block's overflow word like an activation: the guarded rerun (exact split,
+ * float32 shortcut) follows.  A negative or non-finite bound, or n != 3: CPX_ERR_INVALID.  The first call with a bound
+ * synchronises the handle's stream (the largest scaled shortcut weight is read back once per network). */
+int cpx_cnn_set_residual_bounds(cpx_cnn* cnn, const float* bounds, int n);
+/* A diagnostic and test helper, not needed to run a network: the host's choice of sx as cpx_cnn_set_residual_bounds makes it
+ * (pure arithmetic, no device; the window below is this build's and may move with the kernels): bound = the operand's bound, wmax = the largest |shortcut weight| *
+ * w_scale[c] * act_scale.  Returns 1 and *sx = 2^e when a power of two exists with bound sx in [2^3, 2^15] and wmax / sx in
+ * [2^-1, 2^15) -- inside fp16, and high enough that the low planes (2^-24 absolute) keep 22 bits of a typical operand --,
+ * the one that puts the bound at 2^12 (sixteen-fold headroom) or the nearest the window allows; 0 (*sx = 0) when none does. */
+int cpx_cnn_shortcut_scale(float bound, float wmax, float* sx);
 /* in_dev float32 [N, H, W, in_channels] (NHWC, values 0..255) -> logits_dev [N, n_labels] and, when not NULL,
  * probs_dev (sigmoid). */
 int cpx_cnn_forward(cpx_cnn* cnn, const float* in_dev, int N, int H, int W, float* logits_dev, float* probs_dev);
