@@ -5,6 +5,7 @@ selection and prediction aggregation are host work as in the reference."""
 
 import json
 import logging
+import os
 import time
 from pathlib import Path
 
@@ -352,12 +353,25 @@ class WRResNetInterpreter(Interpreter):
 
 
 class LiteInterpreter(Interpreter):
-    """Any float32 `.tflite` graph of the operator set cpx/ml_tools/tflite_reader.py reads (the reference's inceptionv3
-    family, ml_tools/kerasmodel.py:171-180,259-350) on the device graph executor (cpx_graph_*): the reference's
-    LiteInterpreter (interpreter.py:520-560) with the TFLite runtime replaced.  model = <name>.tflite + <name>.json.
-    predict runs the whole batch in one forward (the reference loops sample by sample because its runtime must)."""
+    """Any float32 or dynamic-range quantised `.tflite` graph of the operator set cpx/ml_tools/tflite_reader.py reads (the
+    reference's inceptionv3 family, ml_tools/kerasmodel.py:171-180,259-350; its converter writes INT8 filters,
+    src/tfliteconverter.py:54-62) on the device graph executor (cpx_graph_*): the reference's LiteInterpreter
+    (interpreter.py:520-560) with the TFLite runtime replaced.  model = <name>.tflite + <name>.json.
+    predict runs the whole batch in one forward (the reference loops sample by sample because its runtime must).
+    CPX_TFLITE_QUANT_MATH=hybrid|float (default hybrid) chooses how INT8 filters are run: on the int8 operators, or
+    multiplied out on the host and run in float32."""
 
     TYPE = "TFLite"
+    DEFAULT_QUANT_MATH = "hybrid"
+
+    @classmethod
+    def quant_math(cls):
+        from .tflite_graph import QUANT_MATHS
+
+        mode = os.environ.get("CPX_TFLITE_QUANT_MATH", cls.DEFAULT_QUANT_MATH)
+        if mode not in QUANT_MATHS:
+            raise ValueError("CPX_TFLITE_QUANT_MATH=%r: one of %s" % (mode, ", ".join(QUANT_MATHS)))
+        return mode
 
     def __init__(self, model_file, run_over_network=False, load_model=True, engine=None):
         super().__init__(model_file, run_over_network)
@@ -375,7 +389,8 @@ class LiteInterpreter(Interpreter):
         logging.info("Reading TFLite graph %s", self.model_file)
         with open(str(self.model_file), "rb") as fh:
             self._graph = Graph(fh.read())
-        plan = build_plan(self._graph)   # refuses, by operator, what the executor does not run
+        self._quant_math = self.quant_math()
+        plan = build_plan(self._graph, quantised_math=self._quant_math)   # refuses, by operator, what the executor does not run
         self._plans[(plan.graph_input_shape, None)] = plan
         if plan.output_shape[:2] != (1, 1) or plan.output_shape[2] != len(self.labels):
             raise ValueError("model output %s but %d labels" % (plan.output_shape, len(self.labels)))
@@ -424,7 +439,8 @@ class LiteInterpreter(Interpreter):
         key = ((hwc[0], hwc[1], cin), None if cmap is None else tuple(cmap))
         plan = self._plans.get(key)
         if plan is None:
-            plan = self._plans[key] = build_plan(self._graph, input_shape=key[0], channel_map=cmap)
+            plan = self._plans[key] = build_plan(self._graph, input_shape=key[0], channel_map=cmap,
+                                                 quantised_math=self._quant_math)
         dev = self._devices.get((id(engine), key))
         if dev is None or dev.eng is not engine or not engine.h:
             dev = self._devices[(id(engine), key)] = GraphDevice(engine, plan)

@@ -1,4 +1,4 @@
-"""A float32 TFLite graph (cpx/ml_tools/tflite_reader.py: Graph) turned into a plan the device executor runs
+"""A TFLite graph, float32 or dynamic-range quantised, (cpx/ml_tools/tflite_reader.py: Graph) turned into a plan the device executor runs
 (cpx_graph_create / cpx_graph_forward, include/cpx.h) -- what the reference's LiteInterpreter hands to the TFLite runtime
 (src/ml_tools/interpreter.py:520-560).  build_plan is host work and needs no GPU:
 
@@ -12,7 +12,13 @@
   without constants);
 * tensors get offsets in one arena by lifetime (first write to last read, in operator order); the offsets are per
   sample, the arena of a forward over N samples is N times as large;
-* CONV_2D filters are transposed from TFLite's OHWI to the kernel's [tap][Cin][Cout], Cin padded to 16 and Cout to 32.
+* CONV_2D filters are transposed from TFLite's OHWI to the kernel's [tap][Cin][Cout], Cin padded to 16 and Cout to 32;
+* a CONV_2D / FULLY_CONNECTED with an INT8 filter (dynamic-range quantisation: what the reference's converter writes,
+  src/tfliteconverter.py:54-62) becomes a hybrid operator, CONV_Q8 / FC_Q8 (quantised_math="hybrid"): its second input is
+  a per-sample parameter tensor (1 x 1 x 4: sx, inv, zp) that ONE QUANT_PARAMS operator per input tensor view writes,
+  placed in front of the view's first quantised consumer; the int8 filter is packed in the order the int8 MFMA's B
+  fragment wants (pack_conv_filter_q8), the per-channel integer sums wsum behind it.  The arithmetic: include/cpx.h.
+  quantised_math="float" multiplies the filters out (int8 x scale) and plans the float32 operators.
 
 GraphDevice uploads a plan's constants to an engine's device and runs it."""
 import ctypes as C
@@ -96,11 +102,18 @@ def _channel_const(g, tid, channels, what):
     return v.astype(np.float32)
 
 
-def build_plan(g, input_shape=None, output=None, channel_map=None):
+QUANT_MATHS = ("hybrid", "float")
+Q8_KINDS = (_lib.GRAPH_CONV_Q8, _lib.GRAPH_FC_Q8)
+
+
+def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_math="hybrid"):
     """g: tflite_reader.Graph.  input_shape: (H, W, C) of a sample, default: the flatbuffer's.  output: the tensor the
     forward hands out, default the graph's output; the operators it does not need are dropped.  channel_map: up to 4
     indices into the channels of the sample the CALLER brings ([N, H, W, max(map) + 1 or more]): the graph's input
-    channel c is the caller's channel channel_map[c]."""
+    channel c is the caller's channel channel_map[c].  quantised_math: "hybrid" runs INT8 filters on the int8 operators,
+    "float" multiplies them out on the host."""
+    if quantised_math not in QUANT_MATHS:
+        raise ValueError("quantised_math %r: one of %s" % (quantised_math, ", ".join(QUANT_MATHS)))
     g.check_executable()
     if len(g.inputs) != 1 or len(g.outputs) < 1:
         raise NotImplementedError("graphs with %d inputs" % len(g.inputs))
@@ -127,6 +140,36 @@ def build_plan(g, input_shape=None, output=None, channel_map=None):
         producer[o.out] = o
         return o
 
+    def filter_of(op, tid):
+        """-> (filter, per-output-channel scales or None): INT8 with its scales in hybrid mode, float32 otherwise."""
+        ten = g.quantised_filter(op)
+        if ten is None:
+            return g.const(tid), None
+        if quantised_math == "float":
+            return g.dequantised(tid), None
+        sc = np.asarray(ten["quant"]["scale"], np.float32).reshape(-1)
+        return ten["const"], (np.full(ten["shape"][0], sc[0], np.float32) if sc.size == 1 else sc)
+
+    qparams = {}   # (input tensor view, symmetric) -> parameter tensor id
+
+    def params_of(x, symmetric, src):
+        """The parameter tensor of view x; its QUANT_PARAMS operator goes in front of the first consumer that asks, i.e.
+        behind every producer of x (the flatbuffer's operators are in execution order)."""
+        key = (x.id, bool(symmetric))
+        if key not in qparams:
+            pid = ("quant_params", x.id, bool(symmetric))
+            T[pid] = PlanTensor(pid, 1, 1, 4)
+            o = PlanOp(_lib.GRAPH_QUANT_PARAMS, "QUANT_PARAMS", x.id, pid, param=1.0 if symmetric else 0.0)
+            o.source = src
+            ops.append(o)
+            qparams[key] = pid
+        return qparams[key]
+
+    def overflow_check(what, k):
+        if k * 127 * 255 >= 2 ** 31:
+            raise NotImplementedError("%s: %d products of an 8-bit activation and an INT8 weight could overflow the int32 "
+                                      "accumulator" % (what, k))
+
     for i, op in enumerate(g.ops):
         name = op["name"]
         what = "operator %d (%s)" % (i, name)
@@ -140,7 +183,7 @@ def build_plan(g, input_shape=None, output=None, channel_map=None):
         if op.get("act", 0) not in (ACT_NONE, ACT_RELU, ACT_RELU6):
             raise NotImplementedError("%s: fused activation %d" % (what, op["act"]))
         if name == "CONV_2D":
-            w = g.const(ins[1])
+            w, fscale = filter_of(op, ins[1])
             co, kh, kw, ci = w.shape
             if ci != x.C:
                 raise NotImplementedError("%s: grouped convolution (filter depth %d, input depth %d)" % (what, ci, x.C))
@@ -153,8 +196,12 @@ def build_plan(g, input_shape=None, output=None, channel_map=None):
                 raise NotImplementedError("%s: the %d x %d input is smaller than the kernel" % (what, x.H, x.W))
             T[y] = PlanTensor(y, ho, wo, co)
             bias = g.const(ins[2]) if len(ins) > 2 else None
-            emit(PlanOp(_lib.GRAPH_CONV, name, x.id, y, kh=kh, kw=kw, stride_h=sh, stride_w=sw, pads=(pt, pl, pb, pr),
-                        act=op.get("act", 0), filter=w, scale=None,
+            kind, in1 = _lib.GRAPH_CONV, -1
+            if fscale is not None:
+                overflow_check(what, kh * kw * ci)
+                kind, in1 = _lib.GRAPH_CONV_Q8, params_of(x, False, i)
+            emit(PlanOp(kind, name, x.id, y, in1=in1, kh=kh, kw=kw, stride_h=sh, stride_w=sw, pads=(pt, pl, pb, pr),
+                        act=op.get("act", 0), filter=w, scale=None, filter_scale=fscale,
                         shift=np.zeros(co, np.float32) if bias is None else np.asarray(bias, np.float32).reshape(-1)), i)
         elif name in ("MAX_POOL_2D", "AVERAGE_POOL_2D"):
             kh, kw = op["filter_height"], op["filter_width"]
@@ -189,7 +236,7 @@ def build_plan(g, input_shape=None, output=None, channel_map=None):
                     sc, sf = one, -c
                 T[y] = PlanTensor(y, x.H, x.W, x.C)
                 p = producer.get(x.id)
-                if p is not None and p.kind in (_lib.GRAPH_CONV, _lib.GRAPH_AFFINE) and p.act == ACT_NONE and not p.copy \
+                if p is not None and p.kind in (_lib.GRAPH_CONV, _lib.GRAPH_CONV_Q8, _lib.GRAPH_AFFINE) and p.act == ACT_NONE and not p.copy \
                         and len(consumers.get(x.id, [])) == 1 and x.id != gout:
                     # fold: (v * s0 + h0) * sc + sf; the producer now writes this operator's output
                     s0 = one if p.scale is None else p.scale
@@ -239,13 +286,19 @@ def build_plan(g, input_shape=None, output=None, channel_map=None):
             T[y] = PlanTensor(y, 1, 1, x.C)
             emit(PlanOp(_lib.GRAPH_MEAN, name, x.id, y), i)
         elif name == "FULLY_CONNECTED":
-            w = g.const(ins[1])
+            w, fscale = (None, None) if g.const(ins[1]) is None else filter_of(op, ins[1])
             if w is None or x.H != 1 or x.W != 1 or w.shape[1] != x.C:
                 raise NotImplementedError("%s: weights %s on a %d x %d x %d input" % (what, None if w is None else list(w.shape), x.H, x.W, x.C))
             bias = g.const(ins[2]) if len(ins) > 2 else None
             T[y] = PlanTensor(y, 1, 1, w.shape[0])
-            emit(PlanOp(_lib.GRAPH_FC, name, x.id, y, act=op["act"], weights=np.ascontiguousarray(w, np.float32),
-                        shift=None if bias is None else np.asarray(bias, np.float32).reshape(-1)), i)
+            if fscale is not None:
+                overflow_check(what, w.shape[1])
+                emit(PlanOp(_lib.GRAPH_FC_Q8, name, x.id, y, in1=params_of(x, not op.get("asymmetric_quantize_inputs", False), i),
+                            act=op["act"], filter=w, weights=pack_fc_filter_q8(w), scale=fscale,
+                            shift=np.zeros(w.shape[0], np.float32) if bias is None else np.asarray(bias, np.float32).reshape(-1)), i)
+            else:
+                emit(PlanOp(_lib.GRAPH_FC, name, x.id, y, act=op["act"], weights=np.ascontiguousarray(w, np.float32),
+                            shift=None if bias is None else np.asarray(bias, np.float32).reshape(-1)), i)
         elif name in ("LOGISTIC", "SOFTMAX"):
             T[y] = PlanTensor(y, x.H, x.W, x.C)
             emit(PlanOp(_lib.GRAPH_LOGISTIC if name == "LOGISTIC" else _lib.GRAPH_SOFTMAX, name, x.id, y,
@@ -386,7 +439,53 @@ def build_plan(g, input_shape=None, output=None, channel_map=None):
     for o in ops:
         if o.kind == _lib.GRAPH_CONV:
             o.weights = pack_conv_filter(o.filter)
+        elif o.kind == _lib.GRAPH_CONV_Q8:
+            o.weights = pack_conv_filter_q8(o.filter)
+            # the device multiplies by float32(filter scale x folded scale)
+            o.scale = o.filter_scale if o.scale is None else (o.filter_scale * o.scale).astype(np.float32)
     return plan
+
+
+def pack_conv_filter_q8(w_ohwi):
+    """INT8 OHWI [Cout, kh, kw, Cin] -> bytes: [kh * kw][chunks of GRAPH_CONV_Q8_KC input channels][tiles of GRAPH_CONV_CO
+    output channels][64 lanes][16], lane l = output channel l & 31 of the tile, input channels 16 * (l >> 5) + j of the
+    chunk (the B fragment of v_mfma_i32_32x32x32_i8), zeros beyond Cin and Cout; behind them int32 wsum[Cout rounded up]."""
+    w = np.asarray(w_ohwi)
+    assert w.dtype == np.int8, w.dtype
+    co, kh, kw, ci = w.shape
+    KC, CO = _lib.GRAPH_CONV_Q8_KC, _lib.GRAPH_CONV_CO
+    nch, nt = -(-ci // KC), -(-co // CO)
+    full = np.zeros((nt * CO, kh * kw, nch * KC), np.int8)
+    full[:co, :, :ci] = w.reshape(co, kh * kw, ci)
+    # [tile, c, tap, chunk, half, j] -> [tap, chunk, tile, half, c, j]
+    frag = full.reshape(nt, CO, kh * kw, nch, 2, 16).transpose(2, 3, 0, 4, 1, 5)
+    wsum = np.zeros(nt * CO, np.int32)
+    wsum[:co] = w.reshape(co, -1).astype(np.int64).sum(axis=1)
+    return np.concatenate([np.ascontiguousarray(frag).reshape(-1).view(np.uint8), wsum.view(np.uint8)])
+
+
+def unpack_conv_filter_q8(packed, shape):
+    """The inverse of pack_conv_filter_q8 for a filter of `shape` (OHWI) -> (int8 filter, int32 wsum[Cout])."""
+    co, kh, kw, ci = shape
+    KC, CO = _lib.GRAPH_CONV_Q8_KC, _lib.GRAPH_CONV_CO
+    nch, nt = -(-ci // KC), -(-co // CO)
+    n = kh * kw * nch * nt * 64 * 16
+    packed = np.asarray(packed, np.uint8)
+    assert packed.size == n + 4 * nt * CO, (packed.size, n)
+    frag = packed[:n].view(np.int8).reshape(kh * kw, nch, nt, 2, CO, 16)
+    full = frag.transpose(2, 4, 0, 1, 3, 5).reshape(nt * CO, kh * kw, nch * KC)
+    return np.ascontiguousarray(full[:co, :, :ci]).reshape(co, kh, kw, ci), packed[n:].view(np.int32)[:co].copy()
+
+
+def pack_fc_filter_q8(w):
+    """INT8 [Cout][Cin] -> bytes: int8 [Cout][Cin rounded up to 4] (zeros beyond), then int32 wsum[Cout]."""
+    w = np.asarray(w)
+    assert w.dtype == np.int8, w.dtype
+    co, ci = w.shape
+    full = np.zeros((co, -(-ci // 4) * 4), np.int8)
+    full[:, :ci] = w
+    wsum = w.astype(np.int64).sum(axis=1).astype(np.int32)
+    return np.concatenate([full.reshape(-1).view(np.uint8), wsum.view(np.uint8)])
 
 
 def pack_conv_filter(w_ohwi):
@@ -399,12 +498,12 @@ def pack_conv_filter(w_ohwi):
     return out
 
 
-def load_plan(path, input_shape=None, channel_map=None):
+def load_plan(path, input_shape=None, channel_map=None, quantised_math="hybrid"):
     from .tflite_reader import Graph
 
     with open(str(path), "rb") as fh:
         g = Graph(fh.read())
-    return g, build_plan(g, input_shape=input_shape, channel_map=channel_map)
+    return g, build_plan(g, input_shape=input_shape, channel_map=channel_map, quantised_math=quantised_math)
 
 
 class GraphDevice:
@@ -422,7 +521,8 @@ class GraphDevice:
         def up(a):
             if a is None:
                 return None
-            d = t.from_numpy(np.array(a, dtype=np.float32, order="C")).to(engine.device)
+            # (the packed int8 filters of the hybrid operators travel as bytes)
+            d = t.from_numpy(np.array(a, dtype=np.uint8 if a.dtype == np.uint8 else np.float32, order="C")).to(engine.device)
             self._const.append(d)
             return d.data_ptr()
 

@@ -1,4 +1,4 @@
-"""Pure-Python reader of float32 TFLite models (.tflite).  The flatbuffer is parsed here -- TensorFlow is not needed,
+"""Pure-Python reader of float32 and dynamic-range quantised TFLite models (.tflite).  The flatbuffer is parsed here -- TensorFlow is not needed,
 only NumPy.  Two users:
 
 * `Graph` decodes subgraph 0 of any float32 model made of the operators in OPS below, with their options: CONV_2D
@@ -7,9 +7,13 @@ only NumPy.  Two users:
   (ml_tools/kerasmodel.py:171-180,259-350; the artefact the reference's CI classifies with, .github/workflows/
   release.yml:46 `inc3-tflite-15122023.tar`, is one).  cpx/ml_tools/tflite_graph.py plans such a graph for the device
   executor (cpx_graph_*), the LiteInterpreter of cpx/ml_tools/interpreter.py runs it -- what the reference's
-  LiteInterpreter does with any `.tflite` (src/ml_tools/interpreter.py:520-560,597-628).  check_executable() refuses
-  everything else by operator name and index: DEPTHWISE_CONV_2D, quantised or non-float32 tensors, grouped CONV_2D, a
-  dynamic shape, an operator outside the set.
+  LiteInterpreter does with any `.tflite` (src/ml_tools/interpreter.py:520-560,597-628).  A dynamic-range quantised file
+  (what the reference's converter writes, src/tfliteconverter.py:54-62: the filters of CONV_2D / FULLY_CONNECTED with 1024
+  or more elements INT8 with symmetric scales, everything else float32) is read too: an INT8 constant comes with its
+  quantisation table (`quant`: scale, zero_point, dim), FULLY_CONNECTED with asymmetric_quantize_inputs.
+  check_executable() refuses everything else by operator name and index: DEPTHWISE_CONV_2D, quantised activations,
+  UINT8 / INT16 or asymmetric filters, an INT8 constant anywhere but as such a filter, DEQUANTIZE / QUANTIZE, grouped
+  CONV_2D, a dynamic shape, an operator outside the set.
 * `convert` / `load_tflite` walk ONE topology, a WR-ResNet-22-4, into the Keras-layout weights of
   cpx/ml_tools/wrresnet.py (the fused MFMA network); get_interpreter on such a path converts on load,
   tools/tflite_to_npz.py writes the same arrays to an .npz.
@@ -120,9 +124,19 @@ class Graph:
                     const = np.frombuffer(raw, "<f4").reshape(shape)
                 elif ttype == 2:
                     const = np.frombuffer(raw, "<i4").reshape(shape)
+                elif ttype in (9, 3, 7):
+                    # INT8: a dynamic-range quantised filter; UINT8 / INT16 are decoded so that check_executable can refuse
+                    # them by the operator that reads them
+                    const = np.frombuffer(raw, {9: "i1", 3: "u1", 7: "<i2"}[ttype]).reshape(shape)
                 else:
-                    raise NotImplementedError("tensor %r has type %d: only float32 models are read" % (t.string(3), ttype))
-            self.tensors.append(dict(shape=shape, type=ttype, const=const, name=t.string(3)))
+                    raise NotImplementedError("tensor %r has type %s: only float32 models and INT8 filters are read"
+                                              % (t.string(3), TENSOR_TYPES.get(ttype, ttype)))
+            quant = None
+            q = t.table(4)
+            if q is not None and q.vector(2, "f"):
+                quant = dict(scale=np.array(q.vector(2, "f"), np.float32), zero_point=np.array(q.vector(3, "q"), np.int64),
+                             dim=q.scalar(6, "i", 0))
+            self.tensors.append(dict(shape=shape, type=ttype, const=const, name=t.string(3), quant=quant))
         self.inputs = sub.vector(1, "i")
         self.outputs = sub.vector(2, "i")
         self.ops = []
@@ -145,12 +159,16 @@ class Graph:
                     o.update(axis=opts.scalar(0, "i", 0), act=opts.scalar(1, "b", 0))
                 elif o["name"] in ("ADD", "MUL", "SUB", "FULLY_CONNECTED"):
                     o["act"] = opts.scalar(0, "b", 0)
+                    if o["name"] == "FULLY_CONNECTED":
+                        o["asymmetric_quantize_inputs"] = bool(opts.scalar(3, "b", 0))
                 elif o["name"] == "SOFTMAX":
                     o["beta"] = opts.scalar(0, "f", 0.0)
                 elif o["name"] == "MEAN":
                     o["keep_dims"] = bool(opts.scalar(0, "b", 0))
                 elif o["name"] == "RESHAPE":
                     o["new_shape"] = opts.vector(0, "i")
+            if o["name"] == "FULLY_CONNECTED":
+                o.setdefault("asymmetric_quantize_inputs", False)
             if o["name"] == "MEAN":
                 o.setdefault("keep_dims", False)
                 ax = self.tensors[o["inputs"][1]]["const"] if len(o["inputs"]) > 1 else None
@@ -166,10 +184,28 @@ class Graph:
     def const(self, idx):
         return self.tensors[idx]["const"]
 
+    def quantised_filter(self, op):
+        """The filter tensor of a CONV_2D / FULLY_CONNECTED if it is an INT8 constant (dynamic-range quantisation), else None."""
+        if op["name"] in ("CONV_2D", "FULLY_CONNECTED") and len(op["inputs"]) > 1 and op["inputs"][1] >= 0:
+            ten = self.tensors[op["inputs"][1]]
+            if ten["type"] == 9 and ten["const"] is not None:
+                return ten
+        return None
+
+    def dequantised(self, idx):
+        """A constant as float32: an INT8 filter multiplied out by its scales (per first dimension, or one)."""
+        ten = self.tensors[idx]
+        if ten["type"] != 9:
+            return ten["const"]
+        sc = ten["quant"]["scale"].astype(np.float32)
+        w = ten["const"].astype(np.float32)
+        return (w * sc.reshape((-1,) + (1,) * (w.ndim - 1))).astype(np.float32)
+
     def check_executable(self):
         """Raises NotImplementedError, naming the operator and its index, for whatever the graph executor
         (cpx/ml_tools/tflite_graph.py) does not run: an operator outside OPS, a tensor that is not float32 (int32
-        constants of MEAN / RESHAPE / PAD excepted), grouped CONV_2D, a dynamic shape."""
+        constants of MEAN / RESHAPE / PAD excepted; an INT8 constant as the filter of CONV_2D / FULLY_CONNECTED with
+        symmetric scales along dimension 0 excepted), grouped CONV_2D, a dynamic shape."""
         for i, op in enumerate(self.ops):
             name = op["name"]
             if op["code"] not in OPS:
@@ -180,6 +216,18 @@ class Graph:
                     continue
                 ten = self.tensors[t]
                 int_const = ten["type"] == 2 and ten["const"] is not None and name in ("MEAN", "RESHAPE", "PAD") and k >= 1
+                if ten["type"] == 9 and ten["const"] is not None and k == 1 and name in ("CONV_2D", "FULLY_CONNECTED"):
+                    q = ten["quant"]
+                    if q is None:
+                        raise NotImplementedError("operator %d (%s): the INT8 filter %r has no quantisation scales" % (i, name, ten["name"]))
+                    if np.any(q["zero_point"] != 0):
+                        raise NotImplementedError("operator %d (%s): the INT8 filter %r has a non-zero zero point, only symmetric "
+                                                  "filters are run" % (i, name, ten["name"]))
+                    if q["dim"] != 0 or q["scale"].size not in (1, ten["shape"][0]):
+                        raise NotImplementedError("operator %d (%s): the INT8 filter %r has %d scales along dimension %d, "
+                                                  "only one or one per output channel (dimension 0) are run"
+                                                  % (i, name, ten["name"], q["scale"].size, q["dim"]))
+                    continue
                 if ten["type"] != 0 and not int_const:
                     raise NotImplementedError("operator %d (%s): tensor %r has type %s, only float32 graphs are run"
                                               % (i, name, ten["name"], TENSOR_TYPES.get(ten["type"], ten["type"])))
@@ -227,6 +275,11 @@ def conv_kernel(g, op, groups=2):
 
 
 def convert(g, blocks=3, filters=(16, 64, 128, 256)):
+    for op in g.ops:
+        ten = g.quantised_filter(op)
+        if ten is not None:
+            raise NotImplementedError("tensor %r is an INT8 filter: a dynamic-range quantised WR-ResNet is not converted "
+                                      "(the graph executor runs quantised files)" % ten["name"])
     ops = list(g.ops)
     pos = [0]
 

@@ -35,11 +35,13 @@ static const char* graph_check_op(const cpx_graph_op& o, const std::vector<cpx_g
   if (o.activation != CPX_GRAPH_ACT_NONE && o.activation != CPX_GRAPH_ACT_RELU && o.activation != CPX_GRAPH_ACT_RELU6)
     return "unknown activation";
   const bool same_hw = a.H == y.H && a.W == y.W;
+  auto is_params = [&](int id) { return id >= 0 && t[id].H == 1 && t[id].W == 1 && t[id].C == 4; };
   switch (o.kind) {
     case CPX_GRAPH_CONV:
+    case CPX_GRAPH_CONV_Q8:
     case CPX_GRAPH_MAX_POOL:
     case CPX_GRAPH_AVG_POOL: {
-      const bool conv = o.kind == CPX_GRAPH_CONV;
+      const bool conv = o.kind == CPX_GRAPH_CONV || o.kind == CPX_GRAPH_CONV_Q8;
       if (o.kh < 1 || o.kw < 1 || o.kh > 7 || o.kw > 7) return "kernel sides are 1 to 7";
       if (o.stride_h < 1 || o.stride_w < 1 || o.stride_h > (conv ? 2 : 7) || o.stride_w > (conv ? 2 : 7)) return "bad stride";
       if (o.pad_top < 0 || o.pad_left < 0 || o.pad_bottom < 0 || o.pad_right < 0 || o.pad_top >= o.kh || o.pad_bottom >= o.kh ||
@@ -49,6 +51,10 @@ static const char* graph_check_op(const cpx_graph_op& o, const std::vector<cpx_g
       if (hh < 0 || ww < 0 || y.H != hh / o.stride_h + 1 || y.W != ww / o.stride_w + 1) return "output size does not follow from kernel, stride and pads";
       if (conv && !o.weights) return "CONV without weights";
       if (!conv && a.C != y.C) return "pool changes the channel count";
+      if (o.kind == CPX_GRAPH_CONV_Q8) {
+        if (!is_params(o.in1)) return "CONV_Q8 needs a 1 x 1 x 4 parameter tensor as in1";
+        if (!o.scale || !o.shift) return "CONV_Q8 without scale or shift";
+      }
       break;
     }
     case CPX_GRAPH_ADD:
@@ -65,6 +71,15 @@ static const char* graph_check_op(const cpx_graph_op& o, const std::vector<cpx_g
       break;
     case CPX_GRAPH_FC:
       if (a.H != 1 || a.W != 1 || y.H != 1 || y.W != 1 || !o.weights) return "FULLY_CONNECTED takes and gives 1 x 1 x C";
+      break;
+    case CPX_GRAPH_FC_Q8:
+      if (a.H != 1 || a.W != 1 || y.H != 1 || y.W != 1 || !o.weights) return "FULLY_CONNECTED takes and gives 1 x 1 x C";
+      if (!is_params(o.in1)) return "FC_Q8 needs a 1 x 1 x 4 parameter tensor as in1";
+      if (!o.scale || !o.shift) return "FC_Q8 without scale or shift";
+      break;
+    case CPX_GRAPH_QUANT_PARAMS:
+      if (!is_params(o.out)) return "QUANT_PARAMS writes a 1 x 1 x 4 tensor";
+      if (o.param != 0.0f && o.param != 1.0f) return "QUANT_PARAMS: param is 0 (asymmetric) or 1 (symmetric)";
       break;
     case CPX_GRAPH_PAD:
       if (o.pad_top < 0 || o.pad_left < 0 || o.pad_bottom < 0 || o.pad_right < 0 || a.C != y.C ||

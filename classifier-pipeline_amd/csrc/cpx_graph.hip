@@ -329,6 +329,11 @@ void launch_graph_op(const GraphOpArgs& a, hipStream_t s) {
     case CPX_GRAPH_SOFTMAX:
       hipLaunchKernelGGL(graph_softmax_kernel, dim3(blocks_for((size_t)a.N * a.in0.H * a.in0.W)), dim3(CT), 0, s, a);
       break;
+    case CPX_GRAPH_CONV_Q8:
+    case CPX_GRAPH_FC_Q8:
+    case CPX_GRAPH_QUANT_PARAMS:
+      launch_graph_q8_op(a, s);
+      break;
     default:
       break;
   }

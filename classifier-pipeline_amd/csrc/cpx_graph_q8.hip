@@ -1,0 +1,322 @@
+// cpx_graph_q8.hip -- the hybrid (dynamic-range quantised) operators of the TFLite graph executor: int8 filters, float32
+// activations that are quantised to 8 bits per sample where an operator reads them, int32 accumulation on the int8
+// matrix pipe.  The arithmetic is fixed in include/cpx.h (CPX_GRAPH_QUANT_PARAMS / CONV_Q8 / FC_Q8) so that a NumPy
+// restatement reproduces it bit for bit: every float32 operation below is written as one operation (the build has
+// -ffp-contract=off), the integer sums are exact in any order.
+//
+// CONV_Q8 is an implicit GEMM on v_mfma_i32_32x32x32_i8:
+//   M = output pixels of the WHOLE batch, flattened (128 per workgroup, 32 per wave), as graph_conv_kernel
+//   N = output channels (32 per MFMA tile, up to NTN tiles per wave)
+//   K = kh * kw * Cin walked as (tap) x (chunk of 32 input channels): one MFMA per step and tile
+// A: two threads per pixel load 16 float32 channels each (4 x 128 bits), quantise them with their pixel's sample's
+//    parameters and write 16 bytes with one ds_write_b128 into a [pixel][k] image of 32-byte rows.  Thread t writes bytes
+//    [16 t, 16 t + 16) and lane l of wave w reads bytes [1024 w + 32 (l & 31) + 16 (l >> 5), + 16): both sides touch one
+//    contiguous span per wave, so the 32-byte row needs no padding to stay clear of bank conflicts.  The image is double
+//    buffered: one barrier per step.  No int8 copy of the activation goes to memory.
+// B: the host packs the filter in fragment order ([tap][chunk][tile][lane][16 bytes], GRAPH_CONV_Q8_KC), so a lane takes
+//    its fragment from global memory with one 128-bit load, a step ahead; the four waves share it through the cache.
+// Lane map (checked with exact integers by tests/test_tflite_q8_gpu.py::test_operand_map_exact): lane l holds row / column
+// l & 31 and sixteen consecutive k of half l >> 5 of A and of B; C / D is the map of the other 32 x 32 forms.
+#include <hip/hip_runtime.h>
+
+#include "cpx_kernels.h"
+
+namespace cpx {
+
+namespace {
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int CT = 256;
+constexpr int BM = 128;               // output pixels of a workgroup
+constexpr int KQ = GRAPH_CONV_Q8_KC;  // input channels (bytes of a row of the A image) per step
+
+__device__ __forceinline__ float activate(float v, int act) {
+  if (act == CPX_GRAPH_ACT_RELU) return fmaxf(v, 0.0f);
+  if (act == CPX_GRAPH_ACT_RELU6) return fminf(fmaxf(v, 0.0f), 6.0f);
+  return v;
+}
+
+// q = clamp(round-half-away(float32(x * inv)) + zp, -128, 127)
+__device__ __forceinline__ int quantise(float x, float inv, int zp) {
+  const float v = x * inv;
+  const int q = (int)roundf(v) + zp;
+  return min(max(q, -128), 127);
+}
+
+__device__ __forceinline__ int pack4(int q0, int q1, int q2, int q3) {
+  return (q0 & 255) | ((q1 & 255) << 8) | ((q2 & 255) << 16) | (int)((unsigned)q3 << 24);
+}
+
+// QUANT_PARAMS: one workgroup per sample; out = [sx, inv, zp, 0].  VW = 4: the view's pixels are rows of C / 4 aligned
+// quads.  A thread's (pixel, quad) advances by the workgroup's size without a division.
+constexpr int QT = 1024;
+
+template <int VW>
+__global__ __launch_bounds__(QT) void graph_quant_params_kernel(GraphOpArgs a) {
+  __shared__ float s_lo[QT / 64], s_hi[QT / 64];
+  const size_t n = blockIdx.x;
+  const int tid = threadIdx.x;
+  const float* src = a.in0.p + n * a.in0.sample_stride;
+  const int per = a.in0.C / VW, HW = a.in0.H * a.in0.W;   // vectors per pixel
+  const int dp = QT / per, dq = QT - dp * per;
+  int pix = tid / per, q = tid - pix * per;
+  float lo = 0.0f, hi = 0.0f;   // rmin = min(0, min x), rmax = max(0, max x)
+  while (pix < HW) {
+    const float* e = src + (unsigned)pix * (unsigned)a.in0.cstride + VW * q;
+    if (VW == 4) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(e);
+      lo = fminf(fminf(lo, fminf(v.x, v.y)), fminf(v.z, v.w));
+      hi = fmaxf(fmaxf(hi, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
+    } else {
+      lo = fminf(lo, *e);
+      hi = fmaxf(hi, *e);
+    }
+    pix += dp;
+    q += dq;
+    if (q >= per) {
+      q -= per;
+      ++pix;
+    }
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    lo = fminf(lo, __shfl_xor(lo, d, 64));
+    hi = fmaxf(hi, __shfl_xor(hi, d, 64));
+  }
+  if ((tid & 63) == 0) {
+    s_lo[tid >> 6] = lo;
+    s_hi[tid >> 6] = hi;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  for (int w = 1; w < QT / 64; ++w) {
+    lo = fminf(lo, s_lo[w]);
+    hi = fmaxf(hi, s_hi[w]);
+  }
+  float sx = 1.0f, inv = 1.0f;
+  int zp = 0;
+  if (a.param != 0.0f) {   // symmetric
+    const float m = fmaxf(-lo, hi);
+    if (m != 0.0f) {
+      sx = (float)((double)m / 127.0);
+      inv = (float)(127.0 / (double)m);
+    }
+  } else if (lo != hi) {
+    const double s = ((double)hi - (double)lo) / 255.0;
+    const double ql = (double)lo / s, qh = (double)hi / s;
+    const double z = (128.0 + fabs(ql) < 127.0 + fabs(qh)) ? -128.0 - ql : 127.0 - qh;
+    zp = (int)fmin(fmax(round(z), -128.0), 127.0);
+    sx = (float)s;
+    inv = (float)(1.0 / s);
+  }
+  float* out = a.out.p + n * a.out.sample_stride;
+  out[0] = sx;
+  out[1] = inv;
+  out[2] = (float)zp;
+  out[3] = 0.0f;
+}
+
+struct ConvQ8Geom {
+  long long P;   // N * Ho * Wo
+  int HoWo, nchunks, ntiles, vec4;
+};
+
+template <int NTN>
+__global__ __launch_bounds__(CT) void graph_conv_q8_kernel(GraphOpArgs a, ConvQ8Geom g) {
+  __shared__ __attribute__((aligned(16))) int s_a[2][BM * KQ / 4];   // [pixel][k], bytes
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long p0 = (long long)blockIdx.x * BM;
+  const int tile0 = blockIdx.y * NTN;
+  const int Cin = a.in0.C, H = a.in0.H, W = a.in0.W, Wo = a.out.W;
+
+  // staging role: pixel tid / 2 of the tile, channels [16 * half, 16 * half + 16) of the chunk -- the same pixel for the
+  // whole K walk, so its coordinates and its sample's parameters are worked out once
+  const int spx = tid >> 1, half = tid & 1;
+  const long long sp = p0 + spx;
+  const bool pv = sp < g.P;
+  const long long sn = pv ? sp / g.HoWo : 0;
+  const int srem = pv ? (int)(sp - sn * g.HoWo) : 0;
+  const int soy = srem / Wo, sox = srem - soy * Wo;
+  const int iy0 = soy * a.stride_h - a.pad_top, ix0 = sox * a.stride_w - a.pad_left;
+  const float* in_n = a.in0.p + (size_t)sn * a.in0.sample_stride;
+  const float* sprm = a.in1.p + (size_t)sn * a.in1.sample_stride;
+  const float inv = sprm[1];
+  const int zp = (int)sprm[2];
+  const i32x4* wq = reinterpret_cast<const i32x4*>(a.weights);
+
+  const int steps = a.kh * a.kw * g.nchunks;
+
+  i32x16 acc[NTN];
+#pragma unroll
+  for (int t = 0; t < NTN; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[t][r] = 0;
+
+  f32x4 pre[4];
+  i32x4 bnext[NTN];
+
+  // global -> registers of step s.  A masked element (outside the image or the tile, beyond Cin) is a real 0, which
+  // quantises to zp: what TFLite's padding contributes; beyond Cin the weights are zero and any value would do
+  auto fetch = [&](int s) {
+    const int tap = s / g.nchunks, c0 = (s - tap * g.nchunks) * KQ;
+    const int ky = tap / a.kw, kx = tap - ky * a.kw;
+    const int iy = iy0 + ky, ix = ix0 + kx;
+    const bool inside = pv && iy >= 0 && iy < H && ix >= 0 && ix < W;
+    const int c = c0 + 16 * half;
+    const int pix = inside ? (iy * W + ix) * a.in0.cstride : 0;
+    if (g.vec4) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const bool ok = inside && (c + 4 * q) < Cin;   // Cin % 4 == 0: a quad is valid as a whole
+        const f32x4 v = *reinterpret_cast<const f32x4*>(in_n + (ok ? pix + c + 4 * q : 0));
+        pre[q].x = ok ? v.x : 0.0f;
+        pre[q].y = ok ? v.y : 0.0f;
+        pre[q].z = ok ? v.z : 0.0f;
+        pre[q].w = ok ? v.w : 0.0f;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const bool ok = inside && (c + j) < Cin;
+        const float v = in_n[ok ? pix + c + j : 0];
+        pre[j >> 2][j & 3] = ok ? v : 0.0f;
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < NTN; ++t) {
+      const int tile = min(tile0 + t, g.ntiles - 1);   // a tile beyond the last is not multiplied: load the last
+      bnext[t] = wq[((size_t)s * g.ntiles + tile) * 64 + lane];
+    }
+  };
+
+  fetch(0);
+  for (int s = 0; s < steps; ++s) {
+    int* buf = s_a[s & 1];
+    i32x4 packed;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      packed[q] = pack4(quantise(pre[q].x, inv, zp), quantise(pre[q].y, inv, zp), quantise(pre[q].z, inv, zp),
+                        quantise(pre[q].w, inv, zp));
+    *reinterpret_cast<i32x4*>(buf + 4 * tid) = packed;
+    i32x4 bcur[NTN];
+#pragma unroll
+    for (int t = 0; t < NTN; ++t) bcur[t] = bnext[t];
+    __syncthreads();   // (the other buffer is free: every wave read it before it reached this barrier)
+    if (s + 1 < steps) fetch(s + 1);   // in flight while the matrix cores work on step s
+    const i32x4 af = *reinterpret_cast<const i32x4*>(buf + (32 * wave + (lane & 31)) * (KQ / 4) + 4 * (lane >> 5));
+#pragma unroll
+    for (int t = 0; t < NTN; ++t)
+      if (tile0 + t < g.ntiles) acc[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af, bcur[t], acc[t], 0, 0, 0);
+  }
+
+  // epilogue: accumulator register r of a lane is pixel (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5) of the wave's 32,
+  // channel lane & 31 of the tile; every pixel takes its own sample's sx and zp
+  const long long pb = p0 + 32 * wave;
+  if (pb >= g.P) return;
+  const int* wsum = reinterpret_cast<const int*>(wq + (size_t)steps * g.ntiles * 64);
+  const long long nb = pb / g.HoWo;
+  const int remb = (int)(pb - nb * g.HoWo);
+#pragma unroll
+  for (int t = 0; t < NTN; ++t) {
+    const int ch = (tile0 + t) * 32 + (lane & 31);
+    if (tile0 + t >= g.ntiles || ch >= a.out.C) continue;
+    const float sc = a.scale[ch];
+    const float sh = a.shift[ch];
+    const int ws = wsum[ch];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int i = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+      if (pb + i >= g.P) continue;
+      long long n = nb;
+      int rem = remb + i;
+      while (rem >= g.HoWo) {
+        rem -= g.HoWo;
+        ++n;
+      }
+      const float* prm = a.in1.p + (size_t)n * a.in1.sample_stride;
+      const float sx = prm[0];
+      const int z = (int)prm[2];
+      const float m = sx * sc;
+      const float v = (float)(acc[t][r] - z * ws) * m;
+      a.out.p[(size_t)n * a.out.sample_stride + (unsigned)(rem * a.out.cstride + ch)] = activate(v + sh, a.act);
+    }
+  }
+}
+
+// FC_Q8: one wave per (sample, output).  Weights [Cout][Cin rounded up to 4] int8 (zeros beyond), wsum[Cout] int32 behind.
+// A lane quantises four inputs at a time and sums them against four weights with v_dot4_i32_i8; an integer butterfly follows.
+__global__ __launch_bounds__(CT) void graph_fc_q8_kernel(GraphOpArgs a) {
+  const int lane = threadIdx.x & 63;
+  const size_t wid = (size_t)blockIdx.x * (CT / 64) + (threadIdx.x >> 6);
+  if (wid >= (size_t)a.N * a.out.C) return;
+  const int o = (int)(wid % a.out.C);
+  const size_t n = wid / a.out.C;
+  const int C = a.in0.C, groups = (C + 3) / 4;
+  const float* x = a.in0.p + n * a.in0.sample_stride;
+  const float* prm = a.in1.p + n * a.in1.sample_stride;
+  const float sx = prm[0], inv = prm[1];
+  const int zp = (int)prm[2];
+  const int* w = reinterpret_cast<const int*>(a.weights) + (size_t)o * groups;
+  const int* wsum = reinterpret_cast<const int*>(a.weights) + (size_t)a.out.C * groups;
+  int acc = 0;
+  for (int gidx = lane; gidx < groups; gidx += 64) {
+    int q[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int k = 4 * gidx + j;
+      q[j] = quantise(k < C ? x[k] : 0.0f, inv, zp);   // (beyond Cin the weights are zero)
+    }
+    acc = __builtin_amdgcn_sdot4(pack4(q[0], q[1], q[2], q[3]), w[gidx], acc, false);
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
+  if (lane == 0) {
+    const float m = sx * a.scale[o];
+    const float v = (float)(acc - zp * wsum[o]) * m;
+    a.out.p[n * a.out.sample_stride + o] = activate(v + a.shift[o], a.act);
+  }
+}
+
+}  // namespace
+
+void launch_graph_q8_op(const GraphOpArgs& a, hipStream_t s) {
+  // in0 can be read as aligned quads of channels
+  const int vec4 = (a.in0.C % 4 == 0 && a.in0.cstride % 4 == 0 && a.in0.sample_stride % 4 == 0 &&
+                    (reinterpret_cast<uintptr_t>(a.in0.p) & 15) == 0)
+                       ? 1
+                       : 0;
+  switch (a.kind) {
+    case CPX_GRAPH_QUANT_PARAMS:
+      if (vec4)
+        hipLaunchKernelGGL(graph_quant_params_kernel<4>, dim3((unsigned)a.N), dim3(QT), 0, s, a);
+      else
+        hipLaunchKernelGGL(graph_quant_params_kernel<1>, dim3((unsigned)a.N), dim3(QT), 0, s, a);
+      break;
+    case CPX_GRAPH_CONV_Q8: {
+      ConvQ8Geom g;
+      g.HoWo = a.out.H * a.out.W;
+      g.P = (long long)a.N * g.HoWo;
+      g.nchunks = (a.in0.C + KQ - 1) / KQ;
+      g.ntiles = (a.out.C + GRAPH_CONV_CO - 1) / GRAPH_CONV_CO;
+      g.vec4 = vec4;
+      const unsigned gx = (unsigned)((g.P + BM - 1) / BM);
+      if (g.ntiles == 1)
+        hipLaunchKernelGGL(graph_conv_q8_kernel<1>, dim3(gx, 1), dim3(CT), 0, s, a, g);
+      else if (g.ntiles == 2)
+        hipLaunchKernelGGL(graph_conv_q8_kernel<2>, dim3(gx, 1), dim3(CT), 0, s, a, g);
+      else
+        hipLaunchKernelGGL(graph_conv_q8_kernel<4>, dim3(gx, (g.ntiles + 3) / 4), dim3(CT), 0, s, a, g);
+      break;
+    }
+    case CPX_GRAPH_FC_Q8:
+      hipLaunchKernelGGL(graph_fc_q8_kernel, dim3((unsigned)(((size_t)a.N * a.out.C + 3) / 4)), dim3(CT), 0, s, a);
+      break;
+    default:
+      break;
+  }
+}
+
+}  // namespace cpx

@@ -406,6 +406,11 @@ struct GraphOpArgs {
 void launch_graph_op(const GraphOpArgs& a, hipStream_t s);
 constexpr int GRAPH_CONV_KC = 16;  // CONV weights: Cin padded to this ...
 constexpr int GRAPH_CONV_CO = 32;  // ... and Cout to this
+// The hybrid operators (cpx_graph_q8.hip): CONV_Q8 weights are int8 in the B fragment order of v_mfma_i32_32x32x32_i8,
+// [tap][chunk of GRAPH_CONV_Q8_KC input channels][tile of GRAPH_CONV_CO output channels][lane][16 bytes]: lane l's bytes
+// are output channel l & 31 of the tile, input channels 16 * (l >> 5) + j of the chunk; zeros beyond Cin and Cout.
+void launch_graph_q8_op(const GraphOpArgs& a, hipStream_t s);
+constexpr int GRAPH_CONV_Q8_KC = 32;
 
 // Kernels that use more than 64 KB of dynamic LDS need hipFuncAttributeMaxDynamicSharedMemorySize raised once per
 // (kernel, device): `done` is a per-kernel array indexed by the current device ordinal.

@@ -810,10 +810,30 @@ enum {
   CPX_GRAPH_LOGISTIC = 8,
   CPX_GRAPH_SOFTMAX = 9,     /* over C, param = beta */
   CPX_GRAPH_PAD = 10,        /* zeros around H and W (the four pads) */
-  CPX_GRAPH_CHANNEL_MAP = 11 /* out channel c = in0 channel channel_map[c], c < n_map (n_map = out C <= 4): a
+  CPX_GRAPH_CHANNEL_MAP = 11,/* out channel c = in0 channel channel_map[c], c < n_map (n_map = out C <= 4): a
                                 [N, H, W, 2] sample of cpx_crop_tile feeds a 3-channel graph, a channel repeated as
                                 the reference's preprocess_movement repeats one (ml_tools/preprocess.py:169-189) */
+  /* The hybrid operators of a dynamic-range quantised file (int8 filter, float32 activations): see below. */
+  CPX_GRAPH_CONV_Q8 = 12,    /* CONV_2D with an int8 filter.  in1: the 1 x 1 x 4 parameter tensor of in0.  `weights` is
+                                reinterpreted as BYTES: int8 [kh * kw][chunks of 32 input channels][tiles of 32 output
+                                channels][64 lanes][16] -- lane l: output channel l & 31 of the tile, input channels
+                                16 * (l >> 5) + j of the chunk, zeros beyond Cin / Cout -- and behind them int32
+                                wsum[Cout rounded up to 32], wsum[c] = the sum of filter c over taps and channels.
+                                scale, shift: [Cout], not NULL */
+  CPX_GRAPH_FC_Q8 = 13,      /* FULLY_CONNECTED with an int8 filter on a 1 x 1 x C input.  in1 as CONV_Q8.  `weights` as
+                                bytes: int8 [Cout][Cin rounded up to 4] (zeros beyond), then int32 wsum[Cout].  scale,
+                                shift: [Cout], not NULL */
+  CPX_GRAPH_QUANT_PARAMS = 14/* in0 (its own channels only) -> out, a 1 x 1 x 4 tensor [sx, inv, zp, 0] per sample;
+                                param 0: asymmetric, param 1: symmetric */
 };
+/* The hybrid arithmetic, per sample.  QUANT_PARAMS: rmin = min(0, min x), rmax = max(0, max x) in float32.
+ * rmin == rmax: sx = inv = 1, zp = 0.  Otherwise, in float64 from those two values: s = (rmax - rmin) / 255,
+ * a = -128 - rmin / s, b = 127 - rmax / s, z = a if 128 + |rmin / s| < 127 + |rmax / s| else b,
+ * zp = clamp(round-half-away(z), -128, 127), sx = float32(s), inv = float32(1 / s).  Symmetric (param 1): m = max |x|,
+ * zp = 0, sx = float32(m / 127), inv = float32(127 / m) in float64; m == 0: sx = inv = 1.
+ * CONV_Q8 / FC_Q8: q = clamp(round-half-away(float32(x * inv)) + zp, -128, 127); a padded tap is q = zp (a real 0);
+ * acc = sum q * w in int32 (the caller keeps kh * kw * Cin * 127 * 255 below 2^31);
+ * out = act(float32(acc - zp * wsum[c]) * float32(sx * scale[c]) + shift[c]), each operation in float32 as written. */
 enum { CPX_GRAPH_ACT_NONE = 0, CPX_GRAPH_ACT_RELU = 1, CPX_GRAPH_ACT_RELU6 = 3 }; /* TFLite's ActivationFunctionType */
 
 typedef struct cpx_graph_tensor {
@@ -832,7 +852,7 @@ typedef struct cpx_graph_op {
   int32_t out_c_offset, out_c_stride; /* where the output goes: the channel slice of tensors[out] */
   int32_t n_map, channel_map[4];
   float param;
-  const float* weights; /* device pointers, owned by the caller, alive as long as the graph */
+  const float* weights; /* device pointers, owned by the caller, alive as long as the graph (CONV_Q8 / FC_Q8: bytes) */
   const float* scale;
   const float* shift;
 } cpx_graph_op;

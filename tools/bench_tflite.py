@@ -13,7 +13,14 @@ under `rocprofv3 --kernel-trace --output-format csv -d DIR -- python tools/bench
 
 which needs no GPU: it maps the last forward's launches, in order, onto the plan's operators and prints the time per kind,
 the GPU-busy share of the forward and, for the convolution shape that takes the most time, its algorithmic TFLOP/s and
-the share of the float32 matrix-pipe peak (157.3 TFLOP/s) that is."""
+the share of the float32 matrix-pipe peak (157.3 TFLOP/s) that is.
+
+    python tools/bench_tflite.py --quantised [--batches 32,128]
+
+runs the same Inception-v3 three ways -- the float32 file, its dynamic-range quantised twin (tests/tflite_build_q8.py:
+INT8 filters) on the hybrid operators, and the twin with the filters multiplied out (quantised_math="float") -- and prints
+ms per forward for each, with the hybrid convolutions' algorithmic TOP/s against the int8 matrix-pipe roof (twice the
+BF16 rate: ~5000 TOP/s dense)."""
 import argparse
 import json
 import os
@@ -93,6 +100,56 @@ def timed(torch, fn, steps, warmup):
 
 
 F32_MFMA_PEAK_TFLOPS = 157.3
+I8_MFMA_PEAK_TOPS = 5000.0   # 2 x the ~2.5 PFLOP/s dense BF16 peak: the i8 forms have twice the K in the same cycles
+
+
+def quantised_leg(args):
+    """float32 / hybrid / float-math forwards of one Inception-v3, ms per forward by batch size."""
+    import ctypes as C
+
+    import tflite_build as tb
+    import tflite_build_q8 as tq
+    import torch
+    from cpx import _lib
+    from cpx.engine import TrackEngine
+    from cpx.ml_tools.tflite_graph import GraphDevice, build_plan
+    from cpx.ml_tools.tflite_reader import Graph
+
+    blob = tb.inception_v3(17, (), seed=7, width=args.width)
+    gq = Graph(tq.quantise(blob))
+    plans = {"float32": build_plan(Graph(blob)), "hybrid": build_plan(gq), "quantised_float_math": build_plan(gq, quantised_math="float")}
+    ops8 = 0.0   # algorithmic int8 multiply-adds x 2 of the hybrid convolutions, per sample
+    for o in plans["hybrid"].ops:
+        if o.kind == _lib.GRAPH_CONV_Q8:
+            t, i = plans["hybrid"].tensors[o.out], plans["hybrid"].tensors[o.in0]
+            ops8 += 2.0 * t.H * t.W * t.C * o.kh * o.kw * i.C
+    eng = TrackEngine(model="lepton3", device=0)
+    stream = torch.cuda.ExternalStream(eng.lib.cpx_stream(eng.h), device=eng.device)
+    out = {"model": "inception_v3 width %.2f 160x160x3" % args.width, "hybrid_conv_gop_per_sample": ops8 / 1e9,
+           "hybrid_operators": sum(o.kind in (_lib.GRAPH_CONV_Q8, _lib.GRAPH_FC_Q8) for o in plans["hybrid"].ops),
+           "quant_params_launches": sum(o.kind == _lib.GRAPH_QUANT_PARAMS for o in plans["hybrid"].ops), "batches": []}
+    rng = np.random.default_rng(0)
+    for n in [int(v) for v in args.batches.split(",")]:
+        x = torch.from_numpy(rng.uniform(-1, 1, size=(n, 160, 160, 3)).astype(np.float32)).to(eng.device)
+        y = torch.empty((n, 17), dtype=torch.float32, device=eng.device)
+        rec = {"N": n}
+        for name, plan in plans.items():
+            dev = GraphDevice(eng, plan)
+
+            def forward():
+                rc = eng.lib.cpx_graph_forward(dev._graph, C.c_void_p(x.data_ptr()), n, C.c_void_p(y.data_ptr()))
+                assert rc == 0, eng._err()
+
+            with torch.cuda.stream(stream):
+                rec[name + "_ms"] = timed(torch, forward, args.steps, args.warmup)
+            dev.close()
+        rec["hybrid_over_float32"] = rec["float32_ms"] / rec["hybrid_ms"]
+        # the whole forward's time against the hybrid convolutions' work: a lower bound of what they reach while running
+        rec["hybrid_tops_over_whole_forward"] = ops8 * n / rec["hybrid_ms"] / 1e9
+        rec["i8_roof_share"] = rec["hybrid_tops_over_whole_forward"] / I8_MFMA_PEAK_TOPS
+        out["batches"].append(rec)
+    eng.close()
+    print(json.dumps(out))
 
 
 def split_from_trace(path, plan, n):
@@ -138,7 +195,11 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--width", type=float, default=1.0)
+    ap.add_argument("--quantised", action="store_true",
+                    help="time the float32 file, its dynamic-range quantised twin (hybrid operators) and the twin in float math")
     args = ap.parse_args()
+    if args.quantised:
+        return quantised_leg(args)
     import ctypes as C
 
     import tflite_build as tb

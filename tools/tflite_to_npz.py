@@ -5,8 +5,8 @@ flatbuffer is parsed here, TensorFlow is not needed (only NumPy).
     python tools/tflite_to_npz.py model.tflite /tmp/wr [--sidecar model.json]
     python tools/tflite_to_npz.py --describe model.tflite
 
---describe converts nothing: it prints the operator census, the input and output shapes and the arena bytes per sample
-of ANY graph the device executor runs (cpx/ml_tools/tflite_graph.py: an Inception-v3, say), or the refusal -- the
+--describe converts nothing: it prints the operator census, the input and output shapes, the arena bytes per sample and,
+for a dynamic-range quantised file, the number of hybrid operators with the int8 against the float32 weight bytes of ANY graph the device executor runs (cpx/ml_tools/tflite_graph.py: an Inception-v3, say), or the refusal -- the
 operator and its index -- of one it does not.
 
 The reference loads this artefact with LiteInterpreter (/root/reference/src/ml_tools/interpreter.py:520-560); its CI
@@ -50,6 +50,14 @@ def describe(g):
     print("input shape %s, output shape %s" % (list(plan.input_shape), list(plan.output_shape)))
     print("launches: " + ", ".join("%s: %d" % kv for kv in sorted(plan.census().items())))
     print("arena bytes per sample: %d" % plan.arena_bytes_per_sample)
+    from cpx.ml_tools.tflite_graph import Q8_KINDS
+
+    hybrid = [o for o in plan.ops if o.kind in Q8_KINDS]
+    q8 = sum(int(np.prod(o.filter.shape)) for o in hybrid)
+    f32 = sum(4 * int(np.prod((o.filter if getattr(o, "filter", None) is not None else o.weights).shape)) for o in plan.ops
+              if o.kind not in Q8_KINDS and o.weights is not None)
+    print("hybrid operators (int8 filter, activations quantised per sample): %d; int8 weight bytes: %d, float32 weight bytes: %d"
+          % (len(hybrid), q8, f32))
     return 0
 
 
