@@ -21,7 +21,9 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
+#include "cpx_conv_layout_core.h"
 #include "cpx_kernels.h"
 
 namespace cpx {
@@ -147,8 +149,7 @@ constexpr int KC = 16;  // channels per K step of the bf16 MFMA = per staged chu
 
 // NB bands of 128 output pixels per workgroup, CT threads: four waves share a band (32 pixels each); with CT = 512
 // the second set of four waves takes every other band, so NTM = NB / (CT / 256) bands per wave
-// q = n / d for n < 2^22, d < 2^12 with a host-computed M = floor(2^42 / d) + 1: two scalar multiplies instead of
-// the ~25-instruction reciprocal sequence a runtime division costs (four of them per workgroup otherwise)
+// q = n / d with a host-computed multiplier (cpx_conv_layout_core.h: fill_tiles), four divisions per workgroup otherwise
 struct TileDiv {
   unsigned long long m_nsplit, m_tx, m_ty;
   int nsplit, tiles_x, tiles_y;
@@ -1895,16 +1896,9 @@ int launch_bf3flat_t(const ConvArgs& a, const uint4* wimg, hipStream_t s) {
   const size_t lds = std::max(((size_t)2 * PL * NPXC + (size_t)18 * PL * 32 * NTN) * 16, (size_t)(CT / 64) * 32 * 32 * sizeof(float));
   static bool lds_ready[64], lds_ready_p[64];
   if (!cpx_dyn_lds_ready(reinterpret_cast<const void*>(conv_bf3flat_kernel<NTN, NPXC, PL, H, false, CT, SC>), lds_ready, 160 * 1024 - 1024)) return -1;
-  TileDiv td;
-  td.tiles_x = (a.Ho * a.Wo + BAND - 1) / BAND;
-  td.tiles_y = 1;
-  td.nsplit = (a.Cout / a.groups) / (32 * NTN);
-  const long long blocks = (long long)td.tiles_x * a.N * td.nsplit;
-  if (blocks >= (1 << 22) || td.tiles_x >= 4096) return -3;
-  td.m_nsplit = (1ull << 42) / td.nsplit + 1;
-  td.m_tx = (1ull << 42) / td.tiles_x + 1;
-  td.m_ty = (1ull << 42) + 1;
-  td.total = (int)blocks;
+  TileDiv td{};
+  if (const int rc = fill_tiles(td, (a.Ho * a.Wo + BAND - 1) / BAND, 1, a.N, (a.Cout / a.groups) / (32 * NTN), TILES_PER_LAUNCH)) return rc;
+  const long long blocks = td.total;
   if constexpr (PL == 3 && !H) if (a.guard != nullptr) {  // the guarded rerun of a fp16x2 layer: a small grid that walks the tiles (PERSIST)
     if (!cpx_dyn_lds_ready(reinterpret_cast<const void*>(conv_bf3flat_kernel<NTN, NPXC, PL, false, true, CT>), lds_ready_p, 160 * 1024 - 1024)) return -1;
     hipLaunchKernelGGL((conv_bf3flat_kernel<NTN, NPXC, PL, false, true, CT>), dim3((unsigned)std::min<long long>(blocks, RERUN_GRID), a.groups), dim3(CT), lds, s, a, wimg, td);
@@ -2097,17 +2091,10 @@ static int launch_bf3w_t(const ConvArgs& a, const uint4* wimg, hipStream_t s) {
   // (NH = 2 carries 16 more accumulator registers: the BatchNorm parameters go to LDS there)
   constexpr bool LDSBN = NH > 1 || PL == 2;
   if (!cpx_dyn_lds_ready(reinterpret_cast<const void*>(conv_bf3w_kernel<false, LDSBN, NH, 1, PL, H>), lds_ready, 160 * 1024 - 1024)) return -1;
-  TileDiv td;
+  TileDiv td{};
   td.run = 1;
-  td.tiles_x = (a.Wo + W_TW - 1) / W_TW;
-  td.tiles_y = (a.Ho + W_TH - 1) / W_TH;
-  td.nsplit = (a.Cout / a.groups) / (32 * NH);
-  const long long blocks = (long long)td.tiles_x * td.tiles_y * a.N * td.nsplit;
-  if (blocks >= (1 << 22) || td.tiles_x >= 4096 || td.tiles_y >= 4096) return -3;
-  td.m_nsplit = (1ull << 42) / td.nsplit + 1;
-  td.m_tx = (1ull << 42) / td.tiles_x + 1;
-  td.m_ty = (1ull << 42) / td.tiles_y + 1;
-  td.total = (int)blocks;
+  if (const int rc = fill_tiles(td, (a.Wo + W_TW - 1) / W_TW, (a.Ho + W_TH - 1) / W_TH, a.N, (a.Cout / a.groups) / (32 * NH), TILES_PER_LAUNCH)) return rc;
+  const long long blocks = td.total;
   if constexpr (PL == 3 && !H) if (a.guard != nullptr) {  // the guarded rerun of a fp16x2 layer: a small grid that walks the tiles (PERSIST)
     if (!cpx_dyn_lds_ready(reinterpret_cast<const void*>(conv_bf3w_kernel<false, LDSBN, NH, 1, PL, false, true>), lds_ready_p, 160 * 1024 - 1024)) return -1;
     hipLaunchKernelGGL((conv_bf3w_kernel<false, LDSBN, NH, 1, PL, false, true>), dim3((unsigned)std::min<long long>(blocks, RERUN_GRID), a.groups), dim3(512), lds, s, a, wimg, td);
@@ -2116,32 +2103,31 @@ static int launch_bf3w_t(const ConvArgs& a, const uint4* wimg, hipStream_t s) {
   hipLaunchKernelGGL((conv_bf3w_kernel<false, LDSBN, NH, 1, PL, H>), dim3((unsigned)blocks, a.groups), dim3(512), lds, s, a, wimg, td);
   return 0;
 }
-// the three-plane image of a layer, then (these layers only) the two-plane one
-static size_t bf3w_image3_bytes(const ConvArgs& a) { return (size_t)a.groups * (a.Cin / a.groups / KW) * 3 * 36 * (a.Cout / a.groups) * 16; }
-static size_t bf3w_image2_bytes(const ConvArgs& a) { return (size_t)a.groups * (a.Cin / a.groups / KW) * 3 * 24 * (a.Cout / a.groups) * 16; }
+// The math mode of a launch and the image it reads, chosen once: two fp16 planes, two bf16 planes where the layer has them,
+// else three.  launch(planes, half, image) gets the first two as integral constants.
+template <class F>
+static int with_math(const ConvArgs& a, const WeightImages& im, const uint4* w, F&& launch) {
+  using P2 = std::integral_constant<int, 2>;
+  if (a.planes == 2 && a.half) return launch(P2{}, std::true_type{}, w + im.half / 16);
+  if (a.planes == 2 && im.planes2 != WeightImages::absent) return launch(P2{}, std::false_type{}, w + im.planes2 / 16);
+  return launch(std::integral_constant<int, 3>{}, std::false_type{}, w);
+}
 // (groups with 64 columns: both 32-column slices in one workgroup, NH = 2)
-static int launch_bf3w(const ConvArgs& a, const uint4* wimg, hipStream_t s) {
-  if (a.planes == 2 && a.half) {  // the fp16 image lies behind the two bf16 ones
-    const uint4* wh = wimg + (bf3w_image3_bytes(a) + bf3w_image2_bytes(a)) / 16;
-    // 64 -> 64 channels per group: weights in registers (cpx_cnn_rw.hip).  The launch that carries a stage's 1x1 shortcut goes
-    // there too when the network has fp16 planes of the shortcut's weights (ConvArgs::sc_planes: the shortcut is then three more
-    // fp16 products per output row); as a float32 side product (strided float32 operands) it stays with this kernel, measured
-    // faster than the shortcut as a launch of its own + conv_rw64_kernel with its output as residual
-    // (profiles/r06_conv_rw_experiments.md)
-    if (conv_rw_layer(a) && !a.in_planes && !a.out_planes && (!a.sc_in || a.sc_planes)) {
-      const int rc = launch_conv_rw(a, wh, s);
-      if (rc != -2) return rc;
-    }
-    if (a.Cout / a.groups == 64) return launch_bf3w_t<2, 2, true>(a, wh, s);
-    return launch_bf3w_t<1, 2, true>(a, wh, s);
+static int launch_bf3w(const ConvArgs& a, const WeightImages& im, const uint4* w, hipStream_t s) {
+  // 64 -> 64 channels per group in fp16x2: weights in registers (cpx_cnn_rw.hip).  The launch that carries a stage's 1x1 shortcut goes
+  // there too when the network has fp16 planes of the shortcut's weights (ConvArgs::sc_planes: the shortcut is then three more
+  // fp16 products per output row); as a float32 side product (strided float32 operands) it stays with this kernel, measured
+  // faster than the shortcut as a launch of its own + conv_rw64_kernel with its output as residual
+  // (profiles/r06_conv_rw_experiments.md)
+  if (a.planes == 2 && a.half && conv_rw_layer(a) && !a.in_planes && !a.out_planes && (!a.sc_in || a.sc_planes)) {
+    const int rc = launch_conv_rw(a, w + im.half / 16, s);
+    if (rc != -2) return rc;
   }
-  if (a.planes == 2) {
-    const uint4* w2 = wimg + bf3w_image3_bytes(a) / 16;
-    if (a.Cout / a.groups == 64) return launch_bf3w_t<2, 2>(a, w2, s);
-    return launch_bf3w_t<1, 2>(a, w2, s);
-  }
-  if (a.Cout / a.groups == 64) return launch_bf3w_t<2, 3>(a, wimg, s);
-  return launch_bf3w_t<1, 3>(a, wimg, s);
+  return with_math(a, im, w, [&](auto pl, auto h, const uint4* wi) {
+    constexpr int PL = decltype(pl)::value;
+    constexpr bool H = decltype(h)::value;
+    return a.Cout / a.groups == 64 ? launch_bf3w_t<2, PL, H>(a, wi, s) : launch_bf3w_t<1, PL, H>(a, wi, s);
+  });
 }
 
 template <int NTN, int S, int NB, int TW, int CT, bool C8 = false, int PL = 3, bool H = false>
@@ -2152,16 +2138,9 @@ int launch_bf3_t(const ConvArgs& a, const uint4* wimg, hipStream_t s) {
   if (lds < (CT / 64) * 32 * 32 * sizeof(float)) lds = (CT / 64) * 32 * 32 * sizeof(float);
   static bool lds_ready[64], lds_ready_p[64];
   if (!cpx_dyn_lds_ready(reinterpret_cast<const void*>(conv_bf3_kernel<NTN, S, NB, TW, CT, C8, PL, H>), lds_ready, 160 * 1024 - 1024)) return -1;
-  TileDiv td;
-  td.tiles_x = (a.Wo + TW - 1) / TW;
-  td.tiles_y = (a.Ho + TH - 1) / TH;
-  td.nsplit = (a.Cout / a.groups) / (32 * NTN);
-  const long long blocks = (long long)td.tiles_x * td.tiles_y * a.N * td.nsplit;
-  if (blocks >= (1 << 22) || td.tiles_x >= 4096 || td.tiles_y >= 4096) return -3;  // div_magic's range
-  td.m_nsplit = (1ull << 42) / td.nsplit + 1;
-  td.m_tx = (1ull << 42) / td.tiles_x + 1;
-  td.m_ty = (1ull << 42) / td.tiles_y + 1;
-  td.total = (int)blocks;
+  TileDiv td{};
+  if (const int rc = fill_tiles(td, (a.Wo + TW - 1) / TW, (a.Ho + TH - 1) / TH, a.N, (a.Cout / a.groups) / (32 * NTN), TILES_PER_LAUNCH)) return rc;
+  const long long blocks = td.total;
   if constexpr (PL == 3 && !H) if (a.guard != nullptr) {  // the guarded rerun of a fp16x2 layer: a small grid that walks the tiles (PERSIST)
     if (!cpx_dyn_lds_ready(reinterpret_cast<const void*>(conv_bf3_kernel<NTN, S, NB, TW, CT, C8, PL, false, true>), lds_ready_p, 160 * 1024 - 1024)) return -1;
     hipLaunchKernelGGL((conv_bf3_kernel<NTN, S, NB, TW, CT, C8, PL, false, true>), dim3((unsigned)std::min<long long>(blocks, RERUN_GRID), a.groups), dim3(CT), lds, s, a, wimg, td);
@@ -2171,189 +2150,94 @@ int launch_bf3_t(const ConvArgs& a, const uint4* wimg, hipStream_t s) {
   return 0;
 }
 
-}  // namespace
-
 // band width: with 32-pixel bands a wave's 32 pixels are one row, i.e. 32 consecutive 16-byte LDS entries -- the
 // only A-fragment layout that is conflict-free in ds_read_b128's lane groups ({0-3,12-15,20-27}, ...); with 8 x 16
 // bands lanes 12-13 and 26-27 (4-5 and 20-21) share bank slots and every A read takes two LDS passes.  Measured:
 // no difference on the 160-wide maps (LDS is not the limit), and the 80-wide maps of stage 3 lose 17 % of a 3 x 32
 // tiling to padding, so both stay at 16
-#ifndef CPX_BF3_TW_S2
-#define CPX_BF3_TW_S2 16
-#endif
-#ifndef CPX_BF3_TW_S3
-#define CPX_BF3_TW_S3 16
-#endif
-#ifndef CPX_BF3_NTN_S3
-#define CPX_BF3_NTN_S3 1
-#endif
-#ifndef CPX_BF3_NTN_S4
-#define CPX_BF3_NTN_S4 2
-#endif
-#ifndef CPX_BF3_NB_S2
-#define CPX_BF3_NB_S2 2
-#endif
-#ifndef CPX_BF3_NB_S3
-#define CPX_BF3_NB_S3 2
-#endif
-#ifndef CPX_BF3_NB_S4
-#define CPX_BF3_NB_S4 1
-#endif
-#ifndef CPX_BF3_CT_S2
-#define CPX_BF3_CT_S2 512
-#endif
-#ifndef CPX_BF3_CT_S3
-#define CPX_BF3_CT_S3 512
-#endif
-#ifndef CPX_BF3_CT_S4
-#define CPX_BF3_CT_S4 256
-#endif
+// (conv_bf3_kernel's band width, column tiles, bands and threads per workgroup for 32, 64 and 128 columns per group)
+constexpr int TW_S2 = 16, NB_S2 = 2, CT_S2 = 512;
+constexpr int TW_S3 = 16, NB_S3 = 2, CT_S3 = 512, NTN_S3 = 1;
+constexpr int NB_S4 = 1, CT_S4 = 256, NTN_S4 = 2;
+static_assert(B8_WIMG == (int)WeightImages::C8_HALF_ENTRIES, "conv_block32_kernel<true> and the layout agree on the tap-quad image");
 
-// (8 input channels per group: the tap-paired form, built for the 32 output channels per group the network has)
-static bool bf3_c8(const ConvArgs& a) { return a.Cin / a.groups == 8 && a.Cout / a.groups == 32; }
-// the strided first convolution of a stage (wr_resnet.py:27-30: stride = stage index): the same kernel with a strided
+}  // namespace
+
+// The classes of layer, their kernels and their weight images: cpx_conv_layout_core.h.  A property of the layer shape alone, so
+// that the images built at cpx_cnn_create are the ones every launch of the layer reads (with or without a fused shortcut).
+// The strided first convolution of a stage (wr_resnet.py:27-30: stride = stage index) runs conv_bf3_kernel with a strided
 // patch -- the MFMA loop is unchanged, only the A-fragment addresses carry the stride.  S = 2 (res3b0_branch2a): 33 x 33
 // staged pixels for 16 x 16 outputs and both 32-column tiles of a group in one workgroup (160 KB, one workgroup per CU):
 // 123 TFLOP/s against 95 on the float32 MFMA.  (S = 3, res4b0_branch2a: 24 x 48 staged pixels for 8 x 16 outputs, 138 KB,
 // four waves per CU and the patch split once per 32-column slice: 40 TFLOP/s against 78 on the float32 MFMA -- windows of
-// a stride-3 3 x 3 kernel do not overlap, nothing is reused.  Measured, not shipped.)
-static bool bf3_strided(const ConvArgs& a) {
-  const int cin_g = a.Cin / a.groups, cout_g = a.Cout / a.groups;
-  if (a.ksize != 3 || cin_g < KC || (cin_g % KC) != 0) return false;
-  return a.stride == 2 && cout_g == 64;
+// a stride-3 3 x 3 kernel do not overlap, nothing is reused.  Measured, not shipped: every launch of that layer that is not
+// conv_rw_kernel's goes to the float32 kernel (launch_conv, which honours ConvArgs::guard), as all of them did before round 6.)
+static WeightImages images_of(const ConvArgs& a) { return WeightImages::of(conv_shape_of(a)); }
+bool conv_bf3_supported(const ConvArgs& a) { return conv_class(conv_shape_of(a)) != ConvClass::Unsupported; }
+size_t conv_bf3_weight_bytes(const ConvArgs& a) { return images_of(a).bytes; }
+// (the 8-channel layer's fp16 image is conv_block32_kernel's alone)
+bool conv_bf3_two_planes(const ConvArgs& a) {
+  const WeightImages im = images_of(a);
+  return im.half != WeightImages::absent && im.cls != ConvClass::C8;
 }
-// stride-1 layers with 32 or 64 channels per group (stages 2 and 3): the 16x16x32 form (conv_bf3w_kernel) and its
-// weight image; a property of the layer shape alone, so that the image built at cpx_cnn_create is the one every
-// launch of the layer reads (with or without a fused shortcut)
-static bool bf3w_layer(const ConvArgs& a) {
-  const int cin_g = a.Cin / a.groups, cout_g = a.Cout / a.groups;
-  return a.ksize == 3 && a.stride == 1 && cin_g >= KW && (cin_g % KW) == 0 && (cout_g == 32 || cout_g == 64) && cin_g <= 64;
-}
-// the strided first convolutions conv_rw_kernel takes in fp16x2 (cpx_cnn_rw.hip): the stride-2 one has this file's kernels for
-// the other modes and the rerun; the stride-3 one has none here -- every launch of it that is not conv_rw_kernel's goes to the
-// float32 kernel (launch_conv, which honours ConvArgs::guard), as all of them did before round 6
-static bool rw_stride3(const ConvArgs& a) { return conv_rw_kind(a) == 3; }
-static bool rw_stride2(const ConvArgs& a) { return conv_rw_kind(a) == 2; }
-// [g][chunk of 32][ky][plane 2][kx][quarter][cout_g] of 16-byte entries (split_weights32_kernel)
-static size_t rw_image_bytes(const ConvArgs& a) { return (size_t)a.groups * (a.Cin / a.groups / KW) * 3 * 24 * (a.Cout / a.groups) * 16; }
-bool conv_bf3_supported(const ConvArgs& a) {
-  const int cin_g = a.Cin / a.groups, cout_g = a.Cout / a.groups;
-  if (a.ksize == 3 && a.stride == 1 && bf3_c8(a)) return true;
-  if (bf3_strided(a)) return true;
-  if (rw_stride3(a)) return true;
-  return a.ksize == 3 && a.stride == 1 && cin_g >= KC && (cin_g % KC) == 0 && (cout_g == 32 || cout_g == 64 || cout_g == 128);
-}
-// three-plane image of the layers conv_bf3_kernel / conv_bf3flat_kernel take: [g][chunk of 16][3][9][2][cout_g]
-static size_t image3_bytes(const ConvArgs& a) { return (size_t)a.groups * (a.Cin / a.groups / KC) * 54 * (a.Cout / a.groups) * 16; }
-// stride-1 layers with 128 columns per group (stage 4): the flattened kernel takes them when the map is small
-// (flat_pays, a property of the launch), in either math mode
-static bool flat_layer(const ConvArgs& a) {
-  const int cin_g = a.Cin / a.groups;
-  if (bf3_c8(a) || bf3w_layer(a) || a.ksize != 3 || cin_g < KC || (cin_g % KC) != 0) return false;
-  // ... and the stride-2 first convolution of stage 3 (conv_bf3_kernel<2,2,2,16,512>)
-  return (a.stride == 1 && a.Cout / a.groups == 128) || (a.stride == 2 && bf3_strided(a));
-}
-// the per-channel weight scales of the fp16 image and their inverses: 2 x Cout floats behind the images (16-byte aligned)
-static size_t scales_bytes(const ConvArgs& a) { return ((size_t)2 * a.Cout * sizeof(float) + 15) / 16 * 16; }
-// the 8-channel layer: its three-plane tap-paired image, then the fp16 tap-quad image of conv_block32_kernel<true> and its scales
-static size_t c8_image3_bytes(const ConvArgs& a) { return (size_t)a.groups * 30 * (a.Cout / a.groups) * 16; }
-static size_t c8_half_bytes(const ConvArgs& a) { return (size_t)a.groups * B8_WIMG * 16; }
-size_t conv_bf3_weight_bytes(const ConvArgs& a) {
-  if (rw_stride3(a)) return rw_image_bytes(a) + scales_bytes(a);
-  if (rw_stride2(a) && flat_layer(a)) return image3_bytes(a) + 2 * (image3_bytes(a) / 3 * 2) + scales_bytes(a) + rw_image_bytes(a);
-  if (bf3_c8(a)) return c8_image3_bytes(a) + c8_half_bytes(a) + scales_bytes(a);
-  // the images of the three math modes one after the other: three bf16 planes, two bf16 planes, two fp16 planes, scales
-  if (bf3w_layer(a)) return bf3w_image3_bytes(a) + 2 * bf3w_image2_bytes(a) + scales_bytes(a);
-  return image3_bytes(a) + (flat_layer(a) ? 2 * (image3_bytes(a) / 3 * 2) + scales_bytes(a) : 0);
-}
-bool conv_bf3_two_planes(const ConvArgs& a) { return bf3w_layer(a) || flat_layer(a) || rw_stride3(a); }
 // producer-side split (ConvArgs::out_planes / in_planes): the kernels whose epilogue can store the next layer's fp16
 // planes -- conv_bf3w_kernel and conv_bf3_kernel, i.e. every split-operand launch but the flattened one -- and the one
 // whose staging can take them (conv_bf3w_kernel in fp16x2).  `a` describes the launch (H, W, Ho, Wo filled in).
 bool conv_bf3_can_store_planes(const ConvArgs& a) {
-  if (!conv_bf3_supported(a) || (a.Cout / a.groups) % 4 != 0) return false;
-  if (a.stride != 1) return a.stride == 2 && bf3_strided(a);
-  if (a.Cout / a.groups == 128) return !flat_pays(a, 32, 4 * CPX_BF3_NB_S4, 256);
+  const ConvClass cls = conv_class(conv_shape_of(a));
+  if (cls == ConvClass::Unsupported || cls == ConvClass::Rw3 || (a.Cout / a.groups) % 4 != 0) return false;
+  if (cls == ConvClass::Flat && a.stride == 1) return !flat_pays(a, 32, 4 * NB_S4, 256);
   return true;
 }
-bool conv_bf3_can_load_planes(const ConvArgs& a) { return bf3w_layer(a) && !conv_rw_layer(a); }  // (conv_rw64_kernel stages float32)
-// where the fp16 image and its scales lie inside a two-plane layer's weight images
-static size_t half_image_offset(const ConvArgs& a) {
-  if (rw_stride3(a)) return 0;
-  if (bf3_c8(a)) return c8_image3_bytes(a);
-  return bf3w_layer(a) ? bf3w_image3_bytes(a) + bf3w_image2_bytes(a) : image3_bytes(a) + image3_bytes(a) / 3 * 2;
-}
-// the 32-channel-chunk fp16 image conv_rw_kernel reads of the stride-2 layer: behind this file's images and the scales
-static size_t rw2_image_offset(const ConvArgs& a) { return image3_bytes(a) + 2 * (image3_bytes(a) / 3 * 2) + scales_bytes(a); }
-static size_t scales_offset(const ConvArgs& a) {
-  if (rw_stride3(a)) return rw_image_bytes(a);
-  if (bf3_c8(a)) return c8_image3_bytes(a) + c8_half_bytes(a);
-  return bf3w_layer(a) ? bf3w_image3_bytes(a) + 2 * bf3w_image2_bytes(a) : image3_bytes(a) + 2 * (image3_bytes(a) / 3 * 2);
+bool conv_bf3_can_load_planes(const ConvArgs& a) {  // (conv_rw_kernel stages float32)
+  return conv_class(conv_shape_of(a)) == ConvClass::Wide && !conv_rw_layer(a);
 }
 const float* conv_bf3_weight_scales(const ConvArgs& a, const void* wimg) {
-  return reinterpret_cast<const float*>(reinterpret_cast<const char*>(wimg) + scales_offset(a));
+  const WeightImages im = images_of(a);
+  return im.scales == WeightImages::absent ? nullptr : reinterpret_cast<const float*>(reinterpret_cast<const char*>(wimg) + im.scales);
 }
+// builds every image the layer has: the scales first (the fp16 images are planes of the scaled weights)
 void launch_split_weights(const ConvArgs& a, void* wimg, hipStream_t s) {
-  const int cin_g = a.Cin / a.groups, cout_g = a.Cout / a.groups;
-  if (rw_stride3(a)) {
-    const size_t total32 = (size_t)a.groups * (cin_g / KW) * 36 * cout_g;
-    float* ws = reinterpret_cast<float*>(reinterpret_cast<char*>(wimg) + scales_offset(a));
+  const ConvShape sh = conv_shape_of(a);
+  const WeightImages im = WeightImages::of(sh);
+  const auto image = [wimg](size_t off) { return reinterpret_cast<uint4*>(reinterpret_cast<char*>(wimg) + off); };
+  float* ws = nullptr;
+  if (im.scales != WeightImages::absent) {
+    ws = reinterpret_cast<float*>(image(im.scales));
     hipLaunchKernelGGL(weight_scales_kernel, dim3((unsigned)((a.Cout + 255) / 256)), dim3(256), 0, s, a.weights, ws, ws + a.Cout,
-                       a.groups, 9 * cin_g, cout_g);
-    hipLaunchKernelGGL(split_weights32_kernel, dim3((unsigned)((total32 + 255) / 256)), dim3(256), 0, s, a.weights,
-                       reinterpret_cast<uint4*>(wimg), a.groups, cin_g, cout_g, 2, ws);
+                       sh.groups, 9 * sh.cin_g, sh.cout_g);
+  }
+  if (im.cls == ConvClass::C8) {
+    hipLaunchKernelGGL(split_weights8_kernel, dim3((unsigned)(((size_t)sh.groups * 10 * sh.cout_g + 255) / 256)), dim3(256), 0, s,
+                       a.weights, image(im.planes3), sh.groups, sh.cout_g);
+    hipLaunchKernelGGL(split_weights8h_kernel, dim3((unsigned)((sh.groups * 384 + 255) / 256)), dim3(256), 0, s, a.weights,
+                       image(im.half), sh.groups, ws);
     return;
   }
-  if (bf3_c8(a)) {
-    const size_t total8 = (size_t)a.groups * 10 * cout_g;
-    hipLaunchKernelGGL(split_weights8_kernel, dim3((unsigned)((total8 + 255) / 256)), dim3(256), 0, s, a.weights,
-                       reinterpret_cast<uint4*>(wimg), a.groups, cout_g);
-    float* ws = reinterpret_cast<float*>(reinterpret_cast<char*>(wimg) + scales_offset(a));
-    hipLaunchKernelGGL(weight_scales_kernel, dim3((unsigned)((a.Cout + 255) / 256)), dim3(256), 0, s, a.weights, ws, ws + a.Cout,
-                       a.groups, 9 * cin_g, cout_g);
-    hipLaunchKernelGGL(split_weights8h_kernel, dim3((unsigned)((a.groups * 384 + 255) / 256)), dim3(256), 0, s, a.weights,
-                       reinterpret_cast<uint4*>(wimg) + half_image_offset(a) / 16, a.groups, ws);
-    return;
-  }
-  if (bf3w_layer(a)) {
-    const size_t total32 = (size_t)a.groups * (cin_g / KW) * 36 * cout_g;
-    float* ws = reinterpret_cast<float*>(reinterpret_cast<char*>(wimg) + scales_offset(a));
-    hipLaunchKernelGGL(weight_scales_kernel, dim3((unsigned)((a.Cout + 255) / 256)), dim3(256), 0, s, a.weights, ws, ws + a.Cout,
-                       a.groups, 9 * cin_g, cout_g);
-    hipLaunchKernelGGL(split_weights32_kernel, dim3((unsigned)((total32 + 255) / 256)), dim3(256), 0, s, a.weights,
-                       reinterpret_cast<uint4*>(wimg), a.groups, cin_g, cout_g, 3, nullptr);
-    hipLaunchKernelGGL(split_weights32_kernel, dim3((unsigned)((total32 + 255) / 256)), dim3(256), 0, s, a.weights,
-                       reinterpret_cast<uint4*>(wimg) + bf3w_image3_bytes(a) / 16, a.groups, cin_g, cout_g, 2, nullptr);
-    hipLaunchKernelGGL(split_weights32_kernel, dim3((unsigned)((total32 + 255) / 256)), dim3(256), 0, s, a.weights,
-                       reinterpret_cast<uint4*>(wimg) + half_image_offset(a) / 16, a.groups, cin_g, cout_g, 2, ws);
-    return;
-  }
-  const size_t total = (size_t)a.groups * (cin_g / KC) * 18 * cout_g;
-  hipLaunchKernelGGL(split_weights_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a.weights,
-                     reinterpret_cast<uint4*>(wimg), a.groups, cin_g, cout_g, 3, nullptr);
-  if (flat_layer(a)) {  // the two-plane images of the layers the flattened kernel may take, behind the three-plane one
-    float* ws = reinterpret_cast<float*>(reinterpret_cast<char*>(wimg) + scales_offset(a));
-    hipLaunchKernelGGL(weight_scales_kernel, dim3((unsigned)((a.Cout + 255) / 256)), dim3(256), 0, s, a.weights, ws, ws + a.Cout,
-                       a.groups, 9 * cin_g, cout_g);
-    hipLaunchKernelGGL(split_weights_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a.weights,
-                       reinterpret_cast<uint4*>(wimg) + image3_bytes(a) / 16, a.groups, cin_g, cout_g, 2, nullptr);
-    hipLaunchKernelGGL(split_weights_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a.weights,
-                       reinterpret_cast<uint4*>(wimg) + half_image_offset(a) / 16, a.groups, cin_g, cout_g, 2, ws);
-    if (rw_stride2(a)) {
-      const size_t total32 = (size_t)a.groups * (cin_g / KW) * 36 * cout_g;
-      hipLaunchKernelGGL(split_weights32_kernel, dim3((unsigned)((total32 + 255) / 256)), dim3(256), 0, s, a.weights,
-                         reinterpret_cast<uint4*>(wimg) + rw2_image_offset(a) / 16, a.groups, cin_g, cout_g, 2, ws);
-    }
-  }
+  // one thread per 16-byte entry of a plane: [g][chunk][9][chunk / 8][cout_g]
+  const unsigned grid = (unsigned)(((size_t)sh.groups * (sh.cin_g / 8) * 9 * sh.cout_g + 255) / 256);
+  const auto build = [&](int chunk, size_t off, int planes, const float* wscale) {
+    if (off == WeightImages::absent) return;
+    if (chunk == KW)
+      hipLaunchKernelGGL(split_weights32_kernel, dim3(grid), dim3(256), 0, s, a.weights, image(off), sh.groups, sh.cin_g, sh.cout_g, planes, wscale);
+    else
+      hipLaunchKernelGGL(split_weights_kernel, dim3(grid), dim3(256), 0, s, a.weights, image(off), sh.groups, sh.cin_g, sh.cout_g, planes, wscale);
+  };
+  build(im.chunk, im.planes3, 3, nullptr);
+  build(im.chunk, im.planes2, 2, nullptr);
+  build(im.chunk, im.half, 2, ws);
+  build(KW, im.rw_half, 2, ws);
 }
 int launch_conv_bf3(const ConvArgs& a_in, const void* wimg, hipStream_t s) {
   ConvArgs a = a_in;
-  const int cout_g = a.Cout / a.groups;
-  if (a.stride == 3 && rw_stride3(a) && !a.half) return launch_conv(a, s);  // (the float32 kernel: also the guarded rerun)
+  const WeightImages im = images_of(a);
+  const ConvClass cls = im.cls;
+  if (cls == ConvClass::Unsupported) return -2;
+  if (cls == ConvClass::Rw3 && !a.half) return launch_conv(a, s);  // (the float32 kernel: also the guarded rerun)
   if (a.half) {  // CPX_CNN_MATH_FP16X2: the two-plane layers only, with the network's overflow word
     if (a.planes != 2 || !conv_bf3_two_planes(a) || a.ovf == nullptr) return -2;
     if (a.in_planes && !conv_bf3_can_load_planes(a)) return -2;
-    a.w_scale = reinterpret_cast<const float*>(reinterpret_cast<const char*>(wimg) + scales_offset(a));
+    a.w_scale = conv_bf3_weight_scales(a, wimg);
     a.w_unscale = a.w_scale + a.Cout;
   }
   // pixel offsets are formed with 24-bit multiplies (pix_off): a sample of 2^24 pixels or more is out of their range
@@ -2361,51 +2245,45 @@ int launch_conv_bf3(const ConvArgs& a_in, const void* wimg, hipStream_t s) {
   if (a.in_planes && !a.half) return -2;
   if (a.out_planes && (a.ovf == nullptr || !conv_bf3_can_store_planes(a) || a.residual != nullptr)) return -2;
   const uint4* w = reinterpret_cast<const uint4*>(wimg);
-  if (bf3_c8(a)) return launch_bf3_t<1, 1, CPX_BF3_NB_S2, CPX_BF3_TW_S2, CPX_BF3_CT_S2, true>(a, w, s);
-  if (a.stride == 2) {
-    if (!bf3_strided(a)) return -2;
-    if (a.planes == 2 && a.half && rw_stride2(a) && flat_layer(a) && !a.out_planes && !a.in_planes) {
-      const int rc = launch_conv_rw(a, w + rw2_image_offset(a) / 16, s);
-      if (rc != -2) return rc;
-    }
-    if (a.planes == 2 && a.half) return launch_bf3_t<2, 2, 2, 16, 512, false, 2, true>(a, w + half_image_offset(a) / 16, s);
-    if (a.planes == 2 && flat_layer(a)) return launch_bf3_t<2, 2, 2, 16, 512, false, 2>(a, w + image3_bytes(a) / 16, s);
-    return launch_bf3_t<2, 2, 2, 16, 512>(a, w, s);
-  }
-  if (a.stride == 3 && a.half && rw_stride3(a)) {
-    const int rc = launch_conv_rw(a, w + half_image_offset(a) / 16, s);
+  // (8 input channels per group: the tap-paired form, built for the 32 output channels per group the network has)
+  if (cls == ConvClass::C8) return launch_bf3_t<1, 1, NB_S2, TW_S2, CT_S2, true>(a, w, s);
+  if (cls == ConvClass::Rw3) {
+    const int rc = launch_conv_rw(a, w + im.half / 16, s);
     // (a form conv_rw_kernel does not take -- a residual on a strided layer: the float32 kernel computes it here, and its
     // guarded twin behind finds the overflow word clear)
     return rc == -2 ? launch_conv(a, s) : rc;
   }
-  if (a.stride != 1) return -2;
-  if (bf3w_layer(a)) {
-    if (a.sc_in && ((a.sc_cin / a.groups) & 3)) return -2;  // the fused shortcut walks K in fours
-    return launch_bf3w(a, w, s);
+  if (cls == ConvClass::Stride2Rw && a.planes == 2 && a.half && !a.out_planes && !a.in_planes) {
+    const int rc = launch_conv_rw(a, w + im.rw_half / 16, s);
+    if (rc != -2) return rc;
   }
-  if (cout_g == 32) return launch_bf3_t<1, 1, CPX_BF3_NB_S2, CPX_BF3_TW_S2, CPX_BF3_CT_S2>(a, w, s);
-  if (cout_g == 64) return launch_bf3_t<CPX_BF3_NTN_S3, 1, CPX_BF3_NB_S3, CPX_BF3_TW_S3, CPX_BF3_CT_S3>(a, w, s);
-  // 256 staged pixels + two N tiles = 80 KB: two workgroups per CU.  (Wider maps -- 54 x 54 at frame size 64 -- would
-  // need 384 staged pixels and then fit only one N tile per workgroup: measured slower than the rectangular bands,
-  // 399 vs 371 ms, the patch being activated and split by four column slices instead of two.)
-  if (cout_g == 128 && flat_pays(a, 32, 4 * CPX_BF3_NB_S4, 256)) {
+  if (a.stride == 2)  // Stride2Rw, Flat
+    return with_math(a, im, w, [&](auto pl, auto h, const uint4* wi) {
+      return launch_bf3_t<2, 2, 2, 16, 512, false, decltype(pl)::value, decltype(h)::value>(a, wi, s);
+    });
+  if (cls == ConvClass::Wide) {
+    if (a.sc_in && ((a.sc_cin / a.groups) & 3)) return -2;  // the fused shortcut walks K in fours
+    return launch_bf3w(a, im, w, s);
+  }
+  if (a.Cout / a.groups == 32) return launch_bf3_t<1, 1, NB_S2, TW_S2, CT_S2>(a, w, s);
+  if (a.Cout / a.groups == 64) return launch_bf3_t<NTN_S3, 1, NB_S3, TW_S3, CT_S3>(a, w, s);
+  // Flat at stride 1 (128 columns, stage 4): the flattened kernel takes it when the map is small (flat_pays, a property of the
+  // launch), in every math mode.  256 staged pixels + two N tiles = 80 KB: two workgroups per CU.  (Wider maps -- 54 x 54 at
+  // frame size 64 -- would need 384 staged pixels and then fit only one N tile per workgroup: measured slower than the
+  // rectangular bands, 399 vs 371 ms, the patch being activated and split by four column slices instead of two.)
+  if (flat_pays(a, 32, 4 * NB_S4, 256)) {
     // (the launch that carries stage 4's shortcut with fp16 planes of its weights: ConvArgs::sc_planes)
     if (a.planes == 2 && a.half && a.sc_in && a.sc_planes && conv_shortcut_planes_layer(a, a.sc_cin / a.groups) && !a.residual &&
         a.sc_stride >= 1 && a.sc_xscale > 0.0f && (a.sc_H - 1) / a.sc_stride + 1 == a.Ho && (a.sc_W - 1) / a.sc_stride + 1 == a.Wo &&
         (long long)a.sc_H * a.sc_W * a.sc_cin < (1ll << 31))
-      return launch_bf3flat_t<2, 256, 2, true, 256, true>(a, w + half_image_offset(a) / 16, s);
-    if (a.planes == 2 && a.half) return launch_bf3flat_t<2, 256, 2, true>(a, w + half_image_offset(a) / 16, s);
-    if (a.planes == 2 && flat_layer(a)) return launch_bf3flat_t<2, 256, 2>(a, w + image3_bytes(a) / 16, s);
-    return launch_bf3flat_t<2, 256, 3>(a, w, s);
+      return launch_bf3flat_t<2, 256, 2, true, 256, true>(a, w + im.half / 16, s);
+    return with_math(a, im, w, [&](auto pl, auto h, const uint4* wi) {
+      return launch_bf3flat_t<2, 256, decltype(pl)::value, decltype(h)::value>(a, wi, s);
+    });
   }
-  if (cout_g == 128) {
-    if (a.planes == 2 && a.half)
-      return launch_bf3_t<CPX_BF3_NTN_S4, 1, CPX_BF3_NB_S4, 32, CPX_BF3_CT_S4, false, 2, true>(a, w + half_image_offset(a) / 16, s);
-    if (a.planes == 2 && flat_layer(a))
-      return launch_bf3_t<CPX_BF3_NTN_S4, 1, CPX_BF3_NB_S4, 32, CPX_BF3_CT_S4, false, 2>(a, w + image3_bytes(a) / 16, s);
-    return launch_bf3_t<CPX_BF3_NTN_S4, 1, CPX_BF3_NB_S4, 32, CPX_BF3_CT_S4>(a, w, s);
-  }
-  return -2;
+  return with_math(a, im, w, [&](auto pl, auto h, const uint4* wi) {
+    return launch_bf3_t<NTN_S4, 1, NB_S4, 32, CT_S4, false, decltype(pl)::value, decltype(h)::value>(a, wi, s);
+  });
 }
 
 // a stage-2 residual block in one launch (conv_block32_kernel): `a` the first convolution (BatchNorm prologue, folded
@@ -2427,22 +2305,16 @@ int launch_conv_block32(const ConvArgs& a_in, const ConvArgs& b_in, const void* 
   ConvArgs a = a_in, b = b_in;
   if (!conv_block32_supported(a, b)) return -2;
   if ((long long)a.H * a.W >= (1 << 24)) return -3;
-  a.w_scale = reinterpret_cast<const float*>(reinterpret_cast<const char*>(wimg_a) + scales_offset(a));
+  const WeightImages ia = images_of(a), ib = images_of(b);
+  if (ia.half == WeightImages::absent || ib.half == WeightImages::absent) return -2;
+  a.w_scale = conv_bf3_weight_scales(a, wimg_a);
   a.w_unscale = a.w_scale + a.Cout;
-  b.w_scale = reinterpret_cast<const float*>(reinterpret_cast<const char*>(wimg_b) + scales_offset(b));
+  b.w_scale = conv_bf3_weight_scales(b, wimg_b);
   b.w_unscale = b.w_scale + b.Cout;
-  const uint4* wa = reinterpret_cast<const uint4*>(wimg_a) + half_image_offset(a) / 16;
-  const uint4* wb = reinterpret_cast<const uint4*>(wimg_b) + half_image_offset(b) / 16;
+  const uint4* wa = reinterpret_cast<const uint4*>(wimg_a) + ia.half / 16;
+  const uint4* wb = reinterpret_cast<const uint4*>(wimg_b) + ib.half / 16;
   TileDiv td{};
-  td.tiles_x = (a.W + W_TW - 1) / W_TW;
-  td.tiles_y = (a.H + W_TH - 1) / W_TH;
-  td.nsplit = 1;
-  const long long tiles = (long long)td.tiles_x * td.tiles_y * a.N;
-  if (tiles >= (1 << 22) - 8 || td.tiles_x >= 4096 || td.tiles_y >= 4096) return -3;
-  td.m_nsplit = (1ull << 42) + 1;
-  td.m_tx = (1ull << 42) / td.tiles_x + 1;
-  td.m_ty = (1ull << 42) / td.tiles_y + 1;
-  td.total = (int)tiles;
+  if (const int rc = fill_tiles(td, (a.W + W_TW - 1) / W_TW, (a.H + W_TH - 1) / W_TH, a.N, 1, TILES_PERSISTENT)) return rc;
   const bool c8 = a.Cin / a.groups == 8;
   // blocks past the stage's first: the two convolutions on different waves (cpx_cnn_blk.hip) unless CPX_BLOCK32_SPLIT=0
   static const bool split_roles = [] {
@@ -2461,17 +2333,10 @@ int launch_conv_block32(const ConvArgs& a_in, const ConvArgs& b_in, const void* 
            : !cpx_dyn_lds_ready(reinterpret_cast<const void*>(conv_block32_kernel<false>), lds_ready, 160 * 1024 - 1024))
     return -1;
   // one workgroup per CU (125 KB of LDS), shared among the groups; a multiple of eight per group so that blockIdx.x & 7 is the XCD
-  static int grid_x[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
-  if (grid_x[dev] == 0) {
-    int cus = 256;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8) cus = 256;
-    grid_x[dev] = cus;
-  }
-  int gx = std::max(8, grid_x[dev] / a.groups / 8 * 8);
-  if (const char* e = std::getenv("CPX_BLOCK32_GRID")) gx = std::max(8, std::atoi(e) / 8 * 8);
-  gx = (int)std::min<long long>(gx, (tiles + 7) / 8 * 8);
+  const int cus = cpx_device_cus();
+  if (cus == 0) return -1;
+  const char* e = std::getenv("CPX_BLOCK32_GRID");
+  const int gx = e ? persistent_grid_x(std::atoi(e), 1, td.total) : persistent_grid_x(cus, a.groups, td.total);
   if (c1) hipLaunchKernelGGL((conv_block32_kernel<true, true>), dim3((unsigned)gx, a.groups), dim3(512), lds, s, a, b, wa, wb, td);
   else if (c8) hipLaunchKernelGGL(conv_block32_kernel<true>, dim3((unsigned)gx, a.groups), dim3(512), lds, s, a, b, wa, wb, td);
   else hipLaunchKernelGGL(conv_block32_kernel<false>, dim3((unsigned)gx, a.groups), dim3(512), lds, s, a, b, wa, wb, td);

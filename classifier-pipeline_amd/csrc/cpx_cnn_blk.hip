@@ -28,6 +28,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "cpx_conv_layout_core.h"
 #include "cpx_kernels.h"
 
 namespace cpx {
@@ -78,7 +79,7 @@ __device__ __forceinline__ void static_for(F&& f) {
   }
 }
 struct BlkTiles {
-  unsigned long long m_tx, m_ty;  // floor(2^42 / d) + 1
+  unsigned long long m_tx, m_ty;  // div_magic's multipliers (cpx_conv_layout_core.h: fill_tiles)
   int tiles_x, tiles_y, total;
 };
 __device__ __forceinline__ int div_magic(int n, unsigned long long m) { return (int)(((unsigned long long)n * m) >> 42); }
@@ -438,26 +439,13 @@ __global__ __launch_bounds__(K_CT) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
 // fp16 plane images ([g][ky][plane][kx][quarter][32])
 int launch_conv_block32s(const ConvArgs& a, const ConvArgs& b, const void* wa, const void* wb, hipStream_t s) {
   BlkTiles td{};
-  td.tiles_x = (a.W + K_T - 1) / K_T;
-  td.tiles_y = (a.H + K_T - 1) / K_T;
-  const long long tiles = (long long)td.tiles_x * td.tiles_y * a.N;
-  if (tiles >= (1 << 22) - 8 || td.tiles_x >= 4096 || td.tiles_y >= 4096) return -3;
-  td.m_tx = (1ull << 42) / td.tiles_x + 1;
-  td.m_ty = (1ull << 42) / td.tiles_y + 1;
-  td.total = (int)tiles;
+  if (const int rc = fill_tiles(td, (a.W + K_T - 1) / K_T, (a.H + K_T - 1) / K_T, a.N, TILES_PERSISTENT)) return rc;
   static bool lds_ready[64];
   if (!cpx_dyn_lds_ready(reinterpret_cast<const void*>(conv_block32s_kernel), lds_ready, 160 * 1024 - 1024)) return -1;
-  static int cus_of[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
-  if (cus_of[dev] == 0) {
-    int cus = 256;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8) cus = 256;
-    cus_of[dev] = cus;
-  }
-  int gx = std::max(8, cus_of[dev] / a.groups / 8 * 8);
-  if (const char* e = std::getenv("CPX_BLOCK32_GRID")) gx = std::max(8, std::atoi(e) / 8 * 8);
-  gx = (int)std::min<long long>(gx, (tiles + 7) / 8 * 8);
+  const int cus = cpx_device_cus();
+  if (cus == 0) return -1;
+  const char* e = std::getenv("CPX_BLOCK32_GRID");
+  const int gx = e ? persistent_grid_x(std::atoi(e), 1, td.total) : persistent_grid_x(cus, a.groups, td.total);
   hipLaunchKernelGGL(conv_block32s_kernel, dim3((unsigned)gx, a.groups), dim3(K_CT), K_LDS, s, a, b, reinterpret_cast<const uint4*>(wa),
                      reinterpret_cast<const uint4*>(wb), td);
   return 0;

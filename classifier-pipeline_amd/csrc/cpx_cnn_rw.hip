@@ -47,6 +47,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "cpx_conv_layout_core.h"
 #include "cpx_kernels.h"
 
 namespace cpx {
@@ -83,7 +84,7 @@ __device__ __forceinline__ f32x4 mfma_h(u32x4 w, u32x4 x, f32x4 c) {
 }
 
 struct RwTiles {
-  unsigned long long m_tx, m_ty;  // floor(2^42 / d) + 1 (cpx_cnn_bf3.hip: TileDiv)
+  unsigned long long m_tx, m_ty;  // div_magic's multipliers (cpx_conv_layout_core.h: fill_tiles)
   int tiles_x, tiles_y, total;
 };
 // a loop whose index is a compile-time constant in every iteration (register arrays indexed by it stay registers)
@@ -572,19 +573,8 @@ void launch_split_shortcut(const float* sc_w, void* img, int groups, int cin_g, 
                      groups, cin_g, cout_g, w_scale, factor);
 }
 
-// the layers conv_rw_kernel takes (fp16x2, 3x3, SAME padding; channels per group in -> out):
-//   1  stride 1, 64 -> 64   (stage 3 of WR-ResNet-22-4: the convolutions of its blocks but the strided first one)
-//   2  stride 2, 32 -> 64   (that strided first one)
-//   3  stride 3, 64 -> 128  (stage 4's)
-int conv_rw_kind(const ConvArgs& a) {
-  if (a.ksize != 3 || a.groups < 1 || a.Cin % a.groups || a.Cout % a.groups) return 0;
-  const int cin_g = a.Cin / a.groups, cout_g = a.Cout / a.groups;
-  int kind = 0;
-  if (a.stride == 1 && cin_g == 64 && cout_g == 64) kind = 1;
-  else if (a.stride == 2 && cin_g == 32 && cout_g == 64) kind = 2;
-  else if (a.stride == 3 && cin_g == 64 && cout_g == 128) kind = 3;
-  return kind;
-}
+// the layers conv_rw_kernel takes (fp16x2, 3x3, SAME padding), by the layer's class: cpx_conv_layout_core.h
+int conv_rw_kind(const ConvArgs& a) { return conv_rw_kind_of(conv_shape_of(a)); }
 bool conv_rw_layer(const ConvArgs& a) { return conv_rw_kind(a) == 1; }
 
 namespace {
@@ -594,29 +584,16 @@ int launch_rw_t(const ConvArgs& a, const uint4* wimg, hipStream_t s) {
   constexpr size_t LDS = G::LDS + (SC ? SC_LDS : 0);
   static_assert(LDS <= 160 * 1024 - 1024, "two chunk buffers (and the shortcut's operand) must fit the CU's LDS");
   RwTiles td{};
-  td.tiles_x = (a.Wo + RW_TW - 1) / RW_TW;
-  td.tiles_y = (a.Ho + ROWS - 1) / ROWS;
-  const long long tiles = (long long)td.tiles_x * td.tiles_y * a.N;
-  if (tiles >= (1 << 22) - 8 || td.tiles_x >= 4096 || td.tiles_y >= 4096) return -3;
-  td.m_tx = (1ull << 42) / td.tiles_x + 1;
-  td.m_ty = (1ull << 42) / td.tiles_y + 1;
-  td.total = (int)tiles;
+  if (const int rc = fill_tiles(td, (a.Wo + RW_TW - 1) / RW_TW, (a.Ho + ROWS - 1) / ROWS, a.N, TILES_PERSISTENT)) return rc;
   static bool lds_ready[64];
   if (!cpx_dyn_lds_ready(reinterpret_cast<const void*>(conv_rw_kernel<S, NCH, ROWS, BN, RES, SC>), lds_ready, 160 * 1024 - 1024)) return -1;
   // one workgroup per CU (four waves, each with a SIMD's whole register file), shared among the (group, 64-channel half)
   // pairs; a multiple of eight per pair so that blockIdx.x & 7 names the XCD -- the halves of a group then walk the same tiles
   // on the same XCD at the same time and share the patch in its L2
-  static int cus_of[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
-  if (cus_of[dev] == 0) {
-    int cus = 256;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8) cus = 256;
-    cus_of[dev] = cus;
-  }
+  const int cus = cpx_device_cus();
+  if (cus == 0) return -1;
   const int ny = a.groups * ((a.Cout / a.groups) / RW_WC);
-  int gx = std::max(8, cus_of[dev] / ny / 8 * 8);
-  gx = (int)std::min<long long>(gx, (tiles + 7) / 8 * 8);
+  const int gx = persistent_grid_x(cus, ny, td.total);
   hipLaunchKernelGGL((conv_rw_kernel<S, NCH, ROWS, BN, RES, SC>), dim3((unsigned)gx, (unsigned)ny), dim3(RW_CT), LDS, s, a, wimg, td);
   return 0;
 }

@@ -1,0 +1,133 @@
+// cpx_conv_layout_core.h -- what the split-operand convolution launchers know about a layer on the host: which class of
+// layer it is, the ONE layout of its weight-image buffer, the tile decomposition the kernels divide by, and the width of a
+// persistent grid.  Plain host C++ without HIP, so that tests compile it on its own (tests/native/conv_layout_host.cpp);
+// cpx_cnn_bf3.hip, cpx_cnn_rw.hip and cpx_cnn_blk.hip are its users in the product.
+#pragma once
+#include <stddef.h>
+
+#include <algorithm>
+
+namespace cpx {
+
+// a grouped convolution by shape alone (channels per group); ksize = 0: no shape (groups < 1 or channels not divisible)
+struct ConvShape { int groups, cin_g, cout_g, ksize, stride; };
+template <class Args>
+ConvShape conv_shape_of(const Args& a) {
+  if (a.groups < 1 || a.Cin % a.groups || a.Cout % a.groups) return ConvShape{};
+  return ConvShape{a.groups, a.Cin / a.groups, a.Cout / a.groups, a.ksize, a.stride};
+}
+
+// The classes of layer the split-operand path takes, in the order they are tested (channels per group in -> out):
+//   Rw3        3x3 stride 3, 64 -> 128: conv_rw_kernel in fp16x2, the float32 kernel otherwise (wr_resnet.py:27-30, stage 4)
+//   Stride2Rw  3x3 stride 2, 32 -> 64: conv_rw_kernel in fp16x2, conv_bf3_kernel<2, 2, 2, 16, 512> otherwise (stage 3)
+//   C8         3x3 stride 1, 8 -> 32: the tap-paired form of conv_bf3_kernel, and conv_block32_kernel<true>
+//   Wide       3x3 stride 1, 32 or 64 -> 32 or 64: the 16x16x32 form (conv_bf3w_kernel; 64 -> 64 in fp16x2: conv_rw_kernel)
+//   Flat       3x3, input channels in sixteens, stride 1 with 128 columns (stage 4: conv_bf3flat_kernel where the map is
+//              small, the rectangular bands otherwise) or stride 2 with 64 columns
+//   Plain      3x3 stride 1, input channels in sixteens, 32 or 64 columns: three bf16 planes in every math mode
+enum class ConvClass { Unsupported, Plain, Flat, Wide, C8, Stride2Rw, Rw3 };
+
+inline ConvClass conv_class(const ConvShape& s) {
+  if (s.ksize != 3) return ConvClass::Unsupported;
+  if (s.stride == 3 && s.cin_g == 64 && s.cout_g == 128) return ConvClass::Rw3;
+  if (s.stride == 2 && s.cin_g == 32 && s.cout_g == 64) return ConvClass::Stride2Rw;
+  if (s.stride == 1 && s.cin_g == 8 && s.cout_g == 32) return ConvClass::C8;
+  const bool c32_64 = s.cout_g == 32 || s.cout_g == 64;
+  if (s.stride == 1 && (s.cin_g == 32 || s.cin_g == 64) && c32_64) return ConvClass::Wide;
+  if (s.cin_g < 16 || s.cin_g % 16) return ConvClass::Unsupported;
+  if ((s.stride == 1 && s.cout_g == 128) || (s.stride == 2 && s.cout_g == 64)) return ConvClass::Flat;
+  return s.stride == 1 && c32_64 ? ConvClass::Plain : ConvClass::Unsupported;
+}
+// the layers conv_rw_kernel takes in fp16x2 (cpx_cnn_rw.hip): 1 = stride 1, 64 -> 64 (stage 3's convolutions but the strided
+// first one), 2 = that strided first one, 3 = stage 4's; 0 = not taken
+inline int conv_rw_kind_of(const ConvShape& s) {
+  switch (conv_class(s)) {
+    case ConvClass::Wide: return s.cin_g == 64 && s.cout_g == 64 ? 1 : 0;
+    case ConvClass::Stride2Rw: return 2;
+    case ConvClass::Rw3: return 3;
+    default: return 0;
+  }
+}
+
+// A layer's weight-image buffer: the images of the math modes one after the other, byte offsets from its start.
+// An image is rows of cout_g 16-byte entries (eight channels of one tap, one plane, one output column):
+//   planes3  three bf16 planes  [g][chunk][3][9][2][cout_g] (chunk = 16 channels: 54 rows), Wide [g][chunk of 32][ky][3][kx][4][cout_g]
+//            (108 rows), C8 [g][3][5][2][cout_g] (30 rows: two taps per K step)
+//   planes2  two bf16 planes (CPX_CNN_MATH_BF16X2), the same order with two planes: 36 / 72 rows per chunk
+//   half     two fp16 planes of the scaled weights (CPX_CNN_MATH_FP16X2), as planes2; C8: the tap-quad image of
+//            conv_block32_kernel<true>, C8_HALF_ENTRIES entries per group; Rw3: in chunks of 32 (conv_rw_kernel's only image)
+//   scales   the per-channel powers of two of `half` and their inverses: 2 x Cout floats, rounded up to 16 bytes
+//   rw_half  Stride2Rw only: `half` once more in chunks of 32 channels, the order conv_rw_kernel reads
+// An image the class does not have is `absent`, not an offset.
+struct WeightImages {
+  static constexpr size_t absent = ~(size_t)0;
+  static constexpr size_t C8_HALF_ENTRIES = 3 * 2 * 4 * 32;
+  ConvClass cls = ConvClass::Unsupported;
+  int chunk = 0;  // input channels per chunk of planes3 / planes2 / half: 16 or 32 (0: C8, Unsupported)
+  size_t planes3 = absent, planes2 = absent, half = absent, scales = absent, rw_half = absent, bytes = 0;
+
+  static WeightImages of(const ConvShape& s) {
+    WeightImages l;
+    l.cls = conv_class(s);
+    if (l.cls == ConvClass::Unsupported) return l;
+    const auto put = [&l](size_t& image, size_t size) { image = l.bytes; l.bytes += size; };
+    const size_t row = (size_t)s.cout_g * 16;
+    const size_t scales = ((size_t)2 * s.groups * s.cout_g * sizeof(float) + 15) / 16 * 16;
+    if (l.cls == ConvClass::C8) {
+      put(l.planes3, (size_t)s.groups * 30 * row);
+      put(l.half, (size_t)s.groups * C8_HALF_ENTRIES * 16);
+      put(l.scales, scales);
+      return l;
+    }
+    l.chunk = l.cls == ConvClass::Wide || l.cls == ConvClass::Rw3 ? 32 : 16;
+    // (a chunk of a plane is 9 taps x chunk / 8 rows: either chunking gives the same bytes)
+    const auto image = [&](int planes) { return (size_t)s.groups * (s.cin_g / l.chunk) * (9 * l.chunk / 8 * planes) * row; };
+    if (l.cls != ConvClass::Rw3) put(l.planes3, image(3));
+    if (l.cls == ConvClass::Plain) return l;
+    if (l.cls != ConvClass::Rw3) put(l.planes2, image(2));
+    put(l.half, image(2));
+    put(l.scales, scales);
+    if (l.cls == ConvClass::Stride2Rw) put(l.rw_half, image(2));
+    return l;
+  }
+};
+
+// The kernels divide a workgroup's (or a walked tile's) index by tile counts: q = n / d as (n * m) >> 42 with the host-computed
+// m = floor(2^42 / d) + 1 -- two scalar multiplies instead of the ~25-instruction reciprocal sequence of a runtime division.
+// Exact for n < 2^22, d < 2^12: n (m d - 2^42) <= n d < 2^34 < 2^42, and n m < 2^64.  So a tile count per axis stays below
+// TILE_AXIS_LIMIT and the product of all counts below the caller's limit: TILES_PER_LAUNCH where a workgroup has one unit of
+// work and divides only its own index (< total); TILES_PERSISTENT where a persistent grid walks the tiles in XCD eighths --
+// those kernels form tile indices up to 8 * ceil(total / 8) - 1 <= total + 6 before they compare them with `total`.
+constexpr int TILE_AXIS_LIMIT = 4096;
+constexpr long long TILES_PER_LAUNCH = 1ll << 22;
+constexpr long long TILES_PERSISTENT = (1ll << 22) - 8;
+inline unsigned long long tile_magic(int d) { return (1ull << 42) / (unsigned long long)d + 1; }
+
+// fills tiles_x / tiles_y / total (= tiles_x tiles_y n) and their multipliers of a kernel's tile argument (TileDiv, RwTiles,
+// BlkTiles: schedule_point's way); -3: out of div_magic's range
+template <class Tiles>
+int fill_tiles(Tiles& td, int tiles_x, int tiles_y, long long n, long long limit) {
+  if (tiles_x < 1 || tiles_y < 1 || tiles_x >= TILE_AXIS_LIMIT || tiles_y >= TILE_AXIS_LIMIT) return -3;
+  const long long total = (long long)tiles_x * tiles_y * n;  // (< 2^24 n: no overflow for any int n)
+  if (total >= limit) return -3;
+  td.tiles_x = tiles_x, td.m_tx = tile_magic(tiles_x);
+  td.tiles_y = tiles_y, td.m_ty = tile_magic(tiles_y);
+  td.total = (int)total;
+  return 0;
+}
+// ... and with the columns of a group split among nsplit workgroups per tile (TileDiv): the split is the innermost index
+template <class Tiles>
+int fill_tiles(Tiles& td, int tiles_x, int tiles_y, long long n, int nsplit, long long limit) {
+  if (nsplit < 1 || nsplit >= TILE_AXIS_LIMIT) return -3;
+  td.nsplit = nsplit, td.m_nsplit = tile_magic(nsplit);
+  return fill_tiles(td, tiles_x, tiles_y, n * nsplit, limit);
+}
+
+// A persistent grid's width along x: one workgroup per CU, shared among the ny rows of the grid (groups, or (group, column
+// half) pairs); a multiple of eight per row so that blockIdx.x & 7 names the XCD, and no more than the tiles rounded up to eight
+inline int persistent_grid_x(int cus, int ny, long long tiles) {
+  const int gx = std::max(8, cus / std::max(ny, 1) / 8 * 8);
+  return (int)std::min<long long>(gx, (tiles + 7) / 8 * 8);
+}
+
+}  // namespace cpx

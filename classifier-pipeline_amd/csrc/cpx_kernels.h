@@ -424,6 +424,19 @@ inline bool cpx_dyn_lds_ready(const void* fn, bool* done, int bytes) {
   return true;
 }
 
+// The current device's compute units, asked once per device (256 where the runtime will not say); 0: no current device.
+inline int cpx_device_cus() {
+  static int cus_of[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+  if (cus_of[dev] == 0) {
+    int cus = 256;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8) cus = 256;
+    cus_of[dev] = cus;
+  }
+  return cus_of[dev];
+}
+
 size_t track_lds_bytes(int W, int H);
 int track_max_pixels();
 int track_lds_components();

@@ -41,6 +41,11 @@ CASES = [
     (64, 128, 19, 35, 3, 1, True),
     (128, 64, 18, 17, 3, 1, True),
     (128, 128, 33, 16, 3, 1, False),  # VALID: no padding, output 31 x 14
+    # ... and the layer classes of csrc/cpx_conv_layout_core.h that the cases above do not reach
+    (32, 64, 17, 21, 3, 1, True),     # Plain, 16 -> 32 per group: conv_bf3_kernel<1, 1, ...> without the tap pairing; bf16x3 in every split mode
+    (256, 128, 9, 20, 3, 1, True),    # Plain, 128 -> 64: the 64-column instantiation
+    (32, 128, 21, 18, 3, 2, True),    # Flat at stride 2, 16 -> 64: a strided layer that is not conv_rw_kernel's
+    (256, 256, 8, 32, 3, 1, True),    # res4* on a map whose rectangular bands are full: the 128-column launch (9 x 11 takes the flattened kernel)
 ]
 
 
