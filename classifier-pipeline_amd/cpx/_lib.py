@@ -127,7 +127,7 @@ assert C.sizeof(WRResNetParams) == 1560
 assert C.sizeof(GraphTensor) == 32 and C.sizeof(GraphOp) == 112
 # enum CPX_GRAPH_* (include/cpx.h)
 GRAPH_CONV, GRAPH_MAX_POOL, GRAPH_AVG_POOL, GRAPH_ADD, GRAPH_AFFINE, GRAPH_MEAN, GRAPH_FC, GRAPH_LOGISTIC, GRAPH_SOFTMAX, \
-    GRAPH_PAD, GRAPH_CHANNEL_MAP, GRAPH_CONV_Q8, GRAPH_FC_Q8, GRAPH_QUANT_PARAMS = range(1, 15)
+    GRAPH_PAD, GRAPH_CHANNEL_MAP, GRAPH_CONV_Q8, GRAPH_FC_Q8, GRAPH_QUANT_PARAMS, GRAPH_DWCONV, GRAPH_DWCONV_Q8 = range(1, 17)
 GRAPH_CONV_KC, GRAPH_CONV_CO = 16, 32   # CONV weights: Cin / Cout rounded up to these (csrc/cpx_kernels.h)
 GRAPH_CONV_Q8_KC = 32   # CONV_Q8 weights: int8 in MFMA fragment order, Cin rounded up to this (csrc/cpx_kernels.h)
 HEAD_SIGMOID, HEAD_SOFTMAX = 0, 1

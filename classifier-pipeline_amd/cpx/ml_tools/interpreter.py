@@ -354,7 +354,7 @@ class WRResNetInterpreter(Interpreter):
 
 class LiteInterpreter(Interpreter):
     """Any float32 or dynamic-range quantised `.tflite` graph of the operator set cpx/ml_tools/tflite_reader.py reads (the
-    reference's inceptionv3 family, ml_tools/kerasmodel.py:171-180,259-350; its converter writes INT8 filters,
+    reference's inceptionv3 and mobilenet families, ml_tools/kerasmodel.py:144-151,171-180,259-350; its converter writes INT8 filters,
     src/tfliteconverter.py:54-62) on the device graph executor (cpx_graph_*): the reference's LiteInterpreter
     (interpreter.py:520-560) with the TFLite runtime replaced.  model = <name>.tflite + <name>.json.
     predict runs the whole batch in one forward (the reference loops sample by sample because its runtime must).

@@ -13,6 +13,10 @@
 * tensors get offsets in one arena by lifetime (first write to last read, in operator order); the offsets are per
   sample, the arena of a forward over N samples is N times as large;
 * CONV_2D filters are transposed from TFLite's OHWI to the kernel's [tap][Cin][Cout], Cin padded to 16 and Cout to 32;
+* a DEPTHWISE_CONV_2D (depth multiplier 1: the MobileNetV2 family) is a DWCONV operator, its [1, kh, kw, C] filter packed
+  [tap][C rounded up to 4] (pack_dw_filter); MUL / ADD / SUB fold into it and it writes into a concatenation's slice as
+  a CONV_2D does.  With an INT8 filter (scales along dimension 3) it is the hybrid DWCONV_Q8, which shares the
+  QUANT_PARAMS of its input view with any other quantised consumer (pack_dw_filter_q8: int8 taps, then wsum);
 * a CONV_2D / FULLY_CONNECTED with an INT8 filter (dynamic-range quantisation: what the reference's converter writes,
   src/tfliteconverter.py:54-62) becomes a hybrid operator, CONV_Q8 / FC_Q8 (quantised_math="hybrid"): its second input is
   a per-sample parameter tensor (1 x 1 x 4: sx, inv, zp) that ONE QUANT_PARAMS operator per input tensor view writes,
@@ -26,7 +30,7 @@ import ctypes as C
 import numpy as np
 
 from .. import _lib
-from .tflite_reader import ACT_NONE, ACT_RELU, ACT_RELU6, PADDING_SAME
+from .tflite_reader import ACT_NONE, ACT_RELU, ACT_RELU6, FILTER_OPS, PADDING_SAME
 
 ALIGN = 64   # floats: every tensor of the arena starts on a 256-byte boundary
 
@@ -103,7 +107,8 @@ def _channel_const(g, tid, channels, what):
 
 
 QUANT_MATHS = ("hybrid", "float")
-Q8_KINDS = (_lib.GRAPH_CONV_Q8, _lib.GRAPH_FC_Q8)
+Q8_KINDS = (_lib.GRAPH_CONV_Q8, _lib.GRAPH_FC_Q8, _lib.GRAPH_DWCONV_Q8)
+FOLD_INTO = (_lib.GRAPH_CONV, _lib.GRAPH_CONV_Q8, _lib.GRAPH_DWCONV, _lib.GRAPH_DWCONV_Q8, _lib.GRAPH_AFFINE)
 
 
 def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_math="hybrid"):
@@ -148,7 +153,8 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
         if quantised_math == "float":
             return g.dequantised(tid), None
         sc = np.asarray(ten["quant"]["scale"], np.float32).reshape(-1)
-        return ten["const"], (np.full(ten["shape"][0], sc[0], np.float32) if sc.size == 1 else sc)
+        channels = ten["shape"][FILTER_OPS[op["name"]]]
+        return ten["const"], (np.full(channels, sc[0], np.float32) if sc.size == 1 else sc)
 
     qparams = {}   # (input tensor view, symmetric) -> parameter tensor id
 
@@ -203,6 +209,26 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
             emit(PlanOp(kind, name, x.id, y, in1=in1, kh=kh, kw=kw, stride_h=sh, stride_w=sw, pads=(pt, pl, pb, pr),
                         act=op.get("act", 0), filter=w, scale=None, filter_scale=fscale,
                         shift=np.zeros(co, np.float32) if bias is None else np.asarray(bias, np.float32).reshape(-1)), i)
+        elif name == "DEPTHWISE_CONV_2D":
+            w, fscale = filter_of(op, ins[1])
+            _, kh, kw, co = w.shape
+            if co != x.C:
+                raise NotImplementedError("%s: depth multiplier (filter depth %d, input depth %d), only 1 is run" % (what, co, x.C))
+            sh, sw = op.get("stride_h", 1), op.get("stride_w", 1)
+            if not (1 <= kh <= 7 and 1 <= kw <= 7 and sh in (1, 2) and sw in (1, 2)):
+                raise NotImplementedError("%s: %d x %d kernel with strides %d, %d" % (what, kh, kw, sh, sw))
+            ho, pt, pb = window(x.H, kh, sh, op.get("padding", 0))
+            wo, pl, pr = window(x.W, kw, sw, op.get("padding", 0))
+            if ho < 1 or wo < 1:
+                raise NotImplementedError("%s: the %d x %d input is smaller than the kernel" % (what, x.H, x.W))
+            T[y] = PlanTensor(y, ho, wo, co)
+            bias = g.const(ins[2]) if len(ins) > 2 else None
+            kind, in1 = _lib.GRAPH_DWCONV, -1
+            if fscale is not None:
+                kind, in1 = _lib.GRAPH_DWCONV_Q8, params_of(x, False, i)   # (kh * kw <= 49 products: no overflow)
+            emit(PlanOp(kind, name, x.id, y, in1=in1, kh=kh, kw=kw, stride_h=sh, stride_w=sw, pads=(pt, pl, pb, pr),
+                        act=op.get("act", 0), filter=w, scale=None, filter_scale=fscale,
+                        shift=np.zeros(co, np.float32) if bias is None else np.asarray(bias, np.float32).reshape(-1)), i)
         elif name in ("MAX_POOL_2D", "AVERAGE_POOL_2D"):
             kh, kw = op["filter_height"], op["filter_width"]
             sh, sw = op["stride_h"], op["stride_w"]
@@ -236,7 +262,7 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
                     sc, sf = one, -c
                 T[y] = PlanTensor(y, x.H, x.W, x.C)
                 p = producer.get(x.id)
-                if p is not None and p.kind in (_lib.GRAPH_CONV, _lib.GRAPH_CONV_Q8, _lib.GRAPH_AFFINE) and p.act == ACT_NONE and not p.copy \
+                if p is not None and p.kind in FOLD_INTO and p.act == ACT_NONE and not p.copy \
                         and len(consumers.get(x.id, [])) == 1 and x.id != gout:
                     # fold: (v * s0 + h0) * sc + sf; the producer now writes this operator's output
                     s0 = one if p.scale is None else p.scale
@@ -443,6 +469,11 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
             o.weights = pack_conv_filter_q8(o.filter)
             # the device multiplies by float32(filter scale x folded scale)
             o.scale = o.filter_scale if o.scale is None else (o.filter_scale * o.scale).astype(np.float32)
+        elif o.kind == _lib.GRAPH_DWCONV:
+            o.weights = pack_dw_filter(o.filter)
+        elif o.kind == _lib.GRAPH_DWCONV_Q8:
+            o.weights = pack_dw_filter_q8(o.filter)
+            o.scale = o.filter_scale if o.scale is None else (o.filter_scale * o.scale).astype(np.float32)
     return plan
 
 
@@ -486,6 +517,44 @@ def pack_fc_filter_q8(w):
     full[:, :ci] = w
     wsum = w.astype(np.int64).sum(axis=1).astype(np.int32)
     return np.concatenate([full.reshape(-1).view(np.uint8), wsum.view(np.uint8)])
+
+
+def pack_dw_filter(w_1hwc):
+    """A depthwise filter [1, kh, kw, C] -> float32 [kh * kw][C rounded up to 4], zeros beyond."""
+    _, kh, kw, c = w_1hwc.shape
+    out = np.zeros((kh * kw, -(-c // 4) * 4), np.float32)
+    out[:, :c] = np.asarray(w_1hwc, np.float32).reshape(kh * kw, c)
+    return out
+
+
+def unpack_dw_filter(packed, shape):
+    """The inverse of pack_dw_filter for a filter of `shape` ([1, kh, kw, C])."""
+    _, kh, kw, c = shape
+    return np.ascontiguousarray(np.asarray(packed, np.float32).reshape(kh * kw, -1)[:, :c]).reshape(1, kh, kw, c)
+
+
+def pack_dw_filter_q8(w_1hwc):
+    """An INT8 depthwise filter [1, kh, kw, C] -> bytes: int8 [kh * kw][C rounded up to 4] (zeros beyond), then int32
+    wsum[C rounded up to 4], the filter summed over its taps."""
+    w = np.asarray(w_1hwc)
+    assert w.dtype == np.int8, w.dtype
+    _, kh, kw, c = w.shape
+    cp = -(-c // 4) * 4
+    full = np.zeros((kh * kw, cp), np.int8)
+    full[:, :c] = w.reshape(kh * kw, c)
+    wsum = np.zeros(cp, np.int32)
+    wsum[:c] = w.reshape(kh * kw, c).astype(np.int64).sum(axis=0)
+    return np.concatenate([full.reshape(-1).view(np.uint8), wsum.view(np.uint8)])
+
+
+def unpack_dw_filter_q8(packed, shape):
+    """The inverse of pack_dw_filter_q8 for a filter of `shape` -> (int8 filter, int32 wsum[C])."""
+    _, kh, kw, c = shape
+    cp = -(-c // 4) * 4
+    packed = np.asarray(packed, np.uint8)
+    assert packed.size == kh * kw * cp + 4 * cp, packed.size
+    full = packed[:kh * kw * cp].view(np.int8).reshape(kh * kw, cp)
+    return np.ascontiguousarray(full[:, :c]).reshape(1, kh, kw, c), packed[kh * kw * cp:].view(np.int32)[:c].copy()
 
 
 def pack_conv_filter(w_ohwi):

@@ -2,16 +2,17 @@
 only NumPy.  Two users:
 
 * `Graph` decodes subgraph 0 of any float32 model made of the operators in OPS below, with their options: CONV_2D
-  (dilation 1 only), AVERAGE_POOL_2D, MAX_POOL_2D, CONCATENATION, ADD, SUB, MUL, RELU, RELU6, MEAN, FULLY_CONNECTED,
+  (dilation 1 only), DEPTHWISE_CONV_2D (filter [1, kh, kw, C]; depth multiplier 1 and dilation 1 only), AVERAGE_POOL_2D, MAX_POOL_2D, CONCATENATION, ADD, SUB, MUL, RELU, RELU6, MEAN, FULLY_CONNECTED,
   LOGISTIC, SOFTMAX, RESHAPE, PAD.  That is the set the converter writes for the reference's `inceptionv3` family
   (ml_tools/kerasmodel.py:171-180,259-350; the artefact the reference's CI classifies with, .github/workflows/
-  release.yml:46 `inc3-tflite-15122023.tar`, is one).  cpx/ml_tools/tflite_graph.py plans such a graph for the device
+  release.yml:46 `inc3-tflite-15122023.tar`, is one) and for its `mobilenet` family (MobileNetV2, kerasmodel.py:144-151).  cpx/ml_tools/tflite_graph.py plans such a graph for the device
   executor (cpx_graph_*), the LiteInterpreter of cpx/ml_tools/interpreter.py runs it -- what the reference's
   LiteInterpreter does with any `.tflite` (src/ml_tools/interpreter.py:520-560,597-628).  A dynamic-range quantised file
-  (what the reference's converter writes, src/tfliteconverter.py:54-62: the filters of CONV_2D / FULLY_CONNECTED with 1024
-  or more elements INT8 with symmetric scales, everything else float32) is read too: an INT8 constant comes with its
-  quantisation table (`quant`: scale, zero_point, dim), FULLY_CONNECTED with asymmetric_quantize_inputs.
-  check_executable() refuses everything else by operator name and index: DEPTHWISE_CONV_2D, quantised activations,
+  (what the reference's converter writes, src/tfliteconverter.py:54-62: the filters of CONV_2D / DEPTHWISE_CONV_2D / FULLY_CONNECTED
+  with 1024 or more elements INT8 with symmetric scales -- along dimension 0, a depthwise filter's along dimension 3 --
+  everything else float32) is read too: an INT8 constant comes with its quantisation table (`quant`: scale, zero_point,
+  dim), FULLY_CONNECTED with asymmetric_quantize_inputs.
+  check_executable() refuses everything else by operator name and index: a depth multiplier, quantised activations,
   UINT8 / INT16 or asymmetric filters, an INT8 constant anywhere but as such a filter, DEQUANTIZE / QUANTIZE, grouped
   CONV_2D, a dynamic shape, an operator outside the set.
 * `convert` / `load_tflite` walk ONE topology, a WR-ResNet-22-4, into the Keras-layout weights of
@@ -30,14 +31,16 @@ import struct
 import numpy as np
 
 BN_EPS = np.float32(1e-3)
-OPS = {0: "ADD", 1: "AVERAGE_POOL_2D", 2: "CONCATENATION", 3: "CONV_2D", 9: "FULLY_CONNECTED", 14: "LOGISTIC",
+OPS = {0: "ADD", 1: "AVERAGE_POOL_2D", 2: "CONCATENATION", 3: "CONV_2D", 4: "DEPTHWISE_CONV_2D", 9: "FULLY_CONNECTED", 14: "LOGISTIC",
        17: "MAX_POOL_2D", 18: "MUL", 19: "RELU", 21: "RELU6", 25: "SOFTMAX", 40: "MEAN", 41: "SUB", 22: "RESHAPE", 34: "PAD"}
 # operators that are recognised only to be refused by name (check_executable)
-REFUSED_OPS = {4: "DEPTHWISE_CONV_2D", 6: "DEQUANTIZE", 114: "QUANTIZE", 67: "TRANSPOSE_CONV", 23: "RESIZE_BILINEAR",
+REFUSED_OPS = {6: "DEQUANTIZE", 114: "QUANTIZE", 67: "TRANSPOSE_CONV", 23: "RESIZE_BILINEAR",
                28: "TANH", 39: "TRANSPOSE", 32: "CUSTOM"}
 TENSOR_TYPES = {0: "FLOAT32", 1: "FLOAT16", 2: "INT32", 3: "UINT8", 4: "INT64", 6: "BOOL", 7: "INT16", 9: "INT8"}
 PADDING_SAME, PADDING_VALID = 0, 1
 ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 3
+# operators whose second input may be an INT8 filter -> the dimension its per-channel scales run along (the output channels)
+FILTER_OPS = {"CONV_2D": 0, "FULLY_CONNECTED": 0, "DEPTHWISE_CONV_2D": 3}
 
 
 # ---- flatbuffer access ---------------------------------------------------------------------------------------
@@ -151,6 +154,11 @@ class Graph:
                     if o["dilation_w"] != 1 or o["dilation_h"] != 1:
                         raise NotImplementedError("operator %d (CONV_2D): dilation %d x %d, only 1 x 1 is read"
                                                   % (len(self.ops), o["dilation_h"], o["dilation_w"]))
+                elif o["name"] == "DEPTHWISE_CONV_2D":
+                    # (what does not run -- a depth multiplier, a dilation -- is refused by check_executable)
+                    o.update(padding=opts.scalar(0, "b", 0), stride_w=opts.scalar(1, "i", 1), stride_h=opts.scalar(2, "i", 1),
+                             depth_multiplier=opts.scalar(3, "i", 0), act=opts.scalar(4, "b", 0),
+                             dilation_w=opts.scalar(5, "i", 1), dilation_h=opts.scalar(6, "i", 1))
                 elif o["name"] in ("AVERAGE_POOL_2D", "MAX_POOL_2D"):
                     o.update(padding=opts.scalar(0, "b", 0), stride_w=opts.scalar(1, "i", 1), stride_h=opts.scalar(2, "i", 1),
                              filter_width=opts.scalar(3, "i", 1), filter_height=opts.scalar(4, "i", 1),
@@ -185,27 +193,31 @@ class Graph:
         return self.tensors[idx]["const"]
 
     def quantised_filter(self, op):
-        """The filter tensor of a CONV_2D / FULLY_CONNECTED if it is an INT8 constant (dynamic-range quantisation), else None."""
-        if op["name"] in ("CONV_2D", "FULLY_CONNECTED") and len(op["inputs"]) > 1 and op["inputs"][1] >= 0:
+        """The filter tensor of a CONV_2D / DEPTHWISE_CONV_2D / FULLY_CONNECTED if it is an INT8 constant (dynamic-range
+        quantisation), else None."""
+        if op["name"] in FILTER_OPS and len(op["inputs"]) > 1 and op["inputs"][1] >= 0:
             ten = self.tensors[op["inputs"][1]]
             if ten["type"] == 9 and ten["const"] is not None:
                 return ten
         return None
 
     def dequantised(self, idx):
-        """A constant as float32: an INT8 filter multiplied out by its scales (per first dimension, or one)."""
+        """A constant as float32: an INT8 filter multiplied out by its scales (one, or one per slice of its quantised
+        dimension)."""
         ten = self.tensors[idx]
         if ten["type"] != 9:
             return ten["const"]
         sc = ten["quant"]["scale"].astype(np.float32)
         w = ten["const"].astype(np.float32)
-        return (w * sc.reshape((-1,) + (1,) * (w.ndim - 1))).astype(np.float32)
+        dim = ten["quant"]["dim"] if sc.size > 1 else 0
+        return (w * sc.reshape((1,) * dim + (-1,) + (1,) * (w.ndim - 1 - dim))).astype(np.float32)
 
     def check_executable(self):
         """Raises NotImplementedError, naming the operator and its index, for whatever the graph executor
         (cpx/ml_tools/tflite_graph.py) does not run: an operator outside OPS, a tensor that is not float32 (int32
         constants of MEAN / RESHAPE / PAD excepted; an INT8 constant as the filter of CONV_2D / FULLY_CONNECTED with
-        symmetric scales along dimension 0 excepted), grouped CONV_2D, a dynamic shape."""
+        symmetric scales along dimension 0, or of DEPTHWISE_CONV_2D along dimension 3, excepted), grouped CONV_2D, a
+        DEPTHWISE_CONV_2D with a depth multiplier or a dilation other than 1, a dynamic shape."""
         for i, op in enumerate(self.ops):
             name = op["name"]
             if op["code"] not in OPS:
@@ -216,17 +228,20 @@ class Graph:
                     continue
                 ten = self.tensors[t]
                 int_const = ten["type"] == 2 and ten["const"] is not None and name in ("MEAN", "RESHAPE", "PAD") and k >= 1
-                if ten["type"] == 9 and ten["const"] is not None and k == 1 and name in ("CONV_2D", "FULLY_CONNECTED"):
+                if ten["type"] == 9 and ten["const"] is not None and k == 1 and name in FILTER_OPS:
                     q = ten["quant"]
                     if q is None:
                         raise NotImplementedError("operator %d (%s): the INT8 filter %r has no quantisation scales" % (i, name, ten["name"]))
                     if np.any(q["zero_point"] != 0):
                         raise NotImplementedError("operator %d (%s): the INT8 filter %r has a non-zero zero point, only symmetric "
                                                   "filters are run" % (i, name, ten["name"]))
-                    if q["dim"] != 0 or q["scale"].size not in (1, ten["shape"][0]):
+                    qdim = FILTER_OPS[name]
+                    per_channel = q["dim"] == qdim and len(ten["shape"]) > qdim and q["scale"].size == ten["shape"][qdim]
+                    # (one scale: CONV_2D / FULLY_CONNECTED state dimension 0 with it; a depthwise filter may state either)
+                    if not (per_channel or (q["scale"].size == 1 and q["dim"] in (0, qdim))):
                         raise NotImplementedError("operator %d (%s): the INT8 filter %r has %d scales along dimension %d, "
-                                                  "only one or one per output channel (dimension 0) are run"
-                                                  % (i, name, ten["name"], q["scale"].size, q["dim"]))
+                                                  "only one or one per output channel (dimension %d) are run"
+                                                  % (i, name, ten["name"], q["scale"].size, q["dim"], qdim))
                     continue
                 if ten["type"] != 0 and not int_const:
                     raise NotImplementedError("operator %d (%s): tensor %r has type %s, only float32 graphs are run"
@@ -242,6 +257,24 @@ class Graph:
                 if len(cin) == 4 and cin[3] > 0 and w.shape[3] != cin[3]:
                     raise NotImplementedError("operator %d (CONV_2D): grouped convolution (filter depth %d, input depth %d)"
                                               % (i, w.shape[3], cin[3]))
+            if name == "DEPTHWISE_CONV_2D":
+                w = self.const(op["inputs"][1]) if len(op["inputs"]) > 1 and op["inputs"][1] >= 0 else None
+                if w is None:
+                    raise NotImplementedError("operator %d (DEPTHWISE_CONV_2D): the filter is not a constant" % i)
+                if op.get("dilation_w", 1) != 1 or op.get("dilation_h", 1) != 1:
+                    raise NotImplementedError("operator %d (DEPTHWISE_CONV_2D): dilation %d x %d, only 1 x 1 is run"
+                                              % (i, op.get("dilation_h", 1), op.get("dilation_w", 1)))
+                if w.ndim != 4 or w.shape[0] != 1:
+                    raise NotImplementedError("operator %d (DEPTHWISE_CONV_2D): a filter of shape %s, [1, kh, kw, channels] is run"
+                                              % (i, list(w.shape)))
+                cin = self.tensors[op["inputs"][0]]["shape"]
+                mult = op.get("depth_multiplier", 0)
+                # (TFLite's prepare step checks the field against the shapes too; a field that disagrees is not repaired)
+                if mult != 1:
+                    raise NotImplementedError("operator %d (DEPTHWISE_CONV_2D): depth multiplier %d, only 1 is run" % (i, mult))
+                if len(cin) == 4 and cin[3] > 0 and w.shape[3] != cin[3]:
+                    raise NotImplementedError("operator %d (DEPTHWISE_CONV_2D): depth multiplier 1 with filter depth %d on input "
+                                              "depth %d" % (i, w.shape[3], cin[3]))
             if name == "MEAN" and op["axes"] is None:
                 raise NotImplementedError("operator %d (MEAN): the axes are not a constant" % i)
             if name == "PAD" and op["paddings"] is None:

@@ -39,9 +39,12 @@ static const char* graph_check_op(const cpx_graph_op& o, const std::vector<cpx_g
   switch (o.kind) {
     case CPX_GRAPH_CONV:
     case CPX_GRAPH_CONV_Q8:
+    case CPX_GRAPH_DWCONV:
+    case CPX_GRAPH_DWCONV_Q8:
     case CPX_GRAPH_MAX_POOL:
     case CPX_GRAPH_AVG_POOL: {
-      const bool conv = o.kind == CPX_GRAPH_CONV || o.kind == CPX_GRAPH_CONV_Q8;
+      const bool dw = o.kind == CPX_GRAPH_DWCONV || o.kind == CPX_GRAPH_DWCONV_Q8;
+      const bool conv = dw || o.kind == CPX_GRAPH_CONV || o.kind == CPX_GRAPH_CONV_Q8;
       if (o.kh < 1 || o.kw < 1 || o.kh > 7 || o.kw > 7) return "kernel sides are 1 to 7";
       if (o.stride_h < 1 || o.stride_w < 1 || o.stride_h > (conv ? 2 : 7) || o.stride_w > (conv ? 2 : 7)) return "bad stride";
       if (o.pad_top < 0 || o.pad_left < 0 || o.pad_bottom < 0 || o.pad_right < 0 || o.pad_top >= o.kh || o.pad_bottom >= o.kh ||
@@ -51,6 +54,13 @@ static const char* graph_check_op(const cpx_graph_op& o, const std::vector<cpx_g
       if (hh < 0 || ww < 0 || y.H != hh / o.stride_h + 1 || y.W != ww / o.stride_w + 1) return "output size does not follow from kernel, stride and pads";
       if (conv && !o.weights) return "CONV without weights";
       if (!conv && a.C != y.C) return "pool changes the channel count";
+      if (dw && a.C != y.C) return "DWCONV changes the channel count (depth multiplier 1 only)";
+      if (o.kind == CPX_GRAPH_DWCONV && (reinterpret_cast<uintptr_t>(o.weights) & 15)) return "DWCONV weights are not 16-byte aligned";
+      if (o.kind == CPX_GRAPH_DWCONV_Q8) {
+        if ((reinterpret_cast<uintptr_t>(o.weights) & 3)) return "DWCONV_Q8 weights are not 4-byte aligned";
+        if (!is_params(o.in1)) return "DWCONV_Q8 needs a 1 x 1 x 4 parameter tensor as in1";
+        if (!o.scale || !o.shift) return "DWCONV_Q8 without scale or shift";
+      }
       if (o.kind == CPX_GRAPH_CONV_Q8) {
         if (!is_params(o.in1)) return "CONV_Q8 needs a 1 x 1 x 4 parameter tensor as in1";
         if (!o.scale || !o.shift) return "CONV_Q8 without scale or shift";

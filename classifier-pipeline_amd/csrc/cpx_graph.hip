@@ -334,6 +334,10 @@ void launch_graph_op(const GraphOpArgs& a, hipStream_t s) {
     case CPX_GRAPH_QUANT_PARAMS:
       launch_graph_q8_op(a, s);
       break;
+    case CPX_GRAPH_DWCONV:
+    case CPX_GRAPH_DWCONV_Q8:
+      launch_graph_dw_op(a, s);
+      break;
     default:
       break;
   }

@@ -823,16 +823,27 @@ enum {
   CPX_GRAPH_FC_Q8 = 13,      /* FULLY_CONNECTED with an int8 filter on a 1 x 1 x C input.  in1 as CONV_Q8.  `weights` as
                                 bytes: int8 [Cout][Cin rounded up to 4] (zeros beyond), then int32 wsum[Cout].  scale,
                                 shift: [Cout], not NULL */
-  CPX_GRAPH_QUANT_PARAMS = 14/* in0 (its own channels only) -> out, a 1 x 1 x 4 tensor [sx, inv, zp, 0] per sample;
+  CPX_GRAPH_QUANT_PARAMS = 14,/* in0 (its own channels only) -> out, a 1 x 1 x 4 tensor [sx, inv, zp, 0] per sample;
                                 param 0: asymmetric, param 1: symmetric */
+  CPX_GRAPH_DWCONV = 15,     /* DEPTHWISE_CONV_2D, depth multiplier 1 (input C = output C), kernel sides 1 to 7, strides 1
+                                or 2.  `weights` (16-byte aligned): float32 [kh * kw][C rounded up to 4], zeros beyond.
+                                out = act(acc * scale[c] + shift[c]), NULL scale / shift as for CONV.  acc is the chain
+                                acc = fmaf(x, w, acc) over the taps in raster order (ky outer, kx inner) starting from 0;
+                                a padded tap contributes nothing.  It is the same chain wherever the pixel sits in a
+                                tile, a sample or a batch, and whichever instantiation (16-byte or channel by channel)
+                                runs it */
+  CPX_GRAPH_DWCONV_Q8 = 16   /* DEPTHWISE_CONV_2D with an int8 filter.  in1 as CONV_Q8.  `weights` as bytes: int8
+                                [kh * kw][C rounded up to 4] (zeros beyond), then int32 wsum[C rounded up to 4], the
+                                filter summed over its taps.  q, acc and out as CONV_Q8 below, with K = the taps (a
+                                padded tap is q = zp).  scale, shift: [C], not NULL */
 };
 /* The hybrid arithmetic, per sample.  QUANT_PARAMS: rmin = min(0, min x), rmax = max(0, max x) in float32.
  * rmin == rmax: sx = inv = 1, zp = 0.  Otherwise, in float64 from those two values: s = (rmax - rmin) / 255,
  * a = -128 - rmin / s, b = 127 - rmax / s, z = a if 128 + |rmin / s| < 127 + |rmax / s| else b,
  * zp = clamp(round-half-away(z), -128, 127), sx = float32(s), inv = float32(1 / s).  Symmetric (param 1): m = max |x|,
  * zp = 0, sx = float32(m / 127), inv = float32(127 / m) in float64; m == 0: sx = inv = 1.
- * CONV_Q8 / FC_Q8: q = clamp(round-half-away(float32(x * inv)) + zp, -128, 127); a padded tap is q = zp (a real 0);
- * acc = sum q * w in int32 (the caller keeps kh * kw * Cin * 127 * 255 below 2^31);
+ * CONV_Q8 / FC_Q8 / DWCONV_Q8: q = clamp(round-half-away(float32(x * inv)) + zp, -128, 127); a padded tap is q = zp (a real 0);
+ * acc = sum q * w in int32 (the caller keeps kh * kw * Cin * 127 * 255 below 2^31; DWCONV_Q8 sums kh * kw products);
  * out = act(float32(acc - zp * wsum[c]) * float32(sx * scale[c]) + shift[c]), each operation in float32 as written. */
 enum { CPX_GRAPH_ACT_NONE = 0, CPX_GRAPH_ACT_RELU = 1, CPX_GRAPH_ACT_RELU6 = 3 }; /* TFLite's ActivationFunctionType */
 
@@ -852,7 +863,7 @@ typedef struct cpx_graph_op {
   int32_t out_c_offset, out_c_stride; /* where the output goes: the channel slice of tensors[out] */
   int32_t n_map, channel_map[4];
   float param;
-  const float* weights; /* device pointers, owned by the caller, alive as long as the graph (CONV_Q8 / FC_Q8: bytes) */
+  const float* weights; /* device pointers, owned by the caller, alive as long as the graph (the Q8 kinds: bytes) */
   const float* scale;
   const float* shift;
 } cpx_graph_op;

@@ -1,0 +1,550 @@
+"""DEPTHWISE_CONV_2D of the TFLite graph executor (CPX_GRAPH_DWCONV / DWCONV_Q8, csrc/cpx_graph_dw.hip) on the GPU: the
+float32 operator against the float64 evaluation of the same flatbuffer, the hybrid one against the NumPy restatement of
+its arithmetic, bit for bit (tests/tflite_eval_dw.py, which reads the Graph only).  The flatbuffers are synthetic
+(tests/tflite_build_dw.py); parity with the TFLite runtime on a depthwise operator, float32 or hybrid, is not pinned
+here -- the standing the other operators have (test_tflite_graph_gpu.py::test_released_model_parity is the route where
+the runtime exists)."""
+import json
+import os
+import shutil
+import zlib
+
+import numpy as np
+import pytest
+
+import tflite_build as tb
+import tflite_build_dw as td
+import tflite_eval_dw as ted
+from test_tflite_graph_gpu import CONV_REL, LABELS17, LOGIT_MULTIPLE, samples
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def engine():
+    from cpx.engine import TrackEngine
+
+    eng = TrackEngine(model="lepton3", device=0)
+    yield eng
+    eng.close()
+
+
+def run(engine, blob, x, output=None, quantised_math="hybrid"):
+    import torch
+
+    from cpx.ml_tools.tflite_graph import GraphDevice, build_plan
+    from cpx.ml_tools.tflite_reader import Graph
+
+    g = Graph(blob)
+    plan = build_plan(g, input_shape=x.shape[1:], output=output, quantised_math=quantised_math)
+    dev = GraphDevice(engine, plan)
+    out = dev.forward(torch.from_numpy(np.ascontiguousarray(x)).to(engine.device)).cpu().numpy()
+    dev.close()
+    return g, plan, out
+
+
+def kinds(plan):
+    from cpx import _lib
+
+    names = {_lib.GRAPH_DWCONV: "DWCONV", _lib.GRAPH_DWCONV_Q8: "DWCONV_Q8", _lib.GRAPH_CONV_Q8: "CONV_Q8", _lib.GRAPH_FC_Q8: "FC_Q8",
+             _lib.GRAPH_QUANT_PARAMS: "QUANT_PARAMS"}
+    return [names.get(o.kind, o.name) for o in plan.ops]
+
+
+def dw_weights(rng, kh, kw, c):
+    return (rng.normal(0, np.sqrt(2.0 / (kh * kw)), size=(1, kh, kw, c)).astype(np.float32),
+            rng.normal(0, 0.05, size=c).astype(np.float32))
+
+
+def one_dw(rng, kh, kw, stride, padding, c, size, act=tb.NONE, pad=None):
+    m = td.ModelDW()
+    x = m.tensor([1, size, size, c], name="input")
+    m.inputs = [x]
+    w, b = dw_weights(rng, kh, kw, c)
+    if pad is not None:
+        x = m.pad(x, pad)
+    m.outputs = [m.depthwise(x, w, b, stride, padding, act)]
+    return m.finish()
+
+
+def case_id(c):
+    return "%dx%d_s%d_%s_c%d_at%d" % (c[0], c[1], c[2], "SV"[c[3]], c[4], c[5])
+
+
+def case_seed(c):
+    return c[0] * 100 + c[1] * 10 + c[2] + c[4] + c[5]
+
+
+# ---- 1. float32 against float64 ----
+FLOAT_CASES = [
+    # kh, kw, stride, padding, C, size
+    (3, 3, 1, tb.SAME, 32, 17),
+    (3, 3, 2, tb.SAME, 144, 16),    # even size: one-sided surplus pad
+    (3, 3, 2, tb.VALID, 96, 17),
+    (3, 3, 1, tb.SAME, 3, 7),       # the channel-by-channel path
+    (3, 3, 1, tb.SAME, 30, 5),      # C is no multiple of 4
+    (3, 3, 1, tb.SAME, 4, 2),       # the map is smaller than the kernel: every tap row is masked somewhere
+    (5, 5, 1, tb.SAME, 36, 9),
+    (5, 5, 2, tb.SAME, 8, 8),
+    (7, 7, 1, tb.SAME, 12, 10),
+    (1, 7, 1, tb.SAME, 20, 9),
+    (7, 1, 2, tb.VALID, 20, 9),
+    (1, 1, 1, tb.VALID, 64, 3),
+]
+
+
+def check_float(g, got, x, what):
+    vals, mag = ted.evaluate(g, x, magnitudes=True)
+    t = g.outputs[0]
+    assert got.shape == vals[t].shape
+    rel = float((np.abs(got - vals[t]) / mag[t]).max())
+    print("%s: max |error| / sum |x||w| = %.3g" % (what, rel))
+    assert rel < CONV_REL, rel
+
+
+@pytest.mark.parametrize("case", FLOAT_CASES, ids=case_id)
+def test_depthwise_against_float64(engine, case):
+    kh, kw, stride, padding, c, size = case
+    rng = np.random.default_rng(case_seed(case))
+    blob = one_dw(rng, kh, kw, stride, padding, c, size)
+    x = rng.uniform(-1, 1, size=(2, size, size, c)).astype(np.float32)
+    g, plan, got = run(engine, blob, x)
+    assert kinds(plan) == ["DWCONV"]
+    check_float(g, got, x, str(case))
+
+
+# ---- 2. hybrid against the restatement, bit for bit ----
+def three_samples(rng, size, c):
+    """One sample all positive (zp = -128: a padded tap staged as 0 instead of zp shows at every border), one all negative
+    (zp = 127), one mixed."""
+    return np.stack([rng.uniform(1, 5, size=(size, size, c)), rng.uniform(-4, -0.5, size=(size, size, c)),
+                     rng.uniform(-2, 3, size=(size, size, c))]).astype(np.float32)
+
+
+HYBRID_CASES = [
+    # kh, kw, stride, padding, C, size, one scale per channel
+    (3, 3, 1, tb.SAME, 144, 9, True),
+    (3, 3, 2, tb.SAME, 160, 8, True),
+    (5, 5, 1, tb.SAME, 52, 7, False),   # one scale for the whole filter
+    (3, 3, 1, tb.SAME, 30, 5, True),    # 270 elements: the converter would leave it float32; forced INT8
+    (3, 3, 2, tb.VALID, 6, 9, True),
+]
+
+
+def check_hybrid(g, got, x, what):
+    vals, _ = ted.evaluate_hybrid(g, x)
+    want = vals[g.outputs[0]]
+    assert got.shape == want.shape and got.dtype == want.dtype == np.float32
+    print("%s: %d of %d elements differ from the restatement" % (what, int((got != want).sum()), got.size))
+    assert np.array_equal(got, want)
+    return want
+
+
+@pytest.mark.parametrize("case", HYBRID_CASES, ids=case_id)
+def test_hybrid_depthwise_against_the_restatement(engine, case):
+    from tflite_eval_q8 import quant_params
+
+    kh, kw, stride, padding, c, size, per_channel = case
+    rng = np.random.default_rng(case_seed(case))
+    blob = td.quantise(one_dw(rng, kh, kw, stride, padding, c, size), min_elements=0, dw_per_channel=per_channel)
+    x = three_samples(rng, size, c)
+    g, plan, got = run(engine, blob, x)
+    assert kinds(plan) == ["QUANT_PARAMS", "DWCONV_Q8"]
+    ten = g.quantised_filter(g.ops[0])
+    assert ten["quant"]["scale"].size == (c if per_channel else 1) and ten["quant"]["dim"] == 3
+    _, _, zp = quant_params(x)
+    assert zp[0] == -128 and zp[1] == 127 and -128 < zp[2] < 127
+    want = check_hybrid(g, got, x, str(case))
+    assert float(np.abs(want[0]).max()) > 0.1
+
+
+# ---- 3. PAD ((0, 1), (0, 1)) + VALID at stride 2: MobileNetV2's form ----
+MNV2_PAD = [[0, 0], [0, 1], [0, 1], [0, 0]]
+
+
+def test_pad_then_valid_stride_2(engine):
+    rng = np.random.default_rng(33)
+    blob = one_dw(rng, 3, 3, 2, tb.VALID, 96, 16, pad=MNV2_PAD)
+    x = rng.uniform(-1, 1, size=(2, 16, 16, 96)).astype(np.float32)
+    g, plan, got = run(engine, blob, x)
+    assert kinds(plan) == ["PAD", "DWCONV"] and got.shape == (2, 8, 8, 96)
+    check_float(g, got, x, "pad + valid")
+    # quantised: the padded zeros are real zeros, quantised to zp with everything else
+    xq = three_samples(rng, 16, 96)
+    gq, plan, got = run(engine, td.quantise(blob, min_elements=0), xq)
+    assert kinds(plan) == ["PAD", "QUANT_PARAMS", "DWCONV_Q8"]
+    check_hybrid(gq, got, xq, "pad + valid, hybrid")
+
+
+# ---- 4. the two instantiations agree bit for bit ----
+def sliced_twin(rng, w, b, c, size):
+    """The depthwise convolution of one_dw reading a slice at channel 3 of one concatenation and writing a slice at channel
+    5 of another; MUL by ones copies exactly, so the operator sees the dense graph's values."""
+    m = td.ModelDW()
+    x = m.tensor([1, size, size, c], name="input")
+    m.inputs = [x]
+    ones = np.ones(c, np.float32)
+
+    def conv(co):
+        return m.conv(x, rng.normal(0, 0.3, size=(co, 1, 1, c)).astype(np.float32), np.zeros(co, np.float32), 1, tb.SAME, tb.NONE)
+
+    q = m.binary("MUL", x, ones)
+    m.concat([conv(3), q])
+    d = m.depthwise(q, w, b, 1, tb.SAME, tb.RELU6)
+    m.outputs = [m.binary("MUL", m.concat([conv(5), d]), np.ones(5 + c, np.float32))]
+    return m, q, d
+
+
+@pytest.mark.parametrize("hybrid", [False, True], ids=["float32", "hybrid"])
+def test_the_two_instantiations_agree_bit_for_bit(engine, hybrid):
+    rng = np.random.default_rng(44)
+    c, size = 24, 9
+    w, b = dw_weights(rng, 3, 3, c)
+    m = td.ModelDW()
+    x = m.tensor([1, size, size, c], name="input")
+    m.inputs = [x]
+    m.outputs = [m.depthwise(x, w, b, 1, tb.SAME, tb.RELU6)]
+    dense = m.finish()
+    m, q, d = sliced_twin(rng, w, b, c, size)
+    sliced = m.finish()
+    if hybrid:
+        # the depthwise filter alone: the 1 x 1 convolutions beside it stay float32
+        dense, sliced = (td.quantise(blob, min_elements=9 * c) for blob in (dense, sliced))
+    xs = three_samples(rng, size, c)
+    _, plan_d, got_d = run(engine, dense, xs)
+    _, plan_s, got_s = run(engine, sliced, xs)
+    want_kind = "DWCONV_Q8" if hybrid else "DWCONV"
+    assert kinds(plan_d).count(want_kind) == kinds(plan_s).count(want_kind) == 1 and not plan_s.copies()
+    tq_, td_ = plan_s.tensors[q], plan_s.tensors[d]
+    assert (tq_.c_offset, tq_.c_stride) == (3, 3 + c) and (td_.c_offset, td_.c_stride) == (5, 5 + c)   # no multiples of 4
+    assert got_s.shape == (3, size, size, 5 + c)
+    assert np.array_equal(got_s[..., 5:], got_d) and float(got_d.max()) == 6.0 and float(got_d.min()) == 0.0
+
+
+# ---- 5. channel-sliced stores leave the neighbours alone ----
+@pytest.mark.parametrize("dw_first", [True, False])
+def test_channel_sliced_stores_leave_the_neighbours_alone(engine, dw_first):
+    """A depthwise convolution, a CONV_2D and a pool write their slices of one concatenated tensor; whichever runs last
+    would destroy the others' channels if it stored outside its slice."""
+    rng = np.random.default_rng(9)
+    m = td.ModelDW()
+    x = m.tensor([1, 11, 11, 20], name="input")
+    m.inputs = [x]
+    w, b = dw_weights(rng, 3, 3, 20)
+
+    def dw():
+        return m.depthwise(x, w, b, 1, tb.SAME, tb.RELU)
+
+    d = dw() if dw_first else None
+    c = m.conv(x, rng.normal(0, 0.1, size=(12, 3, 3, 20)).astype(np.float32), rng.normal(0, 0.05, size=12).astype(np.float32),
+               1, tb.SAME, tb.RELU)
+    p = m.pool("MAX_POOL_2D", x, 3, 1, tb.SAME)
+    if d is None:
+        d = dw()
+    m.outputs = [m.unary("RELU6", m.concat([c, d, p]))]
+    xs = rng.uniform(-2, 8, size=(3, 11, 11, 20)).astype(np.float32)
+    g, plan, got = run(engine, m.finish(), xs)
+    assert not plan.copies() and (kinds(plan)[0] == "DWCONV") == dw_first
+    want = ted.evaluate(g, xs)[g.outputs[0]]
+    assert got.shape == want.shape == (3, 11, 11, 52)
+    assert float(np.abs(got - want).max()) < 2e-5
+
+
+@pytest.mark.parametrize("off,extra", [(8, 4), (7, 38)], ids=["quads", "channel_by_channel"])
+@pytest.mark.parametrize("hybrid", [False, True], ids=["float32", "hybrid"])
+def test_sliced_store_leaves_a_sentinel_buffer_untouched(engine, hybrid, off, extra):
+    """The output straight into a channel slice of a buffer filled with a sentinel: a slice at channel 8 of rows of
+    off + C + 4 channels keeps the 16-byte stores, one at channel 7 takes the other instantiation."""
+    import torch
+
+    from cpx.ml_tools.tflite_graph import GraphDevice, build_plan
+    from cpx.ml_tools.tflite_reader import Graph
+
+    rng = np.random.default_rng(31)
+    c, size = 20, 9
+    blob = one_dw(rng, 3, 3, 2, tb.SAME, c, size, act=tb.RELU)
+    if hybrid:
+        blob = td.quantise(blob, min_elements=0)
+    g = Graph(blob)
+    xs = three_samples(rng, size, c)
+    if hybrid:
+        want = ted.evaluate_hybrid(g, xs)[0][g.outputs[0]]
+    else:
+        vals, mag = ted.evaluate(g, xs, magnitudes=True)
+        want, mag = vals[g.outputs[0]], mag[g.outputs[0]]
+    stride = off + c + extra
+    dev = GraphDevice(engine, build_plan(g), out_slice=(off, stride))
+    sentinel = np.float32(-12345.678)
+    out = torch.full((3, want.shape[1], want.shape[2], stride), float(sentinel), dtype=torch.float32, device=engine.device)
+    dev.forward(torch.from_numpy(xs).to(engine.device), out=out)
+    got = out.cpu().numpy()
+    dev.close()
+    if hybrid:
+        assert np.array_equal(got[..., off:off + c], want)
+    else:
+        assert float((np.abs(got[..., off:off + c] - want) / mag).max()) < CONV_REL
+    assert np.all(got[..., :off] == sentinel) and np.all(got[..., off + c:] == sentinel)
+
+
+# ---- 6. batch does not matter ----
+@pytest.mark.parametrize("hybrid", [False, True], ids=["float32", "hybrid"])
+def test_batch_does_not_matter(engine, hybrid):
+    rng = np.random.default_rng(66)
+    blob = one_dw(rng, 3, 3, 1, tb.SAME, 36, 7, act=tb.RELU)   # 7 x 7 = 49 pixels: runs and workgroups cross samples
+    if hybrid:
+        blob = td.quantise(blob, min_elements=0)
+    x = rng.uniform(-2, 3, size=(1, 7, 7, 36)).astype(np.float32)
+    _, _, one = run(engine, blob, x)
+    _, _, five = run(engine, blob, np.repeat(x, 5, axis=0))
+    assert all(np.array_equal(five[k], one[0]) for k in range(5)) and float(np.abs(one).max()) > 0.1
+
+
+# ---- 7. fused RELU6 and the folded MUL + ADD ----
+@pytest.mark.parametrize("act", [tb.RELU, tb.RELU6])
+def test_activation_and_folded_affine(engine, act):
+    rng = np.random.default_rng(5 + act)
+    m = td.ModelDW()
+    x = m.tensor([1, 9, 9, 24], name="input")
+    m.inputs = [x]
+    w, b = dw_weights(rng, 3, 3, 24)
+    y = m.depthwise(x, w, b, 1, tb.SAME, tb.NONE)
+    y = m.binary("MUL", y, rng.uniform(0.5, 2.0, size=24).astype(np.float32))
+    m.outputs = [m.binary("ADD", y, rng.normal(0, 1.0, size=24).astype(np.float32), act)]
+    xs = rng.uniform(-3, 3, size=(2, 9, 9, 24)).astype(np.float32)
+    g, plan, got = run(engine, m.finish(), xs)
+    assert [o.name for o in plan.ops] == ["DEPTHWISE_CONV_2D+MUL+ADD"]
+    want = ted.evaluate(g, xs)[g.outputs[0]]
+    assert float(want.min()) == 0.0 and (act != tb.RELU6 or float(want.max()) == 6.0)   # the inputs reach the clamps
+    assert float(np.abs(got - want).max()) < 2e-5
+    # the same operator with RELU6 fused and nothing folded
+    blob = one_dw(rng, 3, 3, 1, tb.SAME, 24, 9, act=tb.RELU6)
+    xs = rng.uniform(-6, 6, size=(2, 9, 9, 24)).astype(np.float32)
+    g, plan, got = run(engine, blob, xs)
+    want = ted.evaluate(g, xs)[g.outputs[0]]
+    assert float(want.min()) == 0.0 and float(want.max()) == 6.0 and float(np.abs(got - want).max()) < 2e-5
+
+
+# ---- 8. the whole network ----
+# Seed and head_gain are chosen so that the float64 logits alone meet spread >= 100 x tolerance (checked on the CPU).
+# Measured on an MI355X (width 1.0, 160 x 160 x 3, N = 3): float32 on the CPU deviates from float64 by 5.92e-5 on the
+# logits, the device by 6.12e-5 -- ratio 1.03; the logits spread by 4.22.
+MNV2_SEED, MNV2_HEAD_GAIN = 7, 4.0
+
+
+def test_mobilenet_v2_whole_network(engine):
+    """The method of test_tflite_graph_gpu.py::test_inception_v3_whole_network: the device may deviate from float64 by
+    LOGIT_MULTIPLE times what a float32 evaluation of the same graph on the CPU does."""
+    import torch
+
+    from cpx.ml_tools.tflite_reader import Graph
+
+    blob = td.mobilenet_v2(17, (), seed=MNV2_SEED, width=1.0, head_gain=MNV2_HEAD_GAIN)
+    x = samples(3, 160, seed=11)
+    g = Graph(blob)
+    logits_t = g.ops[-1]["inputs"][0]
+    v64 = ted.evaluate(g, x)
+    v32 = ted.evaluate(g, x, dtype=torch.float32)
+    yard = float(np.abs(v32[logits_t] - v64[logits_t]).max())
+    tol = LOGIT_MULTIPLE * yard
+    _, plan, logits = run(engine, blob, x, output=logits_t)
+    assert kinds(plan).count("DWCONV") == 17
+    _, _, probs = run(engine, blob, x)
+    err = float(np.abs(logits - v64[logits_t]).max())
+    spread = min(float(np.ptp(v64[logits_t], axis=1).min()), float(np.ptp(v64[logits_t], axis=0).max()))
+    print("float32-CPU vs float64: %.3g; device vs float64: %.3g (ratio %.2f); spread of the logits %.3g"
+          % (yard, err, err / yard, spread))
+    assert spread >= 100 * tol, (spread, tol)
+    assert err <= tol, (err, yard)
+    assert float(np.abs(probs - v64[g.outputs[0]]).max()) <= 1e-3
+
+
+def test_quantised_mobilenet_v2_whole_network(engine):
+    """Width 0.5.  The hybrid forward against the restatement chained operator by operator, bit for bit; the float math
+    against the float64 evaluation of the dequantised graph, by the yardstick of the test above.  Measured on an MI355X:
+    0 of 51 logits differ; float math 4.48e-5 from float64 on the device and on the CPU (ratio 1.00), spread 4.5."""
+    import torch
+
+    from cpx.ml_tools.tflite_reader import Graph
+
+    blob = td.quantise(td.mobilenet_v2(17, (), seed=MNV2_SEED, width=0.5, head_gain=MNV2_HEAD_GAIN))
+    x = samples(3, 160, seed=11)
+    g = Graph(blob)
+    logits_t = g.ops[-1]["inputs"][0]
+    hyb, _ = ted.evaluate_hybrid(g, x)
+    _, plan, logits = run(engine, blob, x, output=logits_t)
+    n_dw = sum(op["name"] == "DEPTHWISE_CONV_2D" and g.quantised_filter(op) is not None for op in g.ops)
+    # at width 0.5 the depthwise filters of 1024 elements or more (9 x C, C >= 114) are the ten of 192, 288 and 480 channels
+    assert kinds(plan).count("DWCONV_Q8") == n_dw == 10 and kinds(plan).count("DWCONV") == 7
+    dev = float(np.abs(logits - hyb[logits_t]).max())
+    print("device vs hybrid restatement: %.4g (%d of %d logits differ)" % (dev, int((logits != hyb[logits_t]).sum()), logits.size))
+    assert np.array_equal(logits, hyb[logits_t])
+    deq64 = ted.evaluate_dequantised(g, x)
+    deq32 = ted.evaluate_dequantised(g, x, dtype=torch.float32)
+    yard = float(np.abs(deq32[logits_t] - deq64[logits_t]).max())
+    _, fplan, flogits = run(engine, blob, x, output=logits_t, quantised_math="float")
+    assert "DWCONV_Q8" not in kinds(fplan) and "QUANT_PARAMS" not in kinds(fplan) and kinds(fplan).count("DWCONV") == 17
+    err = float(np.abs(flogits - deq64[logits_t]).max())
+    spread = min(float(np.ptp(deq64[logits_t], axis=1).min()), float(np.ptp(deq64[logits_t], axis=0).max()))
+    print("float math: float32-CPU vs float64 %.3g; device vs float64 %.3g (ratio %.2f); spread of the logits %.3g; hybrid vs "
+          "float64 of the dequantised graph %.3g" % (yard, err, err / yard, spread, float(np.abs(hyb[logits_t] - deq64[logits_t]).max())))
+    assert spread >= 100 * LOGIT_MULTIPLE * yard and err <= LOGIT_MULTIPLE * yard, (err, yard, spread)
+
+
+# ---- 9. through the public interface ----
+@pytest.fixture(scope="module")
+def mobilenet_models(tmp_path_factory):
+    """A width-0.25 MobileNetV2 file and its quantised twin + sidecars: three input channels fed from the two-channel
+    sample by the channel map, the `tf` input scaling by the model name."""
+    from helpers import GOLDEN
+
+    d = tmp_path_factory.mktemp("mnv2")
+    with open(os.path.join(GOLDEN, "classify_variants_golden.json")) as fh:
+        golden = json.load(fh)
+    assert golden["labels"] == LABELS17
+    hp = {"frame_size": 32, "model_name": "mobilenet", "channels": ["thermal", "thermal", "filtered"]}
+    blobs = {"mnv2": td.mobilenet_v2(len(LABELS17), (), seed=13, width=0.25, head_gain=4.0)}
+    blobs["mnv2q8"] = td.quantise(blobs["mnv2"])
+    for name, blob in blobs.items():
+        (d / (name + ".tflite")).write_bytes(blob)
+        with open(d / (name + ".json"), "w") as fh:
+            json.dump({"labels": LABELS17, "hyperparams": hp, "type": "thermal", "version": "test"}, fh)
+    return d, blobs, golden["variants"]["inceptionv3_scaling"]
+
+
+def hybrid_operators_exact(engine, blob, x):
+    """Every hybrid operator of the graph on the device's own activations: its output (a forward cut off behind it) equals
+    the restatement of that one operator applied to its input (a forward cut off in front of it), bit for bit."""
+    import tflite_eval_q8 as tq8
+    from cpx.ml_tools.tflite_reader import Graph
+
+    g = Graph(blob)
+    fns = {"CONV_2D": tq8.hybrid_conv, "FULLY_CONNECTED": tq8.hybrid_fc, "DEPTHWISE_CONV_2D": ted.hybrid_depthwise}
+    checked = {}
+    for op in g.ops:
+        ten = g.quantised_filter(op)
+        if ten is None:
+            continue
+        ins = [t for t in op["inputs"] if t >= 0]
+        x_in = x if ins[0] == g.inputs[0] else run(engine, blob, x, output=ins[0])[2]
+        got = run(engine, blob, x, output=op["outputs"][0])[2]
+        want, _ = fns[op["name"]](op, x_in, ten, g.const(ins[2]) if len(ins) > 2 else None)
+        assert np.array_equal(got.reshape(want.shape), want), (op["name"], int((got.reshape(want.shape) != want).sum()))
+        checked[op["name"]] = checked.get(op["name"], 0) + 1
+    print("hybrid operators equal to their restatement on the device's own inputs: %s" % checked)
+    assert checked.get("DEPTHWISE_CONV_2D", 0) > 0 and checked.get("CONV_2D", 0) > 0
+    return checked
+
+
+@pytest.mark.parametrize("name,mode", [("mnv2", None), ("mnv2q8", "hybrid"), ("mnv2q8", "float")],
+                         ids=["float32", "quantised_hybrid", "quantised_float_math"])
+def test_clip_classifier_with_a_mobilenet(tmp_path, monkeypatch, engine, mobilenet_models, name, mode):
+    """test_tflite_graph_gpu.py::test_clip_classifier_with_a_lite_interpreter with a MobileNetV2: the possum fixture
+    tracked, then classified by ClipClassifier's one-file path.  The network inputs are the reference's (`inceptionv3_scaling`
+    of tests/golden/classify_variants_golden.json: the same `tf` scaling), the predictions the evaluator's on those inputs
+    at 1e-3: float64 for the float32 file, the hybrid restatement or the float64 evaluation of the dequantised graph for
+    the quantised one, by CPX_TFLITE_QUANT_MATH."""
+    import classify_oracle as co
+    from helpers import GOLDEN
+    from cpx import _lib
+    from cpx.classify.clipclassifier import ClipClassifier
+    from cpx.config import Config
+    from cpx.config.config import ModelConfig
+    from cpx.ml_tools.interpreter import LiteInterpreter, get_interpreter
+    from cpx.ml_tools.tflite_reader import Graph
+    from cpx.track.trackextractor import extract_file
+
+    d, blobs, gold = mobilenet_models
+    g = Graph(blobs[name])
+    if mode is None:
+        monkeypatch.delenv("CPX_TFLITE_QUANT_MATH", raising=False)
+    else:
+        monkeypatch.setenv("CPX_TFLITE_QUANT_MATH", mode)
+    cfg = Config.get_defaults()
+    cfg.tracking["thermal"].denoise = False
+    cfg.classify.models = [ModelConfig.load({"id": 9, "name": name, "model_file": str(d / (name + ".tflite"))})]
+    src = tmp_path / "possum.cptv"
+    shutil.copy(os.path.join(GOLDEN, "possum.cptv"), src)
+    clip, _, _ = extract_file(src, cfg, False, save_meta=False)
+
+    def evaluator_probs(x2):
+        x3 = np.ascontiguousarray(x2[..., [0, 0, 1]])
+        if mode == "hybrid":
+            return ted.evaluate_hybrid(g, x3)[0][g.outputs[0]].astype(np.float64)
+        return (ted.evaluate(g, x3) if mode is None else ted.evaluate_dequantised(g, x3))[g.outputs[0]]
+
+    interp = get_interpreter(cfg.classify.models[0])
+    assert isinstance(interp, LiteInterpreter) and interp.limits_flags() & _lib.LIMITS_TF_SCALING
+    plan = next(iter(interp._plans.values()))
+    n_q8 = sum(o.kind == _lib.GRAPH_DWCONV_Q8 for o in plan.ops)
+    assert n_q8 + sum(o.kind == _lib.GRAPH_DWCONV for o in plan.ops) == 17 and (n_q8 > 0) == (mode == "hybrid")
+    seen = {}
+    device_predict = interp.predict
+
+    def predict(x):
+        seen["x"] = x.cpu().numpy()
+        return device_predict(x)
+
+    interp.predict = predict
+    assert len(clip.tracks) == len(gold["possum"]) > 0
+    for track, want in zip(clip.tracks, gold["possum"]):
+        assert track.get_id() == want["track_id"]
+        segs = [np.array(s) for s in want["segments"]]
+        pred = interp.classify_track(clip, track, segment_frames=segs)
+        x = seen["x"]
+        assert list(x.shape) == want["shape"]
+        assert [zlib.crc32(np.ascontiguousarray(s).tobytes()) & 0xFFFFFFFF for s in x] == want["crc"]
+        probs = evaluator_probs(x)
+        got = np.array([p.prediction for p in pred.predictions], dtype=np.float64)
+        assert got.shape == probs.shape and float(np.abs(got - probs).max()) <= 1e-3
+        assert float(np.ptp(probs, axis=1).min()) > 0.1     # the labels are told apart by far more than the tolerance
+        score = co.classified_track(probs, prediction_frames=segs, labels=LABELS17)
+        assert float(np.abs(np.array(pred.class_best_score) - score).max()) <= 1e-3
+    # ---- the one-file path: metadata JSON through the existing code ----
+    # What the network was given and what it answered is recorded, chunk by chunk; the metadata is held to the
+    # aggregation of those answers, and the inputs to the oracle chain's.  With float math the answers are held to the
+    # evaluator's on those very inputs at 1e-3.  The hybrid chain has no such bound on inputs of its own choosing: at
+    # width 0.25 only 28 of the 70 operators are hybrid (filters below 1024 elements stay float32), the device's differ from
+    # PyTorch-CPU's in the last bit, and a quantised operator behind them turns that into another q here and there.
+    # Evaluating those float32 operators in float64 and rounding -- as legitimate a float32 result -- moves the
+    # restatement's own probabilities by up to 0.04 on one sample in four (measured on the CPU); on this path the device
+    # was measured 0.0124 from the restatement.  What does hold exactly is checked instead: every hybrid operator's
+    # output equals the restatement of THAT operator on the device's own input, bit for bit (hybrid_operators_exact).
+    fed, answered = [], []
+    plain_predict = LiteInterpreter.predict
+
+    def recording_predict(self, x):
+        out = plain_predict(self, x)
+        fed.extend(x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x))
+        answered.extend(np.asarray(out, np.float64))
+        return out
+
+    monkeypatch.setattr(LiteInterpreter, "predict", recording_predict)
+    meta = ClipClassifier(cfg).process_file(str(src), track=True)
+    monkeypatch.setattr(LiteInterpreter, "predict", plain_predict)
+    assert meta and os.path.exists(src.with_suffix(".txt")) and meta["models"][0]["id"] == 9
+    H, W = clip.res_y, clip.res_x
+    assert len(meta["tracks"]) == len(clip.tracks)
+    for tm, track in zip(meta["tracks"], clip.tracks):
+        assert tm["id"] == track.get_id()
+        (pm,) = tm["predictions"]
+        assert pm["model_id"] == 9 and set(pm["all_class_confidences"]) == set(LABELS17)
+        segs = [np.array(p["frames"]) for p in pm["predictions"]]
+        by_frame = {r.frame_number: r for r in track.bounds_history}
+        x, _ = co.preprocess_segments(lambda q: clip.frame_buffer.get_frame(q).thermal,
+                                      lambda q: clip.frame_buffer.get_frame(q).filtered.astype(np.float64),
+                                      by_frame, track.bounds_history, segs, 32, (1, 1, W - 2, H - 2))
+        x = (np.asarray(x, np.float32) / np.float32(127.5) - np.float32(1.0)).astype(np.float32)
+        x_fed, fed = np.stack(fed[:len(segs)]), fed[len(segs):]
+        probs, answered = np.stack(answered[:len(segs)]), answered[len(segs):]
+        assert x_fed.shape == x.shape and float(np.abs(x_fed - x).max()) <= 1e-5
+        dev = float(np.abs(probs - evaluator_probs(x_fed)).max())
+        print("track %d: the one-file path's probabilities vs the evaluator's on its inputs: %.3g" % (tm["id"], dev))
+        if mode == "hybrid":
+            hybrid_operators_exact(engine, blobs[name], np.ascontiguousarray(x_fed[:5, ..., [0, 0, 1]]))
+        else:
+            assert dev <= 1e-3
+        score = co.classified_track(probs, prediction_frames=segs, labels=LABELS17)
+        got = np.array([pm["all_class_confidences"][l] for l in LABELS17])
+        assert np.abs(got - np.round(score, 3)).max() <= 1e-3 + 1e-9
+        assert pm["tag"] == LABELS17[int(np.argmax(score))]
+    assert not fed and not answered

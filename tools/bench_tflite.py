@@ -20,7 +20,15 @@ the share of the float32 matrix-pipe peak (157.3 TFLOP/s) that is.
 runs the same Inception-v3 three ways -- the float32 file, its dynamic-range quantised twin (tests/tflite_build_q8.py:
 INT8 filters) on the hybrid operators, and the twin with the filters multiplied out (quantised_math="float") -- and prints
 ms per forward for each, with the hybrid convolutions' algorithmic TOP/s against the int8 matrix-pipe roof (twice the
-BF16 rate: ~5000 TOP/s dense)."""
+BF16 rate: ~5000 TOP/s dense).
+
+    python tools/bench_tflite.py --mobilenet [--quantised] [--batches 1,8,32,128]
+
+times a width-1.0 MobileNetV2 (tests/tflite_build_dw.py) the same way against PyTorch-ROCm float32 and, for the largest
+batch, every depthwise launch alone (a one-operator graph of the same shape, HIP events): the bytes it must move -- input
+and output once, the weights -- over its time, against the HBM peak (8.0 TB/s; a float4 copy reaches 6.29).  With
+--quantised the hybrid twin (INT8 filters) is timed beside it.  --kernel-trace with --mobilenet splits a rocprofv3 trace
+of such a run by kind and gives the depthwise launches' bytes per second inside the forward."""
 import argparse
 import json
 import os
@@ -33,7 +41,10 @@ for p in (os.path.join(REPO, "classifier-pipeline_amd"), os.path.join(REPO, "tes
     sys.path.insert(0, p)
 
 KIND_NAMES = {1: "conv", 2: "max_pool", 3: "avg_pool", 4: "add", 5: "affine", 6: "mean", 7: "fc", 8: "logistic", 9: "softmax",
-              10: "pad", 11: "channel_map"}
+              10: "pad", 11: "channel_map", 12: "conv_q8", 13: "fc_q8", 14: "quant_params", 15: "dwconv", 16: "dwconv_q8"}
+DW_KINDS = (15, 16)
+HBM_PEAK_TBS = 8.0          # MI355X HBM3E, specification
+HBM_COPY_TBS = 6.29         # what a float4 copy kernel reaches
 
 
 def torch_model(g, device):
@@ -46,6 +57,8 @@ def torch_model(g, device):
     const = {i: torch.from_numpy(np.array(t["const"])).to(device) for i, t in enumerate(g.tensors)
              if t["const"] is not None and t["type"] == 0}
     wts = {i: c.permute(0, 3, 1, 2).contiguous() for i, c in const.items() if c.ndim == 4}
+    dw_wts = {op["inputs"][1]: const[op["inputs"][1]].permute(3, 0, 1, 2).contiguous() for op in g.ops
+              if op["name"] == "DEPTHWISE_CONV_2D"}   # [1, kh, kw, C] -> [C, 1, kh, kw]
 
     def forward(x_nchw):
         val = {g.inputs[0]: x_nchw}
@@ -59,6 +72,18 @@ def torch_model(g, device):
                 if pt or pb or pl or pr:
                     a = F.pad(a, (pl, pr, pt, pb))
                 r = _act(F.conv2d(a, wts[ins[1]], const[ins[2]], stride=(op["stride_h"], op["stride_w"])), op["act"])
+            elif name == "DEPTHWISE_CONV_2D":
+                w = dw_wts[ins[1]]
+                pt, pb = _pads(a.shape[2], w.shape[2], op["stride_h"], op["padding"])
+                pl, pr = _pads(a.shape[3], w.shape[3], op["stride_w"], op["padding"])
+                if pt or pb or pl or pr:
+                    a = F.pad(a, (pl, pr, pt, pb))
+                r = _act(F.conv2d(a, w, const[ins[2]], stride=(op["stride_h"], op["stride_w"]), groups=w.shape[0]), op["act"])
+            elif name == "PAD":
+                (_, _), (t0, t1), (l0, l1), (_, _) = op["paddings"]
+                r = F.pad(a, (l0, l1, t0, t1))
+            elif name == "ADD":
+                r = _act(a + val[ins[1]], op["act"])
             elif name in ("MAX_POOL_2D", "AVERAGE_POOL_2D"):
                 k, st = (op["filter_height"], op["filter_width"]), (op["stride_h"], op["stride_w"])
                 pt, pb = _pads(a.shape[2], k[0], st[0], op["padding"])
@@ -152,6 +177,109 @@ def quantised_leg(args):
     print(json.dumps(out))
 
 
+def dw_bytes(plan, o, n):
+    """What a depthwise launch must move for n samples: its input and its output once, its weights."""
+    t, i = plan.tensors[o.out], plan.tensors[o.in0]
+    return 4.0 * n * (i.H * i.W * i.C + t.H * t.W * t.C) + o.weights.nbytes
+
+
+def dw_shape(plan, o):
+    t, i = plan.tensors[o.out], plan.tensors[o.in0]
+    return "%dx%d s%d C%d %dx%d->%dx%d%s" % (o.kh, o.kw, o.stride_h, t.C, i.H, i.W, t.H, t.W, " q8" if o.kind == 16 else "")
+
+
+def mobilenet_leg(args):
+    """ms per forward of a MobileNetV2 by batch size against PyTorch-ROCm float32; the depthwise launches alone."""
+    import ctypes as C
+
+    import tflite_build as tb
+    import tflite_build_dw as td
+    import torch
+    from cpx.engine import TrackEngine
+    from cpx.ml_tools.tflite_graph import GraphDevice, build_plan
+    from cpx.ml_tools.tflite_reader import Graph
+
+    blob = td.mobilenet_v2(17, (), seed=7, width=args.width)
+    g = Graph(blob)
+    plans = {"float32": build_plan(g)}
+    if args.quantised:
+        plans["hybrid"] = build_plan(Graph(td.quantise(blob)))
+    batches = [int(v) for v in args.batches.split(",")]
+    if args.kernel_trace:
+        name = "hybrid" if args.quantised else "float32"
+        print(json.dumps(dict(split_from_trace(args.kernel_trace, plans[name], batches[-1]), plan=name)))
+        return
+    torch.backends.cudnn.allow_tf32 = False
+    torch.backends.cuda.matmul.allow_tf32 = False
+    eng = TrackEngine(model="lepton3", device=0)
+    stream = torch.cuda.ExternalStream(eng.lib.cpx_stream(eng.h), device=eng.device)
+    ref = torch_model(g, eng.device)
+    out = {"model": "mobilenet_v2 width %.2f 160x160x3" % args.width, "arena_bytes_per_sample": plans["float32"].arena_bytes_per_sample,
+           "launches_by_kind": {}, "batches": []}
+    for o in plans["float32"].ops:
+        out["launches_by_kind"][KIND_NAMES[o.kind]] = out["launches_by_kind"].get(KIND_NAMES[o.kind], 0) + 1
+    rng = np.random.default_rng(0)
+
+    def forward_of(dev, x, y, n):
+        def forward():
+            rc = eng.lib.cpx_graph_forward(dev._graph, C.c_void_p(x.data_ptr()), n, C.c_void_p(y.data_ptr()))
+            assert rc == 0, eng._err()
+        return forward
+
+    for n in batches:
+        x = torch.from_numpy(rng.uniform(-1, 1, size=(n, 160, 160, 3)).astype(np.float32)).to(eng.device)
+        y = torch.empty((n, 17), dtype=torch.float32, device=eng.device)
+        rec = {"N": n}
+        for name, plan in plans.items():
+            dev = GraphDevice(eng, plan)
+            with torch.cuda.stream(stream):
+                rec[name + "_ms"] = timed(torch, forward_of(dev, x, y, n), args.steps, args.warmup)
+            if name == "float32" and not args.skip_torch:
+                x_nchw = x.permute(0, 3, 1, 2).contiguous()
+                with torch.no_grad():
+                    rec["torch_ms"] = timed(torch, lambda: ref(x_nchw), args.steps, args.warmup)
+                    forward_of(dev, x, y, n)()
+                    torch.cuda.synchronize()
+                    rec["max_abs_diff_vs_torch"] = float((ref(x_nchw) - y).abs().max())
+                rec["ratio_vs_torch"] = rec["torch_ms"] / rec["float32_ms"]
+            dev.close()
+        out["batches"].append(rec)
+    # every depthwise launch of the largest batch alone: a one-operator graph of its shape
+    n = batches[-1]
+    for name, plan in ({} if args.skip_alone else plans).items():
+        rows, total_b, total_ms = [], 0.0, 0.0
+        for o in plan.ops:
+            if o.kind not in DW_KINDS:
+                continue
+            i = plan.tensors[o.in0]
+            m = td.ModelDW()
+            xin = m.tensor([1, i.H, i.W, i.C], name="input")
+            m.inputs = [xin]
+            pad = tb.VALID if o.pads == (0, 0, 0, 0) else tb.SAME
+            m.outputs = [m.depthwise(xin, rng.normal(0, 0.5, size=(1, o.kh, o.kw, i.C)).astype(np.float32),
+                                     np.zeros(i.C, np.float32), (o.stride_h, o.stride_w), pad, o.act)]
+            one = build_plan(Graph(td.quantise(m.finish(), min_elements=0) if o.kind == 16 else m.finish()))
+            k = [p for p in one.ops if p.kind in DW_KINDS][0]
+            assert (k.kind, k.pads, one.output_shape) == (o.kind, o.pads, (plan.tensors[o.out].H, plan.tensors[o.out].W, i.C))
+            # (the hybrid one-operator graph also launches its QUANT_PARAMS, which reads the input once more: launches_timed = 2)
+            x = torch.from_numpy(rng.uniform(-1, 1, size=(n, i.H, i.W, i.C)).astype(np.float32)).to(eng.device)
+            y = torch.empty((n,) + one.output_shape, dtype=torch.float32, device=eng.device)
+            dev = GraphDevice(eng, one)
+            with torch.cuda.stream(stream):
+                ms = timed(torch, forward_of(dev, x, y, n), args.steps, args.warmup)
+            dev.close()
+            b = dw_bytes(one, k, n)
+            rows.append({"shape": dw_shape(one, k), "ms": ms, "mbytes": b / 1e6, "tb_per_s": b / ms / 1e9,
+                         "launches_timed": len(one.ops)})
+            total_b += b
+            total_ms += ms
+        out["depthwise_alone_" + name] = {"N": n, "launches": rows, "ms_sum": total_ms, "tb_per_s": total_b / total_ms / 1e9,
+                                          "share_of_hbm_peak": total_b / total_ms / 1e9 / HBM_PEAK_TBS,
+                                          "share_of_copy_rate": total_b / total_ms / 1e9 / HBM_COPY_TBS}
+    eng.close()
+    print(json.dumps(out))
+
+
 def split_from_trace(path, plan, n):
     """The last forward of a rocprofv3 kernel trace: its launches are the plan's operators in order."""
     import csv
@@ -161,14 +289,20 @@ def split_from_trace(path, plan, n):
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     rows = rows[-len(plan.ops):]
     assert len(rows) == len(plan.ops), "the trace holds no whole forward"
-    by_kind, shapes = {}, {}
+    by_kind, shapes, dws = {}, {}, {}
     for r, o in zip(rows, plan.ops):
         ns = int(r["End_Timestamp"]) - int(r["Start_Timestamp"])
-        assert ("conv" in r["Kernel_Name"]) == (o.kind == 1), (r["Kernel_Name"], o.name)
+        assert ("conv" in r["Kernel_Name"]) == (o.kind in (1, 12)) and ("graph_dw" in r["Kernel_Name"]) == (o.kind in DW_KINDS), \
+            (r["Kernel_Name"], o.name)
         k = by_kind.setdefault(KIND_NAMES[o.kind], {"launches": 0, "ms": 0.0})
         k["launches"] += 1
         k["ms"] += ns / 1e6
-        if o.kind == 1:
+        if o.kind in DW_KINDS:
+            d = dws.setdefault(dw_shape(plan, o), {"launches": 0, "ms": 0.0, "mbytes": 0.0})
+            d["launches"] += 1
+            d["ms"] += ns / 1e6
+            d["mbytes"] += dw_bytes(plan, o, n) / 1e6
+        if o.kind in (1, 12):
             t, i = plan.tensors[o.out], plan.tensors[o.in0]
             key = "%dx%d s%d %d->%d at %dx%d" % (o.kh, o.kw, o.stride_h, i.C, t.C, t.H, t.W)
             s = shapes.setdefault(key, {"launches": 0, "ms": 0.0, "gflop": 0.0})
@@ -178,10 +312,17 @@ def split_from_trace(path, plan, n):
     wall = (int(rows[-1]["End_Timestamp"]) - int(rows[0]["Start_Timestamp"])) / 1e6
     busy = sum(k["ms"] for k in by_kind.values())
     top = max(shapes, key=lambda k: shapes[k]["ms"])
-    conv = by_kind["conv"]
+    conv = {"ms": sum(by_kind[k]["ms"] for k in ("conv", "conv_q8") if k in by_kind)}
     conv_gflop = sum(s["gflop"] for s in shapes.values())
     tf = shapes[top]["gflop"] / shapes[top]["ms"]
-    return {"N": n, "forward_ms_first_start_to_last_end": wall, "kernel_ms_sum": busy, "gpu_busy_share": busy / wall,
+    dw = {}
+    if dws:
+        for d in dws.values():
+            d["tb_per_s"] = d["mbytes"] / d["ms"] / 1e3
+        dw_mb, dw_ms = sum(d["mbytes"] for d in dws.values()), sum(d["ms"] for d in dws.values())
+        dw = {"depthwise": {"launches": dws, "ms": dw_ms, "tb_per_s": dw_mb / dw_ms / 1e3,
+                            "share_of_hbm_peak": dw_mb / dw_ms / 1e3 / HBM_PEAK_TBS, "share_of_copy_rate": dw_mb / dw_ms / 1e3 / HBM_COPY_TBS}}
+    return {**dw, "N": n, "forward_ms_first_start_to_last_end": wall, "kernel_ms_sum": busy, "gpu_busy_share": busy / wall,
             "ms_by_kind": by_kind, "conv_tflops_while_running": conv_gflop / conv["ms"],
             "conv_matrix_pipe_share": conv_gflop / conv["ms"] / F32_MFMA_PEAK_TFLOPS,
             "dominant_conv": dict(shapes[top], shape=top, tflops=tf, matrix_pipe_share=tf / F32_MFMA_PEAK_TFLOPS)}
@@ -197,7 +338,13 @@ def main():
     ap.add_argument("--width", type=float, default=1.0)
     ap.add_argument("--quantised", action="store_true",
                     help="time the float32 file, its dynamic-range quantised twin (hybrid operators) and the twin in float math")
+    ap.add_argument("--mobilenet", action="store_true",
+                    help="time a MobileNetV2 (DEPTHWISE_CONV_2D) instead of the Inception-v3, and its depthwise launches alone")
+    ap.add_argument("--skip-alone", action="store_true",
+                    help="with --mobilenet: do not time the depthwise launches alone (for a run under a profiler: the trace ends with a forward)")
     args = ap.parse_args()
+    if args.mobilenet:
+        return mobilenet_leg(args)
     if args.quantised:
         return quantised_leg(args)
     import ctypes as C
