@@ -176,6 +176,34 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
             raise NotImplementedError("%s: %d products of an 8-bit activation and an INT8 weight could overflow the int32 "
                                       "accumulator" % (what, k))
 
+    def filter_op(i, op, what, x, y, ins):
+        """CONV_2D (filter OHWI) or DEPTHWISE_CONV_2D (filter [1, kh, kw, C]): the float32 operator, or the hybrid one on the
+        parameters of its input view where the filter has scales."""
+        dw = op["name"] == "DEPTHWISE_CONV_2D"
+        w, fscale = filter_of(op, ins[1])
+        kh, kw, depth = w.shape[1:]
+        co = depth if dw else w.shape[0]
+        if depth != x.C:
+            raise NotImplementedError(("%s: depth multiplier (filter depth %d, input depth %d), only 1 is run" if dw else
+                                       "%s: grouped convolution (filter depth %d, input depth %d)") % (what, depth, x.C))
+        sh, sw = op.get("stride_h", 1), op.get("stride_w", 1)
+        if not (1 <= kh <= 7 and 1 <= kw <= 7 and sh in (1, 2) and sw in (1, 2)):
+            raise NotImplementedError("%s: %d x %d kernel with strides %d, %d" % (what, kh, kw, sh, sw))
+        ho, pt, pb = window(x.H, kh, sh, op.get("padding", 0))
+        wo, pl, pr = window(x.W, kw, sw, op.get("padding", 0))
+        if ho < 1 or wo < 1:
+            raise NotImplementedError("%s: the %d x %d input is smaller than the kernel" % (what, x.H, x.W))
+        T[y] = PlanTensor(y, ho, wo, co)
+        bias = g.const(ins[2]) if len(ins) > 2 else None
+        kind, in1 = _lib.GRAPH_DWCONV if dw else _lib.GRAPH_CONV, -1
+        if fscale is not None:
+            if not dw:   # (a depthwise output sums kh * kw <= 49 products)
+                overflow_check(what, kh * kw * depth)
+            kind, in1 = _lib.GRAPH_DWCONV_Q8 if dw else _lib.GRAPH_CONV_Q8, params_of(x, False, i)
+        emit(PlanOp(kind, op["name"], x.id, y, in1=in1, kh=kh, kw=kw, stride_h=sh, stride_w=sw, pads=(pt, pl, pb, pr),
+                    act=op.get("act", 0), filter=w, scale=None, filter_scale=fscale,
+                    shift=np.zeros(co, np.float32) if bias is None else np.asarray(bias, np.float32).reshape(-1)), i)
+
     for i, op in enumerate(g.ops):
         name = op["name"]
         what = "operator %d (%s)" % (i, name)
@@ -188,47 +216,8 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
         x = T[act_ins[0]] if act_ins else None
         if op.get("act", 0) not in (ACT_NONE, ACT_RELU, ACT_RELU6):
             raise NotImplementedError("%s: fused activation %d" % (what, op["act"]))
-        if name == "CONV_2D":
-            w, fscale = filter_of(op, ins[1])
-            co, kh, kw, ci = w.shape
-            if ci != x.C:
-                raise NotImplementedError("%s: grouped convolution (filter depth %d, input depth %d)" % (what, ci, x.C))
-            sh, sw = op.get("stride_h", 1), op.get("stride_w", 1)
-            if not (1 <= kh <= 7 and 1 <= kw <= 7 and sh in (1, 2) and sw in (1, 2)):
-                raise NotImplementedError("%s: %d x %d kernel with strides %d, %d" % (what, kh, kw, sh, sw))
-            ho, pt, pb = window(x.H, kh, sh, op.get("padding", 0))
-            wo, pl, pr = window(x.W, kw, sw, op.get("padding", 0))
-            if ho < 1 or wo < 1:
-                raise NotImplementedError("%s: the %d x %d input is smaller than the kernel" % (what, x.H, x.W))
-            T[y] = PlanTensor(y, ho, wo, co)
-            bias = g.const(ins[2]) if len(ins) > 2 else None
-            kind, in1 = _lib.GRAPH_CONV, -1
-            if fscale is not None:
-                overflow_check(what, kh * kw * ci)
-                kind, in1 = _lib.GRAPH_CONV_Q8, params_of(x, False, i)
-            emit(PlanOp(kind, name, x.id, y, in1=in1, kh=kh, kw=kw, stride_h=sh, stride_w=sw, pads=(pt, pl, pb, pr),
-                        act=op.get("act", 0), filter=w, scale=None, filter_scale=fscale,
-                        shift=np.zeros(co, np.float32) if bias is None else np.asarray(bias, np.float32).reshape(-1)), i)
-        elif name == "DEPTHWISE_CONV_2D":
-            w, fscale = filter_of(op, ins[1])
-            _, kh, kw, co = w.shape
-            if co != x.C:
-                raise NotImplementedError("%s: depth multiplier (filter depth %d, input depth %d), only 1 is run" % (what, co, x.C))
-            sh, sw = op.get("stride_h", 1), op.get("stride_w", 1)
-            if not (1 <= kh <= 7 and 1 <= kw <= 7 and sh in (1, 2) and sw in (1, 2)):
-                raise NotImplementedError("%s: %d x %d kernel with strides %d, %d" % (what, kh, kw, sh, sw))
-            ho, pt, pb = window(x.H, kh, sh, op.get("padding", 0))
-            wo, pl, pr = window(x.W, kw, sw, op.get("padding", 0))
-            if ho < 1 or wo < 1:
-                raise NotImplementedError("%s: the %d x %d input is smaller than the kernel" % (what, x.H, x.W))
-            T[y] = PlanTensor(y, ho, wo, co)
-            bias = g.const(ins[2]) if len(ins) > 2 else None
-            kind, in1 = _lib.GRAPH_DWCONV, -1
-            if fscale is not None:
-                kind, in1 = _lib.GRAPH_DWCONV_Q8, params_of(x, False, i)   # (kh * kw <= 49 products: no overflow)
-            emit(PlanOp(kind, name, x.id, y, in1=in1, kh=kh, kw=kw, stride_h=sh, stride_w=sw, pads=(pt, pl, pb, pr),
-                        act=op.get("act", 0), filter=w, scale=None, filter_scale=fscale,
-                        shift=np.zeros(co, np.float32) if bias is None else np.asarray(bias, np.float32).reshape(-1)), i)
+        if name in ("CONV_2D", "DEPTHWISE_CONV_2D"):
+            filter_op(i, op, what, x, y, ins)
         elif name in ("MAX_POOL_2D", "AVERAGE_POOL_2D"):
             kh, kw = op["filter_height"], op["filter_width"]
             sh, sw = op["stride_h"], op["stride_w"]
@@ -462,18 +451,13 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
     plan.output_shape = (T[gout].H, T[gout].W, T[gout].C)
 
     # ---- weights in the kernel's layout ----
+    packers = {_lib.GRAPH_CONV: pack_conv_filter, _lib.GRAPH_CONV_Q8: pack_conv_filter_q8,
+               _lib.GRAPH_DWCONV: pack_dw_filter, _lib.GRAPH_DWCONV_Q8: pack_dw_filter_q8}
     for o in ops:
-        if o.kind == _lib.GRAPH_CONV:
-            o.weights = pack_conv_filter(o.filter)
-        elif o.kind == _lib.GRAPH_CONV_Q8:
-            o.weights = pack_conv_filter_q8(o.filter)
-            # the device multiplies by float32(filter scale x folded scale)
-            o.scale = o.filter_scale if o.scale is None else (o.filter_scale * o.scale).astype(np.float32)
-        elif o.kind == _lib.GRAPH_DWCONV:
-            o.weights = pack_dw_filter(o.filter)
-        elif o.kind == _lib.GRAPH_DWCONV_Q8:
-            o.weights = pack_dw_filter_q8(o.filter)
-            o.scale = o.filter_scale if o.scale is None else (o.filter_scale * o.scale).astype(np.float32)
+        if o.kind in packers:
+            o.weights = packers[o.kind](o.filter)
+            if o.filter_scale is not None:   # the device multiplies by float32(filter scale x folded scale)
+                o.scale = o.filter_scale if o.scale is None else (o.filter_scale * o.scale).astype(np.float32)
     return plan
 
 
@@ -649,17 +633,20 @@ class GraphDevice:
             assert out is not None and out.is_contiguous() and tuple(out.shape) == (N, oh, ow, self.out_slice[1])
         if out is None:
             out = t.empty((N, oc) if (oh, ow) == (1, 1) else (N, oh, ow, oc), dtype=t.float32, device=self.eng.device)
+        self._enqueue(x, N, out)
+        self.eng.synchronize()
+        return out
+
+    def _enqueue(self, x, N, out):
         for attempt in range(2):
             rc = self.lib.cpx_graph_forward(self._graph, C.c_void_p(x.data_ptr()), N, C.c_void_p(out.data_ptr()))
             if rc == -6 and attempt == 0:   # CPX_ERR_NOMEM: the arena is a plain hipMalloc; torch's cache is invisible to it
                 self.eng.synchronize()
-                t.cuda.empty_cache()
+                self.torch.cuda.empty_cache()
                 continue
             break
         if rc != 0:
             raise _lib.CpxError(rc, self.eng._err())
-        self.eng.synchronize()
-        return out
 
     def forward_async(self, x, out):
         """forward() for a caller that orders its work by the engine's stream (the batched pipeline): the launches are
@@ -670,15 +657,7 @@ class GraphDevice:
         N = int(x.shape[0])
         assert self.out_slice is None and out.dtype == self.torch.float32 and out.is_contiguous() and \
             out.numel() == N * int(np.prod(self.plan.output_shape)), tuple(out.shape)
-        for attempt in range(2):
-            rc = self.lib.cpx_graph_forward(self._graph, C.c_void_p(x.data_ptr()), N, C.c_void_p(out.data_ptr()))
-            if rc == -6 and attempt == 0:   # CPX_ERR_NOMEM: as forward()
-                self.eng.synchronize()
-                self.torch.cuda.empty_cache()
-                continue
-            break
-        if rc != 0:
-            raise _lib.CpxError(rc, self.eng._err())
+        self._enqueue(x, N, out)
 
     def close(self):
         if self._graph is not None:

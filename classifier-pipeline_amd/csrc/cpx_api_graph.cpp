@@ -1,4 +1,4 @@
-// cpx_api_graph.cpp -- the float32 TFLite graph executor's entry points (include/cpx.h: cpx_graph_*).
+// cpx_api_graph.cpp -- the TFLite graph executor's entry points, float32 and hybrid operators alike (include/cpx.h: cpx_graph_*).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -11,7 +11,7 @@
 
 static_assert(sizeof(cpx_graph_tensor) == 32 && sizeof(cpx_graph_op) == 112, "graph layouts are part of the ABI");
 
-// ---- float32 TFLite graph executor (LiteInterpreter.predict, ml_tools/interpreter.py:520-560) ------------------------
+// ---- TFLite graph executor (LiteInterpreter.predict, ml_tools/interpreter.py:520-560) ------------------------
 struct cpx_graph {
   cpx_handle* h = nullptr;
   std::vector<cpx_graph_op> ops;
@@ -56,15 +56,7 @@ static const char* graph_check_op(const cpx_graph_op& o, const std::vector<cpx_g
       if (!conv && a.C != y.C) return "pool changes the channel count";
       if (dw && a.C != y.C) return "DWCONV changes the channel count (depth multiplier 1 only)";
       if (o.kind == CPX_GRAPH_DWCONV && (reinterpret_cast<uintptr_t>(o.weights) & 15)) return "DWCONV weights are not 16-byte aligned";
-      if (o.kind == CPX_GRAPH_DWCONV_Q8) {
-        if ((reinterpret_cast<uintptr_t>(o.weights) & 3)) return "DWCONV_Q8 weights are not 4-byte aligned";
-        if (!is_params(o.in1)) return "DWCONV_Q8 needs a 1 x 1 x 4 parameter tensor as in1";
-        if (!o.scale || !o.shift) return "DWCONV_Q8 without scale or shift";
-      }
-      if (o.kind == CPX_GRAPH_CONV_Q8) {
-        if (!is_params(o.in1)) return "CONV_Q8 needs a 1 x 1 x 4 parameter tensor as in1";
-        if (!o.scale || !o.shift) return "CONV_Q8 without scale or shift";
-      }
+      if (o.kind == CPX_GRAPH_DWCONV_Q8 && (reinterpret_cast<uintptr_t>(o.weights) & 3)) return "DWCONV_Q8 weights are not 4-byte aligned";
       break;
     }
     case CPX_GRAPH_ADD:
@@ -80,12 +72,8 @@ static const char* graph_check_op(const cpx_graph_op& o, const std::vector<cpx_g
       if (y.H != 1 || y.W != 1 || a.C != y.C) return "MEAN gives 1 x 1 x C";
       break;
     case CPX_GRAPH_FC:
-      if (a.H != 1 || a.W != 1 || y.H != 1 || y.W != 1 || !o.weights) return "FULLY_CONNECTED takes and gives 1 x 1 x C";
-      break;
     case CPX_GRAPH_FC_Q8:
       if (a.H != 1 || a.W != 1 || y.H != 1 || y.W != 1 || !o.weights) return "FULLY_CONNECTED takes and gives 1 x 1 x C";
-      if (!is_params(o.in1)) return "FC_Q8 needs a 1 x 1 x 4 parameter tensor as in1";
-      if (!o.scale || !o.shift) return "FC_Q8 without scale or shift";
       break;
     case CPX_GRAPH_QUANT_PARAMS:
       if (!is_params(o.out)) return "QUANT_PARAMS writes a 1 x 1 x 4 tensor";
@@ -103,6 +91,11 @@ static const char* graph_check_op(const cpx_graph_op& o, const std::vector<cpx_g
       break;
     default:
       return "unknown operator kind";
+  }
+  // what a hybrid operator needs beyond its float32 twin (the caller's message names the operator's kind)
+  if (o.kind == CPX_GRAPH_CONV_Q8 || o.kind == CPX_GRAPH_FC_Q8 || o.kind == CPX_GRAPH_DWCONV_Q8) {
+    if (!is_params(o.in1)) return "a hybrid operator needs a 1 x 1 x 4 parameter tensor as in1";
+    if (!o.scale || !o.shift) return "a hybrid operator without scale or shift";
   }
   return nullptr;
 }
@@ -136,7 +129,7 @@ int cpx_graph_create(cpx_handle* h, const cpx_graph_op* ops, int n_ops, const cp
   for (int i = 0; i < n_ops; ++i) {
     if (const char* why = graph_check_op(g->ops[i], g->tensors, input_tensor, output_tensor)) {
       delete g;
-      h->err = "cpx_graph_create: operator " + std::to_string(i) + ": " + why;
+      h->err = "cpx_graph_create: operator " + std::to_string(i) + " (kind " + std::to_string(ops[i].kind) + "): " + why;
       return CPX_ERR_INVALID;
     }
   }

@@ -1,5 +1,6 @@
-// cpx_graph.hip -- the kernels of the float32 TFLite graph executor (cpx_graph_forward, include/cpx.h; what the
-// reference's LiteInterpreter hands to the TFLite runtime, ml_tools/interpreter.py:520-560).  One launch per planned
+// cpx_graph.hip -- the float32 kernels of the TFLite graph executor (cpx_graph_forward, include/cpx.h; what the
+// reference's LiteInterpreter hands to the TFLite runtime, ml_tools/interpreter.py:520-560; the hybrid operators are
+// cpx_graph_q8.hip's, DEPTHWISE_CONV_2D is cpx_graph_dw.hip's, what they share is cpx_graph_core.h).  One launch per planned
 // operator; every kernel reads and writes NHWC views with a channel offset and a row stride, so that the producers of a
 // CONCATENATION write straight into their slice of the concatenated tensor.
 //
@@ -13,6 +14,7 @@
 // masked.  Scale / shift (bias, folded MUL / ADD), the activation and the channel-sliced store happen from the accumulators.
 #include <hip/hip_runtime.h>
 
+#include "cpx_graph_core.h"
 #include "cpx_kernels.h"
 
 namespace cpx {
@@ -21,12 +23,6 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float activate(float v, int act) {
-  if (act == CPX_GRAPH_ACT_RELU) return fmaxf(v, 0.0f);
-  if (act == CPX_GRAPH_ACT_RELU6) return fminf(fmaxf(v, 0.0f), 6.0f);
-  return v;
-}
 
 constexpr int CT = 256;
 constexpr int BM = 128;            // output pixels of a workgroup
@@ -46,18 +42,14 @@ __global__ __launch_bounds__(CT) void graph_conv_kernel(GraphOpArgs a, ConvGeom 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const long long p0 = (long long)blockIdx.x * BM;
   const int cout0 = blockIdx.y * BN;
-  const int Cin = a.in0.C, H = a.in0.H, W = a.in0.W, Wo = a.out.W;
+  const int Cin = a.in0.C, H = a.in0.H, W = a.in0.W;
 
   // staging role: pixel tid / 2 of the tile, channels [8 * half, 8 * half + 8) of the chunk -- the same pixel for the
   // whole K walk, so its coordinates are worked out once
   const int spx = tid >> 1, half = tid & 1;
-  const long long sp = p0 + spx;
-  const bool pv = sp < g.P;
-  const long long sn = pv ? sp / g.HoWo : 0;
-  const int srem = pv ? (int)(sp - sn * g.HoWo) : 0;
-  const int soy = srem / Wo, sox = srem - soy * Wo;
-  const int iy0 = soy * a.stride_h - a.pad_top, ix0 = sox * a.stride_w - a.pad_left;
-  const float* in_n = a.in0.p + (size_t)sn * a.in0.sample_stride;   // 64-bit over the batch, 32-bit inside a sample
+  const ConvPixel sp = conv_pixel(p0 + spx, g.P, g.HoWo, a.out.W);
+  const int iy0 = window_origin(sp.oy, a.stride_h, a.pad_top), ix0 = window_origin(sp.ox, a.stride_w, a.pad_left);
+  const float* in_n = a.in0.p + (size_t)sp.n * a.in0.sample_stride;   // 64-bit over the batch, 32-bit inside a sample
   // weight staging: KC rows of BN channels = KC * BN / 4 float4 (one per thread with NTN = 2)
   constexpr int WQ = BN / 4;
   const int wk = tid / WQ, wc4 = tid - wk * WQ;
@@ -80,7 +72,7 @@ __global__ __launch_bounds__(CT) void graph_conv_kernel(GraphOpArgs a, ConvGeom 
     const int tap = s / nchunks, c0 = (s - tap * nchunks) * KC;
     const int ky = tap / a.kw, kx = tap - ky * a.kw;
     const int iy = iy0 + ky, ix = ix0 + kx;
-    const bool inside = pv && iy >= 0 && iy < H && ix >= 0 && ix < W;
+    const bool inside = sp.valid && iy >= 0 && iy < H && ix >= 0 && ix < W;
     const int c = c0 + 8 * half;
     const int pix = inside ? (iy * W + ix) * a.in0.cstride : 0;
     if (g.vec4) {
@@ -123,8 +115,8 @@ __global__ __launch_bounds__(CT) void graph_conv_kernel(GraphOpArgs a, ConvGeom 
     __syncthreads();
   }
 
-  // epilogue: accumulator register r of a lane is pixel (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5) of the wave's 32,
-  // channel lane & 31 of the tile: 32 lanes store 128 contiguous bytes of one pixel
+  // epilogue: accumulator register r of a lane is pixel acc_row(r, tid) of the wave's 32, channel lane & 31 of the
+  // tile: 32 lanes store 128 contiguous bytes of one pixel
   const long long pb = p0 + 32 * wave;
   if (pb >= g.P) return;
   const long long nb = pb / g.HoWo;
@@ -137,15 +129,10 @@ __global__ __launch_bounds__(CT) void graph_conv_kernel(GraphOpArgs a, ConvGeom 
     const float sh = a.shift ? a.shift[ch] : 0.0f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int i = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+      const int i = acc_row(r, tid);
       if (pb + i >= g.P) continue;
-      long long n = nb;
-      int rem = remb + i;
-      while (rem >= g.HoWo) {
-        rem -= g.HoWo;
-        ++n;
-      }
-      a.out.p[(size_t)n * a.out.sample_stride + (unsigned)(rem * a.out.cstride + ch)] = activate(acc[t][r] * sc + sh, a.act);
+      const SamplePixel o = sample_step(nb, remb + i, g.HoWo);
+      a.out.p[(size_t)o.n * a.out.sample_stride + (unsigned)(o.rem * a.out.cstride + ch)] = activate(acc[t][r] * sc + sh, a.act);
     }
   }
 }
@@ -288,10 +275,7 @@ void launch_graph_op(const GraphOpArgs& a, hipStream_t s) {
       g.P = (long long)a.N * g.HoWo;
       g.cin_pad = (a.in0.C + GRAPH_CONV_KC - 1) / GRAPH_CONV_KC * GRAPH_CONV_KC;
       g.cout_pad = (a.out.C + GRAPH_CONV_CO - 1) / GRAPH_CONV_CO * GRAPH_CONV_CO;
-      g.vec4 = (a.in0.C % 4 == 0 && a.in0.cstride % 4 == 0 && a.in0.sample_stride % 4 == 0 &&
-                (reinterpret_cast<uintptr_t>(a.in0.p) & 15) == 0)
-                   ? 1
-                   : 0;
+      g.vec4 = quads(a.in0);
       const unsigned gx = (unsigned)((g.P + BM - 1) / BM);
       if (g.cout_pad % 64 == 0)
         hipLaunchKernelGGL(graph_conv_kernel<2>, dim3(gx, g.cout_pad / 64), dim3(CT), 0, s, a, g);

@@ -1,8 +1,8 @@
 // cpx_graph_q8.hip -- the hybrid (dynamic-range quantised) operators of the TFLite graph executor: int8 filters, float32
 // activations that are quantised to 8 bits per sample where an operator reads them, int32 accumulation on the int8
 // matrix pipe.  The arithmetic is fixed in include/cpx.h (CPX_GRAPH_QUANT_PARAMS / CONV_Q8 / FC_Q8) so that a NumPy
-// restatement reproduces it bit for bit: every float32 operation below is written as one operation (the build has
-// -ffp-contract=off), the integer sums are exact in any order.
+// restatement reproduces it bit for bit: every float32 operation is written as one operation in cpx_graph_core.h
+// (quantise, quant_params, hybrid_finish; the build has -ffp-contract=off), the integer sums are exact in any order.
 //
 // CONV_Q8 is an implicit GEMM on v_mfma_i32_32x32x32_i8:
 //   M = output pixels of the WHOLE batch, flattened (128 per workgroup, 32 per wave), as graph_conv_kernel
@@ -19,6 +19,7 @@
 // l & 31 and sixteen consecutive k of half l >> 5 of A and of B; C / D is the map of the other 32 x 32 forms.
 #include <hip/hip_runtime.h>
 
+#include "cpx_graph_core.h"
 #include "cpx_kernels.h"
 
 namespace cpx {
@@ -32,19 +33,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int CT = 256;
 constexpr int BM = 128;               // output pixels of a workgroup
 constexpr int KQ = GRAPH_CONV_Q8_KC;  // input channels (bytes of a row of the A image) per step
-
-__device__ __forceinline__ float activate(float v, int act) {
-  if (act == CPX_GRAPH_ACT_RELU) return fmaxf(v, 0.0f);
-  if (act == CPX_GRAPH_ACT_RELU6) return fminf(fmaxf(v, 0.0f), 6.0f);
-  return v;
-}
-
-// q = clamp(round-half-away(float32(x * inv)) + zp, -128, 127)
-__device__ __forceinline__ int quantise(float x, float inv, int zp) {
-  const float v = x * inv;
-  const int q = (int)roundf(v) + zp;
-  return min(max(q, -128), 127);
-}
 
 __device__ __forceinline__ int pack4(int q0, int q1, int q2, int q3) {
   return (q0 & 255) | ((q1 & 255) << 8) | ((q2 & 255) << 16) | (int)((unsigned)q3 << 24);
@@ -96,26 +84,11 @@ __global__ __launch_bounds__(QT) void graph_quant_params_kernel(GraphOpArgs a) {
     lo = fminf(lo, s_lo[w]);
     hi = fmaxf(hi, s_hi[w]);
   }
-  float sx = 1.0f, inv = 1.0f;
-  int zp = 0;
-  if (a.param != 0.0f) {   // symmetric
-    const float m = fmaxf(-lo, hi);
-    if (m != 0.0f) {
-      sx = (float)((double)m / 127.0);
-      inv = (float)(127.0 / (double)m);
-    }
-  } else if (lo != hi) {
-    const double s = ((double)hi - (double)lo) / 255.0;
-    const double ql = (double)lo / s, qh = (double)hi / s;
-    const double z = (128.0 + fabs(ql) < 127.0 + fabs(qh)) ? -128.0 - ql : 127.0 - qh;
-    zp = (int)fmin(fmax(round(z), -128.0), 127.0);
-    sx = (float)s;
-    inv = (float)(1.0 / s);
-  }
+  const QuantParams q8 = quant_params(lo, hi, a.param != 0.0f);
   float* out = a.out.p + n * a.out.sample_stride;
-  out[0] = sx;
-  out[1] = inv;
-  out[2] = (float)zp;
+  out[0] = q8.sx;
+  out[1] = q8.inv;
+  out[2] = (float)q8.zp;
   out[3] = 0.0f;
 }
 
@@ -130,19 +103,15 @@ __global__ __launch_bounds__(CT) void graph_conv_q8_kernel(GraphOpArgs a, ConvQ8
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const long long p0 = (long long)blockIdx.x * BM;
   const int tile0 = blockIdx.y * NTN;
-  const int Cin = a.in0.C, H = a.in0.H, W = a.in0.W, Wo = a.out.W;
+  const int Cin = a.in0.C, H = a.in0.H, W = a.in0.W;
 
   // staging role: pixel tid / 2 of the tile, channels [16 * half, 16 * half + 16) of the chunk -- the same pixel for the
   // whole K walk, so its coordinates and its sample's parameters are worked out once
   const int spx = tid >> 1, half = tid & 1;
-  const long long sp = p0 + spx;
-  const bool pv = sp < g.P;
-  const long long sn = pv ? sp / g.HoWo : 0;
-  const int srem = pv ? (int)(sp - sn * g.HoWo) : 0;
-  const int soy = srem / Wo, sox = srem - soy * Wo;
-  const int iy0 = soy * a.stride_h - a.pad_top, ix0 = sox * a.stride_w - a.pad_left;
-  const float* in_n = a.in0.p + (size_t)sn * a.in0.sample_stride;
-  const float* sprm = a.in1.p + (size_t)sn * a.in1.sample_stride;
+  const ConvPixel sp = conv_pixel(p0 + spx, g.P, g.HoWo, a.out.W);
+  const int iy0 = window_origin(sp.oy, a.stride_h, a.pad_top), ix0 = window_origin(sp.ox, a.stride_w, a.pad_left);
+  const float* in_n = a.in0.p + (size_t)sp.n * a.in0.sample_stride;
+  const float* sprm = a.in1.p + (size_t)sp.n * a.in1.sample_stride;
   const float inv = sprm[1];
   const int zp = (int)sprm[2];
   const i32x4* wq = reinterpret_cast<const i32x4*>(a.weights);
@@ -164,7 +133,7 @@ __global__ __launch_bounds__(CT) void graph_conv_q8_kernel(GraphOpArgs a, ConvQ8
     const int tap = s / g.nchunks, c0 = (s - tap * g.nchunks) * KQ;
     const int ky = tap / a.kw, kx = tap - ky * a.kw;
     const int iy = iy0 + ky, ix = ix0 + kx;
-    const bool inside = pv && iy >= 0 && iy < H && ix >= 0 && ix < W;
+    const bool inside = sp.valid && iy >= 0 && iy < H && ix >= 0 && ix < W;
     const int c = c0 + 16 * half;
     const int pix = inside ? (iy * W + ix) * a.in0.cstride : 0;
     if (g.vec4) {
@@ -212,8 +181,8 @@ __global__ __launch_bounds__(CT) void graph_conv_q8_kernel(GraphOpArgs a, ConvQ8
       if (tile0 + t < g.ntiles) acc[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af, bcur[t], acc[t], 0, 0, 0);
   }
 
-  // epilogue: accumulator register r of a lane is pixel (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5) of the wave's 32,
-  // channel lane & 31 of the tile; every pixel takes its own sample's sx and zp
+  // epilogue: accumulator register r of a lane is pixel acc_row(r, tid) of the wave's 32, channel lane & 31 of the
+  // tile; every pixel takes its own sample's sx and zp
   const long long pb = p0 + 32 * wave;
   if (pb >= g.P) return;
   const int* wsum = reinterpret_cast<const int*>(wq + (size_t)steps * g.ntiles * 64);
@@ -228,20 +197,12 @@ __global__ __launch_bounds__(CT) void graph_conv_q8_kernel(GraphOpArgs a, ConvQ8
     const int ws = wsum[ch];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int i = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+      const int i = acc_row(r, tid);
       if (pb + i >= g.P) continue;
-      long long n = nb;
-      int rem = remb + i;
-      while (rem >= g.HoWo) {
-        rem -= g.HoWo;
-        ++n;
-      }
-      const float* prm = a.in1.p + (size_t)n * a.in1.sample_stride;
-      const float sx = prm[0];
-      const int z = (int)prm[2];
-      const float m = sx * sc;
-      const float v = (float)(acc[t][r] - z * ws) * m;
-      a.out.p[(size_t)n * a.out.sample_stride + (unsigned)(rem * a.out.cstride + ch)] = activate(v + sh, a.act);
+      const SamplePixel o = sample_step(nb, remb + i, g.HoWo);
+      const float* prm = a.in1.p + (size_t)o.n * a.in1.sample_stride;
+      a.out.p[(size_t)o.n * a.out.sample_stride + (unsigned)(o.rem * a.out.cstride + ch)] =
+          hybrid_finish(acc[t][r], (int)prm[2], ws, prm[0], sc, sh, a.act);
     }
   }
 }
@@ -273,21 +234,13 @@ __global__ __launch_bounds__(CT) void graph_fc_q8_kernel(GraphOpArgs a) {
   }
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
-  if (lane == 0) {
-    const float m = sx * a.scale[o];
-    const float v = (float)(acc - zp * wsum[o]) * m;
-    a.out.p[n * a.out.sample_stride + o] = activate(v + a.shift[o], a.act);
-  }
+  if (lane == 0) a.out.p[n * a.out.sample_stride + o] = hybrid_finish(acc, zp, wsum[o], sx, a.scale[o], a.shift[o], a.act);
 }
 
 }  // namespace
 
 void launch_graph_q8_op(const GraphOpArgs& a, hipStream_t s) {
-  // in0 can be read as aligned quads of channels
-  const int vec4 = (a.in0.C % 4 == 0 && a.in0.cstride % 4 == 0 && a.in0.sample_stride % 4 == 0 &&
-                    (reinterpret_cast<uintptr_t>(a.in0.p) & 15) == 0)
-                       ? 1
-                       : 0;
+  const int vec4 = quads(a.in0);
   switch (a.kind) {
     case CPX_GRAPH_QUANT_PARAMS:
       if (vec4)

@@ -383,7 +383,7 @@ struct Mog2Args {
 void launch_mog2_apply(const Mog2Args& a, hipStream_t s);
 void launch_mog2_background(const Mog2Args& a, unsigned char* out, hipStream_t s);
 
-// ---- float32 TFLite graph executor (cpx_graph.hip) ----
+// ---- TFLite graph executor (cpx_graph.hip, cpx_graph_q8.hip, cpx_graph_dw.hip; what they share: cpx_graph_core.h) ----
 // A view of an NHWC tensor of N samples: sample n at p + n * sample_stride, pixel (y, x) channel c at
 // ((y * W + x) * cstride + c).  `p` already points at the view's first channel (the channel offset is added by the caller).
 struct GraphView {

@@ -90,6 +90,10 @@ FLOAT_CASES = [
     (1, 7, 1, tb.SAME, 20, 9),
     (7, 1, 2, tb.VALID, 20, 9),
     (1, 1, 1, tb.VALID, 64, 3),
+    # the instantiations of graph_dw_kernel the cases above do not launch: channel by channel at stride 2 and above 3 columns
+    (3, 3, 2, tb.SAME, 6, 9),
+    (5, 5, 1, tb.SAME, 6, 9),
+    (5, 5, 2, tb.SAME, 6, 9),
 ]
 
 
@@ -128,6 +132,10 @@ HYBRID_CASES = [
     (5, 5, 1, tb.SAME, 52, 7, False),   # one scale for the whole filter
     (3, 3, 1, tb.SAME, 30, 5, True),    # 270 elements: the converter would leave it float32; forced INT8
     (3, 3, 2, tb.VALID, 6, 9, True),
+    # the instantiations of graph_dw_kernel the cases above do not launch
+    (5, 5, 2, tb.SAME, 8, 9, True),     # quads, stride 2, above 3 columns
+    (5, 5, 1, tb.SAME, 6, 9, True),     # channel by channel, above 3 columns
+    (5, 5, 2, tb.SAME, 6, 9, False),    # ... at stride 2
 ]
 
 
