@@ -354,7 +354,8 @@ class WRResNetInterpreter(Interpreter):
 
 class LiteInterpreter(Interpreter):
     """Any float32 or dynamic-range quantised `.tflite` graph of the operator set cpx/ml_tools/tflite_reader.py reads (the
-    reference's inceptionv3 and mobilenet families, ml_tools/kerasmodel.py:144-151,171-180,259-350; its converter writes INT8 filters,
+    reference's inceptionv3, mobilenet and efficientnetb0 / b1 / b5 / efficientnetv2b3 families, ml_tools/kerasmodel.py:144-151,171-216,259-350 --
+    the EfficientNets take the unscaled sample, get_preprocess_fn returns None for them --; its converter writes INT8 filters,
     src/tfliteconverter.py:54-62) on the device graph executor (cpx_graph_*): the reference's LiteInterpreter
     (interpreter.py:520-560) with the TFLite runtime replaced.  model = <name>.tflite + <name>.json.
     predict runs the whole batch in one forward (the reference loops sample by sample because its runtime must).

@@ -4,8 +4,19 @@
 
 * shapes are inferred operator by operator for a given [H, W, C] input with TensorFlow's SAME / VALID arithmetic (SAME's
   surplus padding goes bottom and right);
-* MUL / ADD / SUB by a per-channel constant behind a convolution (or behind another such operator) that nothing else
-  reads are folded into its scale and shift; elsewhere they are one element-wise AFFINE operator;
+* MUL / ADD / SUB / DIV by a per-channel constant behind a convolution (or behind another such operator) that nothing
+  else reads are folded into its scale and shift; elsewhere they are one element-wise AFFINE operator.  x / c is the
+  scale float32(1 / float64(c)); c / x is refused;
+* a swish, which the converter writes as s = LOGISTIC(x); y = MUL(x, s) (either operand order, s read by nothing else),
+  is folded into x's producer as the activation SWISH (_lib.GRAPH_ACT_SWISH) where that producer is one of FOLD_INTO,
+  carries no activation, is no copy and x has no other reader and is not the output; elsewhere it is ONE AFFINE operator
+  with that activation.  A LOGISTIC behind a CONV_2D / DEPTHWISE_CONV_2D (float32 or hybrid) that nothing else reads is
+  folded as the activation LOGISTIC (the gate of a squeeze-and-excite block); behind a FULLY_CONNECTED it stays a launch.
+  fuse_activations=False keeps every LOGISTIC and MUL a launch: the same float32 operations, bit for bit;
+* any other MUL of two activations is a MUL operator: two tensors of one shape, or [H, W, C] by the [1, 1, C] gate of a
+  squeeze-and-excite block in either operand order.  Every other broadcast is refused;
+* MEAN over H and W, with or without keep_dims (and the RESHAPE to [1, 1, 1, C] older Keras versions put behind it, a view),
+  is one operator with two summation orders (include/cpx.h: CPX_GRAPH_MEAN);
 * a CONCATENATION along the channels runs no kernel: every producer of one of its inputs writes straight into its channel
   slice of the concatenated tensor (channel offset + row stride).  Only an input that cannot be placed -- it feeds two
   concatenations, it is the graph's input, it is a view of another tensor -- is copied (a COPY entry: an AFFINE operator
@@ -109,14 +120,16 @@ def _channel_const(g, tid, channels, what):
 QUANT_MATHS = ("hybrid", "float")
 Q8_KINDS = (_lib.GRAPH_CONV_Q8, _lib.GRAPH_FC_Q8, _lib.GRAPH_DWCONV_Q8)
 FOLD_INTO = (_lib.GRAPH_CONV, _lib.GRAPH_CONV_Q8, _lib.GRAPH_DWCONV, _lib.GRAPH_DWCONV_Q8, _lib.GRAPH_AFFINE)
+LOGISTIC_INTO = (_lib.GRAPH_CONV, _lib.GRAPH_CONV_Q8, _lib.GRAPH_DWCONV, _lib.GRAPH_DWCONV_Q8)
+ACT_SWISH, ACT_LOGISTIC = _lib.GRAPH_ACT_SWISH, _lib.GRAPH_ACT_LOGISTIC
 
 
-def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_math="hybrid"):
+def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_math="hybrid", fuse_activations=True):
     """g: tflite_reader.Graph.  input_shape: (H, W, C) of a sample, default: the flatbuffer's.  output: the tensor the
     forward hands out, default the graph's output; the operators it does not need are dropped.  channel_map: up to 4
     indices into the channels of the sample the CALLER brings ([N, H, W, max(map) + 1 or more]): the graph's input
     channel c is the caller's channel channel_map[c].  quantised_math: "hybrid" runs INT8 filters on the int8 operators,
-    "float" multiplies them out on the host."""
+    "float" multiplies them out on the host.  fuse_activations=False: LOGISTIC and the MUL of a swish stay launches."""
     if quantised_math not in QUANT_MATHS:
         raise ValueError("quantised_math %r: one of %s" % (quantised_math, ", ".join(QUANT_MATHS)))
     g.check_executable()
@@ -138,6 +151,22 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
             if t >= 0 and g.const(t) is None:
                 consumers.setdefault(t, []).append(i)
     ops = []
+
+    # ---- swish: s = LOGISTIC(x); y = MUL(x, s) in either operand order, s read by nothing else ----
+    swish_logistic, swish_mul = {}, {}   # operator index of the LOGISTIC -> of the MUL; of the MUL -> x
+    if fuse_activations:
+        for i, op in enumerate(g.ops):
+            if op["name"] != "LOGISTIC":
+                continue
+            xt, st = op["inputs"][0], op["outputs"][0]
+            readers = consumers.get(st, [])
+            if len(readers) != 1 or st == gout or st in g.outputs or g.const(xt) is not None:
+                continue
+            mul = g.ops[readers[0]]
+            if mul["name"] == "MUL" and mul.get("act", 0) == ACT_NONE and sorted(t for t in mul["inputs"] if t >= 0) == sorted((xt, st)) \
+                    and xt != st:
+                swish_logistic[i] = readers[0]
+                swish_mul[readers[0]] = xt
 
     def emit(o, src):
         o.source = src
@@ -209,6 +238,22 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
         what = "operator %d (%s)" % (i, name)
         ins = [t for t in op["inputs"] if t >= 0]
         act_ins = [t for t in ins if g.const(t) is None]
+        if i in swish_logistic:
+            continue   # (its MUL does the work)
+        if i in swish_mul:
+            if swish_mul[i] not in T:
+                raise NotImplementedError("%s reads tensor %d, which no earlier operator wrote" % (what, swish_mul[i]))
+            x, y = T[swish_mul[i]], op["outputs"][0]
+            T[y] = PlanTensor(y, x.H, x.W, x.C)
+            p = producer.get(x.id)
+            if p is not None and p.kind in FOLD_INTO and p.act == ACT_NONE and not p.copy and p.out == x.id \
+                    and len(consumers.get(x.id, [])) == 2 and x.id != gout:
+                p.act, p.out, p.name = ACT_SWISH, y, p.name + "+SWISH"   # the producer now writes the MUL's output
+                producer[y] = p
+                del T[x.id]
+            else:
+                emit(PlanOp(_lib.GRAPH_AFFINE, "SWISH", x.id, y, act=ACT_SWISH), i)
+            continue
         for t in act_ins:
             if t not in T:
                 raise NotImplementedError("%s reads tensor %d, which no earlier operator wrote" % (what, t))
@@ -230,10 +275,23 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
             T[y] = PlanTensor(y, ho, wo, x.C)
             emit(PlanOp(_lib.GRAPH_MAX_POOL if name[0] == "M" else _lib.GRAPH_AVG_POOL, name, x.id, y, kh=kh, kw=kw,
                         stride_h=sh, stride_w=sw, pads=(pt, pl, pb, pr), act=op["act"]), i)
-        elif name in ("ADD", "SUB", "MUL"):
+        elif name in ("ADD", "SUB", "MUL", "DIV"):
             if len(act_ins) == 2:
                 b = T[act_ins[1]]
-                if name == "MUL" or (x.H, x.W, x.C) != (b.H, b.W, b.C):
+                same = (x.H, x.W, x.C) == (b.H, b.W, b.C)
+                if name == "DIV":
+                    raise NotImplementedError("%s of two activations: only a division by a constant is run" % what)
+                if name == "MUL":
+                    # [H, W, C] by the [1, 1, C] gate of its sample, in either order: the gate is in1
+                    if not same and (b.H, b.W, b.C) != (1, 1, x.C):
+                        x, b = b, x
+                    if not same and (b.H, b.W, b.C) != (1, 1, x.C):
+                        raise NotImplementedError("%s of two tensors of shapes %s, %s: only one shape, or [H, W, C] by [1, 1, C]"
+                                                  % (what, (b.H, b.W, b.C), (x.H, x.W, x.C)))
+                    T[y] = PlanTensor(y, x.H, x.W, x.C)
+                    emit(PlanOp(_lib.GRAPH_MUL, name, x.id, y, in1=b.id, act=op["act"]), i)
+                    continue
+                if not same:
                     raise NotImplementedError("%s of two tensors of shapes %s, %s" % (what, (x.H, x.W, x.C), (b.H, b.W, b.C)))
                 T[y] = PlanTensor(y, x.H, x.W, x.C)
                 emit(PlanOp(_lib.GRAPH_ADD, name, x.id, y, in1=b.id, act=op["act"], param=1.0 if name == "ADD" else -1.0), i)
@@ -241,7 +299,13 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
                 cid = next(t for t in ins if g.const(t) is not None)
                 c = _channel_const(g, cid, x.C, what)
                 one, zero = np.ones(x.C, np.float32), np.zeros(x.C, np.float32)
-                if name == "MUL":
+                if name == "DIV":
+                    if ins[0] == cid:
+                        raise NotImplementedError("%s: a constant divided by an activation (c / x) is not run" % what)
+                    if np.any(c == 0):
+                        raise NotImplementedError("%s: division by a constant 0" % what)
+                    sc, sf = (1.0 / c.astype(np.float64)).astype(np.float32), zero
+                elif name == "MUL":
                     sc, sf = c, zero
                 elif name == "ADD":
                     sc, sf = one, c
@@ -316,6 +380,13 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
                             shift=None if bias is None else np.asarray(bias, np.float32).reshape(-1)), i)
         elif name in ("LOGISTIC", "SOFTMAX"):
             T[y] = PlanTensor(y, x.H, x.W, x.C)
+            p = producer.get(x.id)
+            if name == "LOGISTIC" and fuse_activations and p is not None and p.kind in LOGISTIC_INTO and p.act == ACT_NONE \
+                    and not p.copy and p.out == x.id and len(consumers.get(x.id, [])) == 1 and x.id != gout:
+                p.act, p.out, p.name = ACT_LOGISTIC, y, p.name + "+LOGISTIC"
+                producer[y] = p
+                del T[x.id]
+                continue
             emit(PlanOp(_lib.GRAPH_LOGISTIC if name == "LOGISTIC" else _lib.GRAPH_SOFTMAX, name, x.id, y,
                         param=float(op.get("beta", 1.0))), i)
         elif name == "PAD":
@@ -551,12 +622,13 @@ def pack_conv_filter(w_ohwi):
     return out
 
 
-def load_plan(path, input_shape=None, channel_map=None, quantised_math="hybrid"):
+def load_plan(path, input_shape=None, channel_map=None, quantised_math="hybrid", fuse_activations=True):
     from .tflite_reader import Graph
 
     with open(str(path), "rb") as fh:
         g = Graph(fh.read())
-    return g, build_plan(g, input_shape=input_shape, channel_map=channel_map, quantised_math=quantised_math)
+    return g, build_plan(g, input_shape=input_shape, channel_map=channel_map, quantised_math=quantised_math,
+                         fuse_activations=fuse_activations)
 
 
 class GraphDevice:

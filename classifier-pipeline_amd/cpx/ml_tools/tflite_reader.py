@@ -2,10 +2,13 @@
 only NumPy.  Two users:
 
 * `Graph` decodes subgraph 0 of any float32 model made of the operators in OPS below, with their options: CONV_2D
-  (dilation 1 only), DEPTHWISE_CONV_2D (filter [1, kh, kw, C]; depth multiplier 1 and dilation 1 only), AVERAGE_POOL_2D, MAX_POOL_2D, CONCATENATION, ADD, SUB, MUL, RELU, RELU6, MEAN, FULLY_CONNECTED,
+  (dilation 1 only), DEPTHWISE_CONV_2D (filter [1, kh, kw, C]; depth multiplier 1 and dilation 1 only), AVERAGE_POOL_2D, MAX_POOL_2D, CONCATENATION, ADD, SUB, MUL, DIV, RELU, RELU6, MEAN, FULLY_CONNECTED,
   LOGISTIC, SOFTMAX, RESHAPE, PAD.  That is the set the converter writes for the reference's `inceptionv3` family
   (ml_tools/kerasmodel.py:171-180,259-350; the artefact the reference's CI classifies with, .github/workflows/
-  release.yml:46 `inc3-tflite-15122023.tar`, is one) and for its `mobilenet` family (MobileNetV2, kerasmodel.py:144-151).  cpx/ml_tools/tflite_graph.py plans such a graph for the device
+  release.yml:46 `inc3-tflite-15122023.tar`, is one), for its `mobilenet` family (MobileNetV2, kerasmodel.py:144-151) and
+  for its `efficientnetb0` / `b1` / `b5` / `efficientnetv2b3` families (kerasmodel.py:181-216: swish as LOGISTIC + MUL of two
+  activations, the squeeze-and-excite gate as a broadcasting MUL, the in-model Rescaling / Normalization as MUL / SUB /
+  ADD / DIV by constants; HARD_SWISH is refused by name).  cpx/ml_tools/tflite_graph.py plans such a graph for the device
   executor (cpx_graph_*), the LiteInterpreter of cpx/ml_tools/interpreter.py runs it -- what the reference's
   LiteInterpreter does with any `.tflite` (src/ml_tools/interpreter.py:520-560,597-628).  A dynamic-range quantised file
   (what the reference's converter writes, src/tfliteconverter.py:54-62: the filters of CONV_2D / DEPTHWISE_CONV_2D / FULLY_CONNECTED
@@ -32,10 +35,11 @@ import numpy as np
 
 BN_EPS = np.float32(1e-3)
 OPS = {0: "ADD", 1: "AVERAGE_POOL_2D", 2: "CONCATENATION", 3: "CONV_2D", 4: "DEPTHWISE_CONV_2D", 9: "FULLY_CONNECTED", 14: "LOGISTIC",
-       17: "MAX_POOL_2D", 18: "MUL", 19: "RELU", 21: "RELU6", 25: "SOFTMAX", 40: "MEAN", 41: "SUB", 22: "RESHAPE", 34: "PAD"}
+       17: "MAX_POOL_2D", 18: "MUL", 19: "RELU", 21: "RELU6", 25: "SOFTMAX", 40: "MEAN", 41: "SUB", 22: "RESHAPE", 34: "PAD",
+       42: "DIV"}
 # operators that are recognised only to be refused by name (check_executable)
 REFUSED_OPS = {6: "DEQUANTIZE", 114: "QUANTIZE", 67: "TRANSPOSE_CONV", 23: "RESIZE_BILINEAR",
-               28: "TANH", 39: "TRANSPOSE", 32: "CUSTOM"}
+               28: "TANH", 39: "TRANSPOSE", 32: "CUSTOM", 117: "HARD_SWISH"}
 TENSOR_TYPES = {0: "FLOAT32", 1: "FLOAT16", 2: "INT32", 3: "UINT8", 4: "INT64", 6: "BOOL", 7: "INT16", 9: "INT8"}
 PADDING_SAME, PADDING_VALID = 0, 1
 ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 3
@@ -165,7 +169,7 @@ class Graph:
                              act=opts.scalar(5, "b", 0))
                 elif o["name"] == "CONCATENATION":
                     o.update(axis=opts.scalar(0, "i", 0), act=opts.scalar(1, "b", 0))
-                elif o["name"] in ("ADD", "MUL", "SUB", "FULLY_CONNECTED"):
+                elif o["name"] in ("ADD", "MUL", "SUB", "DIV", "FULLY_CONNECTED"):
                     o["act"] = opts.scalar(0, "b", 0)
                     if o["name"] == "FULLY_CONNECTED":
                         o["asymmetric_quantize_inputs"] = bool(opts.scalar(3, "b", 0))

@@ -32,7 +32,8 @@ static const char* graph_check_op(const cpx_graph_op& o, const std::vector<cpx_g
   if (o.out == input || o.in0 == output || o.in1 == output) return "the input is written or the output read";
   const cpx_graph_tensor &a = t[o.in0], &y = t[o.out];
   if (o.out_c_offset != y.c_offset || o.out_c_stride != y.c_stride) return "output slice differs from the tensor's";
-  if (o.activation != CPX_GRAPH_ACT_NONE && o.activation != CPX_GRAPH_ACT_RELU && o.activation != CPX_GRAPH_ACT_RELU6)
+  if (o.activation != CPX_GRAPH_ACT_NONE && o.activation != CPX_GRAPH_ACT_RELU && o.activation != CPX_GRAPH_ACT_RELU6 &&
+      o.activation != CPX_GRAPH_ACT_SWISH && o.activation != CPX_GRAPH_ACT_LOGISTIC)
     return "unknown activation";
   const bool same_hw = a.H == y.H && a.W == y.W;
   auto is_params = [&](int id) { return id >= 0 && t[id].H == 1 && t[id].W == 1 && t[id].C == 4; };
@@ -63,6 +64,13 @@ static const char* graph_check_op(const cpx_graph_op& o, const std::vector<cpx_g
       if (o.in1 < 0) return "ADD needs two inputs";
       if (!same_hw || a.C != y.C || t[o.in1].H != y.H || t[o.in1].W != y.W || t[o.in1].C != y.C) return "ADD of different shapes";
       break;
+    case CPX_GRAPH_MUL: {
+      if (o.in1 < 0) return "MUL needs two inputs";
+      const cpx_graph_tensor& b = t[o.in1];
+      if (!same_hw || a.C != y.C || b.C != y.C) return "MUL changes the shape";
+      if (!(b.H == y.H && b.W == y.W) && !(b.H == 1 && b.W == 1)) return "MUL: in1 has neither the shape of in0 nor 1 x 1 x C";
+      break;
+    }
     case CPX_GRAPH_AFFINE:
     case CPX_GRAPH_LOGISTIC:
     case CPX_GRAPH_SOFTMAX:

@@ -210,7 +210,8 @@ __global__ __launch_bounds__(CT) void graph_channel_map_kernel(GraphOpArgs a) {
   *at(a.out, n, y, x, c) = *at(a.in0, n, y, x, a.map[c]);
 }
 
-// MEAN over H and W: one thread per (sample, channel), pixels in order (channel-contiguous loads across the wave)
+// MEAN over H and W below GRAPH_MEAN_WIDE_PIXELS pixels: one thread per (sample, channel), pixels in order
+// (channel-contiguous loads across the wave)
 __global__ __launch_bounds__(CT) void graph_mean_kernel(GraphOpArgs a) {
   const size_t idx = (size_t)blockIdx.x * CT + threadIdx.x;
   if (idx >= (size_t)a.N * a.in0.C) return;
@@ -221,6 +222,103 @@ __global__ __launch_bounds__(CT) void graph_mean_kernel(GraphOpArgs a) {
   float sum = 0.0f;
   for (int i = 0; i < hw; ++i) sum += src[(unsigned)(i * a.in0.cstride)];
   a.out.p[n * a.out.sample_stride + c] = sum / (float)hw;
+}
+
+// MEAN over H and W from GRAPH_MEAN_WIDE_PIXELS pixels on (the 80 x 80 map in front of an EfficientNet's first
+// squeeze-and-excite block: 6400 dependent loads per thread of the kernel above, a few dozen threads at N = 1).  A
+// workgroup per (sample, MEAN_QG quads of channels); thread = (stripe, quad), quad fastest, so the MEAN_QG lanes of a
+// stripe read 16 * MEAN_QG contiguous bytes of a pixel.  Stripe i of GRAPH_MEAN_STRIPES sums the pixels i, i + 64, ... in
+// that order (independent loads, one chain of adds); the tree s[i] += s[i + d], d = 32 .. 1, combines them in LDS --
+// 16-byte reads of consecutive threads, no bank conflict.  The order depends on H * W alone: not on N, on the channel
+// slice, on VEC or on where the workgroup runs.  VEC: 16-byte loads; otherwise channel by channel, a channel beyond C
+// reads the view's last one and is not stored.
+constexpr int MEAN_QG = CT / GRAPH_MEAN_STRIPES;   // quads of channels per workgroup
+
+template <bool VEC>
+__global__ __launch_bounds__(CT) void graph_mean_wide_kernel(GraphOpArgs a, int groups) {
+  __shared__ __attribute__((aligned(16))) f32x4 s_sum[CT];
+  const int tid = threadIdx.x, stripe = tid / MEAN_QG, q = tid - stripe * MEAN_QG;
+  const size_t n = blockIdx.x / (unsigned)groups;
+  const int grp = (int)(blockIdx.x - n * (unsigned)groups);
+  const int c = 4 * (grp * MEAN_QG + q), C = a.in0.C;
+  const int hw = a.in0.H * a.in0.W;
+  f32x4 sum = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (c < C) {
+    const float* src = a.in0.p + n * a.in0.sample_stride + c;
+    auto load = [&](int i) {
+      const float* p = src + (unsigned)(i * a.in0.cstride);
+      f32x4 v;
+      if (VEC) {
+        v = *reinterpret_cast<const f32x4*>(p);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = p[min(j, C - 1 - c)];
+      }
+      return v;
+    };
+    // four loads in flight, added in the stripe's order
+    constexpr int S = GRAPH_MEAN_STRIPES;
+    int i = stripe;
+    for (; i + 3 * S < hw; i += 4 * S) {
+      const f32x4 v0 = load(i), v1 = load(i + S), v2 = load(i + 2 * S), v3 = load(i + 3 * S);
+      sum += v0;
+      sum += v1;
+      sum += v2;
+      sum += v3;
+    }
+    for (; i < hw; i += S) sum += load(i);
+  }
+  s_sum[tid] = sum;
+  __syncthreads();
+#pragma unroll
+  for (int d = GRAPH_MEAN_STRIPES / 2; d >= 1; d >>= 1) {
+    if (stripe < d) s_sum[tid] += s_sum[tid + d * MEAN_QG];
+    __syncthreads();
+  }
+  if (stripe == 0 && c < C) {
+    const f32x4 v = s_sum[tid];
+    float* dst = a.out.p + n * a.out.sample_stride + c;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (c + j < C) dst[j] = v[j] / (float)hw;
+  }
+}
+
+// MUL of two activations: in1 has in0's shape, or is the 1 x 1 x C gate of its sample.  HBM-bound: 8 bytes moved per
+// element with a gate (the gate's C floats per sample come from the cache), 12 with a same-shape in1.
+// The 16-byte path: an item is a quad of channels of a pixel, quad fastest, pixels flattened over the batch.
+__global__ __launch_bounds__(CT) void graph_mul_quad_kernel(GraphOpArgs a, size_t items, int gate) {
+  const size_t idx = (size_t)blockIdx.x * CT + threadIdx.x;
+  if (idx >= items) return;
+  const int C4 = a.out.C >> 2, hw = a.out.H * a.out.W;
+  size_t n;
+  int c, pix;
+  if ((items >> 32) == 0) {   // 32-bit divisions unless the batch needs more
+    const unsigned i = (unsigned)idx, p = i / (unsigned)C4, nn = p / (unsigned)hw;
+    c = 4 * (int)(i - p * C4);
+    pix = (int)(p - nn * hw);
+    n = nn;
+  } else {
+    const size_t p = idx / C4;
+    c = 4 * (int)(idx - p * C4);
+    n = p / hw;
+    pix = (int)(p - n * hw);
+  }
+  const f32x4 x = *reinterpret_cast<const f32x4*>(a.in0.p + n * a.in0.sample_stride + (unsigned)(pix * a.in0.cstride + c));
+  const f32x4 g = *reinterpret_cast<const f32x4*>(a.in1.p + n * a.in1.sample_stride + (unsigned)(gate ? c : pix * a.in1.cstride + c));
+  f32x4 v;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) v[j] = activate(x[j] * g[j], a.act);
+  *reinterpret_cast<f32x4*>(a.out.p + n * a.out.sample_stride + (unsigned)(pix * a.out.cstride + c)) = v;
+}
+
+// ... and element by element (an odd C, a concatenation slice off the 16-byte grid)
+__global__ __launch_bounds__(CT) void graph_mul_kernel(GraphOpArgs a, int gate) {
+  size_t n;
+  int y, x, c;
+  if (!out_coords(a, (size_t)blockIdx.x * CT + threadIdx.x, &n, &y, &x, &c)) return;
+  const float g = gate ? *at(a.in1, n, 0, 0, c) : *at(a.in1, n, y, x, c);
+  *at(a.out, n, y, x, c) = activate(*at(a.in0, n, y, x, c) * g, a.act);
 }
 
 // FULLY_CONNECTED: one wave per (sample, output); lanes stride over the inputs, a fixed butterfly sums them
@@ -243,7 +341,7 @@ __global__ __launch_bounds__(CT) void graph_logistic_kernel(GraphOpArgs a) {
   size_t n;
   int y, x, c;
   if (!out_coords(a, (size_t)blockIdx.x * CT + threadIdx.x, &n, &y, &x, &c)) return;
-  *at(a.out, n, y, x, c) = 1.0f / (1.0f + expf(-*at(a.in0, n, y, x, c)));
+  *at(a.out, n, y, x, c) = logistic(*at(a.in0, n, y, x, c));
 }
 
 // SOFTMAX over the channels of every pixel: one thread per pixel (the heads this runs have tens of labels)
@@ -302,8 +400,27 @@ void launch_graph_op(const GraphOpArgs& a, hipStream_t s) {
       hipLaunchKernelGGL(graph_channel_map_kernel, dim3(blocks_for(out_elems)), dim3(CT), 0, s, a);
       break;
     case CPX_GRAPH_MEAN:
-      hipLaunchKernelGGL(graph_mean_kernel, dim3(blocks_for((size_t)a.N * a.in0.C)), dim3(CT), 0, s, a);
+      if (a.in0.H * a.in0.W < GRAPH_MEAN_WIDE_PIXELS) {
+        hipLaunchKernelGGL(graph_mean_kernel, dim3(blocks_for((size_t)a.N * a.in0.C)), dim3(CT), 0, s, a);
+      } else {
+        const int groups = (a.in0.C + 4 * MEAN_QG - 1) / (4 * MEAN_QG);
+        const dim3 grid((unsigned)((size_t)a.N * groups));
+        if (quads(a.in0))
+          hipLaunchKernelGGL(graph_mean_wide_kernel<true>, grid, dim3(CT), 0, s, a, groups);
+        else
+          hipLaunchKernelGGL(graph_mean_wide_kernel<false>, grid, dim3(CT), 0, s, a, groups);
+      }
       break;
+    case CPX_GRAPH_MUL: {
+      const int gate = a.in1.H * a.in1.W == 1 && a.in0.H * a.in0.W != 1;
+      if (quads(a.in0) && quads(a.in1) && quads(a.out)) {
+        const size_t items = out_elems / 4;
+        hipLaunchKernelGGL(graph_mul_quad_kernel, dim3(blocks_for(items)), dim3(CT), 0, s, a, items, gate);
+      } else {
+        hipLaunchKernelGGL(graph_mul_kernel, dim3(blocks_for(out_elems)), dim3(CT), 0, s, a, gate);
+      }
+      break;
+    }
     case CPX_GRAPH_FC:
       hipLaunchKernelGGL(graph_fc_kernel, dim3((unsigned)(((size_t)a.N * a.out.C + 3) / 4)), dim3(CT), 0, s, a);
       break;

@@ -21,11 +21,22 @@
 
 namespace cpx {
 
+// LOGISTIC, and the sigmoid of a swish: the ONE place it is written, so that a fused activation and the LOGISTIC launch
+// are the same float32 operations.  expf(-v) overflows to inf for v < -88.7 (the result is 0, not NaN) and is 0 beyond 103.
+CPX_HD inline float logistic(float v) { return 1.0f / (1.0f + expf(-v)); }
+
 CPX_HD inline float activate(float v, int act) {
   if (act == CPX_GRAPH_ACT_RELU) return fmaxf(v, 0.0f);
   if (act == CPX_GRAPH_ACT_RELU6) return fminf(fmaxf(v, 0.0f), 6.0f);
+  if (act == CPX_GRAPH_ACT_SWISH) return v * logistic(v);
+  if (act == CPX_GRAPH_ACT_LOGISTIC) return logistic(v);
   return v;
 }
+
+// ---- MEAN ----
+// at this many pixels and above graph_mean_wide_kernel's order replaces the serial one (include/cpx.h: CPX_GRAPH_MEAN)
+constexpr int GRAPH_MEAN_WIDE_PIXELS = 256;
+constexpr int GRAPH_MEAN_STRIPES = 64;   // lanes that split the pixel range
 
 // ---- the hybrid (dynamic-range quantised) arithmetic ----
 // q = clamp(round-half-away(float32(x * inv)) + zp, -128, 127)

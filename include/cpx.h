@@ -805,7 +805,12 @@ enum {
   CPX_GRAPH_AVG_POOL = 3,    /* ... divided by the number of in-bounds elements */
   CPX_GRAPH_ADD = 4,         /* out = act(in0 + param * in1): param 1 (ADD) or -1 (SUB) */
   CPX_GRAPH_AFFINE = 5,      /* out = act(in0 * scale[c] + shift[c]); NULL scale / shift: 1 / 0 (a bare RELU, a copy) */
-  CPX_GRAPH_MEAN = 6,        /* over H and W -> 1 x 1 x C */
+  CPX_GRAPH_MEAN = 6,        /* over H and W -> 1 x 1 x C: float32(sum) / float32(H * W).  Two summation orders, by the
+                                pixel count alone.  H * W < 256: one chain sum += x over the pixels in raster order.
+                                H * W >= 256: 64 stripes, stripe i the pixels i, i + 64, i + 128, ... summed in that
+                                order from 0, then combined by a fixed tree: s[i] += s[i + d] for every i < d, with
+                                d = 32, 16, 8, 4, 2, 1; the sum is s[0].  Either order depends on (H * W, C) only,
+                                never on N, on the channel slice or on where the work lands on the device */
   CPX_GRAPH_FC = 7,          /* FULLY_CONNECTED on a 1 x 1 x C input: weights [Cout][Cin], shift = bias */
   CPX_GRAPH_LOGISTIC = 8,
   CPX_GRAPH_SOFTMAX = 9,     /* over C, param = beta */
@@ -832,10 +837,12 @@ enum {
                                 a padded tap contributes nothing.  It is the same chain wherever the pixel sits in a
                                 tile, a sample or a batch, and whichever instantiation (16-byte or channel by channel)
                                 runs it */
-  CPX_GRAPH_DWCONV_Q8 = 16   /* DEPTHWISE_CONV_2D with an int8 filter.  in1 as CONV_Q8.  `weights` as bytes: int8
+  CPX_GRAPH_DWCONV_Q8 = 16,  /* DEPTHWISE_CONV_2D with an int8 filter.  in1 as CONV_Q8.  `weights` as bytes: int8
                                 [kh * kw][C rounded up to 4] (zeros beyond), then int32 wsum[C rounded up to 4], the
                                 filter summed over its taps.  q, acc and out as CONV_Q8 below, with K = the taps (a
                                 padded tap is q = zp).  scale, shift: [C], not NULL */
+  CPX_GRAPH_MUL = 17         /* out = act(in0 * in1), one float32 multiply.  in1 has the shape of in0, or is 1 x 1 x C:
+                                the per-sample gate of a squeeze-and-excite block, broadcast over H and W */
 };
 /* The hybrid arithmetic, per sample.  QUANT_PARAMS: rmin = min(0, min x), rmax = max(0, max x) in float32.
  * rmin == rmax: sx = inv = 1, zp = 0.  Otherwise, in float64 from those two values: s = (rmax - rmin) / 255,
@@ -845,7 +852,14 @@ enum {
  * CONV_Q8 / FC_Q8 / DWCONV_Q8: q = clamp(round-half-away(float32(x * inv)) + zp, -128, 127); a padded tap is q = zp (a real 0);
  * acc = sum q * w in int32 (the caller keeps kh * kw * Cin * 127 * 255 below 2^31; DWCONV_Q8 sums kh * kw products);
  * out = act(float32(acc - zp * wsum[c]) * float32(sx * scale[c]) + shift[c]), each operation in float32 as written. */
-enum { CPX_GRAPH_ACT_NONE = 0, CPX_GRAPH_ACT_RELU = 1, CPX_GRAPH_ACT_RELU6 = 3 }; /* TFLite's ActivationFunctionType */
+enum {
+  CPX_GRAPH_ACT_NONE = 0, CPX_GRAPH_ACT_RELU = 1, CPX_GRAPH_ACT_RELU6 = 3, /* TFLite's ActivationFunctionType */
+  /* The planner's own codes, outside TFLite's ActivationFunctionType range (0 to 5): what it folds a LOGISTIC, or a
+   * LOGISTIC and the MUL behind it, into.  Each operation in float32 as written: a fused SWISH is the same float32
+   * operations as a LOGISTIC launch followed by a MUL launch. */
+  CPX_GRAPH_ACT_SWISH = 16,    /* v * (1 / (1 + expf(-v))) */
+  CPX_GRAPH_ACT_LOGISTIC = 17  /* 1 / (1 + expf(-v)): what CPX_GRAPH_LOGISTIC computes */
+};
 
 typedef struct cpx_graph_tensor {
   int32_t H, W, C;

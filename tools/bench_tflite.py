@@ -28,7 +28,15 @@ times a width-1.0 MobileNetV2 (tests/tflite_build_dw.py) the same way against Py
 batch, every depthwise launch alone (a one-operator graph of the same shape, HIP events): the bytes it must move -- input
 and output once, the weights -- over its time, against the HBM peak (8.0 TB/s; a float4 copy reaches 6.29).  With
 --quantised the hybrid twin (INT8 filters) is timed beside it.  --kernel-trace with --mobilenet splits a rocprofv3 trace
-of such a run by kind and gives the depthwise launches' bytes per second inside the forward."""
+of such a run by kind and gives the depthwise launches' bytes per second inside the forward.
+
+    python tools/bench_tflite.py --efficientnet [--batches 1,128]
+
+times an EfficientNet-B0 (tests/tflite_build_se.py; 160 x 160 x 3, the size a frame_size of 32 gives) with the swish and
+the sigmoid fused into their producers and with fuse_activations=False (LOGISTIC and MUL as launches), against
+PyTorch-ROCm float32 on the same graph.  --kernel-trace with --efficientnet (add --unfused for the other plan) splits a
+rocprofv3 trace of such a run by kind and gives, for the MUL, the wide MEAN and the depthwise launches, the bytes they
+must move over their time inside the forward against the HBM peak."""
 import argparse
 import json
 import os
@@ -41,7 +49,7 @@ for p in (os.path.join(REPO, "classifier-pipeline_amd"), os.path.join(REPO, "tes
     sys.path.insert(0, p)
 
 KIND_NAMES = {1: "conv", 2: "max_pool", 3: "avg_pool", 4: "add", 5: "affine", 6: "mean", 7: "fc", 8: "logistic", 9: "softmax",
-              10: "pad", 11: "channel_map", 12: "conv_q8", 13: "fc_q8", 14: "quant_params", 15: "dwconv", 16: "dwconv_q8"}
+              10: "pad", 11: "channel_map", 12: "conv_q8", 13: "fc_q8", 14: "quant_params", 15: "dwconv", 16: "dwconv_q8", 17: "mul"}
 DW_KINDS = (15, 16)
 HBM_PEAK_TBS = 8.0          # MI355X HBM3E, specification
 HBM_COPY_TBS = 6.29         # what a float4 copy kernel reaches
@@ -64,7 +72,7 @@ def torch_model(g, device):
         val = {g.inputs[0]: x_nchw}
         for op in g.ops:
             name, ins = op["name"], op["inputs"]
-            a = val[ins[0]]
+            a = val.get(ins[0])
             if name == "CONV_2D":
                 kh, kw = wts[ins[1]].shape[2:]
                 pt, pb = _pads(a.shape[2], kh, op["stride_h"], op["padding"])
@@ -82,8 +90,9 @@ def torch_model(g, device):
             elif name == "PAD":
                 (_, _), (t0, t1), (l0, l1), (_, _) = op["paddings"]
                 r = F.pad(a, (l0, l1, t0, t1))
-            elif name == "ADD":
-                r = _act(a + val[ins[1]], op["act"])
+            elif name in ("ADD", "SUB", "MUL", "DIV"):
+                p, q = (val[t] if t in val else const[t].reshape(1, -1, 1, 1) for t in ins[:2])
+                r = _act(p + q if name == "ADD" else p - q if name == "SUB" else p * q if name == "MUL" else p / q, op["act"])
             elif name in ("MAX_POOL_2D", "AVERAGE_POOL_2D"):
                 k, st = (op["filter_height"], op["filter_width"]), (op["stride_h"], op["stride_w"])
                 pt, pb = _pads(a.shape[2], k[0], st[0], op["padding"])
@@ -96,7 +105,7 @@ def torch_model(g, device):
             elif name == "CONCATENATION":
                 r = torch.cat([val[t] for t in ins], dim=1)
             elif name == "MEAN":
-                r = a.mean(dim=(2, 3))
+                r = a.mean(dim=(2, 3), keepdim=op["keep_dims"])
             elif name == "FULLY_CONNECTED":
                 r = _act(F.linear(a, const[ins[1]], const[ins[2]]), op["act"])
             elif name == "LOGISTIC":
@@ -280,6 +289,81 @@ def mobilenet_leg(args):
     print(json.dumps(out))
 
 
+def efficientnet_leg(args):
+    """ms per forward of an EfficientNet-B0, fused and unfused, by batch size, against PyTorch-ROCm float32."""
+    import ctypes as C
+
+    import tflite_build_se as ts
+    import torch
+    from cpx.engine import TrackEngine
+    from cpx.ml_tools.tflite_graph import GraphDevice, build_plan
+    from cpx.ml_tools.tflite_reader import Graph
+
+    size = 160
+    g = Graph(ts.efficientnet_b0(17, (), seed=7, width=args.width, size=size))
+    plans = {"fused": build_plan(g), "unfused": build_plan(g, fuse_activations=False)}
+    batches = [int(v) for v in args.batches.split(",")]
+    if args.kernel_trace:
+        name = "unfused" if args.unfused else "fused"
+        print(json.dumps(dict(split_from_trace(args.kernel_trace, plans[name], batches[-1]), plan=name)))
+        return
+    torch.backends.cudnn.allow_tf32 = False
+    torch.backends.cuda.matmul.allow_tf32 = False
+    eng = TrackEngine(model="lepton3", device=0)
+    stream = torch.cuda.ExternalStream(eng.lib.cpx_stream(eng.h), device=eng.device)
+    ref = torch_model(g, eng.device)
+    out = {"model": "efficientnet_b0 width %.2f %dx%dx3" % (args.width, size, size), "batches": []}
+    for name, plan in plans.items():
+        kinds = {}
+        for o in plan.ops:
+            kinds[KIND_NAMES[o.kind]] = kinds.get(KIND_NAMES[o.kind], 0) + 1
+        out[name] = {"launches": len(plan.ops), "launches_by_kind": kinds, "arena_bytes_per_sample": plan.arena_bytes_per_sample}
+    rng = np.random.default_rng(0)
+    for n in batches:
+        x = torch.from_numpy(rng.uniform(0, 255, size=(n, size, size, 3)).astype(np.float32)).to(eng.device)
+        rec, ys = {"N": n}, {}
+        for name, plan in plans.items():
+            if args.unfused and name == "fused" or args.skip_torch and not args.unfused and name == "unfused":
+                continue   # (a run under a profiler ends with forwards of ONE plan)
+            dev = GraphDevice(eng, plan)
+            y = ys[name] = torch.empty((n, 17), dtype=torch.float32, device=eng.device)
+
+            def forward():
+                rc = eng.lib.cpx_graph_forward(dev._graph, C.c_void_p(x.data_ptr()), n, C.c_void_p(y.data_ptr()))
+                assert rc == 0, eng._err()
+
+            with torch.cuda.stream(stream):
+                rec[name + "_ms"] = timed(torch, forward, args.steps, args.warmup)
+            dev.close()
+        if len(ys) == 2:
+            rec["fused_equals_unfused"] = bool(torch.equal(ys["fused"], ys["unfused"]))
+            rec["unfused_over_fused"] = rec["unfused_ms"] / rec["fused_ms"]
+        if not args.skip_torch:
+            x_nchw = x.permute(0, 3, 1, 2).contiguous()
+            with torch.no_grad():
+                rec["torch_ms"] = timed(torch, lambda: ref(x_nchw), args.steps, args.warmup)
+                rec["max_abs_diff_vs_torch"] = float((ref(x_nchw) - next(iter(ys.values()))).abs().max())
+            for name in ys:
+                rec["ratio_vs_torch_" + name] = rec["torch_ms"] / rec[name + "_ms"]
+        out["batches"].append(rec)
+    eng.close()
+    print(json.dumps(out))
+
+
+def hbm_group(plan, o, n):
+    """-> (group, bytes the launch must move for n samples) of the HBM-bound kinds beside the depthwise ones: MUL (in0 and the
+    output once, in1 once: C floats per sample where it is the gate) and the wide MEAN (its input once)."""
+    from cpx import _lib
+
+    t, i = plan.tensors[o.out], plan.tensors[o.in0]
+    if o.kind == _lib.GRAPH_MUL:
+        b = plan.tensors[o.in1]
+        return "mul", 4.0 * n * (2 * t.H * t.W * t.C + b.H * b.W * b.C)
+    if o.kind == _lib.GRAPH_MEAN and i.H * i.W >= _lib.GRAPH_MEAN_WIDE_PIXELS:
+        return "mean_wide", 4.0 * n * (i.H * i.W * i.C + i.C)
+    return None, 0.0
+
+
 def split_from_trace(path, plan, n):
     """The last forward of a rocprofv3 kernel trace: its launches are the plan's operators in order."""
     import csv
@@ -289,7 +373,7 @@ def split_from_trace(path, plan, n):
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     rows = rows[-len(plan.ops):]
     assert len(rows) == len(plan.ops), "the trace holds no whole forward"
-    by_kind, shapes, dws = {}, {}, {}
+    by_kind, shapes, dws, hbm = {}, {}, {}, {}
     for r, o in zip(rows, plan.ops):
         ns = int(r["End_Timestamp"]) - int(r["Start_Timestamp"])
         assert ("conv" in r["Kernel_Name"]) == (o.kind in (1, 12)) and ("graph_dw" in r["Kernel_Name"]) == (o.kind in DW_KINDS), \
@@ -297,6 +381,12 @@ def split_from_trace(path, plan, n):
         k = by_kind.setdefault(KIND_NAMES[o.kind], {"launches": 0, "ms": 0.0})
         k["launches"] += 1
         k["ms"] += ns / 1e6
+        grp, nbytes = hbm_group(plan, o, n)
+        if grp:
+            h = hbm.setdefault(grp, {"launches": 0, "ms": 0.0, "mbytes": 0.0})
+            h["launches"] += 1
+            h["ms"] += ns / 1e6
+            h["mbytes"] += nbytes / 1e6
         if o.kind in DW_KINDS:
             d = dws.setdefault(dw_shape(plan, o), {"launches": 0, "ms": 0.0, "mbytes": 0.0})
             d["launches"] += 1
@@ -322,6 +412,11 @@ def split_from_trace(path, plan, n):
         dw_mb, dw_ms = sum(d["mbytes"] for d in dws.values()), sum(d["ms"] for d in dws.values())
         dw = {"depthwise": {"launches": dws, "ms": dw_ms, "tb_per_s": dw_mb / dw_ms / 1e3,
                             "share_of_hbm_peak": dw_mb / dw_ms / 1e3 / HBM_PEAK_TBS, "share_of_copy_rate": dw_mb / dw_ms / 1e3 / HBM_COPY_TBS}}
+    for h in hbm.values():
+        h["tb_per_s"] = h["mbytes"] / h["ms"] / 1e3
+        h["share_of_hbm_peak"] = h["tb_per_s"] / HBM_PEAK_TBS
+    if hbm:
+        dw["hbm_bound"] = hbm
     return {**dw, "N": n, "forward_ms_first_start_to_last_end": wall, "kernel_ms_sum": busy, "gpu_busy_share": busy / wall,
             "ms_by_kind": by_kind, "conv_tflops_while_running": conv_gflop / conv["ms"],
             "conv_matrix_pipe_share": conv_gflop / conv["ms"] / F32_MFMA_PEAK_TFLOPS,
@@ -342,7 +437,15 @@ def main():
                     help="time a MobileNetV2 (DEPTHWISE_CONV_2D) instead of the Inception-v3, and its depthwise launches alone")
     ap.add_argument("--skip-alone", action="store_true",
                     help="with --mobilenet: do not time the depthwise launches alone (for a run under a profiler: the trace ends with a forward)")
+    ap.add_argument("--efficientnet", action="store_true",
+                    help="time an EfficientNet-B0 (swish, squeeze-and-excite) with its activations fused and unfused")
+    ap.add_argument("--unfused", action="store_true",
+                    help="with --efficientnet: the fuse_activations=False plan alone (a run under a profiler, and its --kernel-trace)")
     args = ap.parse_args()
+    if args.efficientnet:
+        if args.batches == "1,8,32,128":
+            args.batches = "1,128"
+        return efficientnet_leg(args)
     if args.mobilenet:
         return mobilenet_leg(args)
     if args.quantised:

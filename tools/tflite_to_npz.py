@@ -6,7 +6,7 @@ flatbuffer is parsed here, TensorFlow is not needed (only NumPy).
     python tools/tflite_to_npz.py --describe model.tflite
 
 --describe converts nothing: it prints the operator census, the input and output shapes, the arena bytes per sample and,
-for a dynamic-range quantised file, the number of hybrid operators with the int8 against the float32 weight bytes of ANY graph the device executor runs (cpx/ml_tools/tflite_graph.py: an Inception-v3 or a MobileNetV2, say), or the refusal -- the
+for a dynamic-range quantised file, the number of hybrid operators with the int8 against the float32 weight bytes of ANY graph the device executor runs (cpx/ml_tools/tflite_graph.py: an Inception-v3, a MobileNetV2 or an EfficientNet, say; the launches carry what was folded into them: CONV_2D+SWISH, CONV_2D+LOGISTIC, CONV_2D+MUL+ADD), or the refusal -- the
 operator and its index -- of one it does not.
 
 The reference loads this artefact with LiteInterpreter (/root/reference/src/ml_tools/interpreter.py:520-560); its CI
