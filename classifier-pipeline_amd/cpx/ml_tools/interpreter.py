@@ -360,10 +360,17 @@ class LiteInterpreter(Interpreter):
     (interpreter.py:520-560) with the TFLite runtime replaced.  model = <name>.tflite + <name>.json.
     predict runs the whole batch in one forward (the reference loops sample by sample because its runtime must).
     CPX_TFLITE_QUANT_MATH=hybrid|float (default hybrid) chooses how INT8 filters are run: on the int8 operators, or
-    multiplied out on the host and run in float32."""
+    multiplied out on the host and run in float32.
+    The resnet / resnet152 / vgg16 / vgg19 ('caffe') and densenet121 ('torch') families run here too: their
+    preprocess_input subtracts per-channel means of three colour channels, which the graph's INPUT operator does on the
+    device from the unscaled two-channel crop sample (input_mode; the host statements are caffe_preprocess /
+    torch_preprocess).  CPX_TFLITE_FUSE_PREACT=1|0 (default 1): fold a pre-activation into the convolutions that read
+    it (tflite_graph.build_plan: fuse_preactivation) or keep it a launch -- the same bits either way."""
 
     TYPE = "TFLite"
     DEFAULT_QUANT_MATH = "hybrid"
+    DEFAULT_FUSE_PREACT = "1"
+    INPUT_MODE_OF = {"resnet": "caffe", "resnet152": "caffe", "vgg16": "caffe", "vgg19": "caffe", "densenet121": "torch"}
 
     @classmethod
     def quant_math(cls):
@@ -373,6 +380,21 @@ class LiteInterpreter(Interpreter):
         if mode not in QUANT_MATHS:
             raise ValueError("CPX_TFLITE_QUANT_MATH=%r: one of %s" % (mode, ", ".join(QUANT_MATHS)))
         return mode
+
+    @classmethod
+    def fuse_preact(cls):
+        mode = os.environ.get("CPX_TFLITE_FUSE_PREACT", cls.DEFAULT_FUSE_PREACT)
+        if mode not in ("0", "1"):
+            raise ValueError("CPX_TFLITE_FUSE_PREACT=%r: one of 0, 1" % mode)
+        return mode == "1"
+
+    def get_preprocess_fn(self):
+        """The base class's, and the 'caffe' / 'torch' families it refuses: the host statement of what the graph's INPUT
+        operator does on the device; self.input_mode names the mode (None for every other family)."""
+        self.input_mode = self.INPUT_MODE_OF.get(self.params.model_name)
+        if self.input_mode is not None:
+            return caffe_preprocess if self.input_mode == "caffe" else torch_preprocess
+        return super().get_preprocess_fn()
 
     def __init__(self, model_file, run_over_network=False, load_model=True, engine=None):
         super().__init__(model_file, run_over_network)
@@ -391,8 +413,13 @@ class LiteInterpreter(Interpreter):
         with open(str(self.model_file), "rb") as fh:
             self._graph = Graph(fh.read())
         self._quant_math = self.quant_math()
-        plan = build_plan(self._graph, quantised_math=self._quant_math)   # refuses, by operator, what the executor does not run
+        self._fuse_preact = self.fuse_preact()
+        # refuses, by operator, what the executor does not run
+        plan = build_plan(self._graph, quantised_math=self._quant_math, fuse_preactivation=self._fuse_preact)
         self._plans[(plan.graph_input_shape, None)] = plan
+        if self.input_mode is not None and plan.graph_input_shape[2] != 3:
+            raise NotImplementedError("model_name %r: the %r input mode subtracts the means of three colour channels; the "
+                                      "graph has %d input channels" % (self.params.model_name, self.input_mode, plan.graph_input_shape[2]))
         if plan.output_shape[:2] != (1, 1) or plan.output_shape[2] != len(self.labels):
             raise ValueError("model output %s but %d labels" % (plan.output_shape, len(self.labels)))
 
@@ -409,7 +436,9 @@ class LiteInterpreter(Interpreter):
         if not channels or len(channels) > 4 or any(c not in ("thermal", "filtered") for c in channels):
             raise NotImplementedError("channels %s: the crop kernel builds thermal and filtered; a graph's input takes up to "
                                       "four of them, in any order, repeated" % (channels,))
-        return [0 if c == "thermal" else 1 for c in channels]
+        cmap = [0 if c == "thermal" else 1 for c in channels]
+        # 'caffe' models read BGR: the graph's channel c is the sample's channel of channels[2 - c]
+        return cmap[::-1] if self.input_mode == "caffe" else cmap
 
     def limits_flags(self, single=False):
         from .._lib import LIMITS_ALWAYS_CLIP, LIMITS_NO_DIFF_NORM, LIMITS_TF_SCALING, LIMITS_THERMAL_DIFF_NORM
@@ -422,17 +451,20 @@ class LiteInterpreter(Interpreter):
             flags |= LIMITS_NO_DIFF_NORM
         if single:
             flags |= LIMITS_ALWAYS_CLIP
-        if self.preprocess_fn is not None:
+        # the 'tf' families alone: the 'caffe' / 'torch' graphs take the unscaled 0..255 sample (their INPUT operator)
+        if self.preprocess_fn is not None and self.input_mode is None:
             flags |= LIMITS_TF_SCALING
         return flags
 
-    def _device(self, engine, hwc):
-        """One device graph per engine and input shape; hwc: the sample as it arrives."""
-        from .tflite_graph import GraphDevice, build_plan
+    def _plan(self, hwc):
+        """-> (key, plan) for a sample that arrives as hwc; host work.  A sample of the graph's own channel count is taken
+        as preprocessed by the caller; the crop kernel's two-channel sample goes through the channel map, which for the
+        'caffe' / 'torch' families is the INPUT operator."""
+        from .tflite_graph import build_plan
 
         cin = self._plans[next(iter(self._plans))].graph_input_shape[2]
         cmap = None
-        if hwc[2] != cin or (hwc[2] == 2 and self.channel_map() != [0, 1]):
+        if hwc[2] != cin or (hwc[2] == 2 and (self.input_mode is not None or self.channel_map() != [0, 1])):
             cmap = self.channel_map()
             if hwc[2] != 2 or len(cmap) != cin:
                 raise ValueError("samples of %d channels, channels %s, for a graph of %d input channels"
@@ -441,7 +473,15 @@ class LiteInterpreter(Interpreter):
         plan = self._plans.get(key)
         if plan is None:
             plan = self._plans[key] = build_plan(self._graph, input_shape=key[0], channel_map=cmap,
-                                                 quantised_math=self._quant_math)
+                                                 quantised_math=self._quant_math, fuse_preactivation=self._fuse_preact,
+                                                 input_mode=None if cmap is None else self.input_mode)
+        return key, plan
+
+    def _device(self, engine, hwc):
+        """One device graph per engine and input shape; hwc: the sample as it arrives."""
+        from .tflite_graph import GraphDevice
+
+        key, plan = self._plan(hwc)
         dev = self._devices.get((id(engine), key))
         if dev is None or dev.eng is not engine or not engine.h:
             dev = self._devices[(id(engine), key)] = GraphDevice(engine, plan)
@@ -488,6 +528,28 @@ def inc3_preprocess(x):
     """interpreter.py:563-566 (= tf.keras.applications' 'tf' mode), in place on a float32 array."""
     x /= 127.5
     x -= 1.0
+    return x
+
+
+def caffe_preprocess(x):
+    """keras.applications.imagenet_utils._preprocess_numpy_input, mode 'caffe', channels last: RGB -> BGR (a view), then
+    the ImageNet means subtracted in place; the Python-float constants act as float32 on a float32 array."""
+    x = x[..., ::-1]
+    x[..., 0] -= 103.939
+    x[..., 1] -= 116.779
+    x[..., 2] -= 123.68
+    return x
+
+
+def torch_preprocess(x):
+    """... mode 'torch': scaled to 0..1, then normalised channel by channel by the ImageNet means and deviations."""
+    x /= 255.0
+    x[..., 0] -= 0.485
+    x[..., 1] -= 0.456
+    x[..., 2] -= 0.406
+    x[..., 0] /= 0.229
+    x[..., 1] /= 0.224
+    x[..., 2] /= 0.225
     return x
 
 

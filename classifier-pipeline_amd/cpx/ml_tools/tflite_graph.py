@@ -13,6 +13,14 @@
   with that activation.  A LOGISTIC behind a CONV_2D / DEPTHWISE_CONV_2D (float32 or hybrid) that nothing else reads is
   folded as the activation LOGISTIC (the gate of a squeeze-and-excite block); behind a FULLY_CONNECTED it stays a launch.
   fuse_activations=False keeps every LOGISTIC and MUL a launch: the same float32 operations, bit for bit;
+* a pre-activation (DenseNet's and ResNetV2's BatchNorm + ReLU IN FRONT of a convolution: MUL + ADD by constants with a
+  fused RELU on a tensor that has other readers, so one AFFINE) is, with fuse_preactivation=True, dropped where every
+  reader of its output is a float32 CONV and that output is a tensor of its own (not the graph's output, in no
+  concatenation): those convolutions become CONV_PRE, read the AFFINE's input -- a channel slice of a concatenated
+  tensor included -- and apply the two float32 operations and the activation while they stage the patch, bit for bit
+  what the launch did (pack_conv_pre: the constants ride behind the filter image);
+* input_mode "caffe" / "torch" plans the INPUT operator where the channel map stands: the channel map plus the
+  arithmetic of keras.applications' preprocess_input in those modes on the unscaled sample (INPUT_MODES);
 * any other MUL of two activations is a MUL operator: two tensors of one shape, or [H, W, C] by the [1, 1, C] gate of a
   squeeze-and-excite block in either operand order.  Every other broadcast is refused;
 * MEAN over H and W, with or without keep_dims (and the RESHAPE to [1, 1, 1, C] older Keras versions put behind it, a view),
@@ -123,15 +131,30 @@ FOLD_INTO = (_lib.GRAPH_CONV, _lib.GRAPH_CONV_Q8, _lib.GRAPH_DWCONV, _lib.GRAPH_
 LOGISTIC_INTO = (_lib.GRAPH_CONV, _lib.GRAPH_CONV_Q8, _lib.GRAPH_DWCONV, _lib.GRAPH_DWCONV_Q8)
 ACT_SWISH, ACT_LOGISTIC = _lib.GRAPH_ACT_SWISH, _lib.GRAPH_ACT_LOGISTIC
 
+# the 'caffe' / 'torch' modes of keras.applications.imagenet_utils.preprocess_input as the INPUT operator's constants
+# (include/cpx.h: CPX_GRAPH_INPUT): mode -> (param, shift per graph channel, scale or None, the graph reads BGR)
+INPUT_MODES = {
+    "caffe": (1.0, np.array([103.939, 116.779, 123.68], np.float32), None, True),
+    "torch": (255.0, np.array([0.485, 0.456, 0.406], np.float32), np.array([0.229, 0.224, 0.225], np.float32), False),
+}
+PRE_ACTS = (ACT_RELU, ACT_RELU6)
 
-def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_math="hybrid", fuse_activations=True):
+
+def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_math="hybrid", fuse_activations=True,
+               input_mode=None, fuse_preactivation=False):
     """g: tflite_reader.Graph.  input_shape: (H, W, C) of a sample, default: the flatbuffer's.  output: the tensor the
     forward hands out, default the graph's output; the operators it does not need are dropped.  channel_map: up to 4
     indices into the channels of the sample the CALLER brings ([N, H, W, max(map) + 1 or more]): the graph's input
     channel c is the caller's channel channel_map[c].  quantised_math: "hybrid" runs INT8 filters on the int8 operators,
-    "float" multiplies them out on the host.  fuse_activations=False: LOGISTIC and the MUL of a swish stay launches."""
+    "float" multiplies them out on the host.  fuse_activations=False: LOGISTIC and the MUL of a swish stay launches.
+    input_mode: "caffe" | "torch": the caller brings the unscaled 0..255 sample and the channel map becomes the INPUT
+    operator, which also does that mode's arithmetic on exactly three graph channels; channel_map is what the graph
+    reads, so the BGR reversal of 'caffe' is the caller's (LiteInterpreter.channel_map).  fuse_preactivation: an AFFINE with a RELU / RELU6 whose only readers are float32
+    convolutions is dropped and those convolutions become CONV_PRE (the same float32 operations, bit for bit)."""
     if quantised_math not in QUANT_MATHS:
         raise ValueError("quantised_math %r: one of %s" % (quantised_math, ", ".join(QUANT_MATHS)))
+    if input_mode is not None and input_mode not in INPUT_MODES:
+        raise ValueError("input_mode %r: one of %s" % (input_mode, ", ".join(sorted(INPUT_MODES))))
     g.check_executable()
     if len(g.inputs) != 1 or len(g.outputs) < 1:
         raise NotImplementedError("graphs with %d inputs" % len(g.inputs))
@@ -445,6 +468,9 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
             raise NotImplementedError("RESHAPE changes the element count")
 
     # ---- the input: as the caller brings it, or through the channel map ----
+    if input_mode is not None and (channel_map is None or T[gin].C != 3):
+        raise ValueError("input_mode %r subtracts the means of three colour channels: it needs a channel map and a graph of "
+                         "exactly three input channels, not %s and %d" % (input_mode, channel_map, T[gin].C))
     if channel_map is not None:
         cmap = [int(c) for c in channel_map]
         if len(cmap) != T[gin].C or not 1 <= len(cmap) <= 4 or min(cmap) < 0:
@@ -452,7 +478,12 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
         ext = PlanTensor("input", T[gin].H, T[gin].W, max(max(cmap) + 1, 2))
         ext.storage = ext.id
         T[ext.id] = ext
-        o = PlanOp(_lib.GRAPH_CHANNEL_MAP, "CHANNEL_MAP", ext.id, gin, channel_map=cmap)
+        if input_mode is None:
+            o = PlanOp(_lib.GRAPH_CHANNEL_MAP, "CHANNEL_MAP", ext.id, gin, channel_map=cmap)
+        else:
+            param, shift, scale, _ = INPUT_MODES[input_mode]
+            o = PlanOp(_lib.GRAPH_INPUT, "INPUT", ext.id, gin, channel_map=cmap, param=param, shift=shift.copy(),
+                       scale=None if scale is None else scale.copy(), input_mode=input_mode)
         o.source = -1
         ops.insert(0, o)
         plan.input = ext.id
@@ -475,6 +506,27 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
             if o.in1 != -1:
                 needed.add(T[o.in1].storage)
     ops = kept[::-1]
+
+    # ---- the pre-activation of a DenseNet / ResNetV2 block: an AFFINE with a RELU in front of float32 convolutions ----
+    # (the tensor has other readers -- the next concatenation, the shortcut -- so it could not fold into its producer)
+    if fuse_preactivation:
+        for o in list(ops):
+            if o.kind != _lib.GRAPH_AFFINE or o.copy or o.act not in PRE_ACTS or o.in0 == o.out or o.out == gout:
+                continue
+            # its output is a tensor of its own: in no concatenation, not the output's storage, no view of it read
+            if T[o.out].storage != o.out or o.out == out_storage or \
+                    any(t.storage == o.out and k != o.out for k, t in T.items()):
+                continue
+            readers = [r for r in ops if o.out in (r.in0, r.in1)]
+            if not readers or any(r.kind != _lib.GRAPH_CONV or r.in0 != o.out for r in readers):
+                continue
+            cin = T[o.in0].C
+            for r in readers:
+                r.kind, r.in0, r.param, r.name = _lib.GRAPH_CONV_PRE, o.in0, float(o.act), "AFFINE>" + r.name
+                r.pre_scale = np.ones(cin, np.float32) if o.scale is None else o.scale
+                r.pre_shift = np.zeros(cin, np.float32) if o.shift is None else o.shift
+                r.pre_source = o.source
+            ops.remove(o)
     used = set()
     for o in ops:
         used.update((o.in0, o.out) + ((o.in1,) if o.in1 != -1 else ()))
@@ -525,6 +577,8 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
     packers = {_lib.GRAPH_CONV: pack_conv_filter, _lib.GRAPH_CONV_Q8: pack_conv_filter_q8,
                _lib.GRAPH_DWCONV: pack_dw_filter, _lib.GRAPH_DWCONV_Q8: pack_dw_filter_q8}
     for o in ops:
+        if o.kind == _lib.GRAPH_CONV_PRE:
+            o.weights = pack_conv_pre(o.filter, o.pre_scale, o.pre_shift)
         if o.kind in packers:
             o.weights = packers[o.kind](o.filter)
             if o.filter_scale is not None:   # the device multiplies by float32(filter scale x folded scale)
@@ -622,13 +676,24 @@ def pack_conv_filter(w_ohwi):
     return out
 
 
-def load_plan(path, input_shape=None, channel_map=None, quantised_math="hybrid", fuse_activations=True):
+def pack_conv_pre(w_ohwi, pre_scale, pre_shift):
+    """The weights of a CONV_PRE, flat: the pack_conv_filter image, then pre_scale and pre_shift, each Cin rounded up to
+    GRAPH_CONV_KC with zeros beyond."""
+    ci = w_ohwi.shape[3]
+    cip = -(-ci // _lib.GRAPH_CONV_KC) * _lib.GRAPH_CONV_KC
+    consts = np.zeros((2, cip), np.float32)
+    consts[0, :ci], consts[1, :ci] = pre_scale, pre_shift
+    return np.concatenate([pack_conv_filter(w_ohwi).reshape(-1), consts.reshape(-1)])
+
+
+def load_plan(path, input_shape=None, channel_map=None, quantised_math="hybrid", fuse_activations=True, input_mode=None,
+              fuse_preactivation=False):
     from .tflite_reader import Graph
 
     with open(str(path), "rb") as fh:
         g = Graph(fh.read())
     return g, build_plan(g, input_shape=input_shape, channel_map=channel_map, quantised_math=quantised_math,
-                         fuse_activations=fuse_activations)
+                         fuse_activations=fuse_activations, input_mode=input_mode, fuse_preactivation=fuse_preactivation)
 
 
 class GraphDevice:

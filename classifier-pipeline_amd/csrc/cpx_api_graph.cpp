@@ -39,13 +39,14 @@ static const char* graph_check_op(const cpx_graph_op& o, const std::vector<cpx_g
   auto is_params = [&](int id) { return id >= 0 && t[id].H == 1 && t[id].W == 1 && t[id].C == 4; };
   switch (o.kind) {
     case CPX_GRAPH_CONV:
+    case CPX_GRAPH_CONV_PRE:
     case CPX_GRAPH_CONV_Q8:
     case CPX_GRAPH_DWCONV:
     case CPX_GRAPH_DWCONV_Q8:
     case CPX_GRAPH_MAX_POOL:
     case CPX_GRAPH_AVG_POOL: {
       const bool dw = o.kind == CPX_GRAPH_DWCONV || o.kind == CPX_GRAPH_DWCONV_Q8;
-      const bool conv = dw || o.kind == CPX_GRAPH_CONV || o.kind == CPX_GRAPH_CONV_Q8;
+      const bool conv = dw || o.kind == CPX_GRAPH_CONV || o.kind == CPX_GRAPH_CONV_PRE || o.kind == CPX_GRAPH_CONV_Q8;
       if (o.kh < 1 || o.kw < 1 || o.kh > 7 || o.kw > 7) return "kernel sides are 1 to 7";
       if (o.stride_h < 1 || o.stride_w < 1 || o.stride_h > (conv ? 2 : 7) || o.stride_w > (conv ? 2 : 7)) return "bad stride";
       if (o.pad_top < 0 || o.pad_left < 0 || o.pad_bottom < 0 || o.pad_right < 0 || o.pad_top >= o.kh || o.pad_bottom >= o.kh ||
@@ -56,6 +57,10 @@ static const char* graph_check_op(const cpx_graph_op& o, const std::vector<cpx_g
       if (conv && !o.weights) return "CONV without weights";
       if (!conv && a.C != y.C) return "pool changes the channel count";
       if (dw && a.C != y.C) return "DWCONV changes the channel count (depth multiplier 1 only)";
+      if (o.kind == CPX_GRAPH_CONV_PRE) {
+        if (o.param != (float)CPX_GRAPH_ACT_RELU && o.param != (float)CPX_GRAPH_ACT_RELU6) return "CONV_PRE: param is the pre-activation, RELU or RELU6";
+        if (reinterpret_cast<uintptr_t>(o.weights) & 15) return "CONV_PRE weights are not 16-byte aligned";
+      }
       if (o.kind == CPX_GRAPH_DWCONV && (reinterpret_cast<uintptr_t>(o.weights) & 15)) return "DWCONV weights are not 16-byte aligned";
       if (o.kind == CPX_GRAPH_DWCONV_Q8 && (reinterpret_cast<uintptr_t>(o.weights) & 3)) return "DWCONV_Q8 weights are not 4-byte aligned";
       break;
@@ -92,6 +97,9 @@ static const char* graph_check_op(const cpx_graph_op& o, const std::vector<cpx_g
           y.H != a.H + o.pad_top + o.pad_bottom || y.W != a.W + o.pad_left + o.pad_right)
         return "PAD sizes do not add up";
       break;
+    case CPX_GRAPH_INPUT:
+      if (!o.shift || !(o.param > 0.0f)) return "INPUT needs a shift and a positive param";
+      /* fall through */
     case CPX_GRAPH_CHANNEL_MAP:
       if (!same_hw || o.n_map != y.C || o.n_map < 1 || o.n_map > 4) return "channel map of 1 to 4 output channels";
       for (int c = 0; c < o.n_map; ++c)

@@ -12,6 +12,9 @@
 //   K = kh * kw * Cin walked as (tap) x (chunk of 16 input channels) x (pair of channels)
 // Weights arrive [tap][Cin rounded up to 16][Cout rounded up to 32] with zeros beyond, so only the activation side is
 // masked.  Scale / shift (bias, folded MUL / ADD), the activation and the channel-sliced store happen from the accumulators.
+// CONV_PRE is the same kernel with a prologue: the pre-activation act(x * pre_scale[c] + pre_shift[c]) of a DenseNet /
+// ResNetV2 block is applied to the patch on its way from memory to LDS, as the WR-ResNet kernels do (cpx_cnn_bf3.hip), so
+// the AFFINE launch in front of the convolution and its round trip through memory go away.
 #include <hip/hip_runtime.h>
 
 #include "cpx_graph_core.h"
@@ -34,7 +37,9 @@ struct ConvGeom {
   int HoWo, cin_pad, cout_pad, vec4;
 };
 
-template <int NTN>
+// PRE: the input is read as activate(x * pre_scale[c] + pre_shift[c], (int)a.param), the two float32 operations and the
+// activation of graph_affine_kernel; the constants sit behind the filter image, pre_scale[cin_pad] then pre_shift[cin_pad]
+template <int NTN, bool PRE>
 __global__ __launch_bounds__(CT) void graph_conv_kernel(GraphOpArgs a, ConvGeom g) {
   constexpr int BN = 32 * NTN;
   __shared__ __attribute__((aligned(16))) float s_a[KC * AP];   // [k][pixel]
@@ -66,6 +71,11 @@ __global__ __launch_bounds__(CT) void graph_conv_kernel(GraphOpArgs a, ConvGeom 
 
   float pre[8];
   f32x4 pre_w = {0.0f, 0.0f, 0.0f, 0.0f};
+  const float* pre_scale = a.weights + (size_t)a.kh * a.kw * g.cin_pad * g.cout_pad;
+  // activate() for the two codes a pre-activation has, without its branches: fminf(fmaxf(v, 0), 6 or inf), the same bits
+  const float pre_hi = (int)a.param == CPX_GRAPH_ACT_RELU6 ? 6.0f : INFINITY;
+  f32x4 pre_sc[2], pre_sh[2];
+  bool pre_in = false;
 
   // global -> registers of step s (branch-free: a masked element reads the sample's first element and is zeroed)
   auto fetch = [&](int s) {
@@ -93,12 +103,35 @@ __global__ __launch_bounds__(CT) void graph_conv_kernel(GraphOpArgs a, ConvGeom 
         pre[j] = ok ? v : 0.0f;
       }
     }
+    if (PRE) {
+      // the constants of this step's channels travel with the patch, and whether the mask let the pixel through: the
+      // prologue itself waits until the values are needed (below), so the loads stay in flight under the MFMAs.
+      // c + 8 <= cin_pad and the image in front is a multiple of 16 x 32 floats: the quads are in bounds and aligned
+      pre_in = inside;
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        pre_sc[q] = *reinterpret_cast<const f32x4*>(pre_scale + c + 4 * q);
+        pre_sh[q] = *reinterpret_cast<const f32x4*>(pre_scale + g.cin_pad + c + 4 * q);
+      }
+    }
     if (wload)
       pre_w = *reinterpret_cast<const f32x4*>(a.weights + ((size_t)(tap * g.cin_pad + c0 + wk) * g.cout_pad + cout0 + 4 * wc4));
   };
 
   fetch(0);
   for (int s = 0; s < steps; ++s) {
+    if (PRE) {
+      // the prologue, behind the mask: a padded tap and a pixel beyond the batch stay exactly 0, not act(pre_shift); a
+      // channel beyond Cin was fetched as 0 and its constants are the image's zero padding: 0 * 0 + 0
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float v = pre[j];
+        v *= pre_sc[j >> 2][j & 3];
+        v += pre_sh[j >> 2][j & 3];
+        v = fminf(fmaxf(v, 0.0f), pre_hi);
+        pre[j] = pre_in ? v : 0.0f;
+      }
+    }
 #pragma unroll
     for (int j = 0; j < 8; ++j) s_a[(8 * half + j) * AP + spx] = pre[j];
     if (wload) *reinterpret_cast<f32x4*>(s_b + wk * BN + 4 * wc4) = pre_w;
@@ -208,6 +241,18 @@ __global__ __launch_bounds__(CT) void graph_channel_map_kernel(GraphOpArgs a) {
   int y, x, c;
   if (!out_coords(a, (size_t)blockIdx.x * CT + threadIdx.x, &n, &y, &x, &c)) return;
   *at(a.out, n, y, x, c) = *at(a.in0, n, y, x, a.map[c]);
+}
+
+// INPUT: the channel map with the 'caffe' / 'torch' arithmetic of keras.applications' preprocess_input, each operation
+// one correctly rounded float32 operation as written (include/cpx.h); a NULL scale: no second division
+__global__ __launch_bounds__(CT) void graph_input_kernel(GraphOpArgs a) {
+  size_t n;
+  int y, x, c;
+  if (!out_coords(a, (size_t)blockIdx.x * CT + threadIdx.x, &n, &y, &x, &c)) return;
+  float v = *at(a.in0, n, y, x, a.map[c]) / a.param;
+  v -= a.shift[c];
+  if (a.scale) v = v / a.scale[c];
+  *at(a.out, n, y, x, c) = v;
 }
 
 // MEAN over H and W below GRAPH_MEAN_WIDE_PIXELS pixels: one thread per (sample, channel), pixels in order
@@ -367,7 +412,8 @@ unsigned blocks_for(size_t items) { return (unsigned)((items + CT - 1) / CT); }
 void launch_graph_op(const GraphOpArgs& a, hipStream_t s) {
   const size_t out_elems = (size_t)a.N * a.out.H * a.out.W * a.out.C;
   switch (a.kind) {
-    case CPX_GRAPH_CONV: {
+    case CPX_GRAPH_CONV:
+    case CPX_GRAPH_CONV_PRE: {
       ConvGeom g;
       g.HoWo = a.out.H * a.out.W;
       g.P = (long long)a.N * g.HoWo;
@@ -375,10 +421,20 @@ void launch_graph_op(const GraphOpArgs& a, hipStream_t s) {
       g.cout_pad = (a.out.C + GRAPH_CONV_CO - 1) / GRAPH_CONV_CO * GRAPH_CONV_CO;
       g.vec4 = quads(a.in0);
       const unsigned gx = (unsigned)((g.P + BM - 1) / BM);
-      if (g.cout_pad % 64 == 0)
-        hipLaunchKernelGGL(graph_conv_kernel<2>, dim3(gx, g.cout_pad / 64), dim3(CT), 0, s, a, g);
-      else
-        hipLaunchKernelGGL(graph_conv_kernel<1>, dim3(gx, g.cout_pad / 32), dim3(CT), 0, s, a, g);
+      const bool pre = a.kind == CPX_GRAPH_CONV_PRE;
+      if (g.cout_pad % 64 == 0) {
+        const dim3 grid(gx, g.cout_pad / 64);
+        if (pre)
+          hipLaunchKernelGGL((graph_conv_kernel<2, true>), grid, dim3(CT), 0, s, a, g);
+        else
+          hipLaunchKernelGGL((graph_conv_kernel<2, false>), grid, dim3(CT), 0, s, a, g);
+      } else {
+        const dim3 grid(gx, g.cout_pad / 32);
+        if (pre)
+          hipLaunchKernelGGL((graph_conv_kernel<1, true>), grid, dim3(CT), 0, s, a, g);
+        else
+          hipLaunchKernelGGL((graph_conv_kernel<1, false>), grid, dim3(CT), 0, s, a, g);
+      }
       break;
     }
     case CPX_GRAPH_MAX_POOL:
@@ -398,6 +454,9 @@ void launch_graph_op(const GraphOpArgs& a, hipStream_t s) {
       break;
     case CPX_GRAPH_CHANNEL_MAP:
       hipLaunchKernelGGL(graph_channel_map_kernel, dim3(blocks_for(out_elems)), dim3(CT), 0, s, a);
+      break;
+    case CPX_GRAPH_INPUT:
+      hipLaunchKernelGGL(graph_input_kernel, dim3(blocks_for(out_elems)), dim3(CT), 0, s, a);
       break;
     case CPX_GRAPH_MEAN:
       if (a.in0.H * a.in0.W < GRAPH_MEAN_WIDE_PIXELS) {

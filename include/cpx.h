@@ -841,8 +841,20 @@ enum {
                                 [kh * kw][C rounded up to 4] (zeros beyond), then int32 wsum[C rounded up to 4], the
                                 filter summed over its taps.  q, acc and out as CONV_Q8 below, with K = the taps (a
                                 padded tap is q = zp).  scale, shift: [C], not NULL */
-  CPX_GRAPH_MUL = 17         /* out = act(in0 * in1), one float32 multiply.  in1 has the shape of in0, or is 1 x 1 x C:
+  CPX_GRAPH_MUL = 17,        /* out = act(in0 * in1), one float32 multiply.  in1 has the shape of in0, or is 1 x 1 x C:
                                 the per-sample gate of a squeeze-and-excite block, broadcast over H and W */
+  CPX_GRAPH_INPUT = 18,      /* CHANNEL_MAP with the 'caffe' / 'torch' arithmetic of keras.applications' preprocess_input:
+                                out[c] = ((in0[channel_map[c]] / param) - shift[c]) / scale[c], c < n_map, each operation
+                                one correctly rounded float32 operation as written.  shift: [n_map], not NULL; param > 0;
+                                a NULL scale: no second division.  caffe: param 1, shift = the BGR means, scale NULL (the
+                                BGR reversal is the caller's channel_map); torch: param 255, shift = the means, scale =
+                                the standard deviations */
+  CPX_GRAPH_CONV_PRE = 19    /* CONV whose input is read as act_pre(x * pre_scale[c] + pre_shift[c]): the two float32
+                                operations and the activation of AFFINE, so the same bits as an AFFINE launch in front of
+                                a CONV.  `weights` (16-byte aligned): the CONV image, then float32 pre_scale[Cin rounded up
+                                to 16], then pre_shift[the same], zeros beyond Cin.  param = act_pre as a number:
+                                CPX_GRAPH_ACT_RELU or CPX_GRAPH_ACT_RELU6.  A padded tap and a channel beyond Cin
+                                contribute exactly 0, not act_pre(pre_shift).  `activation`, scale, shift: as CONV */
 };
 /* The hybrid arithmetic, per sample.  QUANT_PARAMS: rmin = min(0, min x), rmax = max(0, max x) in float32.
  * rmin == rmax: sx = inv = 1, zp = 0.  Otherwise, in float64 from those two values: s = (rmax - rmin) / 255,

@@ -36,7 +36,13 @@ times an EfficientNet-B0 (tests/tflite_build_se.py; 160 x 160 x 3, the size a fr
 the sigmoid fused into their producers and with fuse_activations=False (LOGISTIC and MUL as launches), against
 PyTorch-ROCm float32 on the same graph.  --kernel-trace with --efficientnet (add --unfused for the other plan) splits a
 rocprofv3 trace of such a run by kind and gives, for the MUL, the wide MEAN and the depthwise launches, the bytes they
-must move over their time inside the forward against the HBM peak."""
+must move over their time inside the forward against the HBM peak.
+
+    python tools/bench_tflite.py --densenet [--batches 1,8,32,128]
+
+times a DenseNet121 (tests/tflite_build_preact.py; 160 x 160 x 3) with its 61 pre-activations folded into the 1 x 1
+convolutions that read them (fuse_preactivation=True: what LiteInterpreter runs) and as AFFINE launches, the same bits,
+against PyTorch-ROCm float32 on the same graph."""
 import argparse
 import json
 import os
@@ -49,7 +55,7 @@ for p in (os.path.join(REPO, "classifier-pipeline_amd"), os.path.join(REPO, "tes
     sys.path.insert(0, p)
 
 KIND_NAMES = {1: "conv", 2: "max_pool", 3: "avg_pool", 4: "add", 5: "affine", 6: "mean", 7: "fc", 8: "logistic", 9: "softmax",
-              10: "pad", 11: "channel_map", 12: "conv_q8", 13: "fc_q8", 14: "quant_params", 15: "dwconv", 16: "dwconv_q8", 17: "mul"}
+              10: "pad", 11: "channel_map", 12: "conv_q8", 13: "fc_q8", 14: "quant_params", 15: "dwconv", 16: "dwconv_q8", 17: "mul", 18: "input", 19: "conv_pre"}
 DW_KINDS = (15, 16)
 HBM_PEAK_TBS = 8.0          # MI355X HBM3E, specification
 HBM_COPY_TBS = 6.29         # what a float4 copy kernel reaches
@@ -79,7 +85,8 @@ def torch_model(g, device):
                 pl, pr = _pads(a.shape[3], kw, op["stride_w"], op["padding"])
                 if pt or pb or pl or pr:
                     a = F.pad(a, (pl, pr, pt, pb))
-                r = _act(F.conv2d(a, wts[ins[1]], const[ins[2]], stride=(op["stride_h"], op["stride_w"])), op["act"])
+                bias = const[ins[2]] if len(ins) > 2 and ins[2] >= 0 else None
+                r = _act(F.conv2d(a, wts[ins[1]], bias, stride=(op["stride_h"], op["stride_w"])), op["act"])
             elif name == "DEPTHWISE_CONV_2D":
                 w = dw_wts[ins[1]]
                 pt, pb = _pads(a.shape[2], w.shape[2], op["stride_h"], op["padding"])
@@ -350,6 +357,61 @@ def efficientnet_leg(args):
     print(json.dumps(out))
 
 
+def densenet_leg(args):
+    """ms per forward of a DenseNet121, pre-activations folded and as launches, by batch size, against PyTorch-ROCm float32."""
+    import ctypes as C
+
+    import tflite_build_preact as tp
+    import torch
+    from cpx.engine import TrackEngine
+    from cpx.ml_tools.tflite_graph import GraphDevice, build_plan
+    from cpx.ml_tools.tflite_reader import Graph
+
+    size = 160
+    g = Graph(tp.densenet121(17, size=size, seed=7))
+    plans = {"fused": build_plan(g, fuse_preactivation=True), "unfused": build_plan(g)}
+    batches = [int(v) for v in args.batches.split(",")]
+    torch.backends.cudnn.allow_tf32 = False
+    torch.backends.cuda.matmul.allow_tf32 = False
+    eng = TrackEngine(model="lepton3", device=0)
+    stream = torch.cuda.ExternalStream(eng.lib.cpx_stream(eng.h), device=eng.device)
+    ref = torch_model(g, eng.device)
+    out = {"model": "densenet121 %dx%dx3" % (size, size), "batches": []}
+    for name, plan in plans.items():
+        kinds = {}
+        for o in plan.ops:
+            kinds[KIND_NAMES[o.kind]] = kinds.get(KIND_NAMES[o.kind], 0) + 1
+        out[name] = {"launches": len(plan.ops), "launches_by_kind": kinds, "arena_bytes_per_sample": plan.arena_bytes_per_sample}
+    rng = np.random.default_rng(0)
+    for n in batches:
+        # (the sample as the 'torch' input mode leaves it: a few units either side of 0)
+        x = torch.from_numpy(rng.uniform(-2.2, 2.6, size=(n, size, size, 3)).astype(np.float32)).to(eng.device)
+        rec, ys = {"N": n}, {}
+        for name, plan in plans.items():
+            dev = GraphDevice(eng, plan)
+            y = ys[name] = torch.empty((n, 17), dtype=torch.float32, device=eng.device)
+
+            def forward():
+                rc = eng.lib.cpx_graph_forward(dev._graph, C.c_void_p(x.data_ptr()), n, C.c_void_p(y.data_ptr()))
+                assert rc == 0, eng._err()
+
+            with torch.cuda.stream(stream):
+                rec[name + "_ms"] = timed(torch, forward, args.steps, args.warmup)
+            dev.close()
+        rec["fused_equals_unfused"] = bool(torch.equal(ys["fused"], ys["unfused"]))
+        rec["unfused_over_fused"] = rec["unfused_ms"] / rec["fused_ms"]
+        if not args.skip_torch:
+            x_nchw = x.permute(0, 3, 1, 2).contiguous()
+            with torch.no_grad():
+                rec["torch_ms"] = timed(torch, lambda: ref(x_nchw), args.steps, args.warmup)
+                rec["max_abs_diff_vs_torch"] = float((ref(x_nchw) - ys["fused"]).abs().max())
+            for name in ys:
+                rec["ratio_vs_torch_" + name] = rec["torch_ms"] / rec[name + "_ms"]
+        out["batches"].append(rec)
+    eng.close()
+    print(json.dumps(out))
+
+
 def hbm_group(plan, o, n):
     """-> (group, bytes the launch must move for n samples) of the HBM-bound kinds beside the depthwise ones: MUL (in0 and the
     output once, in1 once: C floats per sample where it is the gate) and the wide MEAN (its input once)."""
@@ -441,7 +503,11 @@ def main():
                     help="time an EfficientNet-B0 (swish, squeeze-and-excite) with its activations fused and unfused")
     ap.add_argument("--unfused", action="store_true",
                     help="with --efficientnet: the fuse_activations=False plan alone (a run under a profiler, and its --kernel-trace)")
+    ap.add_argument("--densenet", action="store_true",
+                    help="a DenseNet121 with the pre-activations folded into their convolutions and as launches, against PyTorch-ROCm")
     args = ap.parse_args()
+    if args.densenet:
+        return densenet_leg(args)
     if args.efficientnet:
         if args.batches == "1,8,32,128":
             args.batches = "1,128"

@@ -6,8 +6,9 @@ flatbuffer is parsed here, TensorFlow is not needed (only NumPy).
     python tools/tflite_to_npz.py --describe model.tflite
 
 --describe converts nothing: it prints the operator census, the input and output shapes, the arena bytes per sample and,
-for a dynamic-range quantised file, the number of hybrid operators with the int8 against the float32 weight bytes of ANY graph the device executor runs (cpx/ml_tools/tflite_graph.py: an Inception-v3, a MobileNetV2 or an EfficientNet, say; the launches carry what was folded into them: CONV_2D+SWISH, CONV_2D+LOGISTIC, CONV_2D+MUL+ADD), or the refusal -- the
-operator and its index -- of one it does not.
+for a dynamic-range quantised file, the number of hybrid operators with the int8 against the float32 weight bytes of ANY graph the device executor runs (cpx/ml_tools/tflite_graph.py: an Inception-v3, a MobileNetV2 or an EfficientNet, say; the launches carry what was folded into them: CONV_2D+SWISH, CONV_2D+LOGISTIC, CONV_2D+MUL+ADD, AFFINE>CONV_2D for a folded pre-activation), or the refusal -- the
+operator and its index -- of one it does not.  With a sidecar JSON beside the file (or --sidecar) it also prints the
+family's input mode.
 
 The reference loads this artefact with LiteInterpreter (/root/reference/src/ml_tools/interpreter.py:520-560); its CI
 downloads it (.github/workflows/release.yml:46) and tests/clips/possum.txt's prediction came from one.  Anyone holding
@@ -35,7 +36,21 @@ from cpx.ml_tools.tflite_reader import (BN_EPS, OPS, Graph, Table, bn_params, co
                                         identity_variance)
 
 
-def describe(g):
+def input_mode_of(sidecar):
+    """-> (model_name, 'caffe' | 'torch' | 'tf' | None) of a sidecar JSON, as LiteInterpreter reads it."""
+    import json
+
+    from cpx.ml_tools.hyperparams import HyperParams
+    from cpx.ml_tools.interpreter import Interpreter, LiteInterpreter
+
+    hp = HyperParams()
+    with open(sidecar, "r") as fh:
+        hp.update(json.load(fh).get("hyperparams", {}))
+    name = hp.model_name
+    return name, LiteInterpreter.INPUT_MODE_OF.get(name, "tf" if name in Interpreter.TF_SCALED_MODELS else None)
+
+
+def describe(g, sidecar=None):
     from cpx.ml_tools.tflite_graph import build_plan
 
     census = {}
@@ -43,7 +58,7 @@ def describe(g):
         census[op["name"]] = census.get(op["name"], 0) + 1
     print("operators: " + ", ".join("%s: %d" % kv for kv in sorted(census.items())))
     try:
-        plan = build_plan(g)
+        plan = build_plan(g, fuse_preactivation=True)   # (what LiteInterpreter runs)
     except NotImplementedError as e:
         print("refused: %s" % e)
         return 1
@@ -58,6 +73,12 @@ def describe(g):
               if o.kind not in Q8_KINDS and o.weights is not None)
     print("hybrid operators (int8 filter, activations quantised per sample): %d; int8 weight bytes: %d, float32 weight bytes: %d"
           % (len(hybrid), q8, f32))
+    if sidecar is not None and os.path.exists(sidecar):
+        name, mode = input_mode_of(sidecar)
+        how = {"caffe": "BGR, the ImageNet means subtracted from the unscaled sample by the graph's INPUT operator",
+               "torch": "x / 255, ImageNet means and deviations, by the graph's INPUT operator",
+               "tf": "x / 127.5 - 1, by the crop kernel", None: "the unscaled sample"}[mode]
+        print("input mode: %s (model_name %s: %s)" % (mode or "none", name, how))
     return 0
 
 
@@ -71,7 +92,7 @@ def main():
     with open(args.model, "rb") as fh:
         g = Graph(fh.read())
     if args.describe:
-        return describe(g)
+        return describe(g, args.sidecar or os.path.splitext(args.model)[0] + ".json")
     if args.out_base is None:
         ap.error("out_base is required unless --describe is given")
     weights = convert(g)
