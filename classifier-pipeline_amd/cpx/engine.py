@@ -814,6 +814,24 @@ class TrackEngine:
         reqs = np.ascontiguousarray(reqs, dtype=CROP_REQ_DTYPE)
         offs = np.ascontiguousarray(track_offsets, dtype=np.int32)
         n_tracks = offs.size - 1
+        # the kernels index the frames with these fields unchecked: refuse anything outside the uploaded frames here
+        n_frames, H, W = (int(v) for v in frames_dev.shape[-3:])
+        n_frames = min(n_frames, int(track_result.filtered_dev.shape[0]))
+        if n_tracks < 0 or offs[0] != 0 or np.any(np.diff(offs) < 0) or offs[-1] > refs.size:
+            raise ValueError("preprocess_segments: track_offsets must rise from 0 to at most len(refs)")
+        for name, a in (("refs", refs), ("reqs", reqs)):
+            empty = (a["width"] <= 0) | (a["height"] <= 0)
+            bad = ((a["frame"] < 0) | (a["frame"] >= n_frames) | (a["x"] < 0) | (a["y"] < 0)
+                   | (a["x"].astype(np.int64) + a["width"] > W) | (a["y"].astype(np.int64) + a["height"] > H))
+            if name == "refs":
+                bad &= ~empty  # the limits kernel skips an empty region before it reads anything of it
+            else:
+                bad |= (empty | (a["track"] < 0) | (a["track"] >= n_tracks) | (a["sample"] < 0)
+                        | (a["sample"] >= n_samples) | (a["tile"] < 0) | (a["tile"] >= square_width ** 2))
+            if np.any(bad):
+                raise ValueError("preprocess_segments: %s[%d] = %s lies outside %d frames of %d x %d, %d tracks, "
+                                 "%d samples of %d tiles" % (name, int(np.flatnonzero(bad)[0]), a[bad][0], n_frames,
+                                                             W, H, n_tracks, n_samples, square_width ** 2))
         refs_dev = self._to_dev(refs) if refs.size else t.zeros(6, dtype=t.int32, device=self.device)
         offs_dev = t.from_numpy(offs).to(self.device)
         reqs_dev = self._to_dev(reqs) if reqs.size else t.zeros(8, dtype=t.int32, device=self.device)

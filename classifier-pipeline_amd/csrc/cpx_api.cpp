@@ -712,7 +712,7 @@ int cpx_crop_tile(cpx_handle* h, const uint16_t* frames_dev, const float* filter
   a.out = out_dev;
   a.frame_size = frame_size;
   a.square_width = square_width;
-  cpx::launch_crop(a, n_reqs, h->stream);
+  if (cpx::launch_crop(a, n_reqs, h->stream) != 0) return fail(h, CPX_ERR_HIP, "cpx_crop_tile: kernel configuration failed");
   CPX_HIP(h, hipGetLastError());
   return CPX_OK;
 }

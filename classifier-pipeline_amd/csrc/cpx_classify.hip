@@ -243,17 +243,19 @@ __global__ __launch_bounds__(LT) void cpx_crop_kernel(ClassifyArgs a) {
   const bool pre = (lim.flags & CPX_LIMITS_POST_PROCESS) != 0;
   const bool tdn = (lim.flags & CPX_LIMITS_THERMAL_DIFF_NORM) != 0;   // thermal_norm_limits given: no clip at zero
   const bool own = (lim.flags & CPX_LIMITS_NO_DIFF_NORM) != 0;        // Frame.normalize(): both channels per tile
-  const int cth = (lim.flags & CPX_LIMITS_SWAP_CHANNELS) ? 1 : 0, cfi = cth ^ 1;
+  const int cth = (lim.flags & CPX_LIMITS_SWAP_CHANNELS) ? 1 : 0;
   // the input scaling of the Keras 'tf'-mode families and inceptionv3 (interpreter.py:64-98,563-566: x /= 127.5; x -= 1.0
   // in float32, applied to the finished sample, preprocess.py:142-143,200-201)
   // A tiled sample is a float64 array at that point (square_clip pastes the float32 tiles into np.zeros,
   // imageprocessing.py:85-104) and is cast to float32 after the scaling; a single frame (square_width 1) is the
-  // float32 stack of its channels and is scaled in float32.
+  // float32 stack of its channels and is scaled in float32 -- unless normalize() answered a constant-zero channel
+  // with np.zeros (float64, imageprocessing.py:162-164): np.stack then promotes the sample and BOTH channels are
+  // scaled in float64.  Which of the two holds is known once the tile's limits are (`wide` below).
   const bool tfs = (lim.flags & CPX_LIMITS_TF_SCALING) != 0;
   const bool tiled = sq > 1;
-  auto fin = [tfs, tiled](float v) {
+  auto fin = [tfs](float v, bool wide) {
     if (!tfs) return v;
-    return tiled ? (float)((double)v / 127.5 - 1.0) : __fsub_rn(__fdiv_rn(v, 127.5f), 1.0f);
+    return wide ? (float)((double)v / 127.5 - 1.0) : __fsub_rn(__fdiv_rn(v, 127.5f), 1.0f);
   };
   if (pre) pmin = __fsub_rn(pmin, median);
   // ---- both channels: bilinear sample (two float32 passes), paste, per-pixel ops ----
@@ -312,7 +314,7 @@ __global__ __launch_bounds__(LT) void cpx_crop_kernel(ClassifyArgs a) {
       else fo = (float)(255.0 * ((double)fv - dmin) / (dmax - dmin));
     } else if (lim.filt_max == lim.filt_min) fo = (lim.filt_max == 0.0f) ? 0.0f : __fdiv_rn(fv, lim.filt_max);
     else fo = __fdiv_rn(__fmul_rn(255.0f, __fsub_rn(fv, lim.filt_min)), fspan);
-    s_f[k] = fin(fo);
+    s_f[k] = fo;
   }
   tmn = block_min(tmn, sc);
   tmx = block_max(tmx, sc);
@@ -329,22 +331,50 @@ __global__ __launch_bounds__(LT) void cpx_crop_kernel(ClassifyArgs a) {
     fmx = block_max(fmx, sc);
   }
   const float ospan = __fsub_rn(fmx, fmn);
+  const bool zero_t = tmx == tmn && tmx == 0.0f;
+  const bool zero_f = own ? (fmx == fmn && fmx == 0.0f) : (lim.filt_max == lim.filt_min && lim.filt_max == 0.0f);
+  const bool wide = tiled || zero_t || zero_f;
   for (int k = threadIdx.x; k < n; k += LT) {
     const int yy = k / fs, xx = k - yy * fs;
     const float tv = s_t[k];
     float to;
     if (tmx == tmn) to = (tmx == 0.0f) ? 0.0f : __fdiv_rn(tv, tmx);
     else to = __fdiv_rn(__fmul_rn(255.0f, __fsub_rn(tv, tmn)), tspan);
-    float fo = s_f[k];  // (finished above unless the tile normalises it itself)
+    float fo = s_f[k];  // (normalised above unless the tile normalises it itself)
     if (own) {
       const float fv = fo;
-      if (fmx == fmn) fo = (fmx == 0.0f) ? 0.0f : __fdiv_rn(fv, fmx);
+      if (pre) {
+        // post_process_file's filtered crop is float64 (thermal - background), and so is the padded tile the resized
+        // float32 values are pasted into: Frame.normalize() takes np.amin / np.amax of it as np.float64 scalars, which
+        // promote the normalise as the track limits do above; one rounding at the end
+        const double dmin = (double)fmn, dmax = (double)fmx;
+        if (dmax == dmin) fo = (dmax == 0.0) ? 0.0f : (float)((double)fv / dmax);
+        else fo = (float)(255.0 * ((double)fv - dmin) / (dmax - dmin));
+      } else if (fmx == fmn) fo = (fmx == 0.0f) ? 0.0f : __fdiv_rn(fv, fmx);
       else fo = __fdiv_rn(__fmul_rn(255.0f, __fsub_rn(fv, fmn)), ospan);
-      fo = fin(fo);
     }
-    const float tf = fin(to);
+    fo = fin(fo, wide);
+    const float tf = fin(to, wide);
     *reinterpret_cast<float2*>(out + ((size_t)yy * OW + xx) * 2) = cth == 0 ? make_float2(tf, fo) : make_float2(fo, tf);
   }
+}
+
+// np.sum of n contiguous float32: NumPy's pairwise sum is a plain loop below 8 elements and, for 8 <= n <= 128 (one
+// pairwise block), eight running lanes combined as a tree plus a tail loop.  Bit parity holds for n <= 128 only.
+__device__ __forceinline__ float np_sum_f32(const float* v, int n) {
+  float total = 0.0f;
+  if (n < 8) {
+    for (int l = 0; l < n; ++l) total += v[l];
+    return total;
+  }
+  float r[8];
+  for (int j = 0; j < 8; ++j) r[j] = v[j];
+  int i;
+  for (i = 8; i < n - (n % 8); i += 8)
+    for (int j = 0; j < 8; ++j) r[j] += v[i + j];
+  total = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+  for (; i < n; ++i) total += v[i];
+  return total;
 }
 
 // class_best_score per track (trackprediction.py:127-171) + low-evidence cap (interpreter.py:151-168)
@@ -368,25 +398,14 @@ __global__ __launch_bounds__(64) void cpx_aggregate_kernel(AggregateArgs a) {
   const int s1 = lo;
   const int L = a.n_labels;
   float* out = a.scores + (size_t)t * L;
-  float total = 0.0f;
+  float total;
   // np.sum(predictions, axis=0) over at most a few segments: plain float32 accumulation in segment order
   for (int l = 0; l < L; ++l) {
     float s = 0.0f;
     for (int k = s0; k < s1; ++k) s += a.probs[(size_t)k * L + l];
     out[l] = s;
   }
-  // np.sum(class_best_score): pairwise over L <= 128 labels collapses to NumPy's 8-lane scheme; L < 8 is a loop
-  if (L < 8) {
-    for (int l = 0; l < L; ++l) total += out[l];
-  } else {
-    float r[8];
-    for (int j = 0; j < 8; ++j) r[j] = out[j];
-    int i;
-    for (i = 8; i < L - (L % 8); i += 8)
-      for (int j = 0; j < 8; ++j) r[j] += out[i + j];
-    total = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < L; ++i) total += out[i];
-  }
+  total = np_sum_f32(out, L);
   int best = 0;
   for (int l = 0; l < L; ++l) {
     out[l] = (s1 > s0) ? out[l] / total : 0.0f;
@@ -398,8 +417,7 @@ __global__ __launch_bounds__(64) void cpx_aggregate_kernel(AggregateArgs a) {
     int distinct = 0;
     for (int j = 0; j < per; ++j) distinct += (j == 0 || q[j].frame != q[j - 1].frame);  // frames are sorted
     if ((float)distinct < (float)per / 4.0f && best != a.fp_index) {
-      float tot2 = 0.0f;
-      for (int l = 0; l < L; ++l) tot2 += out[l];
+      const float tot2 = np_sum_f32(out, L);  // np.sum(class_best_score) again (interpreter.py:151-168): same order
       if (tot2 > 0.5f) {
         const float scale = 0.5f / tot2;
         for (int l = 0; l < L; ++l) out[l] *= scale;
@@ -416,8 +434,12 @@ void launch_aggregate(const AggregateArgs& a, hipStream_t s) {
 void launch_limits(const ClassifyArgs& a, int n_tracks, hipStream_t s) {
   hipLaunchKernelGGL(cpx_limits_kernel, dim3(n_tracks), dim3(LTL), 0, s, a);
 }
-void launch_crop(const ClassifyArgs& a, int n_reqs, hipStream_t s) {
+int launch_crop(const ClassifyArgs& a, int n_reqs, hipStream_t s) {
+  // two float32 [fs][fs] tiles: more than 64 KB from frame_size 91 on (128 KB at the API's limit of 128)
+  static bool lds_ready[64];
+  if (!cpx_dyn_lds_ready(reinterpret_cast<const void*>(cpx_crop_kernel), lds_ready, 160 * 1024 - 1024)) return -1;
   hipLaunchKernelGGL(cpx_crop_kernel, dim3(n_reqs), dim3(LT), (size_t)2 * a.frame_size * a.frame_size * sizeof(float), s, a);
+  return 0;
 }
 
 }  // namespace cpx

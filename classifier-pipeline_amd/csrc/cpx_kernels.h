@@ -174,7 +174,7 @@ struct AggregateArgs {
 };
 void launch_aggregate(const AggregateArgs& a, hipStream_t s);
 void launch_limits(const ClassifyArgs& a, int n_tracks, hipStream_t s);
-void launch_crop(const ClassifyArgs& a, int n_reqs, hipStream_t s);
+int launch_crop(const ClassifyArgs& a, int n_reqs, hipStream_t s);
 
 struct ConvArgs {
   int N, H, W, Cin, Cout, groups, ksize, stride, relu;

@@ -473,7 +473,9 @@ int cpx_track_limits_batch_ex(cpx_handle* h, const uint16_t* frames_dev, const f
                               const int32_t* track_offsets_dev, int n_tracks, cpx_track_limits* limits_dev, int flags);
 
 /* out_dev: float [n_samples, square_width*frame_size, square_width*frame_size, 2] (NHWC; thermal, filtered).
- * Every tile of every sample must be covered by exactly one request. */
+ * Every tile of every sample must be covered by exactly one request.  frame_size 1..128 (two float32 tiles of
+ * frame_size^2 in LDS: 128 KB at 128), square_width 1..16.  Every request's rectangle lies inside the frame and its
+ * frame / track / sample / tile are in range: the kernel does not check (cpx.engine.preprocess_segments does). */
 int cpx_crop_tile(cpx_handle* h, const uint16_t* frames_dev, const float* filtered_dev,
                   const cpx_frame_info* info_dev, const cpx_crop_req* reqs_dev, int n_reqs,
                   const cpx_track_limits* limits_dev, int frame_size, int square_width, float* out_dev);
@@ -481,7 +483,10 @@ int cpx_crop_tile(cpx_handle* h, const uint16_t* frames_dev, const float* filter
 /* Per-track aggregation of the segment predictions (classify/trackprediction.py:127-171 with
  * smooth_predictions = False: sum over the track's segments, normalised to sum 1) plus the low-evidence
  * cap of Interpreter.track_prediction_from_raw (ml_tools/interpreter.py:151-168).  Samples of a track are
- * contiguous (cpx_plan_segments).  scores_dev float [n_tracks, L]; best_dev int32 [n_tracks] (argmax). */
+ * contiguous (cpx_plan_segments).  scores_dev float [n_tracks, L]; best_dev int32 [n_tracks] (argmax; -1 and a
+ * zero score row for a track without a sample).  Both sums over the labels follow NumPy's float32 np.sum order, which
+ * gives bit parity with the reference for n_labels <= 128; above that the call still runs, and the scores agree
+ * with NumPy's to rounding only. */
 int cpx_aggregate_predictions(cpx_handle* h, const float* probs_dev, const int32_t* sample_track_dev,
                               int n_samples, const struct cpx_crop_req* reqs_dev, int n_tracks, int n_labels,
                               int false_positive_index, int square_width, float* scores_dev, int32_t* best_dev);

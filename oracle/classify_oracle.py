@@ -1,18 +1,32 @@
 """TEST INFRASTRUCTURE ONLY -- CPU restatement (NumPy) of the reference's
 classification pre-processing and prediction aggregation; the checker for the
-HIP crop/tile kernel.  Pinned by tests/golden/*_classify_fs*.npz, which were
-produced by the reference's own Interpreter.classify_track
-(tests/golden/make_golden_classify.py); tests/test_oracle_golden.py compares
-bit for bit.
+HIP crop/tile kernel.  Every branch is pinned, bit for bit, by fixtures the
+reference itself produced (tests/test_oracle_golden.py):
+  default model                       *_classify_fs*.npz (make_golden_classify.py), busy_classify_fs32.json,
+                                      classify_crafted_golden.json (frame sizes 32, 48, 64, 96, 128)
+  thermal_diff_norm, diff_norm=False, classify_variants_golden.json (make_golden_classify_variants.py, fs 32) and
+  both, channel order, input scaling, classify_crafted_golden.json (make_golden_classify_crafted.py, fs 32 and 64;
+  single frames (preprocess_frames)   single frames also 96 and 128)
+  post_process=True                   postprocess_golden.npz (make_golden_postprocess.py, <clip>.txt mode)
+  post_process with diff_norm=False,  postprocess_variants_golden.json (make_golden_classify_crafted.py)
+  swapped channels, input scaling
+  constant tiles (max == min)         the 1 x 1 / 1 x 7 / 7 x 1 regions of classify_crafted_golden.json
+  classified_track                    the class_best_score of the classify goldens
+A branch without such a fixture must not serve as the expectation of a GPU test.
 
 Follows (paths relative to /root/reference/src):
+  ml_tools/interpreter.py:255-313   preprocess_frames (single-frame models)
   ml_tools/interpreter.py:315-363   get_limits
   ml_tools/interpreter.py:365-474   preprocess_segments
   ml_tools/preprocess.py:56-113     preprocess_frame
+  ml_tools/preprocess.py:119-144    preprocess_single_frame
   ml_tools/imageprocessing.py:11-82 resize_and_pad / resize_cv
   ml_tools/preprocess.py:151-202    preprocess_movement (+ imageprocessing.py:85-104 square_clip)
+  ml_tools/frame.py:187-191         Frame.normalize
+  classify/clipclassifier.py:465-552 post_process_file's crops, limits and preprocess_frame call
   classify/trackprediction.py:127-171 classified_track
-cv2.resize is oracle/cv2_shim.py:resize (not pinned by any reference golden).
+cv2.resize is oracle/cv2_shim.py:resize (not pinned by any reference golden: the goldens above were made
+with the reference running on the same shim).
 """
 
 import numpy as np
@@ -82,25 +96,107 @@ def normalize(data, mn=None, mx=None, new_max=1):
     return new_max * (np.float32(data) - mn) / (mx - mn)
 
 
-def preprocess_frame(thermal, filtered, region, fs, crop, median, limits, clip_at_zero):
-    """preprocess.py:56-113 for the classify call (calculate_filtered=False, sub_median=True,
-    filtered_norm_limits given, thermal_norm_limits None) -> (thermal f32 [fs,fs], filtered f32 [fs,fs])."""
+def get_thermal_limits(regions, thermal_of):
+    """thermal_norm_limits of get_limits (interpreter.py:338-345, thermal_diff_norm=True): min / max of
+    float32(thermal) - np.median(float32 thermal) over the WHOLE frame of every usable region, both starting at None."""
+    lo = hi = None
+    for r in reversed(regions):
+        if r.blank or r.width <= 0 or r.height <= 0:
+            continue
+        th = thermal_of(r.frame_number)
+        if th is None:
+            continue
+        th = np.float32(th)
+        diff = th - np.median(th)
+        new_max, new_min = np.amax(diff), np.amin(diff)
+        if lo is None or new_min < lo:
+            lo = new_min
+        if hi is None or new_max > hi:
+            hi = new_max
+    return lo, hi
+
+
+def post_process_limits(regions_by_frame, filtered_of):
+    """The limits of ClipClassifier.post_process_file (clipclassifier.py:476-500): over the SAMPLED regions only, in
+    frame order, both started by the first crop (the max is not floored at 0); np.min / np.max of the float64 crop
+    thermal - background, so the limits are np.float64 scalars."""
+    limits = None
+    for fn in sorted(regions_by_frame):
+        r = regions_by_frame[fn]
+        sub = np.asarray(filtered_of(fn)[r.y : r.y + r.height, r.x : r.x + r.width], dtype=np.float64)
+        f_min, f_max = np.min(sub), np.max(sub)
+        if limits is None:
+            limits = [f_min, f_max]
+        else:
+            if f_min < limits[0]:
+                limits[0] = f_min
+            if f_max > limits[1]:
+                limits[1] = f_max
+    return limits
+
+
+def preprocess_frame(thermal, filtered, region, fs, crop, median, limits, clip_at_zero, thermal_limits=None,
+                     sub_median=True):
+    """preprocess.py:56-113 for the classify calls (calculate_filtered=False) -> (thermal [fs,fs], filtered [fs,fs]),
+    each float32 or -- where NumPy makes it so -- float64: normalize()'s np.zeros for a constant-zero tile, and the
+    filtered channel under float64 limits (post_process_file).
+      limits          filtered_norm_limits, or None (diff_norm=False and post_process_file without diff_norm):
+                      Frame.normalize() then normalises BOTH channels over the tile itself (frame.py:187-191)
+      thermal_limits  thermal_norm_limits (thermal_diff_norm=True): no clip at zero (preprocess.py:92); used for the
+                      thermal normalise only when `limits` is given too (preprocess.py:95-109)
+      sub_median      False for post_process_file, which subtracts the frame median from the crop BEFORE the resize
+                      (clipclassifier.py:480-486) and passes cropped=True, sub_median=False."""
     t = np.float32(thermal[region.y : region.y + region.height, region.x : region.x + region.width])
-    f = np.float32(filtered[region.y : region.y + region.height, region.x : region.x + region.width])
+    f = filtered[region.y : region.y + region.height, region.x : region.x + region.width]
+    if sub_median:
+        f = np.float32(f)
+    else:
+        t -= median
+        f = np.asarray(f, dtype=np.float64)  # (np.float64(a 1 x 1 array) would be a scalar)
     t = resize_and_pad(t, fs, region, crop)
     f = resize_and_pad(f, fs, region, crop, pad=0)
-    t -= median
-    if clip_at_zero:
+    if sub_median:
+        t -= median
+    if thermal_limits is None and clip_at_zero:
         np.clip(t, 0, None, out=t)
-    f = normalize(f, mn=limits[0], mx=limits[1], new_max=255)
-    t = normalize(t, new_max=255)
+    if limits is not None:
+        f = normalize(f, mn=limits[0], mx=limits[1], new_max=255)
+        if thermal_limits is not None:
+            t = normalize(t, mn=thermal_limits[0], mx=thermal_limits[1], new_max=255)
+        else:
+            t = normalize(t, new_max=255)
+    else:
+        t = normalize(t, new_max=255)
+        f = normalize(f, new_max=255)
     return t, f
 
 
-def preprocess_segments(thermal_of, filtered_of, regions_by_frame, track_regions, segments, fs, crop):
-    """interpreter.py:365-474 + preprocess.py:151-202 for channels (thermal, filtered),
-    wr-resnet (no preprocess_fn).  segments: list of 25 frame numbers each.
-    filtered frames are integer valued (float32 after Frame.float_arrays())."""
+def inc3_preprocess(x):
+    """interpreter.py:563-566, in the dtype of x."""
+    x /= 127.5
+    x -= 1.0
+    return x
+
+
+def _model_limits(track_regions, filtered_of, thermal_of, diff_norm, thermal_diff_norm):
+    """get_limits as preprocess_segments / preprocess_frames call it (interpreter.py:268-269,403-406)."""
+    limits = thermal_limits = None
+    if diff_norm or thermal_diff_norm:
+        if diff_norm:
+            limits = get_limits(track_regions, filtered_of)
+        if thermal_diff_norm:
+            thermal_limits = get_thermal_limits(track_regions, thermal_of)
+    return limits, thermal_limits
+
+
+def preprocess_segments(thermal_of, filtered_of, regions_by_frame, track_regions, segments, fs, crop, square_width=5,
+                        diff_norm=True, thermal_diff_norm=False, channels=("thermal", "filtered"), tf_scaling=False,
+                        post_process=False):
+    """interpreter.py:365-474 + preprocess.py:151-202 (square_clip: imageprocessing.py:85-104).  segments: list of
+    square_width**2 frame numbers each.  filtered frames are float32 after Frame.float_arrays().
+    post_process=True is ClipClassifier.post_process_file's preparation of the same segments instead
+    (clipclassifier.py:465-552): limits over the sampled crops, median first, always clipped at zero, no thermal
+    limits ever (:465)."""
     medians, unique = {}, {}
     clip_at_zero = True
     for seg in segments:
@@ -112,24 +208,55 @@ def preprocess_segments(thermal_of, filtered_of, regions_by_frame, track_regions
             unique[fn] = r
             th = thermal_of(fn)
             medians[fn] = np.median(th)
-            if clip_at_zero:
+            if clip_at_zero and not post_process:
                 sub = np.float32(th[r.y : r.y + r.height, r.x : r.x + r.width]) - medians[fn]
                 if np.median(sub) <= 0:
                     clip_at_zero = False
-    limits = get_limits(track_regions, filtered_of)
+    if post_process:
+        limits = post_process_limits(unique, filtered_of) if diff_norm else None
+        thermal_limits = None
+    else:
+        limits, thermal_limits = _model_limits(track_regions, filtered_of, thermal_of, diff_norm, thermal_diff_norm)
     data = {}
     for fn, r in unique.items():
-        data[fn] = preprocess_frame(thermal_of(fn), filtered_of(fn), r, fs, crop, medians[fn], limits, clip_at_zero)
-    out = np.zeros((len(segments), 5 * fs, 5 * fs, 2), dtype=np.float64)
+        data[fn] = preprocess_frame(thermal_of(fn), filtered_of(fn), r, fs, crop, medians[fn], limits, clip_at_zero,
+                                    thermal_limits=thermal_limits, sub_median=not post_process)
+    sq = square_width
+    out = np.zeros((len(segments), sq * fs, sq * fs, 2), dtype=np.float64)
+    order = [("thermal", "filtered").index(c) for c in channels]
     for s, seg in enumerate(segments):
-        assert len(seg) == 25, "parity runs use full 25-frame segments (short ones are padded at random, F13)"
+        assert len(seg) == sq * sq, "parity runs use full segments (short ones are padded at random, F13)"
         for i, fn in enumerate(seg):
-            ty, tx = divmod(i, 5)
-            t, f = data[int(fn)]
-            out[s, ty * fs : (ty + 1) * fs, tx * fs : (tx + 1) * fs, 0] = np.float32(t)
-            out[s, ty * fs : (ty + 1) * fs, tx * fs : (tx + 1) * fs, 1] = np.float32(f)
-    info = dict(medians=medians, limits=limits, clip_at_zero=clip_at_zero)
+            ty, tx = divmod(i, sq)
+            tile = data[int(fn)]
+            for c, src in enumerate(order):
+                out[s, ty * fs : (ty + 1) * fs, tx * fs : (tx + 1) * fs, c] = np.float32(tile[src])
+    if tf_scaling:
+        out = inc3_preprocess(out)  # on the float64 tiled array, cast after (preprocess.py:200-202)
+    info = dict(medians=medians, limits=limits, thermal_limits=thermal_limits, clip_at_zero=clip_at_zero)
     return np.float32(out), info
+
+
+def preprocess_frames(thermal_of, filtered_of, track_regions, samples, fs, crop, diff_norm=True,
+                      thermal_diff_norm=False, channels=("thermal", "filtered"), tf_scaling=False):
+    """Single-frame models: interpreter.py:255-313 + preprocess.py:119-144.  samples: the regions to classify
+    (frames_for_prediction with frames_per_classify = 1: every usable region of the track).  preprocess_frame runs with
+    its defaults median=None, clip_thermals_at_zero=True; the sample is np.stack of its channels -- float32, unless
+    normalize() returned np.zeros for a constant-zero tile, which makes the stack float64 -- and the input scaling
+    runs in that dtype."""
+    limits, thermal_limits = _model_limits(track_regions, filtered_of, thermal_of, diff_norm, thermal_diff_norm)
+    order = [("thermal", "filtered").index(c) for c in channels]
+    out = []
+    for r in samples:
+        th = thermal_of(r.frame_number)
+        tile = preprocess_frame(th, filtered_of(r.frame_number), r, fs, crop, np.median(th), limits, True,
+                                thermal_limits=thermal_limits)
+        image = np.stack([tile[src] for src in order], axis=2)
+        if tf_scaling:
+            image = inc3_preprocess(image)
+        out.append(image)
+    info = dict(limits=limits, thermal_limits=thermal_limits, clip_at_zero=True)
+    return np.float32(np.array(out)), info
 
 
 def classified_track(predictions, smooth_masses=None, prediction_frames=None, labels=None, square_width=5):

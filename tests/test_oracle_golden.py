@@ -114,6 +114,194 @@ def test_classify_oracle_matches_reference_inputs(name, fs):
         assert np.array_equal(score, np.array(m["class_best_score"]))
 
 
+_CLIP_RUNS = {}
+
+
+def _classify_clip(name):
+    """The oracle's tracks and filtered frames of a fixture clip, once per session, as callables for classify_oracle."""
+    if name not in _CLIP_RUNS:
+        out, frames = _run(name, 0)
+        _, _, _, bgf, _ = load_clip(name)
+        proc = [i for i in range(frames.shape[0]) if not bgf[i]]
+        fr = out["frames"]
+        _CLIP_RUNS[name] = (out, lambda q: frames[proc[q]], lambda q: fr[q]["filtered"].astype(np.float64),
+                            (1, 1, frames.shape[2] - 2, frames.shape[1] - 2))
+    return _CLIP_RUNS[name]
+
+
+def oracle_kwargs(hyperparams):
+    """Model hyper-parameters (the sidecar's "hyperparams") -> the variant arguments of classify_oracle."""
+    return dict(diff_norm=hyperparams.get("diff_norm", True), thermal_diff_norm=hyperparams.get("thermal_diff_norm", False),
+                channels=tuple(hyperparams.get("channels", ["thermal", "filtered"])),
+                tf_scaling=hyperparams.get("model_name", "wr-resnet") == "inceptionv3")
+
+
+VARIANTS = ["thermal_diff_norm", "no_diff_norm", "thermal_diff_norm_no_diff_norm", "channels_swapped", "single_frame",
+            "single_frame_thermal_diff_norm", "inceptionv3_scaling", "inceptionv3_scaling_single_frame"]
+
+
+@pytest.mark.parametrize("variant", VARIANTS)
+@pytest.mark.parametrize("name", ["hedgehog", "possum"])
+def test_classify_oracle_variants_match_reference_inputs(name, variant):
+    """Every model variant of oracle/classify_oracle.py (thermal limits, per-tile normalise, channel order, the
+    single-frame path, both input scalings) against the CRC32 of what the reference's own Interpreter built
+    (tests/golden/make_golden_classify_variants.py), sample by sample."""
+    import classify_oracle as co
+
+    with open(os.path.join(GOLDEN, "classify_variants_golden.json")) as fh:
+        g = json.load(fh)["variants"][variant]
+    hp = g["hyperparams"]
+    out, thermal_of, filtered_of, crop = _classify_clip(name)
+    assert len(out["tracks"]) == len(g[name])
+    for t, want in zip(out["tracks"], g[name]):
+        assert t.id == want["track_id"]
+        if hp.get("square_width", 5) == 1:
+            samples = [r for r in t.bounds if not r.blank and r.width > 0 and r.height > 0]
+            assert [r.frame_number for r in samples] == want["segments"]
+            x, _ = co.preprocess_frames(thermal_of, filtered_of, t.bounds, samples, hp["frame_size"], crop,
+                                        **oracle_kwargs(hp))
+        else:
+            by_frame = {r.frame_number: r for r in t.bounds}
+            x, _ = co.preprocess_segments(thermal_of, filtered_of, by_frame, t.bounds, want["segments"], hp["frame_size"],
+                                          crop, **oracle_kwargs(hp))
+        assert list(x.shape) == want["shape"] and x.dtype == np.float32
+        assert [crc(s) for s in x] == want["crc"], (name, variant, t.id)
+
+
+@pytest.mark.parametrize("name", ["possum", "hedgehog"])
+def test_classify_oracle_post_process_matches_reference_inputs(name):
+    """classify_oracle.preprocess_segments(post_process=True) against the network inputs of the reference's
+    ClipClassifier.post_process_file in its <clip>.txt mode (tests/golden/make_golden_postprocess.py), bit for bit.
+    That mode re-reads the file with a fresh background model which, unlike the tracking walk, stands still on
+    FFC-affected frames; neither fixture clip has one, so the filtered frames of the oracle's tracking walk are the
+    second walk's."""
+    import classify_oracle as co
+
+    with open(os.path.join(GOLDEN, "postprocess_golden.json")) as fh:
+        gold = json.load(fh)["runs"][name + "_meta"]
+    z = np.load(os.path.join(GOLDEN, "postprocess_golden.npz"))
+    out, thermal_of, filtered_of, crop = _classify_clip(name)
+    assert out["ffc_frames"] == []
+    n = 0
+    for g in gold["tracks"]:
+        if not g["segments"]:
+            continue
+        by_frame = {p[4]: Rect(*p) for p in g["positions"]}
+        x, _ = co.preprocess_segments(thermal_of, filtered_of, by_frame, None, g["segments"], 32, crop, post_process=True)
+        want = z["%s_meta_t%d_input" % (name, g["id"])]
+        assert x.shape == want.shape
+        assert np.array_equal(x, want), (name, g["id"], float(np.abs(x - want).max()))
+        n += len(x)
+    assert n >= 1
+
+
+@pytest.mark.parametrize("variant", ["no_diff_norm", "channels_swapped", "inceptionv3_scaling"])
+@pytest.mark.parametrize("name", ["possum", "hedgehog"])
+def test_classify_oracle_post_process_variants_match_reference_inputs(name, variant):
+    """The post-process path combined with diff_norm = False (Frame.normalize on a float64 filtered crop), swapped
+    channels and the input scaling, against the CRC32 of what the reference's post_process_file fed its model
+    (tests/golden/postprocess_variants_golden.json, <clip>.txt mode)."""
+    import classify_oracle as co
+
+    with open(os.path.join(GOLDEN, "postprocess_variants_golden.json")) as fh:
+        gold = json.load(fh)["%s_%s" % (name, variant)]
+    with open(os.path.join(GOLDEN, "postprocess_golden.json")) as fh:
+        positions = {t["id"]: t["positions"] for t in json.load(fh)["runs"][name + "_meta"]["tracks"]}
+    out, thermal_of, filtered_of, crop = _classify_clip(name)
+    assert out["ffc_frames"] == []
+    n = 0
+    for g in gold["tracks"]:
+        if not g["segments"]:
+            continue
+        by_frame = {p[4]: Rect(*p) for p in positions[g["id"]]}
+        x, _ = co.preprocess_segments(thermal_of, filtered_of, by_frame, None, g["segments"], 32, crop, post_process=True,
+                                      **dict(oracle_kwargs(gold["hyperparams"]), thermal_diff_norm=False))
+        assert [crc(s) for s in x] == g["crc"], (name, variant, g["id"])
+        n += len(x)
+    assert n >= 1
+
+
+_CRAFTED = {}
+
+
+def _crafted():
+    """The crafted clip (tests/classify_crafted.py) through the oracle's pixel stage, once per session."""
+    import classify_crafted as cc
+    import track_oracle as to
+
+    if not _CRAFTED:
+        with open(os.path.join(GOLDEN, "classify_crafted_golden.json")) as fh:
+            _CRAFTED["gold"] = json.load(fh)
+        frames = cc.clip_frames()
+        out = to.track_clip(frames, cc.TIME_ON, cc.LAST_FFC, None, to.OracleConfig("lepton3"), keep=True, do_tracking=False)
+        _CRAFTED["frames"] = frames
+        _CRAFTED["filtered"] = np.stack([f["filtered"] for f in out["frames"]]).astype(np.int32)
+    return _CRAFTED["gold"], _CRAFTED["frames"], _CRAFTED["filtered"]
+
+
+def test_crafted_clip_and_cases_are_the_golden_ones():
+    """The seeded clip, the oracle's filtered frames of it and the case list are what the reference was run on; the
+    case list still hits every geometry class at every frame size."""
+    import classify_crafted as cc
+
+    gold, frames, filtered = _crafted()
+    assert crc(frames) == gold["frames_crc"] and crc(filtered) == gold["filtered_crc"]
+    tracks = cc.tracks()
+    assert [(t["name"], [list(r.as_tuple()) for r in t["regions"]], t["segments"]) for t in tracks] == [
+        (t["name"], t["regions"], t["segments"]) for t in gold["tracks"]]
+    for fs in cc.FRAME_SIZES:
+        cc.coverage(fs, tracks)
+    assert {cc.run_key(v, fs) for v, fs in cc.RUNS} == set(gold["runs"])
+    for t in tracks:
+        assert cc.clip_at_zero_expected(frames, t) == gold["clip_at_zero"][t["name"]]
+    assert gold["clip_at_zero"]["clip_on"] and not gold["clip_at_zero"]["clip_off"]
+
+
+def crafted_oracle_inputs(variant, fs, frames, filtered, track):
+    """classify_oracle on one crafted track -> (network inputs float32, info)."""
+    import classify_crafted as cc
+    import classify_oracle as co
+
+    hp = dict({"frame_size": fs}, **cc.VARIANTS[variant])
+    thermal_of, filtered_of = (lambda q: frames[q]), (lambda q: filtered[q].astype(np.float64))
+    if hp.get("square_width", 5) == 1:
+        return co.preprocess_frames(thermal_of, filtered_of, track["regions"], cc.usable(track["regions"]), fs, cc.CROP,
+                                    **oracle_kwargs(hp))
+    by_frame = {r.frame_number: r for r in track["regions"]}
+    return co.preprocess_segments(thermal_of, filtered_of, by_frame, track["regions"], track["segments"], fs, cc.CROP,
+                                  **oracle_kwargs(hp))
+
+
+def _crafted_runs():
+    import classify_crafted as cc
+
+    return cc.RUNS
+
+
+@pytest.mark.parametrize("variant,fs", _crafted_runs())
+def test_classify_oracle_matches_reference_on_crafted_tracks(variant, fs):
+    """oracle/classify_oracle.py, every variant and frame size, against the CRC32 of what the reference's Interpreter
+    built for the crafted tracks (tests/golden/make_golden_classify_crafted.py)."""
+    import classify_crafted as cc
+
+    gold, frames, filtered = _crafted()
+    run = gold["runs"][cc.run_key(variant, fs)]
+    for t, want in zip(cc.tracks(), run["tracks"]):
+        x, info = crafted_oracle_inputs(variant, fs, frames, filtered, t)
+        got = [crc(s) for s in x]
+        bad = [i for i, (a, b) in enumerate(zip(got, want["crc"])) if a != b]
+        assert len(got) == len(want["crc"]) and not bad, (
+            t["name"], bad[:5], [(float(x[i].min()), float(x[i].max()), float(x[i].astype(np.float64).mean()),
+                                  want["min"][i], want["max"][i], want["mean"][i]) for i in bad[:1]])
+        if "square_width" not in cc.VARIANTS[variant]:
+            assert info["clip_at_zero"] == gold["clip_at_zero"][t["name"]]
+
+
+class Rect:
+    def __init__(self, x, y, width, height, frame_number, blank=False):
+        self.x, self.y, self.width, self.height, self.frame_number, self.blank = x, y, width, height, frame_number, blank
+
+
 @pytest.mark.parametrize("name,dn", [("possum", 0), ("hedgehog", 0), ("possum", 1)])
 def test_thumbnail_oracle_matches_reference(name, dn):
     """oracle/thumbnail_oracle.py (+ the findContours / TC89_L1 restatement in cv2_shim) against the

@@ -102,3 +102,64 @@ def test_post_process_file_equals_reference(tmp_path, name, with_metadata):
                 assert sp["frames"] == sq["frames"] and sp["prediction"] == sq["prediction"] and sp["mass"] == sq["mass"]
     assert pos == len(chunks)
     assert [m["id"] for m in meta["models"]] == [m["id"] for m in gold["models"]]
+
+
+@pytest.mark.parametrize("variant", ["no_diff_norm", "channels_swapped", "inceptionv3_scaling"])
+@pytest.mark.parametrize("name", ["possum", "hedgehog"])
+def test_post_process_file_model_variants_equal_reference(tmp_path, name, variant):
+    """post_process_file (<clip>.txt mode) for models with diff_norm = False (the tile's own normalise of a float64
+    filtered crop), swapped channels and the inceptionv3 input scaling: the same segments and, by CRC32, the same
+    network inputs as the reference's (tests/golden/postprocess_variants_golden.json)."""
+    import torch
+
+    from cpx.classify.clipclassifier import ClipClassifier
+    from cpx.config.config import Config, ModelConfig
+    from cpx.ml_tools.interpreter import Interpreter
+    from cpx.track.trackextractor import extract_file
+    from helpers import crc
+
+    with open(os.path.join(GOLDEN, "postprocess_variants_golden.json")) as fh:
+        gold = json.load(fh)["%s_%s" % (name, variant)]
+    clip_file = tmp_path / (name + ".cptv")
+    shutil.copy(os.path.join(GOLDEN, name + ".cptv"), clip_file)
+    mfile = tmp_path / "model.json"
+    mfile.write_text(json.dumps({"labels": LABELS, "hyperparams": gold["hyperparams"], "type": "thermal",
+                                 "version": "golden"}))
+    cfg = Config.get_defaults()
+    cfg.tracking["thermal"].denoise = False
+    cfg.classify.models = [ModelConfig.load({"id": 7, "name": "wr-test", "model_file": str(mfile)})]
+    extract_file(clip_file, cfg, False)
+    chunks, seg_log = [], {}
+
+    class Capture(Interpreter):
+        TYPE = "capture"
+
+        def shape(self):
+            return 1, (None, 160, 160, 2)
+
+        def predict(self, frames):
+            x = frames.cpu().numpy() if isinstance(frames, torch.Tensor) else np.asarray(frames, dtype=np.float32)
+            chunks.append(np.array(x, dtype=np.float32, copy=True))
+            return fake_predict(x)
+
+    interp = Capture(mfile)
+    interp.id, interp.port = 7, 8123
+    orig = interp.frames_for_prediction
+
+    def logged(clip, track, **args):
+        segs = orig(clip, track, **args)
+        seg_log[track.get_id()] = [[int(f) for f in s.frame_indices] for s in segs]
+        return segs
+
+    interp.frames_for_prediction = logged
+    classifier = ClipClassifier(cfg)
+    classifier.get_classifier = lambda model, location=None: interp
+    with IdentityDraws():
+        assert classifier.post_process_file(clip_file, None) is not False
+    x = np.concatenate(chunks)
+    pos = 0
+    for g in gold["tracks"]:
+        assert seg_log.get(g["id"], []) == g["segments"], g["id"]
+        assert [crc(s) for s in x[pos:pos + len(g["segments"])]] == g["crc"], (name, variant, g["id"])
+        pos += len(g["segments"])
+    assert pos == len(x) >= 1
