@@ -365,11 +365,19 @@ class LiteInterpreter(Interpreter):
     preprocess_input subtracts per-channel means of three colour channels, which the graph's INPUT operator does on the
     device from the unscaled two-channel crop sample (input_mode; the host statements are caffe_preprocess /
     torch_preprocess).  CPX_TFLITE_FUSE_PREACT=1|0 (default 1): fold a pre-activation into the convolutions that read
-    it (tflite_graph.build_plan: fuse_preactivation) or keep it a launch -- the same bits either way."""
+    it (tflite_graph.build_plan: fuse_preactivation) or keep it a launch -- the same bits either way.
+    CPX_TFLITE_FUSE_PREACT_DW=1|0 (default 0; it needs CPX_TFLITE_FUSE_PREACT=1) also folds a bare RELU into the depthwise
+    convolutions and SLICEs that read it (fuse_preactivation_dw): the same bits, 6 % faster at N = 128 and 11 % slower at
+    N = 1 on a NASNet-layout graph, hence off.  The nasnet family runs here
+    (STRIDED_SLICE / SLICE); CPX_TFLITE_FOLD_WINDOWS=1|0 (default 1): 1 x 1 pools and chains of PAD / SLICE as one SLICE
+    launch, a PAD folded into the VALID convolution behind it (build_plan: fold_windows), or every one of them a launch --
+    again the same bits."""
 
     TYPE = "TFLite"
     DEFAULT_QUANT_MATH = "hybrid"
     DEFAULT_FUSE_PREACT = "1"
+    DEFAULT_FOLD_WINDOWS = "1"
+    DEFAULT_FUSE_PREACT_DW = "0"
     INPUT_MODE_OF = {"resnet": "caffe", "resnet152": "caffe", "vgg16": "caffe", "vgg19": "caffe", "densenet121": "torch"}
 
     @classmethod
@@ -386,6 +394,20 @@ class LiteInterpreter(Interpreter):
         mode = os.environ.get("CPX_TFLITE_FUSE_PREACT", cls.DEFAULT_FUSE_PREACT)
         if mode not in ("0", "1"):
             raise ValueError("CPX_TFLITE_FUSE_PREACT=%r: one of 0, 1" % mode)
+        return mode == "1"
+
+    @classmethod
+    def fuse_preact_dw(cls):
+        mode = os.environ.get("CPX_TFLITE_FUSE_PREACT_DW", cls.DEFAULT_FUSE_PREACT_DW)
+        if mode not in ("0", "1"):
+            raise ValueError("CPX_TFLITE_FUSE_PREACT_DW=%r: one of 0, 1" % mode)
+        return mode == "1"
+
+    @classmethod
+    def fold_windows(cls):
+        mode = os.environ.get("CPX_TFLITE_FOLD_WINDOWS", cls.DEFAULT_FOLD_WINDOWS)
+        if mode not in ("0", "1"):
+            raise ValueError("CPX_TFLITE_FOLD_WINDOWS=%r: one of 0, 1" % mode)
         return mode == "1"
 
     def get_preprocess_fn(self):
@@ -414,8 +436,11 @@ class LiteInterpreter(Interpreter):
             self._graph = Graph(fh.read())
         self._quant_math = self.quant_math()
         self._fuse_preact = self.fuse_preact()
+        self._fold_windows = self.fold_windows()
+        self._fuse_preact_dw = self.fuse_preact_dw() and self._fuse_preact
         # refuses, by operator, what the executor does not run
-        plan = build_plan(self._graph, quantised_math=self._quant_math, fuse_preactivation=self._fuse_preact)
+        plan = build_plan(self._graph, quantised_math=self._quant_math, fuse_preactivation=self._fuse_preact,
+                          fuse_preactivation_dw=self._fuse_preact_dw, fold_windows=self._fold_windows)
         self._plans[(plan.graph_input_shape, None)] = plan
         if self.input_mode is not None and plan.graph_input_shape[2] != 3:
             raise NotImplementedError("model_name %r: the %r input mode subtracts the means of three colour channels; the "
@@ -474,6 +499,7 @@ class LiteInterpreter(Interpreter):
         if plan is None:
             plan = self._plans[key] = build_plan(self._graph, input_shape=key[0], channel_map=cmap,
                                                  quantised_math=self._quant_math, fuse_preactivation=self._fuse_preact,
+                                                 fuse_preactivation_dw=self._fuse_preact_dw, fold_windows=self._fold_windows,
                                                  input_mode=None if cmap is None else self.input_mode)
         return key, plan
 

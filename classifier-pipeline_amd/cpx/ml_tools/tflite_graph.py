@@ -19,6 +19,31 @@
   concatenation): those convolutions become CONV_PRE, read the AFFINE's input -- a channel slice of a concatenated
   tensor included -- and apply the two float32 operations and the activation while they stage the patch, bit for bit
   what the launch did (pack_conv_pre: the constants ride behind the filter image);
+* STRIDED_SLICE / SLICE over H and W (tflite_reader.resolve_slice: start, stride, count per axis) is one SLICE operator,
+  a copy with a signed pad (negative: a crop), a stride and an optional RELU / RELU6 (include/cpx.h: CPX_GRAPH_SLICE);
+* with fold_windows=True (a NASNet's adjust block and stride-2 separable convolutions, MobileNetV2's stride-2 blocks)
+  - a 1 x 1 AVERAGE_POOL_2D / MAX_POOL_2D without an activation is a SLICE: the mean or maximum of one element is it.
+    The pool kernel's mean is (0 + e) / 1, which makes +0.0 of a -0.0: the SLICE of an average pool carries param 1 and
+    adds 0.0f too (include/cpx.h), so that not even that bit moves;
+  - a PAD, a SLICE or such a pool followed by a SLICE or such a pool that reads only inside its input (no positive pad
+    of its own) is ONE SLICE, start and stride composed affinely: PAD((0,1),(0,1)) -> [:, 1:, 1:, :] -> 1 x 1 stride 2
+    is pad_top = pad_left = -1, stride 2.  A crop followed by a PAD is not composed: its zeros lie inside the original;
+  - a PAD whose only reader is a VALID CONV_2D / DEPTHWISE_CONV_2D, float32 or hybrid, with every pad below the kernel
+    side, is dropped and the reader takes its input with the four explicit pads.  Not into MAX_POOL ("padding never wins")
+    nor into a wider AVERAGE_POOL ("divided by the in-bounds count"): different arithmetic.
+  The dropped tensor must be one of its own (in no concatenation, no view of it read, not the graph's input or
+  output) and read by the folding operator alone (the QUANT_PARAMS of a hybrid reader's view move to the PAD's input);
+* with fuse_preactivation_dw=True the pre-activation pass (behind the window folds) also drops a BARE RELU / RELU6 every
+  reader of which reads it as in0 and is a float32 CONV (-> CONV_PRE, scale 1, shift 0), a float32 DWCONV (-> DWCONV_PRE)
+  or a SLICE without an activation (which takes it).  The hybrid DWCONV_Q8 quantises with the parameters of the STORED
+  tensor and keeps the launch.
+  Both keywords yield the bits of the launches they replace.  A SLICE moves values; activate() is the one the AFFINE
+  launch ran, and act(0) = 0, so it commutes with selection and zero padding.  The depthwise sum is one chain from +0 in
+  raster order: a tap that the PAD launch made a stored 0 is fmaf(0, w, acc) = acc for finite w (acc is never -0: it
+  starts at +0, and x + (+-0) = x, +0 + (+-0) = +0 when rounding to nearest), a tap the kernel masks is skipped -- the same
+  acc; the implicit-GEMM patch holds 0 for a padded tap either way and its K walk (tap, chunk) does not change; a hybrid
+  padded tap is q = zp, a real 0, whether read or masked, and QUANT_PARAMS already takes rmin = min(0, min x),
+  rmax = max(0, max x), which zeros do not move;
 * input_mode "caffe" / "torch" plans the INPUT operator where the channel map stands: the channel map plus the
   arithmetic of keras.applications' preprocess_input in those modes on the unscaled sample (INPUT_MODES);
 * any other MUL of two activations is a MUL operator: two tensors of one shape, or [H, W, C] by the [1, 1, C] gate of a
@@ -49,7 +74,7 @@ import ctypes as C
 import numpy as np
 
 from .. import _lib
-from .tflite_reader import ACT_NONE, ACT_RELU, ACT_RELU6, FILTER_OPS, PADDING_SAME
+from .tflite_reader import ACT_NONE, ACT_RELU, ACT_RELU6, FILTER_OPS, PADDING_SAME, SLICE_OPS, resolve_slice
 
 ALIGN = 64   # floats: every tensor of the arena starts on a 256-byte boundary
 
@@ -115,6 +140,13 @@ def window(size, k, s, padding):
     return (size - k) // s + 1, 0, 0
 
 
+def slice_pads(H, W, ho, wo, sh, sw, pad_top, pad_left):
+    """The four pads of a SLICE operator (include/cpx.h: CPX_GRAPH_SLICE) that makes ho x wo pixels of an H x W input
+    with the signed pad_top / pad_left: pad_bottom / pad_right are what the output size implies, negative where input rows
+    are left over."""
+    return (pad_top, pad_left, (ho - 1) * sh + 1 - H - pad_top, (wo - 1) * sw + 1 - W - pad_left)
+
+
 def _channel_const(g, tid, channels, what):
     c = g.const(tid)
     v = np.asarray(c, np.float32).reshape(-1)
@@ -141,7 +173,7 @@ PRE_ACTS = (ACT_RELU, ACT_RELU6)
 
 
 def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_math="hybrid", fuse_activations=True,
-               input_mode=None, fuse_preactivation=False):
+               input_mode=None, fuse_preactivation=False, fold_windows=False, fuse_preactivation_dw=False):
     """g: tflite_reader.Graph.  input_shape: (H, W, C) of a sample, default: the flatbuffer's.  output: the tensor the
     forward hands out, default the graph's output; the operators it does not need are dropped.  channel_map: up to 4
     indices into the channels of the sample the CALLER brings ([N, H, W, max(map) + 1 or more]): the graph's input
@@ -150,7 +182,10 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
     input_mode: "caffe" | "torch": the caller brings the unscaled 0..255 sample and the channel map becomes the INPUT
     operator, which also does that mode's arithmetic on exactly three graph channels; channel_map is what the graph
     reads, so the BGR reversal of 'caffe' is the caller's (LiteInterpreter.channel_map).  fuse_preactivation: an AFFINE with a RELU / RELU6 whose only readers are float32
-    convolutions is dropped and those convolutions become CONV_PRE (the same float32 operations, bit for bit)."""
+    convolutions is dropped and those convolutions become CONV_PRE (the same float32 operations, bit for bit).
+    fold_windows: 1 x 1 pools and chains of PAD / SLICE become one SLICE, a PAD folds into the VALID convolution behind it.
+    fuse_preactivation_dw: a bare RELU / RELU6 is also dropped in front of float32 depthwise convolutions (DWCONV_PRE) and
+    SLICEs; both keep every bit (the module's docstring)."""
     if quantised_math not in QUANT_MATHS:
         raise ValueError("quantised_math %r: one of %s" % (quantised_math, ", ".join(QUANT_MATHS)))
     if input_mode is not None and input_mode not in INPUT_MODES:
@@ -418,6 +453,13 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
                 raise NotImplementedError("%s with paddings %s: only H and W are padded" % (what, pd))
             T[y] = PlanTensor(y, x.H + pd[1][0] + pd[1][1], x.W + pd[2][0] + pd[2][1], x.C)
             emit(PlanOp(_lib.GRAPH_PAD, name, x.id, y, pads=(pd[1][0], pd[2][0], pd[1][1], pd[2][1])), i)
+        elif name in SLICE_OPS:
+            (_, (y0, sh, ho), (x0, sw, wo), _) = resolve_slice(op, (1, x.H, x.W, x.C), what)
+            if sh > 7 or sw > 7:
+                raise NotImplementedError("%s: strides %d, %d, only 1 to 7 are run" % (what, sh, sw))
+            T[y] = PlanTensor(y, ho, wo, x.C)
+            emit(PlanOp(_lib.GRAPH_SLICE, name, x.id, y, stride_h=sh, stride_w=sw,
+                        pads=slice_pads(x.H, x.W, ho, wo, sh, sw, -y0, -x0)), i)
         elif name == "RESHAPE":
             shp = g.const(ins[1]) if len(ins) > 1 else None
             shp = [int(v) for v in (shp.reshape(-1) if shp is not None else (op.get("new_shape") or g.tensors[y]["shape"]))]
@@ -507,25 +549,103 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
                 needed.add(T[o.in1].storage)
     ops = kept[::-1]
 
+    def own_tensor(tid):
+        """tid is a tensor of its own: in no concatenation, no view of it read, neither the graph's input nor its output."""
+        return T[tid].storage == tid and tid not in (out_storage, gout, plan.input, gin) and \
+            not any(t.storage == tid and k != tid for k, t in T.items())
+
+    def readers_of(tid):
+        return [r for r in ops if tid in (r.in0, r.in1)]
+
+    # ---- window folds: 1 x 1 pools and chains of PAD / SLICE as one SLICE, a PAD into the VALID convolution behind it ----
+    if fold_windows:
+        for o in ops:
+            # the mean or the maximum of one element is the element; the mean is 0 + e, which makes +0.0 of a -0.0 (param 1)
+            if o.kind in (_lib.GRAPH_MAX_POOL, _lib.GRAPH_AVG_POOL) and (o.kh, o.kw) == (1, 1) and o.act == ACT_NONE:
+                a, y = T[o.in0], T[o.out]
+                o.param = 1.0 if o.kind == _lib.GRAPH_AVG_POOL else 0.0
+                o.kind, o.pads = _lib.GRAPH_SLICE, slice_pads(a.H, a.W, y.H, y.W, o.stride_h, o.stride_w, 0, 0)
+        changed = True
+        while changed:
+            changed = False
+            for b in ops:
+                # b reads only inside its input: t[y * sb - pb], no pad of its own.  Behind a: t[y] = in[y * sa - pa] (0
+                # outside in), b is in[y * sa * sb - (pb * sa + pa)], 0 outside in -- start and stride compose affinely
+                if b.kind != _lib.GRAPH_SLICE or max(b.pads) > 0 or not own_tensor(b.in0) or readers_of(b.in0) != [b]:
+                    continue
+                a = next((p for p in ops if p.out == b.in0), None)
+                if a is None or a.kind not in (_lib.GRAPH_PAD, _lib.GRAPH_SLICE) or a.act != ACT_NONE or b.act != ACT_NONE \
+                        or a.stride_h * b.stride_h > 7 or a.stride_w * b.stride_w > 7:
+                    continue
+                src, y = T[a.in0], T[b.out]
+                sh, sw = a.stride_h * b.stride_h, a.stride_w * b.stride_w
+                b.pads = slice_pads(src.H, src.W, y.H, y.W, sh, sw, b.pads[0] * a.stride_h + a.pads[0],
+                                    b.pads[1] * a.stride_w + a.pads[1])
+                b.in0, b.stride_h, b.stride_w, b.name = a.in0, sh, sw, a.name + ">" + b.name
+                b.param = max(a.param, b.param)   # (+ 0.0f anywhere in a chain of copies is + 0.0f at its end)
+                ops.remove(a)
+                changed = True
+                break
+        for p in list(ops):
+            # PAD + VALID = the operator with explicit pads, float32 or hybrid: the implicit-GEMM patch holds 0 for a padded
+            # tap either way, a depthwise chain skips it, and the zeros change no QUANT_PARAMS (rmin = min(0, min x)), so
+            # the QUANT_PARAMS of the padded view read the unpadded tensor
+            if p.kind != _lib.GRAPH_PAD or not own_tensor(p.out):
+                continue
+            readers = readers_of(p.out)
+            params = [r for r in readers if r.kind == _lib.GRAPH_QUANT_PARAMS]
+            rest = [r for r in readers if r.kind != _lib.GRAPH_QUANT_PARAMS]
+            if len(rest) != 1:
+                continue
+            r = rest[0]
+            if r.kind not in (_lib.GRAPH_CONV, _lib.GRAPH_CONV_Q8, _lib.GRAPH_DWCONV, _lib.GRAPH_DWCONV_Q8) or r.in0 != p.out \
+                    or r.pads != (0, 0, 0, 0) or any(readers_of(q.out) != [r] for q in params):
+                continue
+            pt, pl, pb, pr = p.pads
+            if max(pt, pb) >= r.kh or max(pl, pr) >= r.kw:
+                continue
+            r.in0, r.pads, r.name = p.in0, p.pads, "PAD>" + r.name
+            for q in params:
+                q.in0 = p.in0
+            ops.remove(p)
+
     # ---- the pre-activation of a DenseNet / ResNetV2 block: an AFFINE with a RELU in front of float32 convolutions ----
     # (the tensor has other readers -- the next concatenation, the shortcut -- so it could not fold into its producer)
-    if fuse_preactivation:
+    # with fuse_preactivation_dw a bare RELU / RELU6 may also be read by float32 depthwise convolutions (-> DWCONV_PRE) and
+    # by SLICEs without an activation (which take it as theirs): NASNet's Activation('relu') in front of every separable
+    # convolution and of the two paths of an adjust block.  It runs behind the window folds: the PAD between the RELU and a
+    # stride-2 depthwise convolution has to be gone first
+    if fuse_preactivation or fuse_preactivation_dw:
         for o in list(ops):
             if o.kind != _lib.GRAPH_AFFINE or o.copy or o.act not in PRE_ACTS or o.in0 == o.out or o.out == gout:
                 continue
             # its output is a tensor of its own: in no concatenation, not the output's storage, no view of it read
-            if T[o.out].storage != o.out or o.out == out_storage or \
-                    any(t.storage == o.out and k != o.out for k, t in T.items()):
+            if not own_tensor(o.out):
                 continue
-            readers = [r for r in ops if o.out in (r.in0, r.in1)]
-            if not readers or any(r.kind != _lib.GRAPH_CONV or r.in0 != o.out for r in readers):
+            readers = readers_of(o.out)
+            if not readers or any(r.in0 != o.out or r.in1 == o.out for r in readers):
+                continue
+            bare = o.scale is None and o.shift is None
+            if fuse_preactivation and all(r.kind == _lib.GRAPH_CONV for r in readers):
+                pass
+            elif fuse_preactivation_dw and bare and all(
+                    r.kind in (_lib.GRAPH_CONV, _lib.GRAPH_DWCONV) or (r.kind == _lib.GRAPH_SLICE and r.act == ACT_NONE)
+                    for r in readers):
+                pass
+            else:
                 continue
             cin = T[o.in0].C
             for r in readers:
-                r.kind, r.in0, r.param, r.name = _lib.GRAPH_CONV_PRE, o.in0, float(o.act), "AFFINE>" + r.name
-                r.pre_scale = np.ones(cin, np.float32) if o.scale is None else o.scale
-                r.pre_shift = np.zeros(cin, np.float32) if o.shift is None else o.shift
-                r.pre_source = o.source
+                r.in0 = o.in0
+                if r.kind == _lib.GRAPH_CONV:
+                    r.kind, r.param, r.name = _lib.GRAPH_CONV_PRE, float(o.act), "AFFINE>" + r.name
+                    r.pre_scale = np.ones(cin, np.float32) if o.scale is None else o.scale
+                    r.pre_shift = np.zeros(cin, np.float32) if o.shift is None else o.shift
+                    r.pre_source = o.source
+                elif r.kind == _lib.GRAPH_DWCONV:
+                    r.kind, r.param, r.name = _lib.GRAPH_DWCONV_PRE, float(o.act), o.name + ">" + r.name
+                else:
+                    r.act, r.name = o.act, o.name + ">" + r.name
             ops.remove(o)
     used = set()
     for o in ops:
@@ -575,7 +695,8 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
 
     # ---- weights in the kernel's layout ----
     packers = {_lib.GRAPH_CONV: pack_conv_filter, _lib.GRAPH_CONV_Q8: pack_conv_filter_q8,
-               _lib.GRAPH_DWCONV: pack_dw_filter, _lib.GRAPH_DWCONV_Q8: pack_dw_filter_q8}
+               _lib.GRAPH_DWCONV: pack_dw_filter, _lib.GRAPH_DWCONV_PRE: pack_dw_filter,
+               _lib.GRAPH_DWCONV_Q8: pack_dw_filter_q8}
     for o in ops:
         if o.kind == _lib.GRAPH_CONV_PRE:
             o.weights = pack_conv_pre(o.filter, o.pre_scale, o.pre_shift)
@@ -687,13 +808,14 @@ def pack_conv_pre(w_ohwi, pre_scale, pre_shift):
 
 
 def load_plan(path, input_shape=None, channel_map=None, quantised_math="hybrid", fuse_activations=True, input_mode=None,
-              fuse_preactivation=False):
+              fuse_preactivation=False, fold_windows=False, fuse_preactivation_dw=False):
     from .tflite_reader import Graph
 
     with open(str(path), "rb") as fh:
         g = Graph(fh.read())
     return g, build_plan(g, input_shape=input_shape, channel_map=channel_map, quantised_math=quantised_math,
-                         fuse_activations=fuse_activations, input_mode=input_mode, fuse_preactivation=fuse_preactivation)
+                         fuse_activations=fuse_activations, input_mode=input_mode, fuse_preactivation=fuse_preactivation,
+                         fold_windows=fold_windows, fuse_preactivation_dw=fuse_preactivation_dw)
 
 
 class GraphDevice:

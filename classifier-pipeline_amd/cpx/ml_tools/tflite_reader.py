@@ -3,7 +3,8 @@ only NumPy.  Two users:
 
 * `Graph` decodes subgraph 0 of any float32 model made of the operators in OPS below, with their options: CONV_2D
   (dilation 1 only), DEPTHWISE_CONV_2D (filter [1, kh, kw, C]; depth multiplier 1 and dilation 1 only), AVERAGE_POOL_2D, MAX_POOL_2D, CONCATENATION, ADD, SUB, MUL, DIV, RELU, RELU6, MEAN, FULLY_CONNECTED,
-  LOGISTIC, SOFTMAX, RESHAPE, PAD.  That is the set the converter writes for the reference's `inceptionv3` family
+  LOGISTIC, SOFTMAX, RESHAPE, PAD, STRIDED_SLICE, SLICE (over H and W, resolved on the host by resolve_slice into start,
+  stride and count per axis; a NASNet's Cropping2D).  That is the set the converter writes for the reference's `inceptionv3` family
   (ml_tools/kerasmodel.py:171-180,259-350; the artefact the reference's CI classifies with, .github/workflows/
   release.yml:46 `inc3-tflite-15122023.tar`, is one), for its `mobilenet` family (MobileNetV2, kerasmodel.py:144-151) and
   for its `efficientnetb0` / `b1` / `b5` / `efficientnetv2b3` families (kerasmodel.py:181-216: swish as LOGISTIC + MUL of two
@@ -36,7 +37,8 @@ import numpy as np
 BN_EPS = np.float32(1e-3)
 OPS = {0: "ADD", 1: "AVERAGE_POOL_2D", 2: "CONCATENATION", 3: "CONV_2D", 4: "DEPTHWISE_CONV_2D", 9: "FULLY_CONNECTED", 14: "LOGISTIC",
        17: "MAX_POOL_2D", 18: "MUL", 19: "RELU", 21: "RELU6", 25: "SOFTMAX", 40: "MEAN", 41: "SUB", 22: "RESHAPE", 34: "PAD",
-       42: "DIV"}
+       42: "DIV", 45: "STRIDED_SLICE", 65: "SLICE"}
+SLICE_OPS = ("STRIDED_SLICE", "SLICE")
 # operators that are recognised only to be refused by name (check_executable)
 REFUSED_OPS = {6: "DEQUANTIZE", 114: "QUANTIZE", 67: "TRANSPOSE_CONV", 23: "RESIZE_BILINEAR",
                28: "TANH", 39: "TRANSPOSE", 32: "CUSTOM", 117: "HARD_SWISH"}
@@ -179,6 +181,26 @@ class Graph:
                     o["keep_dims"] = bool(opts.scalar(0, "b", 0))
                 elif o["name"] == "RESHAPE":
                     o["new_shape"] = opts.vector(0, "i")
+                elif o["name"] == "STRIDED_SLICE":
+                    o.update(begin_mask=opts.scalar(0, "i", 0), end_mask=opts.scalar(1, "i", 0), ellipsis_mask=opts.scalar(2, "i", 0),
+                             new_axis_mask=opts.scalar(3, "i", 0), shrink_axis_mask=opts.scalar(4, "i", 0),
+                             offset=bool(opts.scalar(5, "b", 0)))
+            if o["name"] in SLICE_OPS:
+                for k, key in enumerate(("begin", "end", "strides") if o["name"] == "STRIDED_SLICE" else ("begin", "size"), 1):
+                    v = self.tensors[o["inputs"][k]]["const"] if len(o["inputs"]) > k and o["inputs"][k] >= 0 else None
+                    o[key] = None if v is None else [int(e) for e in np.asarray(v).reshape(-1)]
+                for key in ("begin_mask", "end_mask", "ellipsis_mask", "new_axis_mask", "shrink_axis_mask"):
+                    o.setdefault(key, 0)
+                o.setdefault("offset", False)
+                # (start, stride, count) per axis on the flatbuffer's own shape; None where that shape is dynamic or the
+                # operator is one check_executable refuses
+                o["slice"] = None
+                shape = self.tensors[o["inputs"][0]]["shape"]
+                if len(shape) == 4 and min(shape[1:]) > 0:
+                    try:
+                        o["slice"] = resolve_slice(o, shape, "operator %d (%s)" % (len(self.ops), o["name"]))
+                    except NotImplementedError:
+                        pass
             if o["name"] == "FULLY_CONNECTED":
                 o.setdefault("asymmetric_quantize_inputs", False)
             if o["name"] == "MEAN":
@@ -218,8 +240,8 @@ class Graph:
 
     def check_executable(self):
         """Raises NotImplementedError, naming the operator and its index, for whatever the graph executor
-        (cpx/ml_tools/tflite_graph.py) does not run: an operator outside OPS, a tensor that is not float32 (int32
-        constants of MEAN / RESHAPE / PAD excepted; an INT8 constant as the filter of CONV_2D / FULLY_CONNECTED with
+        (cpx/ml_tools/tflite_graph.py) does not run: an operator outside OPS, a STRIDED_SLICE / SLICE that resolve_slice
+        refuses, a tensor that is not float32 (int32 constants of MEAN / RESHAPE / PAD / STRIDED_SLICE / SLICE excepted; an INT8 constant as the filter of CONV_2D / FULLY_CONNECTED with
         symmetric scales along dimension 0, or of DEPTHWISE_CONV_2D along dimension 3, excepted), grouped CONV_2D, a
         DEPTHWISE_CONV_2D with a depth multiplier or a dilation other than 1, a dynamic shape."""
         for i, op in enumerate(self.ops):
@@ -227,11 +249,16 @@ class Graph:
             if op["code"] not in OPS:
                 raise NotImplementedError("operator %d (%s) is not in the set the graph executor runs: %s"
                                           % (i, REFUSED_OPS.get(op["code"], name), ", ".join(sorted(OPS.values()))))
+            if name in SLICE_OPS:
+                shape = self.tensors[op["inputs"][0]]["shape"]
+                # (a dynamic H or W: the planner resolves against the shape it plans for, and refuses there)
+                resolve_slice(op, shape if len(shape) == 4 and min(shape[1:]) > 0 else None, "operator %d (%s)" % (i, name))
             for k, t in enumerate(list(op["inputs"]) + list(op["outputs"])):
                 if t < 0:
                     continue
                 ten = self.tensors[t]
-                int_const = ten["type"] == 2 and ten["const"] is not None and name in ("MEAN", "RESHAPE", "PAD") and k >= 1
+                int_const = ten["type"] == 2 and ten["const"] is not None and k >= 1 and \
+                    name in ("MEAN", "RESHAPE", "PAD") + SLICE_OPS
                 if ten["type"] == 9 and ten["const"] is not None and k == 1 and name in FILTER_OPS:
                     q = ten["quant"]
                     if q is None:
@@ -283,6 +310,53 @@ class Graph:
                 raise NotImplementedError("operator %d (MEAN): the axes are not a constant" % i)
             if name == "PAD" and op["paddings"] is None:
                 raise NotImplementedError("operator %d (PAD): the paddings are not a constant" % i)
+
+
+def resolve_slice(op, shape, what):
+    """A STRIDED_SLICE / SLICE operator of a Graph on an input of `shape` ([N, H, W, C]; N may be unknown, < 1) ->
+    [(start, stride, count)] per axis, with TensorFlow's rules: a masked begin / end is the axis' edge, a negative index
+    counts from the end, both are clamped to [0, size]; SLICE's size -1 runs to the end.  shape None: only what does not
+    depend on the shape is checked, and None returned.  Refused, by `what` (the operator's name and index): begin / end /
+    strides / size that are not constants, an ellipsis, new-axis or shrink-axis mask, `offset`, a stride below 1, an empty
+    result, anything but the full range on the batch and on the channel axis."""
+    strided = op["name"] == "STRIDED_SLICE"
+    keys = ("begin", "end", "strides") if strided else ("begin", "size")
+    for key in keys:
+        if op.get(key) is None:
+            raise NotImplementedError("%s: %s is not a constant" % (what, key))
+        if len(op[key]) != 4:
+            raise NotImplementedError("%s: %s has %d elements, only slices of [N, H, W, C] tensors are run" % (what, key, len(op[key])))
+    if strided:
+        for key in ("ellipsis_mask", "new_axis_mask", "shrink_axis_mask"):
+            if op.get(key, 0):
+                raise NotImplementedError("%s: %s %d, only begin_mask and end_mask are run" % (what, key, op[key]))
+        if op.get("offset", False):
+            raise NotImplementedError("%s: offset (end counted from begin) is not run" % what)
+        if min(op["strides"]) < 1:
+            raise NotImplementedError("%s: strides %s, only strides of 1 and above are run" % (what, op["strides"]))
+    if shape is None:
+        return None
+    out = []
+    for ax in range(4):
+        d = max(int(shape[ax]), 1) if ax == 0 else int(shape[ax])
+        b = op["begin"][ax]
+        if strided:
+            s, e = op["strides"][ax], op["end"][ax]
+            b = 0 if op["begin_mask"] >> ax & 1 else min(max(b + d if b < 0 else b, 0), d)
+            e = d if op["end_mask"] >> ax & 1 else min(max(e + d if e < 0 else e, 0), d)
+        else:
+            s, z = 1, op["size"][ax]
+            e = d if z == -1 else b + z
+            if b < 0 or z < -1 or e > d:
+                raise NotImplementedError("%s: begin %s, size %s reach beyond the input %s" % (what, op["begin"], op["size"], list(shape)))
+        count = max(-(-(e - b) // s), 0)
+        if count < 1:
+            raise NotImplementedError("%s: the result is empty along axis %d" % (what, ax))
+        if ax in (0, 3) and (b, s, count) != (0, 1, d):
+            raise NotImplementedError("%s: only the full range is run on the %s axis, not %d:%d:%d of %d"
+                                      % (what, "batch" if ax == 0 else "channel", b, e, s, d))
+        out.append((b, s, count))
+    return out
 
 
 # ---- the walk: operators in order -> Keras-layout names -------------------------------------------------------

@@ -42,10 +42,11 @@ static const char* graph_check_op(const cpx_graph_op& o, const std::vector<cpx_g
     case CPX_GRAPH_CONV_PRE:
     case CPX_GRAPH_CONV_Q8:
     case CPX_GRAPH_DWCONV:
+    case CPX_GRAPH_DWCONV_PRE:
     case CPX_GRAPH_DWCONV_Q8:
     case CPX_GRAPH_MAX_POOL:
     case CPX_GRAPH_AVG_POOL: {
-      const bool dw = o.kind == CPX_GRAPH_DWCONV || o.kind == CPX_GRAPH_DWCONV_Q8;
+      const bool dw = o.kind == CPX_GRAPH_DWCONV || o.kind == CPX_GRAPH_DWCONV_PRE || o.kind == CPX_GRAPH_DWCONV_Q8;
       const bool conv = dw || o.kind == CPX_GRAPH_CONV || o.kind == CPX_GRAPH_CONV_PRE || o.kind == CPX_GRAPH_CONV_Q8;
       if (o.kh < 1 || o.kw < 1 || o.kh > 7 || o.kw > 7) return "kernel sides are 1 to 7";
       if (o.stride_h < 1 || o.stride_w < 1 || o.stride_h > (conv ? 2 : 7) || o.stride_w > (conv ? 2 : 7)) return "bad stride";
@@ -61,7 +62,10 @@ static const char* graph_check_op(const cpx_graph_op& o, const std::vector<cpx_g
         if (o.param != (float)CPX_GRAPH_ACT_RELU && o.param != (float)CPX_GRAPH_ACT_RELU6) return "CONV_PRE: param is the pre-activation, RELU or RELU6";
         if (reinterpret_cast<uintptr_t>(o.weights) & 15) return "CONV_PRE weights are not 16-byte aligned";
       }
-      if (o.kind == CPX_GRAPH_DWCONV && (reinterpret_cast<uintptr_t>(o.weights) & 15)) return "DWCONV weights are not 16-byte aligned";
+      if (o.kind == CPX_GRAPH_DWCONV_PRE && o.param != (float)CPX_GRAPH_ACT_RELU && o.param != (float)CPX_GRAPH_ACT_RELU6)
+        return "DWCONV_PRE: param is the pre-activation, RELU or RELU6";
+      if ((o.kind == CPX_GRAPH_DWCONV || o.kind == CPX_GRAPH_DWCONV_PRE) && (reinterpret_cast<uintptr_t>(o.weights) & 15))
+        return "DWCONV weights are not 16-byte aligned";
       if (o.kind == CPX_GRAPH_DWCONV_Q8 && (reinterpret_cast<uintptr_t>(o.weights) & 3)) return "DWCONV_Q8 weights are not 4-byte aligned";
       break;
     }
@@ -97,6 +101,18 @@ static const char* graph_check_op(const cpx_graph_op& o, const std::vector<cpx_g
           y.H != a.H + o.pad_top + o.pad_bottom || y.W != a.W + o.pad_left + o.pad_right)
         return "PAD sizes do not add up";
       break;
+    case CPX_GRAPH_SLICE: {
+      // pad_top / pad_left are signed (negative: a crop); the kernel masks every read by the input's size
+      if (o.kh != 1 || o.kw != 1) return "SLICE: kh = kw = 1";
+      if (o.stride_h < 1 || o.stride_w < 1 || o.stride_h > 7 || o.stride_w > 7) return "bad stride";
+      if (o.activation != CPX_GRAPH_ACT_NONE && o.activation != CPX_GRAPH_ACT_RELU && o.activation != CPX_GRAPH_ACT_RELU6)
+        return "SLICE: the activation is NONE, RELU or RELU6";
+      const int hh = a.H + o.pad_top + o.pad_bottom - 1, ww = a.W + o.pad_left + o.pad_right - 1;
+      if (hh < 0 || ww < 0 || y.H != hh / o.stride_h + 1 || y.W != ww / o.stride_w + 1) return "SLICE: output size does not follow from stride and pads";
+      if (a.C != y.C) return "SLICE changes the channel count";
+      if (o.param != 0.0f && o.param != 1.0f) return "SLICE: param is 0 (a copy) or 1 (-0.0 becomes +0.0)";
+      break;
+    }
     case CPX_GRAPH_INPUT:
       if (!o.shift || !(o.param > 0.0f)) return "INPUT needs a shift and a positive param";
       /* fall through */

@@ -495,7 +495,9 @@ void launch_graph_op(const GraphOpArgs& a, hipStream_t s) {
       launch_graph_q8_op(a, s);
       break;
     case CPX_GRAPH_DWCONV:
+    case CPX_GRAPH_DWCONV_PRE:
     case CPX_GRAPH_DWCONV_Q8:
+    case CPX_GRAPH_SLICE:
       launch_graph_dw_op(a, s);
       break;
     default:

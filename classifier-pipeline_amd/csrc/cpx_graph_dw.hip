@@ -1,5 +1,6 @@
-// cpx_graph_dw.hip -- DEPTHWISE_CONV_2D of the TFLite graph executor (CPX_GRAPH_DWCONV / CPX_GRAPH_DWCONV_Q8,
-// include/cpx.h): depth multiplier 1, kernels up to 7 x 7, strides 1 and 2.  A depthwise convolution does kh * kw
+// cpx_graph_dw.hip -- DEPTHWISE_CONV_2D of the TFLite graph executor (CPX_GRAPH_DWCONV / CPX_GRAPH_DWCONV_PRE /
+// CPX_GRAPH_DWCONV_Q8, include/cpx.h): depth multiplier 1, kernels up to 7 x 7, strides 1 and 2; and CPX_GRAPH_SLICE, the
+// strided, cropping, zero-padding copy that shares its work item and its borders (below the depthwise kernel).  A depthwise convolution does kh * kw
 // multiply-adds per output element against about 8 bytes moved, far below the vector ridge: the matrix pipe has
 // nothing to offer, the job is to move every byte once, 16 bytes per lane.
 //
@@ -21,7 +22,13 @@
 // loaded, with the [sx, inv, zp] of its sample (no int8 copy goes to memory; a padded tap is a real 0, i.e. q = zp),
 // plain int32 multiply-adds, and the finish of the other hybrid operators (cpx_graph_core.h).  Weights: int8
 // [tap][C rounded up to 4], then int32 wsum[C rounded up to 4].
+//
+// DWCONV_PRE (PRE, float32 only) reads its input as act_pre(x), act_pre = (int)param: activate() on the loaded quad in
+// front of operand(), the bits a graph_affine_kernel launch without constants would have stored.  act_pre(0) = 0, so a
+// padded tap still contributes nothing.
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
 
 #include "cpx_graph_core.h"
 #include "cpx_kernels.h"
@@ -150,7 +157,7 @@ struct DwHybrid {
   }
 };
 
-template <class Arith, bool VEC, int SW, int KWM>
+template <class Arith, bool VEC, int SW, int KWM, bool PRE>
 __global__ __launch_bounds__(CT) void graph_dw_kernel(GraphOpArgs a, DwGeom g) {
   typedef typename Arith::V V;
   DwItem it;
@@ -181,7 +188,12 @@ __global__ __launch_bounds__(CT) void graph_dw_kernel(GraphOpArgs a, DwGeom g) {
     // column j of the run's window feeds output r as tap kx = j - r * SW: for every r the taps arrive in rising kx
 #pragma unroll
     for (int j = 0; j < NC; ++j) {
-      const V x = ar.operand(load4<VEC>(in_n, coff[j], row, c, C));
+      f32x4 xin = load4<VEC>(in_n, coff[j], row, c, C);
+      if (PRE) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) xin[e] = activate(xin[e], (int)a.param);
+      }
+      const V x = ar.operand(xin);
 #pragma unroll
       for (int r = 0; r < RUN; ++r) {
         const int kx = j - r * SW;
@@ -201,14 +213,14 @@ __global__ __launch_bounds__(CT) void graph_dw_kernel(GraphOpArgs a, DwGeom g) {
 }
 
 // the instantiation by [16-byte path][stride 2 along W][more than 3 columns]
-template <class Arith>
+template <class Arith, bool PRE>
 void launch_dw(const GraphOpArgs& a, hipStream_t s) {
   typedef void (*Kernel)(GraphOpArgs, DwGeom);
   static const Kernel kernels[2][2][2] = {
-      {{graph_dw_kernel<Arith, false, 1, 3>, graph_dw_kernel<Arith, false, 1, 7>},
-       {graph_dw_kernel<Arith, false, 2, 3>, graph_dw_kernel<Arith, false, 2, 7>}},
-      {{graph_dw_kernel<Arith, true, 1, 3>, graph_dw_kernel<Arith, true, 1, 7>},
-       {graph_dw_kernel<Arith, true, 2, 3>, graph_dw_kernel<Arith, true, 2, 7>}}};
+      {{graph_dw_kernel<Arith, false, 1, 3, PRE>, graph_dw_kernel<Arith, false, 1, 7, PRE>},
+       {graph_dw_kernel<Arith, false, 2, 3, PRE>, graph_dw_kernel<Arith, false, 2, 7, PRE>}},
+      {{graph_dw_kernel<Arith, true, 1, 3, PRE>, graph_dw_kernel<Arith, true, 1, 7, PRE>},
+       {graph_dw_kernel<Arith, true, 2, 3, PRE>, graph_dw_kernel<Arith, true, 2, 7, PRE>}}};
   DwGeom g;
   g.groups = (a.out.C + 3) / 4;
   g.runs = (a.out.W + RUN - 1) / RUN;
@@ -217,13 +229,56 @@ void launch_dw(const GraphOpArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(kernels[vec][a.stride_w != 1][a.kw > 3], dim3((unsigned)((g.items + CT - 1) / CT)), dim3(CT), 0, s, a, g);
 }
 
+// SLICE: out[n, y, x, c] = act(in0[n, y * stride_h - pad_top, x * stride_w - pad_left, c]), 0 outside the input (a signed
+// pad: negative crops, positive pads with zeros; act(0) = 0).  A copy: the depthwise work item with a run of one pixel
+// and its branch-free border, one 16-byte load and store per item (VEC) or channel by channel; no LDS.  param 1: the
+// value goes through v + 0.0f behind the activation, which is what graph_pool_kernel's sum from 0 makes of the one
+// element of a 1 x 1 AVERAGE_POOL_2D: a -0.0 becomes +0.0, every other value is itself.  The grid is
+// capped and strided over: a large batch re-uses its workgroups instead of launching millions of them.
+constexpr unsigned SLICE_MAX_BLOCKS = 16384;
+
+template <bool VEC>
+__global__ __launch_bounds__(CT) void graph_slice_kernel(GraphOpArgs a, DwGeom g) {
+  const int C = a.in0.C, H = a.in0.H, W = a.in0.W;
+  for (size_t idx = (size_t)blockIdx.x * CT + threadIdx.x; idx < g.items; idx += (size_t)gridDim.x * CT) {
+    DwItem it;
+    dw_item<1>(idx, g, a.out.H, &it);
+    const int iy = window_origin(it.oy, a.stride_h, a.pad_top), ix = window_origin(it.ox0, a.stride_w, a.pad_left);
+    const int col = ix >= 0 && ix < W ? ix * a.in0.cstride + it.c : -1;
+    const int row = iy >= 0 && iy < H ? iy * W * a.in0.cstride : -1;
+    f32x4 v = load4<VEC>(a.in0.p + it.n * a.in0.sample_stride, col, row, it.c, C);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      v[e] = activate(v[e], a.act);
+      v[e] = a.param != 0.0f ? v[e] + 0.0f : v[e];
+    }
+    store4<VEC>(a.out.p + it.n * a.out.sample_stride + it.c + (unsigned)((it.oy * a.out.W + it.ox0) * a.out.cstride), v, it.c, C);
+  }
+}
+
+void launch_slice(const GraphOpArgs& a, hipStream_t s) {
+  DwGeom g;
+  g.groups = (a.out.C + 3) / 4;
+  g.runs = a.out.W;
+  g.items = (size_t)a.N * a.out.H * g.runs * g.groups;
+  const unsigned blocks = (unsigned)std::min<size_t>((g.items + CT - 1) / CT, SLICE_MAX_BLOCKS);
+  if (quads(a.in0) && quads(a.out))
+    hipLaunchKernelGGL(graph_slice_kernel<true>, dim3(blocks), dim3(CT), 0, s, a, g);
+  else
+    hipLaunchKernelGGL(graph_slice_kernel<false>, dim3(blocks), dim3(CT), 0, s, a, g);
+}
+
 }  // namespace
 
 void launch_graph_dw_op(const GraphOpArgs& a, hipStream_t s) {
-  if (a.kind == CPX_GRAPH_DWCONV_Q8)
-    launch_dw<DwHybrid>(a, s);
+  if (a.kind == CPX_GRAPH_SLICE)
+    launch_slice(a, s);
+  else if (a.kind == CPX_GRAPH_DWCONV_Q8)
+    launch_dw<DwHybrid, false>(a, s);
+  else if (a.kind == CPX_GRAPH_DWCONV_PRE)
+    launch_dw<DwFloat, true>(a, s);
   else
-    launch_dw<DwFloat>(a, s);
+    launch_dw<DwFloat, false>(a, s);
 }
 
 }  // namespace cpx

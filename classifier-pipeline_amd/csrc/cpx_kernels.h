@@ -411,7 +411,8 @@ constexpr int GRAPH_CONV_CO = 32;  // ... and Cout to this
 // are output channel l & 31 of the tile, input channels 16 * (l >> 5) + j of the chunk; zeros beyond Cin and Cout.
 void launch_graph_q8_op(const GraphOpArgs& a, hipStream_t s);
 constexpr int GRAPH_CONV_Q8_KC = 32;
-// DEPTHWISE_CONV_2D, float32 and hybrid (cpx_graph_dw.hip): weights [tap][C rounded up to 4], float32 or int8 + wsum.
+// DEPTHWISE_CONV_2D, float32 (with or without a pre-activation) and hybrid, and SLICE (cpx_graph_dw.hip): weights
+// [tap][C rounded up to 4], float32 or int8 + wsum.
 void launch_graph_dw_op(const GraphOpArgs& a, hipStream_t s);
 
 // Kernels that use more than 64 KB of dynamic LDS need hipFuncAttributeMaxDynamicSharedMemorySize raised once per

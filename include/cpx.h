@@ -854,12 +854,26 @@ enum {
                                 a NULL scale: no second division.  caffe: param 1, shift = the BGR means, scale NULL (the
                                 BGR reversal is the caller's channel_map); torch: param 255, shift = the means, scale =
                                 the standard deviations */
-  CPX_GRAPH_CONV_PRE = 19    /* CONV whose input is read as act_pre(x * pre_scale[c] + pre_shift[c]): the two float32
+  CPX_GRAPH_CONV_PRE = 19,   /* CONV whose input is read as act_pre(x * pre_scale[c] + pre_shift[c]): the two float32
                                 operations and the activation of AFFINE, so the same bits as an AFFINE launch in front of
                                 a CONV.  `weights` (16-byte aligned): the CONV image, then float32 pre_scale[Cin rounded up
                                 to 16], then pre_shift[the same], zeros beyond Cin.  param = act_pre as a number:
                                 CPX_GRAPH_ACT_RELU or CPX_GRAPH_ACT_RELU6.  A padded tap and a channel beyond Cin
                                 contribute exactly 0, not act_pre(pre_shift).  `activation`, scale, shift: as CONV */
+  CPX_GRAPH_SLICE = 20,      /* STRIDED_SLICE / SLICE over H and W, a 1 x 1 pool, a PAD, or a chain of them as ONE copy:
+                                out[n, y, x, c] = act(in0[n, y * stride_h - pad_top, x * stride_w - pad_left, c]), exactly
+                                0 where that row or column lies outside in0.  pad_top / pad_left are SIGNED: negative is
+                                a crop, positive zero padding; strides 1 to 7 subsample; kh = kw = 1.  pad_bottom /
+                                pad_right are what the output size implies: out H = (in H + pad_top + pad_bottom - 1) /
+                                stride_h + 1, the same for W; in C = out C.  `activation`: NONE, RELU or RELU6
+                                (act(0) = 0: the zero region needs no special case).  param 0: a copy, every bit as
+                                it is.  param 1: out = act(..) + 0.0f, one float32 addition: a -0.0 becomes +0.0 and
+                                nothing else changes -- what AVG_POOL's sum from 0 makes of the one element of a
+                                1 x 1 window.  No weights */
+  CPX_GRAPH_DWCONV_PRE = 21  /* DWCONV whose input is read as act_pre(x): the activation of an AFFINE without constants,
+                                so the same bits as a RELU / RELU6 launch in front of a DWCONV.  param = act_pre as a
+                                number: CPX_GRAPH_ACT_RELU or CPX_GRAPH_ACT_RELU6.  No constants ride along: `weights`,
+                                `activation`, scale, shift as DWCONV.  A padded tap contributes nothing.  float32 only */
 };
 /* The hybrid arithmetic, per sample.  QUANT_PARAMS: rmin = min(0, min x), rmax = max(0, max x) in float32.
  * rmin == rmax: sx = inv = 1, zp = 0.  Otherwise, in float64 from those two values: s = (rmax - rmin) / 255,

@@ -42,7 +42,17 @@ must move over their time inside the forward against the HBM peak.
 
 times a DenseNet121 (tests/tflite_build_preact.py; 160 x 160 x 3) with its 61 pre-activations folded into the 1 x 1
 convolutions that read them (fuse_preactivation=True: what LiteInterpreter runs) and as AFFINE launches, the same bits,
-against PyTorch-ROCm float32 on the same graph."""
+against PyTorch-ROCm float32 on the same graph.
+
+    python tools/bench_tflite.py --nasnet [--batches 1,8,128]
+
+times a NASNet-layout graph (tests/tflite_build_nas.py, a structural stand-in: 160 x 160 x 3, penultimate 1056 as
+NASNetMobile's) with the window folds and the depthwise pre-activation on (fold_windows, fuse_preactivation_dw: what
+LiteInterpreter runs) and with every PAD, 1 x 1 pool, STRIDED_SLICE and RELU a launch, the same bits, against PyTorch-ROCm
+float32 on the same graph; and, for the largest batch, every SLICE launch of the folded plan alone (a one-operator graph,
+HIP events): the bytes it must move -- what it reads of its input and its output once -- over its time, against the HBM
+peak and the float4-copy rate.  --mobilenet times the folded plan beside the plain one too; --folded chooses it for a run
+under a profiler and for its --kernel-trace (--nasnet: --unfused chooses the other plan)."""
 import argparse
 import json
 import os
@@ -55,8 +65,10 @@ for p in (os.path.join(REPO, "classifier-pipeline_amd"), os.path.join(REPO, "tes
     sys.path.insert(0, p)
 
 KIND_NAMES = {1: "conv", 2: "max_pool", 3: "avg_pool", 4: "add", 5: "affine", 6: "mean", 7: "fc", 8: "logistic", 9: "softmax",
-              10: "pad", 11: "channel_map", 12: "conv_q8", 13: "fc_q8", 14: "quant_params", 15: "dwconv", 16: "dwconv_q8", 17: "mul", 18: "input", 19: "conv_pre"}
-DW_KINDS = (15, 16)
+              10: "pad", 11: "channel_map", 12: "conv_q8", 13: "fc_q8", 14: "quant_params", 15: "dwconv", 16: "dwconv_q8", 17: "mul", 18: "input", 19: "conv_pre",
+              20: "slice", 21: "dwconv_pre"}
+DW_KINDS = (15, 16, 21)
+FOLDS = dict(fold_windows=True, fuse_preactivation_dw=True, fuse_preactivation=True)
 HBM_PEAK_TBS = 8.0          # MI355X HBM3E, specification
 HBM_COPY_TBS = 6.29         # what a float4 copy kernel reaches
 
@@ -97,6 +109,13 @@ def torch_model(g, device):
             elif name == "PAD":
                 (_, _), (t0, t1), (l0, l1), (_, _) = op["paddings"]
                 r = F.pad(a, (l0, l1, t0, t1))
+            elif name in ("STRIDED_SLICE", "SLICE"):
+                from cpx.ml_tools.tflite_reader import resolve_slice
+
+                (_, (y0, sy, ny), (x0, sx, nx), _) = resolve_slice(op, [1, a.shape[2], a.shape[3], a.shape[1]], name)
+                r = a[:, :, y0:y0 + sy * (ny - 1) + 1:sy, x0:x0 + sx * (nx - 1) + 1:sx]
+            elif name == "RELU":
+                r = torch.relu(a)
             elif name in ("ADD", "SUB", "MUL", "DIV"):
                 p, q = (val[t] if t in val else const[t].reshape(1, -1, 1, 1) for t in ins[:2])
                 r = _act(p + q if name == "ADD" else p - q if name == "SUB" else p * q if name == "MUL" else p / q, op["act"])
@@ -217,12 +236,15 @@ def mobilenet_leg(args):
 
     blob = td.mobilenet_v2(17, (), seed=7, width=args.width)
     g = Graph(blob)
-    plans = {"float32": build_plan(g)}
+    plans = {"float32": build_plan(g), "folded": build_plan(g, **FOLDS)}
     if args.quantised:
         plans["hybrid"] = build_plan(Graph(td.quantise(blob)))
+        plans["hybrid_folded"] = build_plan(Graph(td.quantise(blob)), **FOLDS)
+    if args.folded and args.skip_torch:
+        plans = {"folded": plans["folded"]}   # (a run under a profiler ends with forwards of ONE plan)
     batches = [int(v) for v in args.batches.split(",")]
     if args.kernel_trace:
-        name = "hybrid" if args.quantised else "float32"
+        name = "folded" if args.folded else "hybrid" if args.quantised else "float32"
         print(json.dumps(dict(split_from_trace(args.kernel_trace, plans[name], batches[-1]), plan=name)))
         return
     torch.backends.cudnn.allow_tf32 = False
@@ -230,9 +252,10 @@ def mobilenet_leg(args):
     eng = TrackEngine(model="lepton3", device=0)
     stream = torch.cuda.ExternalStream(eng.lib.cpx_stream(eng.h), device=eng.device)
     ref = torch_model(g, eng.device)
-    out = {"model": "mobilenet_v2 width %.2f 160x160x3" % args.width, "arena_bytes_per_sample": plans["float32"].arena_bytes_per_sample,
-           "launches_by_kind": {}, "batches": []}
-    for o in plans["float32"].ops:
+    first = next(iter(plans))
+    out = {"model": "mobilenet_v2 width %.2f 160x160x3" % args.width, "arena_bytes_per_sample": plans[first].arena_bytes_per_sample,
+           "launches": {k: len(v.ops) for k, v in plans.items()}, "launches_by_kind": {}, "batches": []}
+    for o in plans[first].ops:
         out["launches_by_kind"][KIND_NAMES[o.kind]] = out["launches_by_kind"].get(KIND_NAMES[o.kind], 0) + 1
     rng = np.random.default_rng(0)
 
@@ -263,6 +286,8 @@ def mobilenet_leg(args):
     # every depthwise launch of the largest batch alone: a one-operator graph of its shape
     n = batches[-1]
     for name, plan in ({} if args.skip_alone else plans).items():
+        if "folded" in name:
+            continue   # (the same depthwise shapes with explicit pads)
         rows, total_b, total_ms = [], 0.0, 0.0
         for o in plan.ops:
             if o.kind not in DW_KINDS:
@@ -412,6 +437,115 @@ def densenet_leg(args):
     print(json.dumps(out))
 
 
+def slice_bytes(plan, o, n):
+    """What a SLICE launch must move for n samples: the input elements it reads (one per output element that lies inside
+    the input) and its output once."""
+    t, i = plan.tensors[o.out], plan.tensors[o.in0]
+    rows = sum(0 <= y * o.stride_h - o.pads[0] < i.H for y in range(t.H))
+    cols = sum(0 <= x * o.stride_w - o.pads[1] < i.W for x in range(t.W))
+    return 4.0 * n * t.C * (rows * cols + t.H * t.W)
+
+
+def nasnet_leg(args):
+    """ms per forward of a NASNet-layout graph, folds on and off, by batch size, against PyTorch-ROCm float32; the SLICE
+    launches alone."""
+    import ctypes as C
+
+    import tflite_build_nas as tn
+    import torch
+    from cpx import _lib
+    from cpx.engine import TrackEngine
+    from cpx.ml_tools.tflite_graph import GraphDevice, PlanOp, Plan, PlanTensor, build_plan
+    from cpx.ml_tools.tflite_reader import Graph
+
+    size = 160
+    g = Graph(tn.nasnet(17, size=size, penultimate=int(1056 * args.width) // 24 * 24, num_blocks=args.nasnet_blocks,
+                        stem_filters=32, seed=7))
+    # windows_only: fold_windows alone; conv_pre_only: fuse_preactivation alone (RELU into the 1 x 1 convolutions, no fold)
+    plans = {"folded": build_plan(g, **FOLDS), "unfolded": build_plan(g), "windows_only": build_plan(g, fold_windows=True),
+             "conv_pre_only": build_plan(g, fuse_preactivation=True)}
+    batches = [int(v) for v in args.batches.split(",")]
+    if args.kernel_trace:
+        name = "unfolded" if args.unfused else "folded"
+        print(json.dumps(dict(split_from_trace(args.kernel_trace, plans[name], batches[-1]), plan=name)))
+        return
+    torch.backends.cudnn.allow_tf32 = False
+    torch.backends.cuda.matmul.allow_tf32 = False
+    eng = TrackEngine(model="lepton3", device=0)
+    stream = torch.cuda.ExternalStream(eng.lib.cpx_stream(eng.h), device=eng.device)
+    ref = torch_model(g, eng.device)
+    out = {"model": "nasnet stand-in, %d blocks, penultimate %d, %dx%dx3" % (args.nasnet_blocks, int(1056 * args.width) // 24 * 24, size, size),
+           "batches": []}
+    for name, plan in plans.items():
+        kinds = {}
+        for o in plan.ops:
+            kinds[KIND_NAMES[o.kind]] = kinds.get(KIND_NAMES[o.kind], 0) + 1
+        out[name] = {"launches": len(plan.ops), "launches_by_kind": kinds, "arena_bytes_per_sample": plan.arena_bytes_per_sample}
+    rng = np.random.default_rng(0)
+
+    def forward_of(dev, x, y, n):
+        def forward():
+            rc = eng.lib.cpx_graph_forward(dev._graph, C.c_void_p(x.data_ptr()), n, C.c_void_p(y.data_ptr()))
+            assert rc == 0, eng._err()
+        return forward
+
+    for n in batches:
+        x = torch.from_numpy(rng.uniform(-1, 1, size=(n, size, size, 3)).astype(np.float32)).to(eng.device)
+        rec, ys = {"N": n}, {}
+        for name, plan in plans.items():
+            if args.skip_torch and name != ("unfolded" if args.unfused else "folded"):
+                continue   # (a run under a profiler ends with forwards of ONE plan)
+            dev = GraphDevice(eng, plan)
+            y = ys[name] = torch.empty((n, 17), dtype=torch.float32, device=eng.device)
+            with torch.cuda.stream(stream):
+                rec[name + "_ms"] = timed(torch, forward_of(dev, x, y, n), args.steps, args.warmup)
+            dev.close()
+        if len(ys) > 1:
+            rec["folded_equals_unfolded"] = all(bool(torch.equal(ys["folded"], v)) for v in ys.values())
+            rec["unfolded_over_folded"] = rec["unfolded_ms"] / rec["folded_ms"]
+        if not args.skip_torch:
+            x_nchw = x.permute(0, 3, 1, 2).contiguous()
+            with torch.no_grad():
+                rec["torch_ms"] = timed(torch, lambda: ref(x_nchw), args.steps, args.warmup)
+                rec["max_abs_diff_vs_torch"] = float((ref(x_nchw) - next(iter(ys.values()))).abs().max())
+            for name in ("folded", "unfolded"):
+                rec["ratio_vs_torch_" + name] = rec["torch_ms"] / rec[name + "_ms"]
+        out["batches"].append(rec)
+    # every SLICE launch of the folded plan alone, at the largest batch: a one-operator plan of its shape
+    n = batches[-1]
+    rows, total_b, total_ms = [], 0.0, 0.0
+    seen = set()
+    for o in ([] if args.skip_alone else plans["folded"].ops):
+        i, t = plans["folded"].tensors[o.in0], plans["folded"].tensors[o.out]
+        key = (o.kind, i.H, i.W, i.C, o.pads, o.stride_h, o.act)
+        if o.kind != _lib.GRAPH_SLICE or key in seen:
+            continue
+        seen.add(key)
+        one = Plan()
+        one.tensors = {0: PlanTensor(0, i.H, i.W, i.C), 1: PlanTensor(1, t.H, t.W, t.C)}
+        for v in one.tensors.values():
+            v.arena_offset, v.storage = 0, v.id
+        one.ops = [PlanOp(_lib.GRAPH_SLICE, o.name, 0, 1, stride_h=o.stride_h, stride_w=o.stride_w, pads=o.pads, act=o.act, param=o.param)]
+        one.input, one.output, one.input_shape, one.output_shape = 0, 1, (i.H, i.W, i.C), (t.H, t.W, t.C)
+        x = torch.from_numpy(rng.uniform(-1, 1, size=(n, i.H, i.W, i.C)).astype(np.float32)).to(eng.device)
+        y = torch.empty((n, t.H, t.W, t.C), dtype=torch.float32, device=eng.device)
+        dev = GraphDevice(eng, one)
+        with torch.cuda.stream(stream):
+            ms = timed(torch, forward_of(dev, x, y, n), args.steps, args.warmup)
+        dev.close()
+        b = slice_bytes(one, one.ops[0], n)
+        rows.append({"shape": "%s %dx%dx%d -> %dx%d pads %s stride %d" % (o.name, i.H, i.W, i.C, t.H, t.W, list(o.pads), o.stride_h),
+                     "ms": ms, "mbytes": b / 1e6, "tb_per_s": b / ms / 1e9})
+        total_b += b
+        total_ms += ms
+    if rows:
+        out["slice_alone"] = {"N": n, "launches": rows, "ms_sum": total_ms, "tb_per_s": total_b / total_ms / 1e9,
+                              "share_of_hbm_peak": total_b / total_ms / 1e9 / HBM_PEAK_TBS,
+                              "share_of_copy_rate": total_b / total_ms / 1e9 / HBM_COPY_TBS}
+    eng.close()
+    print(json.dumps(out))
+
+
 def hbm_group(plan, o, n):
     """-> (group, bytes the launch must move for n samples) of the HBM-bound kinds beside the depthwise ones: MUL (in0 and the
     output once, in1 once: C floats per sample where it is the gate) and the wide MEAN (its input once)."""
@@ -421,6 +555,8 @@ def hbm_group(plan, o, n):
     if o.kind == _lib.GRAPH_MUL:
         b = plan.tensors[o.in1]
         return "mul", 4.0 * n * (2 * t.H * t.W * t.C + b.H * b.W * b.C)
+    if o.kind == _lib.GRAPH_SLICE:
+        return "slice", slice_bytes(plan, o, n)
     if o.kind == _lib.GRAPH_MEAN and i.H * i.W >= _lib.GRAPH_MEAN_WIDE_PIXELS:
         return "mean_wide", 4.0 * n * (i.H * i.W * i.C + i.C)
     return None, 0.0
@@ -438,7 +574,7 @@ def split_from_trace(path, plan, n):
     by_kind, shapes, dws, hbm = {}, {}, {}, {}
     for r, o in zip(rows, plan.ops):
         ns = int(r["End_Timestamp"]) - int(r["Start_Timestamp"])
-        assert ("conv" in r["Kernel_Name"]) == (o.kind in (1, 12)) and ("graph_dw" in r["Kernel_Name"]) == (o.kind in DW_KINDS), \
+        assert ("conv" in r["Kernel_Name"]) == (o.kind in (1, 12, 19)) and ("graph_dw" in r["Kernel_Name"]) == (o.kind in DW_KINDS), \
             (r["Kernel_Name"], o.name)
         k = by_kind.setdefault(KIND_NAMES[o.kind], {"launches": 0, "ms": 0.0})
         k["launches"] += 1
@@ -454,7 +590,7 @@ def split_from_trace(path, plan, n):
             d["launches"] += 1
             d["ms"] += ns / 1e6
             d["mbytes"] += dw_bytes(plan, o, n) / 1e6
-        if o.kind in (1, 12):
+        if o.kind in (1, 12, 19):
             t, i = plan.tensors[o.out], plan.tensors[o.in0]
             key = "%dx%d s%d %d->%d at %dx%d" % (o.kh, o.kw, o.stride_h, i.C, t.C, t.H, t.W)
             s = shapes.setdefault(key, {"launches": 0, "ms": 0.0, "gflop": 0.0})
@@ -464,7 +600,7 @@ def split_from_trace(path, plan, n):
     wall = (int(rows[-1]["End_Timestamp"]) - int(rows[0]["Start_Timestamp"])) / 1e6
     busy = sum(k["ms"] for k in by_kind.values())
     top = max(shapes, key=lambda k: shapes[k]["ms"])
-    conv = {"ms": sum(by_kind[k]["ms"] for k in ("conv", "conv_q8") if k in by_kind)}
+    conv = {"ms": sum(by_kind[k]["ms"] for k in ("conv", "conv_q8", "conv_pre") if k in by_kind)}
     conv_gflop = sum(s["gflop"] for s in shapes.values())
     tf = shapes[top]["gflop"] / shapes[top]["ms"]
     dw = {}
@@ -505,7 +641,16 @@ def main():
                     help="with --efficientnet: the fuse_activations=False plan alone (a run under a profiler, and its --kernel-trace)")
     ap.add_argument("--densenet", action="store_true",
                     help="a DenseNet121 with the pre-activations folded into their convolutions and as launches, against PyTorch-ROCm")
+    ap.add_argument("--nasnet", action="store_true",
+                    help="a NASNet-layout graph with the window folds and the depthwise pre-activation on and off, against PyTorch-ROCm")
+    ap.add_argument("--nasnet-blocks", type=int, default=2, help="with --nasnet: normal cells per stage (NASNetMobile: 4, NASNetLarge: 6)")
+    ap.add_argument("--folded", action="store_true",
+                    help="with --mobilenet: the fold_windows plan alone (a run under a profiler, and its --kernel-trace)")
     args = ap.parse_args()
+    if args.nasnet:
+        if args.batches == "1,8,32,128":
+            args.batches = "1,8,128"
+        return nasnet_leg(args)
     if args.densenet:
         return densenet_leg(args)
     if args.efficientnet:

@@ -6,7 +6,7 @@ flatbuffer is parsed here, TensorFlow is not needed (only NumPy).
     python tools/tflite_to_npz.py --describe model.tflite
 
 --describe converts nothing: it prints the operator census, the input and output shapes, the arena bytes per sample and,
-for a dynamic-range quantised file, the number of hybrid operators with the int8 against the float32 weight bytes of ANY graph the device executor runs (cpx/ml_tools/tflite_graph.py: an Inception-v3, a MobileNetV2 or an EfficientNet, say; the launches carry what was folded into them: CONV_2D+SWISH, CONV_2D+LOGISTIC, CONV_2D+MUL+ADD, AFFINE>CONV_2D for a folded pre-activation), or the refusal -- the
+for a dynamic-range quantised file, the number of hybrid operators with the int8 against the float32 weight bytes of ANY graph the device executor runs (cpx/ml_tools/tflite_graph.py: an Inception-v3, a MobileNetV2 or an EfficientNet, say; the launches carry what was folded into them: CONV_2D+SWISH, CONV_2D+LOGISTIC, CONV_2D+MUL+ADD, AFFINE>CONV_2D for a folded pre-activation; a second line gives the launches with the window folds on, as LiteInterpreter runs the file: PAD>DEPTHWISE_CONV_2D, RELU>DEPTHWISE_CONV_2D, PAD>STRIDED_SLICE>AVERAGE_POOL_2D), or the refusal -- the
 operator and its index -- of one it does not.  With a sidecar JSON beside the file (or --sidecar) it also prints the
 family's input mode.
 
@@ -58,13 +58,16 @@ def describe(g, sidecar=None):
         census[op["name"]] = census.get(op["name"], 0) + 1
     print("operators: " + ", ".join("%s: %d" % kv for kv in sorted(census.items())))
     try:
-        plan = build_plan(g, fuse_preactivation=True)   # (what LiteInterpreter runs)
+        # every PAD, 1 x 1 pool and slice a launch (CPX_TFLITE_FOLD_WINDOWS=0), and what LiteInterpreter runs
+        unfolded = build_plan(g, fuse_preactivation=True)
+        plan = build_plan(g, fuse_preactivation=True, fuse_preactivation_dw=True, fold_windows=True)
     except NotImplementedError as e:
         print("refused: %s" % e)
         return 1
     print("input shape %s, output shape %s" % (list(plan.input_shape), list(plan.output_shape)))
-    print("launches: " + ", ".join("%s: %d" % kv for kv in sorted(plan.census().items())))
-    print("arena bytes per sample: %d" % plan.arena_bytes_per_sample)
+    print("launches: " + ", ".join("%s: %d" % kv for kv in sorted(unfolded.census().items())))
+    print("folded launches (%d of %d): " % (len(plan.ops), len(unfolded.ops)) + ", ".join("%s: %d" % kv for kv in sorted(plan.census().items())))
+    print("arena bytes per sample: %d (unfolded: %d)" % (plan.arena_bytes_per_sample, unfolded.arena_bytes_per_sample))
     from cpx.ml_tools.tflite_graph import Q8_KINDS
 
     hybrid = [o for o in plan.ops if o.kind in Q8_KINDS]
