@@ -19,6 +19,14 @@
 // Fragments: a wave owns whole pixel rows, so the row read for tap row 0 of output row o is tap row 1 of o - 1 and tap row 2
 // of o - 2 (cpx_cnn_rw.hip): A reads 11 patch rows per kx for 9 mid rows (+ the two extra mid columns as three 16-pixel edge
 // groups without reuse), B 10 mid rows per kx for 8 output rows.
+// The halo carry: the two extra mid columns of a tile at ox are image columns ox + 15 and ox + 16 -- mid columns 0 and 1 of
+// the tile at ox + 16, the same sums of the same taps in the same order.  Where a workgroup walks a tile row right to left
+// (cpx_conv_layout_core.h: WALK_ROWS), that tile is the one B works on while A starts this one, so A copies the 36 pixels
+// (4.6 KB) from M[k & 1] to M[(k + 1) & 1] instead of computing them: 243 products instead of 297 on A's longer half, no
+// edge epilogue.  `carry` is decided from the two tiles' coordinates alone, whatever the walk; CPX_BLOCK32_CARRY=0 turns it off.
+// Hazards, with no barrier beyond the step's two: the source columns were written by A in step k - 1 and B only reads them
+// in step k; the destination buffer was last read by B in step k - 1 and is read again in step k + 1; a barrier lies
+// between each pair.  The overflow word is unchanged: the carried planes were range-checked by the tile that computed them.
 // Arithmetic: conv_block32_kernel's (fp16x2, the same planes and scales); the taps are summed kx-major, another float32
 // order of the same terms -- logits within 1e-5 of the two-launch form (tests/test_cnn_gpu.py).
 // Reference semantics: /root/reference/src/ml_tools/resnet/wr_resnet.py:49-98 (wr_block).
@@ -78,12 +86,6 @@ __device__ __forceinline__ void static_for(F&& f) {
     static_for<I + 1, N>(f);
   }
 }
-struct BlkTiles {
-  unsigned long long m_tx, m_ty;  // div_magic's multipliers (cpx_conv_layout_core.h: fill_tiles)
-  int tiles_x, tiles_y, total;
-};
-__device__ __forceinline__ int div_magic(int n, unsigned long long m) { return (int)(((unsigned long long)n * m) >> 42); }
-
 constexpr int K_T = 16;                          // output tile: 16 x 16
 constexpr int K_PP = 20, K_PNPX = 400;           // the staged input patch: 20 x 20
 constexpr int K_PNPXP = 402;                     // pixels per (plane, quarter pair) region, x 32 B = 64 mod 128 (cpx_cnn_bf3.hip: B_NPXP)
@@ -102,7 +104,7 @@ constexpr int K_WIMG = 3 * K_WROW;
 // rows behind the products
 constexpr size_t K_LDS = (size_t)(K_PBUF + 2 * K_MBUF) * 16;
 
-__global__ __launch_bounds__(K_CT) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_block32s_kernel(ConvArgs a, ConvArgs b, const uint4* __restrict__ wa, const uint4* __restrict__ wb, BlkTiles td) {
+__global__ __launch_bounds__(K_CT) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_block32s_kernel(ConvArgs a, ConvArgs b, const uint4* __restrict__ wa, const uint4* __restrict__ wb, BlkTiles td, int carry_on) {
   if (*a.ovf != 0) return;  // (the block's guarded three-plane launches follow)
   extern __shared__ __attribute__((aligned(16))) uint4 lds4[];
   uint4* s_P = lds4;
@@ -139,21 +141,13 @@ __global__ __launch_bounds__(K_CT) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
     if (b.out_shift) ob = *reinterpret_cast<const f32x4*>(b.out_shift + ch_l);
   }
 
-  // ---- tiles: every XCD walks its own contiguous eighth of the tile space (conv_block32_kernel) ----
-  const int per_xcd = (td.total + 7) >> 3;
-  auto tile_of = [&](int t) { return (t & 7) * per_xcd + (t >> 3); };
-  // tile j of this workgroup -> (n, oy, ox); false: it has fewer (its tiles ascend within its XCD's eighth)
+  // ---- tiles: every XCD walks its own contiguous eighth of the tiles or of the tile rows (cpx_conv_layout_core.h: walk_tile) ----
+  // tile j of this workgroup -> (n, oy, ox); false: it has fewer
   auto get_tile = [&](int j, int& n_, int& oy_, int& ox_) {
-    const int t = (int)blockIdx.x + j * (int)gridDim.x;
-    if (t >= 8 * per_xcd) return false;
-    int tile = tile_of(t);
-    if (tile >= td.total) return false;
-    int qd = div_magic(tile, td.m_tx);
-    ox_ = (tile - qd * td.tiles_x) * K_T;
-    tile = qd;
-    qd = div_magic(tile, td.m_ty);
-    oy_ = (tile - qd * td.tiles_y) * K_T;
-    n_ = qd;
+    int ty, tx;
+    if (!walk_tile(td, (int)blockIdx.x, (int)gridDim.x, j, n_, ty, tx)) return false;
+    oy_ = ty * K_T;
+    ox_ = tx * K_T;
     return true;
   };
 
@@ -211,7 +205,8 @@ __global__ __launch_bounds__(K_CT) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
   // A: first convolution of the tile whose patch is in P.  Rows: mid rows 9 hh .. 9 hh + 8 (16 columns each) from patch rows
   // 9 hh .. 9 hh + 10; edge groups: mid columns 16, 17 of all 18 rows = 36 pixels in groups of 16 (e -> row e >> 1, column
   // 16 + (e & 1)); the half hh = 1 takes groups 0 and 1, hh = 0 the third (4 pixels).  `between(s)`: staging hooks, step s of 33 + 9
-  auto conv_a = [&](auto&& between) __attribute__((always_inline)) {
+  // `carry`: mid columns 16 and 17 come from the previous tile's buffer (carry_load / carry_store) -- no edge groups
+  auto conv_a = [&](const bool carry, auto&& between) __attribute__((always_inline)) {
     const uint4* pb = s_P + ((q >> 1) * K_PNPXP + (9 * hh) * K_PP + i16) * 2 + (q & 1);
 #pragma unroll
     for (int o = 0; o < 11; ++o) acc[o] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
@@ -239,6 +234,7 @@ __global__ __launch_bounds__(K_CT) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
       between(sc);
       __builtin_amdgcn_sched_barrier(0);  // (pins the fragment reads three steps ahead of their products: cpx_cnn_rw.hip)
     });
+    if (carry) return;  // (uniform)
     // the edge groups: per-lane pixel, no reuse across taps.  (hh == 0: one group, 32 + i16; hh == 1: two)
     int eb[2];
 #pragma unroll
@@ -301,6 +297,23 @@ __global__ __launch_bounds__(K_CT) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
         mid_put(par, oy_, ox_, acc[9 + k], min(e, 35) >> 1, 16 + (e & 1), e < 36);
       }
     }
+  };
+  // A, carried tile: its mid columns 16 and 17 are image columns ox + 15 and ox + 16, mid columns 0 and 1 of the tile to its
+  // right -- the same float32 sums of the same taps in the same order (kx-major with ky inside, planes w_lo x_hi, w_hi x_lo,
+  // w_hi x_hi in conv_a's row loop and in its edge loop alike), range-checked into hmax when that tile computed them.  When
+  // that tile is the one B works on, they lie in M[par ^ 1]: 18 rows x 2 columns x 2 planes x 2 quarter pairs x 32 B = 288
+  // entries, one per A thread and a second one for the first 32; two columns of a row are four consecutive entries
+  auto carry_idx = [&](const int e) { return (((e >> 2) / K_MP) * K_MNPXP + ((e >> 2) % K_MP) * K_MP) * 2 + (e & 3); };
+  u32x4 cc[2];
+  auto carry_load = [&](const int par) __attribute__((always_inline)) {
+    const uint4* src = s_M + (par ^ 1) * K_MBUF;
+    cc[0] = __builtin_bit_cast(u32x4, src[carry_idx(tid)]);
+    if (tid < 32) cc[1] = __builtin_bit_cast(u32x4, src[carry_idx(256 + tid)]);
+  };
+  auto carry_store = [&](const int par) __attribute__((always_inline)) {
+    uint4* dst = s_M + par * K_MBUF + K_T * 2;
+    dst[carry_idx(tid)] = __builtin_bit_cast(uint4, cc[0]);
+    if (tid < 32) dst[carry_idx(256 + tid)] = __builtin_bit_cast(uint4, cc[1]);
   };
   // B: second convolution of the tile whose mid is in M[par]: output rows 8 hh .. 8 hh + 7 from mid rows 8 hh .. 8 hh + 9
   auto conv_b = [&](const int par, auto&& between) __attribute__((always_inline)) {
@@ -382,13 +395,23 @@ __global__ __launch_bounds__(K_CT) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
     };
     if (is_a) {
       if (v1) {
-        conv_a([&](auto sc) __attribute__((always_inline)) {
+        // tile k + 1 is the left neighbour of tile k: decided from the coordinates alone, whatever the walk (k = -1, a run's
+        // first tile and a tile whose right neighbour was another workgroup's compute their own columns)
+        const bool carry = carry_on && v0 && n0 == n1 && oy0 == oy1 && ox1 + K_T == ox0;  // (uniform)
+        conv_a(carry, [&](auto sc) __attribute__((always_inline)) {
           constexpr int s = decltype(sc)::value;
           if constexpr (s % 5 == 2 && s / 5 < K_NP) stage(s / 5);
+          // (the carried columns' LDS reads three steps ahead of their stores, as the fragments: no wait beside the products)
+          if constexpr (s == 24) {
+            if (carry) carry_load((k + 1) & 1);
+          }
+          if constexpr (s == 27) {
+            if (carry) carry_store((k + 1) & 1);
+          }
           if constexpr (s >= 25 && s <= 32) mid_row((k + 1) & 1, oy1, ox1, s - 25);  // (one step behind the row's last product)
         });
         mid_row((k + 1) & 1, oy1, ox1, 8);
-        mid_edges((k + 1) & 1, oy1, ox1);
+        if (!carry) mid_edges((k + 1) & 1, oy1, ox1);
       } else {
 #pragma unroll
         for (int i = 0; i < K_NP; ++i) stage(i);
@@ -446,8 +469,13 @@ int launch_conv_block32s(const ConvArgs& a, const ConvArgs& b, const void* wa, c
   if (cus == 0) return -1;
   const char* e = std::getenv("CPX_BLOCK32_GRID");
   const int gx = e ? persistent_grid_x(std::atoi(e), 1, td.total) : persistent_grid_x(cus, a.groups, td.total);
+  // CPX_BLOCK32_CARRY=0: every tile computes its own halo columns; CPX_BLOCK32_WALK=0 | 1: the tile-interleaved walk or the
+  // row runs whatever choose_walk says (both read at every launch, as the grid: for the bitwise tests and the timing)
+  const char* ec = std::getenv("CPX_BLOCK32_CARRY");
+  const char* ew = std::getenv("CPX_BLOCK32_WALK");
+  set_walk(td, ew ? (std::atoi(ew) ? WALK_ROWS : WALK_TILES) : choose_walk(td, gx));
   hipLaunchKernelGGL(conv_block32s_kernel, dim3((unsigned)gx, a.groups), dim3(K_CT), K_LDS, s, a, b, reinterpret_cast<const uint4*>(wa),
-                     reinterpret_cast<const uint4*>(wb), td);
+                     reinterpret_cast<const uint4*>(wb), td, ec ? (std::atoi(ec) != 0) : 1);
   return 0;
 }
 

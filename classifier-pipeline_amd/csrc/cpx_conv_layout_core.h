@@ -1,6 +1,8 @@
 // cpx_conv_layout_core.h -- what the split-operand convolution launchers know about a layer on the host: which class of
 // layer it is, the ONE layout of its weight-image buffer, the tile decomposition the kernels divide by, and the width of a
-// persistent grid.  Plain host C++ without HIP, so that tests compile it on its own (tests/native/conv_layout_host.cpp);
+// persistent grid, and the order in which conv_block32s_kernel's workgroups walk the tiles (host + device: the one function
+// the kernel calls).  Plain host C++ without HIP, so that tests compile it on its own (tests/native/conv_layout_host.cpp,
+// block_walk_host.cpp);
 // cpx_cnn_bf3.hip, cpx_cnn_rw.hip and cpx_cnn_blk.hip are its users in the product.
 #pragma once
 #include <stddef.h>
@@ -128,6 +130,76 @@ int fill_tiles(Tiles& td, int tiles_x, int tiles_y, long long n, int nsplit, lon
 inline int persistent_grid_x(int cus, int ny, long long tiles) {
   const int gx = std::max(8, cus / std::max(ny, 1) / 8 * 8);
   return (int)std::min<long long>(gx, (tiles + 7) / 8 * 8);
+}
+
+// ---- the order in which conv_block32s_kernel's persistent workgroups walk the tiles (cpx_cnn_blk.hip), host + device ----
+// Both walks hand out UNITS: every XCD (blockIdx.x & 7) owns a contiguous eighth of the units, its gx / 8 workgroups
+// interleave within it, and a workgroup's units ascend.  The unit is
+//   WALK_TILES  one tile: a workgroup's consecutive tiles lie gx / 8 apart and are never neighbours;
+//   WALK_ROWS   one tile row of one sample, walked from its rightmost tile to its leftmost: every tile but a row's first has
+//               its right neighbour as the workgroup's previous tile, which is what the kernel's halo carry needs, and
+//               vertically adjacent rows of a sample are in flight in the same XCD at the same time.
+#if defined(__HIPCC__)
+#define CPX_WALK_HD __host__ __device__ __forceinline__
+#else
+#define CPX_WALK_HD inline
+#endif
+enum { WALK_TILES = 0, WALK_ROWS = 1 };
+struct BlkTiles {
+  unsigned long long m_tx, m_ty;  // tile_div's multipliers (fill_tiles)
+  int tiles_x, tiles_y, total;
+  int walk, units;                // WALK_*; units = total (WALK_TILES) or total / tiles_x (WALK_ROWS): set_walk
+};
+CPX_WALK_HD int tile_div(int n, unsigned long long m) { return (int)(((unsigned long long)n * m) >> 42); }
+inline void set_walk(BlkTiles& td, int walk) {
+  td.walk = walk;
+  td.units = walk == WALK_ROWS ? td.total / td.tiles_x : td.total;
+}
+// tile j (0, 1, ..) of workgroup bx of a grid gx wide (a multiple of eight) -> sample n, tile row ty, tile column tx; false:
+// the workgroup has fewer.  No division: a caller stops at the first false, so j stays below total + 3 and a unit index
+// below units + 7 -- inside tile_div's range (TILES_PERSISTENT).
+CPX_WALK_HD bool walk_tile(const BlkTiles& td, int bx, int gx, int j, int& n, int& ty, int& tx) {
+  int col = 0;
+  if (td.walk == WALK_ROWS) {
+    const int jr = tile_div(j, td.m_tx);
+    col = j - jr * td.tiles_x;
+    j = jr;
+  }
+  const int per_xcd = (td.units + 7) >> 3;
+  const int t = bx + j * gx;
+  if (t >= 8 * per_xcd) return false;
+  int unit = (t & 7) * per_xcd + (t >> 3);
+  if (unit >= td.units) return false;
+  if (td.walk == WALK_ROWS) {
+    tx = td.tiles_x - 1 - col;
+  } else {
+    const int qd = tile_div(unit, td.m_tx);
+    tx = unit - qd * td.tiles_x;
+    unit = qd;
+  }
+  n = tile_div(unit, td.m_ty);
+  ty = unit - n * td.tiles_y;
+  return true;
+}
+// The largest number of tiles one workgroup walks: XCD 0's eighth is never smaller than another's, and its first workgroup
+// gets ceil(eighth / (gx / 8)) units.
+inline long long walk_max_tiles(const BlkTiles& td, int walk, int gx) {
+  const long long units = walk == WALK_ROWS ? td.total / td.tiles_x : td.total;
+  const long long per_xcd = (units + 7) / 8, wgs = gx / 8;
+  return (per_xcd + wgs - 1) / wgs * (walk == WALK_ROWS ? td.tiles_x : 1);
+}
+// The launcher's choice.  A carried tile (every tile of a row run but its first) costs 1 - WALK_CARRY_SAVING of a tile that
+// computes its own halo columns; the launch ends with its slowest workgroup, so the row runs are taken when their largest
+// per-workgroup cost, in tiles, is below the tile walk's largest count.  The saving is measured (profiles/
+// block32_carry_experiments.md: six launches of 1,536 samples, 10 x 10 tiles, nine tiles in ten carried): 54.47 ms on
+// interleaved tiles, 51.54 ms on row runs with the carry = 5.4 % of the launch, 6.0 % of a carried tile (the row runs
+// without the carry measure 54.87 ms: the walk alone gains nothing, and the 6.0 % is net of what it costs).  At the
+// bench's shape (1,559 samples, 128 workgroups per group): 122 rows = 1,220 tiles, 1,098 of them carried, against 1,218;
+// a 3-sample batch on the same grid would walk 10 tiles against 3 and stays tile-interleaved.
+constexpr double WALK_CARRY_SAVING = 0.06;
+inline int choose_walk(const BlkTiles& td, int gx) {
+  const double rows = (double)walk_max_tiles(td, WALK_ROWS, gx) / td.tiles_x * (td.tiles_x - WALK_CARRY_SAVING * (td.tiles_x - 1));
+  return rows < (double)walk_max_tiles(td, WALK_TILES, gx) ? WALK_ROWS : WALK_TILES;
 }
 
 }  // namespace cpx
