@@ -360,7 +360,10 @@ class LiteInterpreter(Interpreter):
     (interpreter.py:520-560) with the TFLite runtime replaced.  model = <name>.tflite + <name>.json.
     predict runs the whole batch in one forward (the reference loops sample by sample because its runtime must).
     CPX_TFLITE_QUANT_MATH=hybrid|float (default hybrid) chooses how INT8 filters are run: on the int8 operators, or
-    multiplied out on the host and run in float32.
+    multiplied out on the host and run in float32.  CPX_TFLITE_CONV_MATH=f32|fp16x2 (default f32) chooses how float32
+    convolutions are run: on the exact float32 kernel, or as two fp16 planes per operand on the fp16 matrix pipe behind one
+    RANGE launch per input view (build_plan: conv_math; float32-grade, not the same bits; a pre-activation then stays a
+    launch).
     The resnet / resnet152 / vgg16 / vgg19 ('caffe') and densenet121 ('torch') families run here too: their
     preprocess_input subtracts per-channel means of three colour channels, which the graph's INPUT operator does on the
     device from the unscaled two-channel crop sample (input_mode; the host statements are caffe_preprocess /
@@ -375,6 +378,7 @@ class LiteInterpreter(Interpreter):
 
     TYPE = "TFLite"
     DEFAULT_QUANT_MATH = "hybrid"
+    DEFAULT_CONV_MATH = "f32"
     DEFAULT_FUSE_PREACT = "1"
     DEFAULT_FOLD_WINDOWS = "1"
     DEFAULT_FUSE_PREACT_DW = "0"
@@ -387,6 +391,15 @@ class LiteInterpreter(Interpreter):
         mode = os.environ.get("CPX_TFLITE_QUANT_MATH", cls.DEFAULT_QUANT_MATH)
         if mode not in QUANT_MATHS:
             raise ValueError("CPX_TFLITE_QUANT_MATH=%r: one of %s" % (mode, ", ".join(QUANT_MATHS)))
+        return mode
+
+    @classmethod
+    def conv_math(cls):
+        from .tflite_graph import CONV_MATHS
+
+        mode = os.environ.get("CPX_TFLITE_CONV_MATH", cls.DEFAULT_CONV_MATH)
+        if mode not in CONV_MATHS:
+            raise ValueError("CPX_TFLITE_CONV_MATH=%r: one of %s" % (mode, ", ".join(CONV_MATHS)))
         return mode
 
     @classmethod
@@ -435,12 +448,14 @@ class LiteInterpreter(Interpreter):
         with open(str(self.model_file), "rb") as fh:
             self._graph = Graph(fh.read())
         self._quant_math = self.quant_math()
+        self._conv_math = self.conv_math()
         self._fuse_preact = self.fuse_preact()
         self._fold_windows = self.fold_windows()
         self._fuse_preact_dw = self.fuse_preact_dw() and self._fuse_preact
         # refuses, by operator, what the executor does not run
         plan = build_plan(self._graph, quantised_math=self._quant_math, fuse_preactivation=self._fuse_preact,
-                          fuse_preactivation_dw=self._fuse_preact_dw, fold_windows=self._fold_windows)
+                          fuse_preactivation_dw=self._fuse_preact_dw, fold_windows=self._fold_windows,
+                          conv_math=self._conv_math)
         self._plans[(plan.graph_input_shape, None)] = plan
         if self.input_mode is not None and plan.graph_input_shape[2] != 3:
             raise NotImplementedError("model_name %r: the %r input mode subtracts the means of three colour channels; the "
@@ -500,7 +515,8 @@ class LiteInterpreter(Interpreter):
             plan = self._plans[key] = build_plan(self._graph, input_shape=key[0], channel_map=cmap,
                                                  quantised_math=self._quant_math, fuse_preactivation=self._fuse_preact,
                                                  fuse_preactivation_dw=self._fuse_preact_dw, fold_windows=self._fold_windows,
-                                                 input_mode=None if cmap is None else self.input_mode)
+                                                 input_mode=None if cmap is None else self.input_mode,
+                                                 conv_math=self._conv_math)
         return key, plan
 
     def _device(self, engine, hwc):

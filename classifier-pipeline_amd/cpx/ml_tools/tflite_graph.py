@@ -66,7 +66,19 @@
   a per-sample parameter tensor (1 x 1 x 4: sx, inv, zp) that ONE QUANT_PARAMS operator per input tensor view writes,
   placed in front of the view's first quantised consumer; the int8 filter is packed in the order the int8 MFMA's B
   fragment wants (pack_conv_filter_q8), the per-channel integer sums wsum behind it.  The arithmetic: include/cpx.h.
-  quantised_math="float" multiplies the filters out (int8 x scale) and plans the float32 operators.
+  quantised_math="float" multiplies the filters out (int8 x scale) and plans the float32 operators;
+* conv_math="fp16x2" (default "f32": nothing changes) plans every operator that would have been a float32 CONV as
+  CONV_F16X2: float32 in and out, every operand as two fp16 planes of 11 + 11 significand bits, three plane products on
+  the fp16 matrix pipe with float32 accumulation (include/cpx.h fixes the arithmetic, tests/tflite_eval_h2.py restates
+  it).  Its second input is the per-sample RANGE tensor (1 x 1 x 4: up, down) of its input view, the exact power of two
+  that brings the sample's largest magnitude below 2^15; ONE RANGE operator per input tensor view is shared by its
+  consumers and placed in front of the first, as QUANT_PARAMS is, and a PAD folded into such a convolution moves the
+  RANGE to the PAD's input (zeros do not change max |x|).  The filter is scaled per output channel by the power of two
+  that puts its largest magnitude in [8, 16), split the same way and packed in the MFMA's fragment order
+  (pack_conv_filter_f16x2).  Fused activations and folded MUL / ADD work unchanged: the epilogue is CONV's.  A
+  pre-activation is NOT folded into a convolution that goes fp16x2 (CONV_PRE has no fp16x2 form): with
+  conv_math="fp16x2" its AFFINE stays a launch whatever fuse_preactivation says.  Depthwise, FULLY_CONNECTED and the
+  hybrid kinds are untouched; quantised_math="float" composes (the multiplied-out filters are split like any others).
 
 GraphDevice uploads a plan's constants to an engine's device and runs it."""
 import ctypes as C
@@ -158,9 +170,12 @@ def _channel_const(g, tid, channels, what):
 
 
 QUANT_MATHS = ("hybrid", "float")
+CONV_MATHS = ("f32", "fp16x2")
 Q8_KINDS = (_lib.GRAPH_CONV_Q8, _lib.GRAPH_FC_Q8, _lib.GRAPH_DWCONV_Q8)
-FOLD_INTO = (_lib.GRAPH_CONV, _lib.GRAPH_CONV_Q8, _lib.GRAPH_DWCONV, _lib.GRAPH_DWCONV_Q8, _lib.GRAPH_AFFINE)
-LOGISTIC_INTO = (_lib.GRAPH_CONV, _lib.GRAPH_CONV_Q8, _lib.GRAPH_DWCONV, _lib.GRAPH_DWCONV_Q8)
+FOLD_INTO = (_lib.GRAPH_CONV, _lib.GRAPH_CONV_Q8, _lib.GRAPH_CONV_F16X2, _lib.GRAPH_DWCONV, _lib.GRAPH_DWCONV_Q8,
+             _lib.GRAPH_AFFINE)
+LOGISTIC_INTO = (_lib.GRAPH_CONV, _lib.GRAPH_CONV_Q8, _lib.GRAPH_CONV_F16X2, _lib.GRAPH_DWCONV, _lib.GRAPH_DWCONV_Q8)
+PARAM_KINDS = (_lib.GRAPH_QUANT_PARAMS, _lib.GRAPH_RANGE)   # operators that write the 1 x 1 x 4 tensor of a view
 ACT_SWISH, ACT_LOGISTIC = _lib.GRAPH_ACT_SWISH, _lib.GRAPH_ACT_LOGISTIC
 
 # the 'caffe' / 'torch' modes of keras.applications.imagenet_utils.preprocess_input as the INPUT operator's constants
@@ -173,7 +188,7 @@ PRE_ACTS = (ACT_RELU, ACT_RELU6)
 
 
 def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_math="hybrid", fuse_activations=True,
-               input_mode=None, fuse_preactivation=False, fold_windows=False, fuse_preactivation_dw=False):
+               input_mode=None, fuse_preactivation=False, fold_windows=False, fuse_preactivation_dw=False, conv_math="f32"):
     """g: tflite_reader.Graph.  input_shape: (H, W, C) of a sample, default: the flatbuffer's.  output: the tensor the
     forward hands out, default the graph's output; the operators it does not need are dropped.  channel_map: up to 4
     indices into the channels of the sample the CALLER brings ([N, H, W, max(map) + 1 or more]): the graph's input
@@ -185,9 +200,13 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
     convolutions is dropped and those convolutions become CONV_PRE (the same float32 operations, bit for bit).
     fold_windows: 1 x 1 pools and chains of PAD / SLICE become one SLICE, a PAD folds into the VALID convolution behind it.
     fuse_preactivation_dw: a bare RELU / RELU6 is also dropped in front of float32 depthwise convolutions (DWCONV_PRE) and
-    SLICEs; both keep every bit (the module's docstring)."""
+    SLICEs; both keep every bit (the module's docstring).  conv_math: "f32" runs float32 convolutions on the exact float32
+    kernel, "fp16x2" as two fp16 planes on the fp16 matrix pipe behind one RANGE launch per input view; a pre-activation
+    is then not folded into them (no CONV_PRE is planned: the AFFINE stays a launch)."""
     if quantised_math not in QUANT_MATHS:
         raise ValueError("quantised_math %r: one of %s" % (quantised_math, ", ".join(QUANT_MATHS)))
+    if conv_math not in CONV_MATHS:
+        raise ValueError("conv_math %r: one of %s" % (conv_math, ", ".join(CONV_MATHS)))
     if input_mode is not None and input_mode not in INPUT_MODES:
         raise ValueError("input_mode %r: one of %s" % (input_mode, ", ".join(sorted(INPUT_MODES))))
     g.check_executable()
@@ -258,6 +277,19 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
             qparams[key] = pid
         return qparams[key]
 
+    ranges = {}   # input tensor view -> RANGE tensor id
+
+    def range_of(x, src):
+        """The RANGE tensor of view x, placed as params_of places QUANT_PARAMS: in front of the first consumer that asks."""
+        if x.id not in ranges:
+            pid = ("range", x.id)
+            T[pid] = PlanTensor(pid, 1, 1, 4)
+            o = PlanOp(_lib.GRAPH_RANGE, "RANGE", x.id, pid)
+            o.source = src
+            ops.append(o)
+            ranges[x.id] = pid
+        return ranges[x.id]
+
     def overflow_check(what, k):
         if k * 127 * 255 >= 2 ** 31:
             raise NotImplementedError("%s: %d products of an 8-bit activation and an INT8 weight could overflow the int32 "
@@ -287,6 +319,8 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
             if not dw:   # (a depthwise output sums kh * kw <= 49 products)
                 overflow_check(what, kh * kw * depth)
             kind, in1 = _lib.GRAPH_DWCONV_Q8 if dw else _lib.GRAPH_CONV_Q8, params_of(x, False, i)
+        elif conv_math == "fp16x2" and not dw:
+            kind, in1 = _lib.GRAPH_CONV_F16X2, range_of(x, i)
         emit(PlanOp(kind, op["name"], x.id, y, in1=in1, kh=kh, kw=kw, stride_h=sh, stride_w=sw, pads=(pt, pl, pb, pr),
                     act=op.get("act", 0), filter=w, scale=None, filter_scale=fscale,
                     shift=np.zeros(co, np.float32) if bias is None else np.asarray(bias, np.float32).reshape(-1)), i)
@@ -593,12 +627,13 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
             if p.kind != _lib.GRAPH_PAD or not own_tensor(p.out):
                 continue
             readers = readers_of(p.out)
-            params = [r for r in readers if r.kind == _lib.GRAPH_QUANT_PARAMS]
-            rest = [r for r in readers if r.kind != _lib.GRAPH_QUANT_PARAMS]
+            params = [r for r in readers if r.kind in PARAM_KINDS]
+            rest = [r for r in readers if r.kind not in PARAM_KINDS]
             if len(rest) != 1:
                 continue
             r = rest[0]
-            if r.kind not in (_lib.GRAPH_CONV, _lib.GRAPH_CONV_Q8, _lib.GRAPH_DWCONV, _lib.GRAPH_DWCONV_Q8) or r.in0 != p.out \
+            if r.kind not in (_lib.GRAPH_CONV, _lib.GRAPH_CONV_Q8, _lib.GRAPH_CONV_F16X2, _lib.GRAPH_DWCONV,
+                              _lib.GRAPH_DWCONV_Q8) or r.in0 != p.out \
                     or r.pads != (0, 0, 0, 0) or any(readers_of(q.out) != [r] for q in params):
                 continue
             pt, pl, pb, pr = p.pads
@@ -607,6 +642,14 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
             r.in0, r.pads, r.name = p.in0, p.pads, "PAD>" + r.name
             for q in params:
                 q.in0 = p.in0
+                # the PAD's input may have a RANGE of its own (another fp16x2 reader): one per view, the earlier one
+                twin = next((t for t in ops if t is not q and t.kind == _lib.GRAPH_RANGE == q.kind and t.in0 == q.in0), None)
+                if twin is not None:
+                    first, second = (twin, q) if ops.index(twin) < ops.index(q) else (q, twin)
+                    for c in ops:
+                        if c.in1 == second.out:
+                            c.in1 = first.out
+                    ops.remove(second)
             ops.remove(p)
 
     # ---- the pre-activation of a DenseNet / ResNetV2 block: an AFFINE with a RELU in front of float32 convolutions ----
@@ -695,6 +738,7 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
 
     # ---- weights in the kernel's layout ----
     packers = {_lib.GRAPH_CONV: pack_conv_filter, _lib.GRAPH_CONV_Q8: pack_conv_filter_q8,
+               _lib.GRAPH_CONV_F16X2: pack_conv_filter_f16x2,
                _lib.GRAPH_DWCONV: pack_dw_filter, _lib.GRAPH_DWCONV_PRE: pack_dw_filter,
                _lib.GRAPH_DWCONV_Q8: pack_dw_filter_q8}
     for o in ops:
@@ -736,6 +780,57 @@ def unpack_conv_filter_q8(packed, shape):
     frag = packed[:n].view(np.int8).reshape(kh * kw, nch, nt, 2, CO, 16)
     full = frag.transpose(2, 4, 0, 1, 3, 5).reshape(nt * CO, kh * kw, nch * KC)
     return np.ascontiguousarray(full[:co, :, :ci]).reshape(co, kh, kw, ci), packed[n:].view(np.int32)[:co].copy()
+
+
+def split_filter_f16x2(w_ohwi):
+    """float32 OHWI [Cout, kh, kw, Cin] -> (wh, wl, kw): kw[c] = clamp(4 - e, -100, 100) with max |w[c]| = f * 2^e, f in
+    [0.5, 1), which puts max |w[c]| * 2^kw[c] in [8, 16) (an all-zero or non-finite filter: kw = 0); wh = fp16(w * 2^kw)
+    rounded to nearest even, wl = fp16(w * 2^kw - wh), the difference exact in float32 (include/cpx.h: CONV_F16X2)."""
+    w = np.ascontiguousarray(w_ohwi, np.float32)
+    m = np.abs(w.reshape(w.shape[0], -1)).max(axis=1) if w.size else np.zeros(w.shape[0], np.float32)
+    ok = (m > 0) & np.isfinite(m)
+    e = np.frexp(np.where(ok, m, np.float32(8.0)))[1]   # (8 = 0.5 * 2^4: kw = 0)
+    kw = np.clip(4 - e, -100, 100).astype(np.int32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        ws = (w * np.ldexp(np.float32(1.0), kw).astype(np.float32)[:, None, None, None]).astype(np.float32)
+        wh = ws.astype(np.float16)
+        wl = (ws - wh.astype(np.float32)).astype(np.float16)
+    return wh, wl, kw
+
+
+def pack_conv_filter_f16x2(w_ohwi):
+    """float32 OHWI [Cout, kh, kw, Cin] -> bytes: fp16 [kh * kw][chunks of GRAPH_CONV_H2_KC input channels][tiles of
+    GRAPH_CONV_CO output channels][plane: wh, wl][k half m][64 lanes][8], lane l = output channel l & 31 of the tile, input
+    channels 16 * m + 8 * (l >> 5) + j of the chunk (the B fragment of v_mfma_f32_32x32x16_f16), zeros beyond Cin and Cout;
+    behind them float32 wdown[Cout rounded up] = 2^-kw (split_filter_f16x2; 1 beyond Cout)."""
+    wh, wl, kwc = split_filter_f16x2(w_ohwi)
+    co, kh, kw, ci = wh.shape
+    KC, CO = _lib.GRAPH_CONV_H2_KC, _lib.GRAPH_CONV_CO
+    nch, nt = -(-ci // KC), -(-co // CO)
+    full = np.zeros((2, nt * CO, kh * kw, nch * KC), np.float16)
+    full[0, :co, :, :ci] = wh.reshape(co, kh * kw, ci)
+    full[1, :co, :, :ci] = wl.reshape(co, kh * kw, ci)
+    # [plane, tile, c, tap, chunk, m, half, j] -> [tap, chunk, tile, plane, m, half, c, j]
+    frag = full.reshape(2, nt, CO, kh * kw, nch, 2, 2, 8).transpose(3, 4, 1, 0, 5, 6, 2, 7)
+    wdown = np.ones(nt * CO, np.float32)
+    wdown[:co] = np.ldexp(np.float32(1.0), -kwc).astype(np.float32)
+    return np.concatenate([np.ascontiguousarray(frag).reshape(-1).view(np.uint8), wdown.view(np.uint8)])
+
+
+def unpack_conv_filter_f16x2(packed, shape):
+    """The inverse of pack_conv_filter_f16x2 for a filter of `shape` (OHWI) -> (wh, wl, kw): the two fp16 planes and
+    the int32 exponents of split_filter_f16x2."""
+    co, kh, kw, ci = shape
+    KC, CO = _lib.GRAPH_CONV_H2_KC, _lib.GRAPH_CONV_CO
+    nch, nt = -(-ci // KC), -(-co // CO)
+    n = 2 * kh * kw * nch * nt * 4 * 64 * 8
+    packed = np.asarray(packed, np.uint8)
+    assert packed.size == n + 4 * nt * CO, (packed.size, n)
+    frag = packed[:n].view(np.float16).reshape(kh * kw, nch, nt, 2, 2, 2, CO, 8)
+    full = frag.transpose(3, 2, 6, 0, 1, 4, 5, 7).reshape(2, nt * CO, kh * kw, nch * KC)
+    planes = np.ascontiguousarray(full[:, :co, :, :ci]).reshape(2, co, kh, kw, ci)
+    kwc = (-np.frexp(packed[n:].view(np.float32)[:co])[1] + 1).astype(np.int32)   # wdown = 0.5 * 2^(1 - kw)
+    return planes[0], planes[1], kwc
 
 
 def pack_fc_filter_q8(w):
@@ -808,14 +903,14 @@ def pack_conv_pre(w_ohwi, pre_scale, pre_shift):
 
 
 def load_plan(path, input_shape=None, channel_map=None, quantised_math="hybrid", fuse_activations=True, input_mode=None,
-              fuse_preactivation=False, fold_windows=False, fuse_preactivation_dw=False):
+              fuse_preactivation=False, fold_windows=False, fuse_preactivation_dw=False, conv_math="f32"):
     from .tflite_reader import Graph
 
     with open(str(path), "rb") as fh:
         g = Graph(fh.read())
     return g, build_plan(g, input_shape=input_shape, channel_map=channel_map, quantised_math=quantised_math,
                          fuse_activations=fuse_activations, input_mode=input_mode, fuse_preactivation=fuse_preactivation,
-                         fold_windows=fold_windows, fuse_preactivation_dw=fuse_preactivation_dw)
+                         fold_windows=fold_windows, fuse_preactivation_dw=fuse_preactivation_dw, conv_math=conv_math)
 
 
 class GraphDevice:

@@ -41,13 +41,15 @@ static const char* graph_check_op(const cpx_graph_op& o, const std::vector<cpx_g
     case CPX_GRAPH_CONV:
     case CPX_GRAPH_CONV_PRE:
     case CPX_GRAPH_CONV_Q8:
+    case CPX_GRAPH_CONV_F16X2:
     case CPX_GRAPH_DWCONV:
     case CPX_GRAPH_DWCONV_PRE:
     case CPX_GRAPH_DWCONV_Q8:
     case CPX_GRAPH_MAX_POOL:
     case CPX_GRAPH_AVG_POOL: {
       const bool dw = o.kind == CPX_GRAPH_DWCONV || o.kind == CPX_GRAPH_DWCONV_PRE || o.kind == CPX_GRAPH_DWCONV_Q8;
-      const bool conv = dw || o.kind == CPX_GRAPH_CONV || o.kind == CPX_GRAPH_CONV_PRE || o.kind == CPX_GRAPH_CONV_Q8;
+      const bool conv = dw || o.kind == CPX_GRAPH_CONV || o.kind == CPX_GRAPH_CONV_PRE || o.kind == CPX_GRAPH_CONV_Q8 ||
+                        o.kind == CPX_GRAPH_CONV_F16X2;
       if (o.kh < 1 || o.kw < 1 || o.kh > 7 || o.kw > 7) return "kernel sides are 1 to 7";
       if (o.stride_h < 1 || o.stride_w < 1 || o.stride_h > (conv ? 2 : 7) || o.stride_w > (conv ? 2 : 7)) return "bad stride";
       if (o.pad_top < 0 || o.pad_left < 0 || o.pad_bottom < 0 || o.pad_right < 0 || o.pad_top >= o.kh || o.pad_bottom >= o.kh ||
@@ -67,6 +69,10 @@ static const char* graph_check_op(const cpx_graph_op& o, const std::vector<cpx_g
       if ((o.kind == CPX_GRAPH_DWCONV || o.kind == CPX_GRAPH_DWCONV_PRE) && (reinterpret_cast<uintptr_t>(o.weights) & 15))
         return "DWCONV weights are not 16-byte aligned";
       if (o.kind == CPX_GRAPH_DWCONV_Q8 && (reinterpret_cast<uintptr_t>(o.weights) & 3)) return "DWCONV_Q8 weights are not 4-byte aligned";
+      if (o.kind == CPX_GRAPH_CONV_F16X2) {
+        if (reinterpret_cast<uintptr_t>(o.weights) & 15) return "CONV_F16X2 weights are not 16-byte aligned";
+        if (!is_params(o.in1)) return "CONV_F16X2 needs the 1 x 1 x 4 RANGE tensor of its input as in1";
+      }
       break;
     }
     case CPX_GRAPH_ADD:
@@ -95,6 +101,9 @@ static const char* graph_check_op(const cpx_graph_op& o, const std::vector<cpx_g
     case CPX_GRAPH_QUANT_PARAMS:
       if (!is_params(o.out)) return "QUANT_PARAMS writes a 1 x 1 x 4 tensor";
       if (o.param != 0.0f && o.param != 1.0f) return "QUANT_PARAMS: param is 0 (asymmetric) or 1 (symmetric)";
+      break;
+    case CPX_GRAPH_RANGE:
+      if (!is_params(o.out)) return "RANGE writes a 1 x 1 x 4 tensor";
       break;
     case CPX_GRAPH_PAD:
       if (o.pad_top < 0 || o.pad_left < 0 || o.pad_bottom < 0 || o.pad_right < 0 || a.C != y.C ||

@@ -1,6 +1,6 @@
 // cpx_graph.hip -- the float32 kernels of the TFLite graph executor (cpx_graph_forward, include/cpx.h; what the
 // reference's LiteInterpreter hands to the TFLite runtime, ml_tools/interpreter.py:520-560; the hybrid operators are
-// cpx_graph_q8.hip's, DEPTHWISE_CONV_2D is cpx_graph_dw.hip's, what they share is cpx_graph_core.h).  One launch per planned
+// cpx_graph_q8.hip's, the fp16x2 convolution is cpx_graph_h2.hip's, DEPTHWISE_CONV_2D is cpx_graph_dw.hip's, what they share is cpx_graph_core.h).  One launch per planned
 // operator; every kernel reads and writes NHWC views with a channel offset and a row stride, so that the producers of a
 // CONCATENATION write straight into their slice of the concatenated tensor.
 //
@@ -499,6 +499,10 @@ void launch_graph_op(const GraphOpArgs& a, hipStream_t s) {
     case CPX_GRAPH_DWCONV_Q8:
     case CPX_GRAPH_SLICE:
       launch_graph_dw_op(a, s);
+      break;
+    case CPX_GRAPH_RANGE:
+    case CPX_GRAPH_CONV_F16X2:
+      launch_graph_h2_op(a, s);
       break;
     default:
       break;

@@ -78,6 +78,34 @@ CPX_HD inline float hybrid_finish(int acc, int zp, int wsum, float sx, float sca
   return activate(v + shift, act);
 }
 
+// ---- the fp16x2 convolution's range scaling ----
+// RANGE of one sample from m = max |x| (include/cpx.h): m = f * 2^e with f in [0.5, 1), k = min(15 - e, 100) (>= -113),
+// up = 2^k, down = 2^-k; m zero, infinite or NaN: 1, 1.  In integers on the float's bits, so that host and device agree
+// whatever their frexp makes of a subnormal (a subnormal m has e <= -126: the clamp holds, k = 100).
+struct RangeParams {
+  float up, down;
+};
+CPX_HD inline float pow2f(int k) {   // 2^k for -126 <= k <= 127
+  union {
+    uint32_t u;
+    float f;
+  } v;
+  v.u = (uint32_t)(127 + k) << 23;
+  return v.f;
+}
+CPX_HD inline RangeParams range_params(float m) {
+  union {
+    float f;
+    uint32_t u;
+  } v;
+  v.f = m;
+  const int field = (int)((v.u >> 23) & 255);
+  if (!(m > 0.0f) || field == 255) return RangeParams{1.0f, 1.0f};
+  int k = field == 0 ? 100 : 15 - (field - 126);
+  k = k > 100 ? 100 : k;
+  return RangeParams{pow2f(k), pow2f(-k)};
+}
+
 // ---- views ----
 // the view (GraphView's fields) can be read and written as aligned quads of channels: 16-byte loads and stores
 template <class View>

@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include "cpx_graph_core.h"
+#include "cpx_graph_minmax.h"
 #include "cpx_kernels.h"
 
 namespace cpx {
@@ -38,52 +39,16 @@ __device__ __forceinline__ int pack4(int q0, int q1, int q2, int q3) {
   return (q0 & 255) | ((q1 & 255) << 8) | ((q2 & 255) << 16) | (int)((unsigned)q3 << 24);
 }
 
-// QUANT_PARAMS: one workgroup per sample; out = [sx, inv, zp, 0].  VW = 4: the view's pixels are rows of C / 4 aligned
-// quads.  A thread's (pixel, quad) advances by the workgroup's size without a division.
-constexpr int QT = 1024;
+// QUANT_PARAMS: one workgroup per sample; out = [sx, inv, zp, 0].  The reduction is sample_min_max (cpx_graph_minmax.h),
+// which RANGE shares.
+constexpr int QT = GRAPH_MINMAX_THREADS;
 
 template <int VW>
 __global__ __launch_bounds__(QT) void graph_quant_params_kernel(GraphOpArgs a) {
-  __shared__ float s_lo[QT / 64], s_hi[QT / 64];
   const size_t n = blockIdx.x;
-  const int tid = threadIdx.x;
-  const float* src = a.in0.p + n * a.in0.sample_stride;
-  const int per = a.in0.C / VW, HW = a.in0.H * a.in0.W;   // vectors per pixel
-  const int dp = QT / per, dq = QT - dp * per;
-  int pix = tid / per, q = tid - pix * per;
-  float lo = 0.0f, hi = 0.0f;   // rmin = min(0, min x), rmax = max(0, max x)
-  while (pix < HW) {
-    const float* e = src + (unsigned)pix * (unsigned)a.in0.cstride + VW * q;
-    if (VW == 4) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(e);
-      lo = fminf(fminf(lo, fminf(v.x, v.y)), fminf(v.z, v.w));
-      hi = fmaxf(fmaxf(hi, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
-    } else {
-      lo = fminf(lo, *e);
-      hi = fmaxf(hi, *e);
-    }
-    pix += dp;
-    q += dq;
-    if (q >= per) {
-      q -= per;
-      ++pix;
-    }
-  }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    lo = fminf(lo, __shfl_xor(lo, d, 64));
-    hi = fmaxf(hi, __shfl_xor(hi, d, 64));
-  }
-  if ((tid & 63) == 0) {
-    s_lo[tid >> 6] = lo;
-    s_hi[tid >> 6] = hi;
-  }
-  __syncthreads();
-  if (tid != 0) return;
-  for (int w = 1; w < QT / 64; ++w) {
-    lo = fminf(lo, s_lo[w]);
-    hi = fmaxf(hi, s_hi[w]);
-  }
+  float lo, hi;
+  sample_min_max<VW>(a.in0, n, &lo, &hi);
+  if (threadIdx.x != 0) return;
   const QuantParams q8 = quant_params(lo, hi, a.param != 0.0f);
   float* out = a.out.p + n * a.out.sample_stride;
   out[0] = q8.sx;

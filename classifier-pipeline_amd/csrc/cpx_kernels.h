@@ -411,6 +411,12 @@ constexpr int GRAPH_CONV_CO = 32;  // ... and Cout to this
 // are output channel l & 31 of the tile, input channels 16 * (l >> 5) + j of the chunk; zeros beyond Cin and Cout.
 void launch_graph_q8_op(const GraphOpArgs& a, hipStream_t s);
 constexpr int GRAPH_CONV_Q8_KC = 32;
+// CONV_F16X2 and RANGE (cpx_graph_h2.hip): the filter as two fp16 planes in the B fragment order of
+// v_mfma_f32_32x32x16_f16, [tap][chunk of GRAPH_CONV_H2_KC input channels][tile of GRAPH_CONV_CO output channels][plane: wh,
+// wl][k half m][lane][8 fp16]: lane l's halves are output channel l & 31 of the tile, input channels 16 * m + 8 * (l >> 5) + j
+// of the chunk; zeros beyond Cin and Cout; float32 wdown[Cout rounded up to GRAPH_CONV_CO] behind the planes.
+void launch_graph_h2_op(const GraphOpArgs& a, hipStream_t s);
+constexpr int GRAPH_CONV_H2_KC = 32;
 // DEPTHWISE_CONV_2D, float32 (with or without a pre-activation) and hybrid, and SLICE (cpx_graph_dw.hip): weights
 // [tap][C rounded up to 4], float32 or int8 + wsum.
 void launch_graph_dw_op(const GraphOpArgs& a, hipStream_t s);

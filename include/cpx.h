@@ -870,11 +870,33 @@ enum {
                                 it is.  param 1: out = act(..) + 0.0f, one float32 addition: a -0.0 becomes +0.0 and
                                 nothing else changes -- what AVG_POOL's sum from 0 makes of the one element of a
                                 1 x 1 window.  No weights */
-  CPX_GRAPH_DWCONV_PRE = 21  /* DWCONV whose input is read as act_pre(x): the activation of an AFFINE without constants,
+  CPX_GRAPH_DWCONV_PRE = 21, /* DWCONV whose input is read as act_pre(x): the activation of an AFFINE without constants,
                                 so the same bits as a RELU / RELU6 launch in front of a DWCONV.  param = act_pre as a
                                 number: CPX_GRAPH_ACT_RELU or CPX_GRAPH_ACT_RELU6.  No constants ride along: `weights`,
                                 `activation`, scale, shift as DWCONV.  A padded tap contributes nothing.  float32 only */
+  /* CONV_2D with float32 in and out on the fp16 matrix pipe: every operand as two fp16 planes, see below. */
+  CPX_GRAPH_RANGE = 22,      /* in0 (its own channels only) -> out, a 1 x 1 x 4 tensor [up, down, 0, 0] per sample: the
+                                exact power-of-two scaling that brings the sample's largest magnitude below 2^15 */
+  CPX_GRAPH_CONV_F16X2 = 23  /* CONV_2D, float32 in, float32 out.  in1: the 1 x 1 x 4 RANGE tensor of in0.  `weights`
+                                (16-byte aligned) is reinterpreted as BYTES: fp16 [kh * kw][chunks of 32 input
+                                channels][tiles of 32 output channels][plane: wh, wl][k half m: 0, 1][64 lanes][8] --
+                                lane l: output channel l & 31 of the tile, input channels 16 * m + 8 * (l >> 5) + j of
+                                the chunk (the B fragment of v_mfma_f32_32x32x16_f16), zeros beyond Cin / Cout -- and
+                                behind them float32 wdown[Cout rounded up to 32], wdown[c] = 2^-kw[c].  `activation`,
+                                scale, shift: as CONV, NULL included */
 };
+/* The fp16x2 arithmetic, per sample.  RANGE: m = max |x| over the view in float32.  m == 0 or m not finite (inf, NaN):
+ * up = down = 1.  Otherwise m = f * 2^e with f in [0.5, 1) (frexp), k = min(15 - e, 100), up = 2^k, down = 2^-k: both
+ * normal float32 (a finite float32 has e <= 128, so k >= -113 and needs no lower clamp; the upper one holds for
+ * m < 2^-86, subnormals included) and m * up < 2^15 always: nothing a sample holds rounds to an fp16 infinity.
+ * CONV_F16X2: xs = float32(x * up) (exact unless it underflows), xh = RNE_fp16(xs), xl = RNE_fp16(xs - xh) (the
+ * difference is exact in float32); a padded tap, a pixel beyond the batch and a channel beyond Cin are 0 in both planes.
+ * The caller scales filter c by 2^kw[c], which puts max |w[c]| in [8, 16) (an all-zero filter: kw = 0), and splits the
+ * scaled weights the same way into wh, wl.  acc = sum (wl * xh + wh * xl + wh * xh): every product exact, summed in
+ * float32 by the matrix pipe over K walked as (tap) x (chunk of 32 channels) x (16 channels), the three plane products
+ * of a K block in that order; the order depends on the operator's shape only, never on N, on where the pixel sits in
+ * a tile or on the channel slice.  out = act(float32(acc * float32(down * wdown[c])) * scale[c] + shift[c]): the first
+ * factor is an exact power of two, the rest is CONV's epilogue. */
 /* The hybrid arithmetic, per sample.  QUANT_PARAMS: rmin = min(0, min x), rmax = max(0, max x) in float32.
  * rmin == rmax: sx = inv = 1, zp = 0.  Otherwise, in float64 from those two values: s = (rmax - rmin) / 255,
  * a = -128 - rmin / s, b = 127 - rmax / s, z = a if 128 + |rmin / s| < 127 + |rmax / s| else b,

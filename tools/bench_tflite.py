@@ -52,7 +52,16 @@ LiteInterpreter runs) and with every PAD, 1 x 1 pool, STRIDED_SLICE and RELU a l
 float32 on the same graph; and, for the largest batch, every SLICE launch of the folded plan alone (a one-operator graph,
 HIP events): the bytes it must move -- what it reads of its input and its output once -- over its time, against the HBM
 peak and the float4-copy rate.  --mobilenet times the folded plan beside the plain one too; --folded chooses it for a run
-under a profiler and for its --kernel-trace (--nasnet: --unfused chooses the other plan)."""
+under a profiler and for its --kernel-trace (--nasnet: --unfused chooses the other plan).
+
+    python tools/bench_tflite.py --conv-math fp16x2 [--mobilenet | --efficientnet | --densenet] [--batches 1,8,32,128]
+
+times the chosen network (default: the Inception-v3) as LiteInterpreter plans it with conv_math="f32" (the exact float32
+convolution: the yardstick) and with conv_math="fp16x2" (two fp16 planes per operand behind one RANGE launch per input
+view), both in the same process on the same input, in --rounds alternating rounds: the median over the rounds and their
+scatter.  With --skip-torch the fp16x2 plan alone runs (a run under a profiler); --kernel-trace with --conv-math fp16x2
+splits such a trace by kind, RANGE and the new kernel included, and gives the fp16x2 convolutions' float32-equivalent
+TFLOP/s against the 16 / 3 x 157.3 roof and RANGE's bytes per second against the HBM peak."""
 import argparse
 import json
 import os
@@ -66,7 +75,8 @@ for p in (os.path.join(REPO, "classifier-pipeline_amd"), os.path.join(REPO, "tes
 
 KIND_NAMES = {1: "conv", 2: "max_pool", 3: "avg_pool", 4: "add", 5: "affine", 6: "mean", 7: "fc", 8: "logistic", 9: "softmax",
               10: "pad", 11: "channel_map", 12: "conv_q8", 13: "fc_q8", 14: "quant_params", 15: "dwconv", 16: "dwconv_q8", 17: "mul", 18: "input", 19: "conv_pre",
-              20: "slice", 21: "dwconv_pre"}
+              20: "slice", 21: "dwconv_pre", 22: "range", 23: "conv_f16x2"}
+CONV_KINDS = (1, 12, 19, 23)
 DW_KINDS = (15, 16, 21)
 FOLDS = dict(fold_windows=True, fuse_preactivation_dw=True, fuse_preactivation=True)
 HBM_PEAK_TBS = 8.0          # MI355X HBM3E, specification
@@ -160,6 +170,8 @@ def timed(torch, fn, steps, warmup):
 
 
 F32_MFMA_PEAK_TFLOPS = 157.3
+# three fp16 plane products per float32 product on a pipe 16 times as fast as v_mfma_f32_32x32x2_f32
+F16X2_ROOF_TFLOPS = F32_MFMA_PEAK_TFLOPS * 16.0 / 3.0
 I8_MFMA_PEAK_TOPS = 5000.0   # 2 x the ~2.5 PFLOP/s dense BF16 peak: the i8 forms have twice the K in the same cycles
 
 
@@ -574,7 +586,7 @@ def split_from_trace(path, plan, n):
     by_kind, shapes, dws, hbm = {}, {}, {}, {}
     for r, o in zip(rows, plan.ops):
         ns = int(r["End_Timestamp"]) - int(r["Start_Timestamp"])
-        assert ("conv" in r["Kernel_Name"]) == (o.kind in (1, 12, 19)) and ("graph_dw" in r["Kernel_Name"]) == (o.kind in DW_KINDS), \
+        assert ("conv" in r["Kernel_Name"]) == (o.kind in CONV_KINDS) and ("graph_dw" in r["Kernel_Name"]) == (o.kind in DW_KINDS), \
             (r["Kernel_Name"], o.name)
         k = by_kind.setdefault(KIND_NAMES[o.kind], {"launches": 0, "ms": 0.0})
         k["launches"] += 1
@@ -590,7 +602,13 @@ def split_from_trace(path, plan, n):
             d["launches"] += 1
             d["ms"] += ns / 1e6
             d["mbytes"] += dw_bytes(plan, o, n) / 1e6
-        if o.kind in (1, 12, 19):
+        if o.kind == 22:   # RANGE reads its view once
+            i = plan.tensors[o.in0]
+            h = hbm.setdefault("range", {"launches": 0, "ms": 0.0, "mbytes": 0.0})
+            h["launches"] += 1
+            h["ms"] += ns / 1e6
+            h["mbytes"] += 4.0 * n * i.H * i.W * i.C / 1e6
+        if o.kind in CONV_KINDS:
             t, i = plan.tensors[o.out], plan.tensors[o.in0]
             key = "%dx%d s%d %d->%d at %dx%d" % (o.kh, o.kw, o.stride_h, i.C, t.C, t.H, t.W)
             s = shapes.setdefault(key, {"launches": 0, "ms": 0.0, "gflop": 0.0})
@@ -600,7 +618,7 @@ def split_from_trace(path, plan, n):
     wall = (int(rows[-1]["End_Timestamp"]) - int(rows[0]["Start_Timestamp"])) / 1e6
     busy = sum(k["ms"] for k in by_kind.values())
     top = max(shapes, key=lambda k: shapes[k]["ms"])
-    conv = {"ms": sum(by_kind[k]["ms"] for k in ("conv", "conv_q8", "conv_pre") if k in by_kind)}
+    conv = {"ms": sum(by_kind[k]["ms"] for k in ("conv", "conv_q8", "conv_pre", "conv_f16x2") if k in by_kind)}
     conv_gflop = sum(s["gflop"] for s in shapes.values())
     tf = shapes[top]["gflop"] / shapes[top]["ms"]
     dw = {}
@@ -618,7 +636,75 @@ def split_from_trace(path, plan, n):
     return {**dw, "N": n, "forward_ms_first_start_to_last_end": wall, "kernel_ms_sum": busy, "gpu_busy_share": busy / wall,
             "ms_by_kind": by_kind, "conv_tflops_while_running": conv_gflop / conv["ms"],
             "conv_matrix_pipe_share": conv_gflop / conv["ms"] / F32_MFMA_PEAK_TFLOPS,
-            "dominant_conv": dict(shapes[top], shape=top, tflops=tf, matrix_pipe_share=tf / F32_MFMA_PEAK_TFLOPS)}
+            "dominant_conv": dict(shapes[top], shape=top, tflops=tf, matrix_pipe_share=tf / F32_MFMA_PEAK_TFLOPS),
+            **({"conv_f16x2_roof_tflops": F16X2_ROOF_TFLOPS, "conv_share_of_f16x2_roof": conv_gflop / conv["ms"] / F16X2_ROOF_TFLOPS}
+               if "conv_f16x2" in by_kind else {})}
+
+
+def conv_math_leg(args):
+    """The chosen network as LiteInterpreter plans it, conv_math f32 and fp16x2, same process, same input, alternating rounds."""
+    import ctypes as C
+
+    import torch
+    from cpx import _lib
+    from cpx.engine import TrackEngine
+    from cpx.ml_tools.tflite_graph import GraphDevice, build_plan
+    from cpx.ml_tools.tflite_reader import Graph
+
+    if args.mobilenet:
+        import tflite_build_dw as td
+        name, blob = "mobilenet_v2", td.mobilenet_v2(17, (), seed=7, width=args.width)
+    elif args.efficientnet:
+        import tflite_build_se as ts
+        name, blob = "efficientnet_b0", ts.efficientnet_b0(17, (), seed=7, width=args.width, size=160)
+    elif args.densenet:
+        import tflite_build_preact as tp
+        name, blob = "densenet121", tp.densenet121(17, size=160, seed=7)
+    else:
+        import tflite_build as tb
+        name, blob = "inception_v3", tb.inception_v3(17, (), seed=7, width=args.width)
+    g = Graph(blob)
+    folds = dict(fuse_preactivation=True, fold_windows=True)   # LiteInterpreter's defaults
+    plans = {m: build_plan(g, conv_math=m, **folds) for m in ("f32", "fp16x2")}
+    batches = [int(v) for v in args.batches.split(",")]
+    if args.kernel_trace:
+        print(json.dumps(dict(split_from_trace(args.kernel_trace, plans["fp16x2"], batches[-1]), plan="fp16x2", model=name)))
+        return
+    census = {m: {KIND_NAMES[k]: sum(o.kind == k for o in p.ops) for k in sorted(set(o.kind for o in p.ops))} for m, p in plans.items()}
+    flops = sum(2.0 * plans["f32"].tensors[o.out].H * plans["f32"].tensors[o.out].W * plans["f32"].tensors[o.out].C * o.kh * o.kw
+                * plans["f32"].tensors[o.in0].C for o in plans["f32"].ops if o.kind in (_lib.GRAPH_CONV, _lib.GRAPH_CONV_PRE))
+    eng = TrackEngine(model="lepton3", device=0)
+    stream = torch.cuda.ExternalStream(eng.lib.cpx_stream(eng.h), device=eng.device)
+    maths = ("fp16x2",) if args.skip_torch else ("f32", "fp16x2")
+    devs = {m: GraphDevice(eng, plans[m]) for m in maths}
+    out = {"model": "%s 160x160x3" % name, "conv_gflop_per_sample": flops / 1e9, "launches_by_kind": census, "rounds": args.rounds,
+           "batches": []}
+    rng = np.random.default_rng(0)
+    for n in batches:
+        x = torch.from_numpy(rng.uniform(-1, 1, size=(n, 160, 160, 3)).astype(np.float32)).to(eng.device)
+        ys = {m: torch.empty((n, 17), dtype=torch.float32, device=eng.device) for m in maths}
+        torch.cuda.synchronize()
+        ms = {m: [] for m in maths}
+        for _ in range(args.rounds):
+            for m in maths:
+                def fwd(m=m):
+                    rc = eng.lib.cpx_graph_forward(devs[m]._graph, C.c_void_p(x.data_ptr()), n, C.c_void_p(ys[m].data_ptr()))
+                    assert rc == 0, eng._err()
+
+                with torch.cuda.stream(stream):
+                    ms[m].append(timed(torch, fwd, args.steps, args.warmup))
+        rec = {"N": n}
+        for m in maths:
+            rec[m] = {"ms": float(np.median(ms[m])), "ms_min": min(ms[m]), "ms_max": max(ms[m]),
+                      "conv_tflops_if_all_time_were_conv": flops * n / float(np.median(ms[m])) / 1e9}
+        if len(maths) == 2:
+            rec["speedup"] = rec["f32"]["ms"] / rec["fp16x2"]["ms"]
+            rec["max_abs_diff"] = float((ys["f32"] - ys["fp16x2"]).abs().max())
+        out["batches"].append(rec)
+    for d in devs.values():
+        d.close()
+    eng.close()
+    print(json.dumps(out))
 
 
 def main():
@@ -646,7 +732,15 @@ def main():
     ap.add_argument("--nasnet-blocks", type=int, default=2, help="with --nasnet: normal cells per stage (NASNetMobile: 4, NASNetLarge: 6)")
     ap.add_argument("--folded", action="store_true",
                     help="with --mobilenet: the fold_windows plan alone (a run under a profiler, and its --kernel-trace)")
+    ap.add_argument("--conv-math", default="f32", choices=("f32", "fp16x2"),
+                    help="fp16x2: time the network (default Inception-v3; --mobilenet, --efficientnet, --densenet) with both "
+                         "convolution maths in the same process; with --kernel-trace: split a trace of the fp16x2 plan")
+    ap.add_argument("--rounds", type=int, default=3, help="with --conv-math fp16x2: alternating rounds per batch size (median, scatter)")
     args = ap.parse_args()
+    if args.conv_math == "fp16x2":
+        if (args.mobilenet or args.efficientnet or args.densenet) and args.batches == "1,8,32,128":
+            args.batches = "1,128"
+        return conv_math_leg(args)
     if args.nasnet:
         if args.batches == "1,8,32,128":
             args.batches = "1,8,128"

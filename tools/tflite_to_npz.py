@@ -50,7 +50,7 @@ def input_mode_of(sidecar):
     return name, LiteInterpreter.INPUT_MODE_OF.get(name, "tf" if name in Interpreter.TF_SCALED_MODELS else None)
 
 
-def describe(g, sidecar=None):
+def describe(g, sidecar=None, conv_math="f32"):
     from cpx.ml_tools.tflite_graph import build_plan
 
     census = {}
@@ -76,6 +76,21 @@ def describe(g, sidecar=None):
               if o.kind not in Q8_KINDS and o.weights is not None)
     print("hybrid operators (int8 filter, activations quantised per sample): %d; int8 weight bytes: %d, float32 weight bytes: %d"
           % (len(hybrid), q8, f32))
+    if conv_math != "f32":
+        # what CPX_TFLITE_CONV_MATH=fp16x2 makes of the file, with LiteInterpreter's default folds
+        from cpx import _lib
+
+        base = build_plan(g, fuse_preactivation=True, fold_windows=True)
+        h2 = build_plan(g, fuse_preactivation=True, fold_windows=True, conv_math=conv_math)
+        n_h2 = sum(o.kind == _lib.GRAPH_CONV_F16X2 for o in h2.ops)
+        n_range = sum(o.kind == _lib.GRAPH_RANGE for o in h2.ops)
+        n_pre = sum(o.kind == _lib.GRAPH_CONV_PRE for o in base.ops)
+        print("conv_math %s: %d convolutions go fp16x2 behind %d RANGE launches; %d pre-activations stay AFFINE launches; "
+              "%d launches instead of %d" % (conv_math, n_h2, n_range,
+                                            sum(o.kind == _lib.GRAPH_AFFINE for o in h2.ops) - sum(o.kind == _lib.GRAPH_AFFINE for o in base.ops),
+                                            len(h2.ops), len(base.ops)))
+        if n_pre:
+            print("conv_math %s: %d CONV_PRE of the float32 plan run as CONV_F16X2 behind their AFFINE" % (conv_math, n_pre))
     if sidecar is not None and os.path.exists(sidecar):
         name, mode = input_mode_of(sidecar)
         how = {"caffe": "BGR, the ImageNet means subtracted from the unscaled sample by the graph's INPUT operator",
@@ -91,11 +106,13 @@ def main():
     ap.add_argument("out_base", nargs="?", help="writes <out_base>.npz (and copies the sidecar to <out_base>.json)")
     ap.add_argument("--describe", action="store_true", help="print what the graph executor makes of the file; writes nothing")
     ap.add_argument("--sidecar", default=None, help="the model's JSON sidecar (default: <model>.json next to it)")
+    ap.add_argument("--conv-math", default="f32", choices=("f32", "fp16x2"),
+                    help="with --describe: also print how many convolutions go fp16x2 and how many RANGE launches that adds")
     args = ap.parse_args()
     with open(args.model, "rb") as fh:
         g = Graph(fh.read())
     if args.describe:
-        return describe(g, args.sidecar or os.path.splitext(args.model)[0] + ".json")
+        return describe(g, args.sidecar or os.path.splitext(args.model)[0] + ".json", conv_math=args.conv_math)
     if args.out_base is None:
         ap.error("out_base is required unless --describe is given")
     weights = convert(g)
