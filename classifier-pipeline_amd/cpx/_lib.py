@@ -128,7 +128,8 @@ assert C.sizeof(GraphTensor) == 32 and C.sizeof(GraphOp) == 112
 # enum CPX_GRAPH_* (include/cpx.h)
 GRAPH_CONV, GRAPH_MAX_POOL, GRAPH_AVG_POOL, GRAPH_ADD, GRAPH_AFFINE, GRAPH_MEAN, GRAPH_FC, GRAPH_LOGISTIC, GRAPH_SOFTMAX, \
     GRAPH_PAD, GRAPH_CHANNEL_MAP, GRAPH_CONV_Q8, GRAPH_FC_Q8, GRAPH_QUANT_PARAMS, GRAPH_DWCONV, GRAPH_DWCONV_Q8, GRAPH_MUL, \
-    GRAPH_INPUT, GRAPH_CONV_PRE, GRAPH_SLICE, GRAPH_DWCONV_PRE, GRAPH_RANGE, GRAPH_CONV_F16X2 = range(1, 24)
+    GRAPH_INPUT, GRAPH_CONV_PRE, GRAPH_SLICE, GRAPH_DWCONV_PRE, GRAPH_RANGE, GRAPH_CONV_F16X2, GRAPH_CONV_GROUPED, \
+    GRAPH_CONV_Q8_GROUPED = range(1, 26)
 # enum CPX_GRAPH_ACT_*: the planner's own activation codes, outside TFLite's ActivationFunctionType
 GRAPH_ACT_SWISH, GRAPH_ACT_LOGISTIC = 16, 17
 GRAPH_MEAN_WIDE_PIXELS = 256   # MEAN: from this many pixels on the striped summation order (csrc/cpx_graph_core.h)

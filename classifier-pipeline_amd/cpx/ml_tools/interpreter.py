@@ -272,15 +272,18 @@ class Interpreter:
 class WRResNetInterpreter(Interpreter):
     """WR-ResNet on the MFMA kernels; model = <name>.npz (Keras-layout weights) or a released <name>.tflite (read in
     pure Python on load: cpx/ml_tools/tflite_reader.py -- what the reference's LiteInterpreter takes,
-    interpreter.py:520-560) + the sidecar <name>.json."""
+    interpreter.py:520-560) + the sidecar <name>.json.  quantised_math="float": a dynamic-range quantised .tflite has its
+    INT8 filters multiplied out on load (get_interpreter passes it under CPX_TFLITE_QUANT_MATH=float; by default such a
+    file runs TFLite's hybrid arithmetic on the graph executor, LiteInterpreter)."""
 
     TYPE = "cpx-hip"
 
-    def __init__(self, model_file, run_over_network=False, load_model=True, engine=None):
+    def __init__(self, model_file, run_over_network=False, load_model=True, engine=None, quantised_math=None):
         super().__init__(model_file, run_over_network)
         self._engine = engine
         self._net = None
         self._weights = None
+        self._quantised_math = quantised_math
         if self.params.model_name != "wr-resnet":
             # the samples of the other families are prepared here (crop / resize / normalise / tile / input scaling);
             # their NETWORKS are not built: they classify through a model server (run_over_network: POST /predict,
@@ -301,7 +304,7 @@ class WRResNetInterpreter(Interpreter):
             from .tflite_reader import load_tflite
 
             logging.info("Reading TFLite model %s", self.model_file)
-            self._weights = load_tflite(self.model_file)
+            self._weights = load_tflite(self.model_file, quantised_math=self._quantised_math)
         else:
             self._weights = load_weights(self.model_file.with_suffix(".npz"))
         n = self._weights["prediction/bias"].shape[0]
@@ -374,7 +377,9 @@ class LiteInterpreter(Interpreter):
     N = 1 on a NASNet-layout graph, hence off.  The nasnet family runs here
     (STRIDED_SLICE / SLICE); CPX_TFLITE_FOLD_WINDOWS=1|0 (default 1): 1 x 1 pools and chains of PAD / SLICE as one SLICE
     launch, a PAD folded into the VALID convolution behind it (build_plan: fold_windows), or every one of them a launch --
-    again the same bits."""
+    again the same bits.
+    A grouped CONV_2D runs here as well (build_plan: grouped_convolutions=True, always): the WR-ResNet-22-4's own file,
+    float32 or dynamic-range quantised -- get_interpreter sends the quantised one here."""
 
     TYPE = "TFLite"
     DEFAULT_QUANT_MATH = "hybrid"
@@ -455,7 +460,7 @@ class LiteInterpreter(Interpreter):
         # refuses, by operator, what the executor does not run
         plan = build_plan(self._graph, quantised_math=self._quant_math, fuse_preactivation=self._fuse_preact,
                           fuse_preactivation_dw=self._fuse_preact_dw, fold_windows=self._fold_windows,
-                          conv_math=self._conv_math)
+                          conv_math=self._conv_math, grouped_convolutions=True)
         self._plans[(plan.graph_input_shape, None)] = plan
         if self.input_mode is not None and plan.graph_input_shape[2] != 3:
             raise NotImplementedError("model_name %r: the %r input mode subtracts the means of three colour channels; the "
@@ -516,7 +521,7 @@ class LiteInterpreter(Interpreter):
                                                  quantised_math=self._quant_math, fuse_preactivation=self._fuse_preact,
                                                  fuse_preactivation_dw=self._fuse_preact_dw, fold_windows=self._fold_windows,
                                                  input_mode=None if cmap is None else self.input_mode,
-                                                 conv_math=self._conv_math)
+                                                 conv_math=self._conv_math, grouped_convolutions=True)
         return key, plan
 
     def _device(self, engine, hwc):
@@ -618,11 +623,24 @@ def get_interpreter(model, run_over_network=False, load_model=True, seed=None):
         raise NotImplementedError(
             "model type %r (%s): cpx runs WR-ResNet models as <name>.npz + <name>.json or as a released <name>.tflite "
             "(TensorFlow / RandomForest runtimes are not part of this build)" % (model.type, model.model_file))
-    if suffix == ".tflite" and not run_over_network and _sidecar_model_name(model.model_file) != "wr-resnet":
+    wr = suffix != ".tflite" or run_over_network or _sidecar_model_name(model.model_file) == "wr-resnet"
+    quantised = False
+    if wr and suffix == ".tflite" and not run_over_network:
+        # a WR-ResNet file as the reference's converter writes it (Optimize.DEFAULT: INT8 filters) runs TFLite's hybrid
+        # arithmetic on the graph executor, as every other family does; CPX_TFLITE_QUANT_MATH=float multiplies the filters
+        # out and keeps the fused kernels.  A float32 file goes to the fused kernels as ever
+        from .tflite_reader import has_quantised_filters
+
+        try:
+            quantised = has_quantised_filters(model.model_file)
+        except OSError:
+            pass   # (no such file: the WR-ResNet route reports it where it loads)
+    if not wr or (quantised and LiteInterpreter.quant_math() == "hybrid"):
         # the reference's route for every .tflite (interpreter.py:597-628): the graph executor takes the file as it is
         classifier = LiteInterpreter(model.model_file, run_over_network, load_model)
     else:
-        classifier = WRResNetInterpreter(model.model_file, run_over_network, load_model)
+        classifier = WRResNetInterpreter(model.model_file, run_over_network, load_model,
+                                         quantised_math="float" if quantised else None)
     classifier.id = model.id
     classifier.port = model.port
     if seed is not None:

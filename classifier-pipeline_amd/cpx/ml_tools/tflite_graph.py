@@ -78,7 +78,21 @@
   (pack_conv_filter_f16x2).  Fused activations and folded MUL / ADD work unchanged: the epilogue is CONV's.  A
   pre-activation is NOT folded into a convolution that goes fp16x2 (CONV_PRE has no fp16x2 form): with
   conv_math="fp16x2" its AFFINE stays a launch whatever fuse_preactivation says.  Depthwise, FULLY_CONNECTED and the
-  hybrid kinds are untouched; quantised_math="float" composes (the multiplied-out filters are split like any others).
+  hybrid kinds are untouched; quantised_math="float" composes (the multiplied-out filters are split like any others);
+* with grouped_convolutions=True (default False: a grouped CONV_2D is refused by name, as ever) a CONV_2D whose filter depth
+  divides the input depth is a CONV_GROUPED of G = input depth / filter depth groups (Cout % G == 0; a WR-ResNet's
+  convolutions are groups = 2, src/ml_tools/resnet/wr_resnet.py:12-20): ONE launch, the group a grid dimension, each
+  group's outputs bit for bit what CONV computes from that group's channel slice (pack_conv_filter_grouped: G CONV images
+  one after another).  With an INT8 filter (one scale or one per output channel) hybrid math plans CONV_Q8_GROUPED on the
+  QUANT_PARAMS of the WHOLE input view -- the tensor is quantised once per sample, before the groups are walked, as the
+  TFLite runtime's published hybrid kernels do (taken from their text; parity with the runtime is not pinned, as for
+  every hybrid operator here) -- and the int32 overflow check counts kh * kw * (Cin / G) products;
+  quantised_math="float" multiplies the filter out and plans CONV_GROUPED.  Strides 1 to 3 on either axis (the network's
+  last stage has stride 3).  The kinds have CONV's epilogue: MUL / ADD by constants, a swish and a LOGISTIC fold into
+  them.  Kept as launches: a pre-activation in front of a grouped convolution stays an AFFINE launch (there is no grouped
+  CONV_PRE), and conv_math="fp16x2" leaves grouped convolutions on the float32 kernel.  Still refused, by operator name
+  and index: a filter depth that does not divide the input depth, a Cout that G does not divide, dilation, a grouped
+  DEPTHWISE_CONV_2D (a depth multiplier), strides above 3.
 
 GraphDevice uploads a plan's constants to an engine's device and runs it."""
 import ctypes as C
@@ -171,10 +185,12 @@ def _channel_const(g, tid, channels, what):
 
 QUANT_MATHS = ("hybrid", "float")
 CONV_MATHS = ("f32", "fp16x2")
-Q8_KINDS = (_lib.GRAPH_CONV_Q8, _lib.GRAPH_FC_Q8, _lib.GRAPH_DWCONV_Q8)
+Q8_KINDS = (_lib.GRAPH_CONV_Q8, _lib.GRAPH_FC_Q8, _lib.GRAPH_DWCONV_Q8, _lib.GRAPH_CONV_Q8_GROUPED)
+GROUPED_KINDS = (_lib.GRAPH_CONV_GROUPED, _lib.GRAPH_CONV_Q8_GROUPED)
 FOLD_INTO = (_lib.GRAPH_CONV, _lib.GRAPH_CONV_Q8, _lib.GRAPH_CONV_F16X2, _lib.GRAPH_DWCONV, _lib.GRAPH_DWCONV_Q8,
-             _lib.GRAPH_AFFINE)
-LOGISTIC_INTO = (_lib.GRAPH_CONV, _lib.GRAPH_CONV_Q8, _lib.GRAPH_CONV_F16X2, _lib.GRAPH_DWCONV, _lib.GRAPH_DWCONV_Q8)
+             _lib.GRAPH_AFFINE) + GROUPED_KINDS
+LOGISTIC_INTO = (_lib.GRAPH_CONV, _lib.GRAPH_CONV_Q8, _lib.GRAPH_CONV_F16X2, _lib.GRAPH_DWCONV, _lib.GRAPH_DWCONV_Q8) + \
+    GROUPED_KINDS
 PARAM_KINDS = (_lib.GRAPH_QUANT_PARAMS, _lib.GRAPH_RANGE)   # operators that write the 1 x 1 x 4 tensor of a view
 ACT_SWISH, ACT_LOGISTIC = _lib.GRAPH_ACT_SWISH, _lib.GRAPH_ACT_LOGISTIC
 
@@ -188,7 +204,8 @@ PRE_ACTS = (ACT_RELU, ACT_RELU6)
 
 
 def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_math="hybrid", fuse_activations=True,
-               input_mode=None, fuse_preactivation=False, fold_windows=False, fuse_preactivation_dw=False, conv_math="f32"):
+               input_mode=None, fuse_preactivation=False, fold_windows=False, fuse_preactivation_dw=False, conv_math="f32",
+               grouped_convolutions=False):
     """g: tflite_reader.Graph.  input_shape: (H, W, C) of a sample, default: the flatbuffer's.  output: the tensor the
     forward hands out, default the graph's output; the operators it does not need are dropped.  channel_map: up to 4
     indices into the channels of the sample the CALLER brings ([N, H, W, max(map) + 1 or more]): the graph's input
@@ -202,14 +219,15 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
     fuse_preactivation_dw: a bare RELU / RELU6 is also dropped in front of float32 depthwise convolutions (DWCONV_PRE) and
     SLICEs; both keep every bit (the module's docstring).  conv_math: "f32" runs float32 convolutions on the exact float32
     kernel, "fp16x2" as two fp16 planes on the fp16 matrix pipe behind one RANGE launch per input view; a pre-activation
-    is then not folded into them (no CONV_PRE is planned: the AFFINE stays a launch)."""
+    is then not folded into them (no CONV_PRE is planned: the AFFINE stays a launch).  grouped_convolutions: False refuses a
+    grouped CONV_2D by name, True plans it as CONV_GROUPED / CONV_Q8_GROUPED (the module's docstring)."""
     if quantised_math not in QUANT_MATHS:
         raise ValueError("quantised_math %r: one of %s" % (quantised_math, ", ".join(QUANT_MATHS)))
     if conv_math not in CONV_MATHS:
         raise ValueError("conv_math %r: one of %s" % (conv_math, ", ".join(CONV_MATHS)))
     if input_mode is not None and input_mode not in INPUT_MODES:
         raise ValueError("input_mode %r: one of %s" % (input_mode, ", ".join(sorted(INPUT_MODES))))
-    g.check_executable()
+    g.check_executable(grouped=grouped_convolutions)
     if len(g.inputs) != 1 or len(g.outputs) < 1:
         raise NotImplementedError("graphs with %d inputs" % len(g.inputs))
     gin = g.inputs[0]
@@ -302,11 +320,21 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
         w, fscale = filter_of(op, ins[1])
         kh, kw, depth = w.shape[1:]
         co = depth if dw else w.shape[0]
+        groups = 1
         if depth != x.C:
-            raise NotImplementedError(("%s: depth multiplier (filter depth %d, input depth %d), only 1 is run" if dw else
-                                       "%s: grouped convolution (filter depth %d, input depth %d)") % (what, depth, x.C))
+            if dw or not grouped_convolutions:
+                raise NotImplementedError(("%s: depth multiplier (filter depth %d, input depth %d), only 1 is run" if dw else
+                                           "%s: grouped convolution (filter depth %d, input depth %d)") % (what, depth, x.C))
+            if depth < 1 or x.C % depth != 0:
+                raise NotImplementedError("%s: grouped convolution whose filter depth %d does not divide the input depth %d"
+                                          % (what, depth, x.C))
+            groups = x.C // depth
+            if co % groups != 0:
+                raise NotImplementedError("%s: grouped convolution of %d groups (filter depth %d, input depth %d) that do "
+                                          "not divide its %d output channels" % (what, groups, depth, x.C, co))
         sh, sw = op.get("stride_h", 1), op.get("stride_w", 1)
-        if not (1 <= kh <= 7 and 1 <= kw <= 7 and sh in (1, 2) and sw in (1, 2)):
+        strides = (1, 2, 3) if groups > 1 else (1, 2)
+        if not (1 <= kh <= 7 and 1 <= kw <= 7 and sh in strides and sw in strides):
             raise NotImplementedError("%s: %d x %d kernel with strides %d, %d" % (what, kh, kw, sh, sw))
         ho, pt, pb = window(x.H, kh, sh, op.get("padding", 0))
         wo, pl, pr = window(x.W, kw, sw, op.get("padding", 0))
@@ -317,12 +345,16 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
         kind, in1 = _lib.GRAPH_DWCONV if dw else _lib.GRAPH_CONV, -1
         if fscale is not None:
             if not dw:   # (a depthwise output sums kh * kw <= 49 products)
-                overflow_check(what, kh * kw * depth)
+                overflow_check(what, kh * kw * depth)   # (depth: the channels of ONE group)
             kind, in1 = _lib.GRAPH_DWCONV_Q8 if dw else _lib.GRAPH_CONV_Q8, params_of(x, False, i)
+            if groups > 1:
+                kind = _lib.GRAPH_CONV_Q8_GROUPED   # the parameters are the whole view's, shared like any other reader's
+        elif groups > 1:
+            kind = _lib.GRAPH_CONV_GROUPED          # (also with conv_math="fp16x2": there is no grouped fp16x2 kernel)
         elif conv_math == "fp16x2" and not dw:
             kind, in1 = _lib.GRAPH_CONV_F16X2, range_of(x, i)
         emit(PlanOp(kind, op["name"], x.id, y, in1=in1, kh=kh, kw=kw, stride_h=sh, stride_w=sw, pads=(pt, pl, pb, pr),
-                    act=op.get("act", 0), filter=w, scale=None, filter_scale=fscale,
+                    act=op.get("act", 0), filter=w, scale=None, filter_scale=fscale, groups=groups,
                     shift=np.zeros(co, np.float32) if bias is None else np.asarray(bias, np.float32).reshape(-1)), i)
 
     for i, op in enumerate(g.ops):
@@ -744,6 +776,11 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
     for o in ops:
         if o.kind == _lib.GRAPH_CONV_PRE:
             o.weights = pack_conv_pre(o.filter, o.pre_scale, o.pre_shift)
+        if o.kind in GROUPED_KINDS:
+            pack = pack_conv_filter_grouped if o.kind == _lib.GRAPH_CONV_GROUPED else pack_conv_filter_q8_grouped
+            o.weights = pack(o.filter, o.groups)
+            if o.filter_scale is not None:
+                o.scale = o.filter_scale if o.scale is None else (o.filter_scale * o.scale).astype(np.float32)
         if o.kind in packers:
             o.weights = packers[o.kind](o.filter)
             if o.filter_scale is not None:   # the device multiplies by float32(filter scale x folded scale)
@@ -780,6 +817,61 @@ def unpack_conv_filter_q8(packed, shape):
     frag = packed[:n].view(np.int8).reshape(kh * kw, nch, nt, 2, CO, 16)
     full = frag.transpose(2, 4, 0, 1, 3, 5).reshape(nt * CO, kh * kw, nch * KC)
     return np.ascontiguousarray(full[:co, :, :ci]).reshape(co, kh, kw, ci), packed[n:].view(np.int32)[:co].copy()
+
+
+def _group_rows(w_ohwi, groups):
+    w = np.asarray(w_ohwi)
+    co = w.shape[0]
+    if groups < 2 or co % groups != 0:
+        raise ValueError("%d groups for a filter of %d output channels" % (groups, co))
+    return [w[g * (co // groups):(g + 1) * (co // groups)] for g in range(groups)]
+
+
+def pack_conv_filter_grouped(w_ohwi, groups):
+    """float32 OHWI [Cout, kh, kw, Cin / groups] of a grouped CONV_2D -> float32, flat: `groups` pack_conv_filter images
+    for Cin / groups -> Cout / groups one after another, image g of the filter rows [g * Cout / groups, (g + 1) * Cout /
+    groups): byte for byte what pack_conv_filter makes of those rows (include/cpx.h: CPX_GRAPH_CONV_GROUPED)."""
+    return np.concatenate([pack_conv_filter(r).reshape(-1) for r in _group_rows(w_ohwi, groups)])
+
+
+def unpack_conv_filter_grouped(packed, shape, groups):
+    """The inverse of pack_conv_filter_grouped for a filter of `shape` (OHWI, I = Cin / groups)."""
+    co, kh, kw, ci = shape
+    cog = co // groups
+    cip = -(-ci // _lib.GRAPH_CONV_KC) * _lib.GRAPH_CONV_KC
+    cop = -(-cog // _lib.GRAPH_CONV_CO) * _lib.GRAPH_CONV_CO
+    img = np.asarray(packed, np.float32).reshape(groups, kh * kw, cip, cop)[:, :, :ci, :cog]
+    # [g, tap, ci, co] -> [g, co, tap, ci]
+    return np.ascontiguousarray(img.transpose(0, 3, 1, 2)).reshape(co, kh, kw, ci)
+
+
+def pack_conv_filter_q8_grouped(w_ohwi, groups):
+    """INT8 OHWI [Cout, kh, kw, Cin / groups] of a grouped CONV_2D -> bytes: `groups` fragment images of
+    pack_conv_filter_q8 for Cin / groups -> Cout / groups one after another (image g of the filter rows of group g, byte
+    for byte what pack_conv_filter_q8 makes of them), then int32 wsum[groups][Cout / groups rounded up to GRAPH_CONV_CO],
+    each group's own rows summed (include/cpx.h: CPX_GRAPH_CONV_Q8_GROUPED)."""
+    images, wsums = [], []
+    for r in _group_rows(w_ohwi, groups):
+        one = pack_conv_filter_q8(r)
+        nws = 4 * (-(-r.shape[0] // _lib.GRAPH_CONV_CO) * _lib.GRAPH_CONV_CO)
+        images.append(one[:-nws])
+        wsums.append(one[-nws:])
+    return np.concatenate(images + wsums)
+
+
+def unpack_conv_filter_q8_grouped(packed, shape, groups):
+    """The inverse of pack_conv_filter_q8_grouped for a filter of `shape` (OHWI, I = Cin / groups) -> (int8 filter, int32
+    wsum[Cout])."""
+    co, kh, kw, ci = shape
+    cog = co // groups
+    KC, CO = _lib.GRAPH_CONV_Q8_KC, _lib.GRAPH_CONV_CO
+    n = kh * kw * (-(-ci // KC)) * (-(-cog // CO)) * 64 * 16
+    nws = 4 * (-(-cog // CO) * CO)
+    packed = np.asarray(packed, np.uint8)
+    assert packed.size == groups * (n + nws), (packed.size, n, nws)
+    parts = [unpack_conv_filter_q8(np.concatenate([packed[g * n:(g + 1) * n], packed[groups * n + g * nws:groups * n + (g + 1) * nws]]),
+                                   (cog, kh, kw, ci)) for g in range(groups)]
+    return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
 
 
 def split_filter_f16x2(w_ohwi):
@@ -903,14 +995,16 @@ def pack_conv_pre(w_ohwi, pre_scale, pre_shift):
 
 
 def load_plan(path, input_shape=None, channel_map=None, quantised_math="hybrid", fuse_activations=True, input_mode=None,
-              fuse_preactivation=False, fold_windows=False, fuse_preactivation_dw=False, conv_math="f32"):
+              fuse_preactivation=False, fold_windows=False, fuse_preactivation_dw=False, conv_math="f32",
+              grouped_convolutions=False):
     from .tflite_reader import Graph
 
     with open(str(path), "rb") as fh:
         g = Graph(fh.read())
     return g, build_plan(g, input_shape=input_shape, channel_map=channel_map, quantised_math=quantised_math,
                          fuse_activations=fuse_activations, input_mode=input_mode, fuse_preactivation=fuse_preactivation,
-                         fold_windows=fold_windows, fuse_preactivation_dw=fuse_preactivation_dw, conv_math=conv_math)
+                         fold_windows=fold_windows, fuse_preactivation_dw=fuse_preactivation_dw, conv_math=conv_math,
+                         grouped_convolutions=grouped_convolutions)
 
 
 class GraphDevice:
@@ -955,6 +1049,8 @@ class GraphDevice:
                 n.n_map = len(o.channel_map)
                 for c, v in enumerate(o.channel_map):
                     n.channel_map[c] = v
+            if o.kind in GROUPED_KINDS:
+                n.n_map = o.groups   # (a convolution has no channel map: the field carries the number of groups)
             n.weights, n.scale, n.shift = up(o.weights), up(o.scale), up(o.shift)
         self._graph = C.c_void_p()
         rc = self.lib.cpx_graph_create(engine.h, ops, len(plan.ops), tens, len(ids), ids[plan.input], ids[out_id],

@@ -18,15 +18,20 @@ only NumPy.  Two users:
   dim), FULLY_CONNECTED with asymmetric_quantize_inputs.
   check_executable() refuses everything else by operator name and index: a depth multiplier, quantised activations,
   UINT8 / INT16 or asymmetric filters, an INT8 constant anywhere but as such a filter, DEQUANTIZE / QUANTIZE, grouped
-  CONV_2D, a dynamic shape, an operator outside the set.
+  CONV_2D (check_executable(grouped=True) lets one through where the filter depth divides the input depth and the groups
+  divide the output channels: the graph executor's CONV_GROUPED / CONV_Q8_GROUPED), a dynamic shape, an operator outside
+  the set.
 * `convert` / `load_tflite` walk ONE topology, a WR-ResNet-22-4, into the Keras-layout weights of
   cpx/ml_tools/wrresnet.py (the fused MFMA network); get_interpreter on such a path converts on load,
-  tools/tflite_to_npz.py writes the same arrays to an .npz.
+  tools/tflite_to_npz.py writes the same arrays to an .npz.  A dynamic-range quantised file is refused by the name of its
+  first INT8 tensor unless quantised_math="float" is given, which multiplies the filters out, float32(int8) * scale
+  (get_interpreter does under CPX_TFLITE_QUANT_MATH=float; by default it hands such a file to the graph executor).
 
 What is read: the float32 graph of WR-ResNet-22-4 (src/ml_tools/resnet/wr_resnet.py:5-98) as the TFLite converter
 writes it -- CONV_2D (filter OHWI, bias, fused ReLU: a convolution with the BatchNorm that follows it folded in), MUL +
 ADD by per-channel constants (a BatchNorm that follows a residual ADD cannot be folded: scale and shift), RELU, ADD of
-two activations (the residual), MEAN (global average pooling), FULLY_CONNECTED, LOGISTIC / SOFTMAX.  The walk follows
+two activations (the residual, with or without the ReLU behind it fused; the 1 x 1 shortcut in front of the block's
+BatchNorm, behind it or behind the main branch), MEAN (global average pooling), FULLY_CONNECTED, LOGISTIC / SOFTMAX.  The walk follows
 the operators in order and fills the Keras-layout names; a folded or affine-only BatchNorm becomes gamma = scale,
 beta = shift, moving_mean = 0, moving_variance = 1 - eps (so that the loader's gamma / sqrt(var + eps) gives the scale
 back exactly).  Anything else (quantised tensors, another topology) is refused with the operator that stopped the walk."""
@@ -238,12 +243,13 @@ class Graph:
         dim = ten["quant"]["dim"] if sc.size > 1 else 0
         return (w * sc.reshape((1,) * dim + (-1,) + (1,) * (w.ndim - 1 - dim))).astype(np.float32)
 
-    def check_executable(self):
+    def check_executable(self, grouped=False):
         """Raises NotImplementedError, naming the operator and its index, for whatever the graph executor
         (cpx/ml_tools/tflite_graph.py) does not run: an operator outside OPS, a STRIDED_SLICE / SLICE that resolve_slice
         refuses, a tensor that is not float32 (int32 constants of MEAN / RESHAPE / PAD / STRIDED_SLICE / SLICE excepted; an INT8 constant as the filter of CONV_2D / FULLY_CONNECTED with
         symmetric scales along dimension 0, or of DEPTHWISE_CONV_2D along dimension 3, excepted), grouped CONV_2D, a
-        DEPTHWISE_CONV_2D with a depth multiplier or a dilation other than 1, a dynamic shape."""
+        DEPTHWISE_CONV_2D with a depth multiplier or a dilation other than 1, a dynamic shape.  grouped=True lets a grouped
+        CONV_2D through where the filter depth divides the input depth and the groups divide the output channels."""
         for i, op in enumerate(self.ops):
             name = op["name"]
             if op["code"] not in OPS:
@@ -286,8 +292,16 @@ class Graph:
                     raise NotImplementedError("operator %d (CONV_2D): the filter is not a constant" % i)
                 cin = self.tensors[op["inputs"][0]]["shape"]
                 if len(cin) == 4 and cin[3] > 0 and w.shape[3] != cin[3]:
-                    raise NotImplementedError("operator %d (CONV_2D): grouped convolution (filter depth %d, input depth %d)"
-                                              % (i, w.shape[3], cin[3]))
+                    if not grouped:
+                        raise NotImplementedError("operator %d (CONV_2D): grouped convolution (filter depth %d, input depth %d)"
+                                                  % (i, w.shape[3], cin[3]))
+                    if w.shape[3] < 1 or cin[3] % w.shape[3] != 0:
+                        raise NotImplementedError("operator %d (CONV_2D): grouped convolution whose filter depth %d does not "
+                                                  "divide the input depth %d" % (i, w.shape[3], cin[3]))
+                    if w.shape[0] % (cin[3] // w.shape[3]) != 0:
+                        raise NotImplementedError("operator %d (CONV_2D): grouped convolution of %d groups (filter depth %d, input "
+                                                  "depth %d) that do not divide its %d output channels"
+                                                  % (i, cin[3] // w.shape[3], w.shape[3], cin[3], w.shape[0]))
             if name == "DEPTHWISE_CONV_2D":
                 w = self.const(op["inputs"][1]) if len(op["inputs"]) > 1 and op["inputs"][1] >= 0 else None
                 if w is None:
@@ -375,9 +389,10 @@ def bn_params(scale, shift):
             "moving_mean": np.zeros(c, np.float32), "moving_variance": np.full(c, identity_variance(), np.float32)}
 
 
-def conv_kernel(g, op, groups=2):
-    """TFLite OHWI [Cout, kh, kw, Cin/groups] -> Keras HWIO [kh, kw, Cin/groups, Cout]; bias."""
-    w = g.const(op["inputs"][1])
+def conv_kernel(g, op, groups=2, const=None):
+    """TFLite OHWI [Cout, kh, kw, Cin/groups] -> Keras HWIO [kh, kw, Cin/groups, Cout]; bias.  const: how a constant is
+    read (default g.const; g.dequantised multiplies an INT8 filter out)."""
+    w = (const or g.const)(op["inputs"][1])
     b = g.const(op["inputs"][2]) if len(op["inputs"]) > 2 and op["inputs"][2] >= 0 else None
     if w is None:
         raise ValueError("CONV_2D without a constant filter")
@@ -385,12 +400,19 @@ def conv_kernel(g, op, groups=2):
     return k, (np.zeros(w.shape[0], np.float32) if b is None else b.astype(np.float32))
 
 
-def convert(g, blocks=3, filters=(16, 64, 128, 256)):
+def convert(g, blocks=3, filters=(16, 64, 128, 256), quantised_math=None):
+    """quantised_math: None refuses an INT8 filter by its tensor's name; "float" multiplies every INT8 filter out,
+    float32(int8) * scale, and converts the float32 network the file stands for."""
+    if quantised_math not in (None, "float"):
+        raise ValueError("quantised_math %r: None or 'float'" % (quantised_math,))
     for op in g.ops:
         ten = g.quantised_filter(op)
-        if ten is not None:
+        if ten is not None and quantised_math is None:
             raise NotImplementedError("tensor %r is an INT8 filter: a dynamic-range quantised WR-ResNet is not converted "
-                                      "(the graph executor runs quantised files)" % ten["name"])
+                                      "(the graph executor runs quantised files: LiteInterpreter, build_plan(..., "
+                                      "grouped_convolutions=True); or multiply the filters out: convert(g, "
+                                      "quantised_math=\"float\"), CPX_TFLITE_QUANT_MATH=float)" % ten["name"])
+    const = g.dequantised if quantised_math == "float" else g.const
     ops = list(g.ops)
     pos = [0]
 
@@ -418,37 +440,42 @@ def convert(g, blocks=3, filters=(16, 64, 128, 256)):
 
     w = {}
     op = take("CONV_2D")
-    w["conv1_1/kernel"], w["conv1_1/bias"] = conv_kernel(g, op)
+    w["conv1_1/kernel"], w["conv1_1/bias"] = conv_kernel(g, op, const=const)
     c_in = filters[0]
     for stage in (2, 3, 4):
         f = filters[stage - 1]
         for d in range(blocks):
             b = "%db%d" % (stage, d)
+            shortcut = None
+            nxt = peek()
+            if d == 0 and nxt is not None and nxt["name"] == "CONV_2D" and g.const(nxt["inputs"][1]).shape[1] == 1:
+                shortcut = take("CONV_2D")              # the shortcut reads the block's raw input: it may come first
             sc, sh = affine(c_in)                       # pre-activation BatchNorm + ReLU of the block's input
             for k, v in bn_params(sc, sh).items():
                 w["bn%s_branch2a/%s" % (b, k)] = v
             nxt = peek()
-            shortcut = None
-            if d == 0:
-                # the 1x1 shortcut convolution reads the activated input; the converter may put it before or after
-                # the main branch
+            if d == 0 and shortcut is None:
+                # the 1x1 shortcut convolution; the converter may put it before or after the main branch
                 if nxt["name"] == "CONV_2D" and g.const(nxt["inputs"][1]).shape[1] == 1:
                     shortcut = take("CONV_2D")
             a = take("CONV_2D")                         # conv a with the following BatchNorm folded in, ReLU fused
-            w["res%s_branch2a/kernel" % b], w["res%s_branch2a/bias" % b] = conv_kernel(g, a)
+            w["res%s_branch2a/kernel" % b], w["res%s_branch2a/bias" % b] = conv_kernel(g, a, const=const)
             if a["act"] != 1:
                 take("RELU")
             for k, v in bn_params(np.ones(f, np.float32), np.zeros(f, np.float32)).items():
                 w["bn%s_branch2b/%s" % (b, k)] = v
             cb = take("CONV_2D")
-            w["res%s_branch2b/kernel" % b], w["res%s_branch2b/bias" % b] = conv_kernel(g, cb)
+            w["res%s_branch2b/kernel" % b], w["res%s_branch2b/bias" % b] = conv_kernel(g, cb, const=const)
             if d == 0 and shortcut is None:
                 shortcut = take("CONV_2D")
             if shortcut is not None:
-                w["shortcut%d/kernel" % stage], w["shortcut%d/bias" % stage] = conv_kernel(g, shortcut)
+                w["shortcut%d/kernel" % stage], w["shortcut%d/bias" % stage] = conv_kernel(g, shortcut, const=const)
             add = take("ADD")
-            if add["act"] != 0:
-                raise ValueError("operator %d: the residual ADD carries an activation" % (pos[0] - 1))
+            # (the ReLU behind the residual ADD, wr_resnet.py:96-97, is fused into it by the converter; the network the
+            # weights go to applies it either way)
+            if add["act"] not in (0, 1):
+                raise ValueError("operator %d: the residual ADD carries the activation %d, neither none nor RELU"
+                                 % (pos[0] - 1, add["act"]))
             c_in = f
     sc, sh = affine(c_in)
     for k, v in bn_params(sc, sh).items():
@@ -457,7 +484,7 @@ def convert(g, blocks=3, filters=(16, 64, 128, 256)):
     n_hidden = 0
     while True:
         fc = take("FULLY_CONNECTED")
-        wt = g.const(fc["inputs"][1])
+        wt = const(fc["inputs"][1])
         bias = g.const(fc["inputs"][2]) if len(fc["inputs"]) > 2 and fc["inputs"][2] >= 0 else np.zeros(wt.shape[0], np.float32)
         nxt = peek()
         last = nxt is None or nxt["name"] in ("LOGISTIC", "SOFTMAX")
@@ -473,8 +500,16 @@ def convert(g, blocks=3, filters=(16, 64, 128, 256)):
     return w
 
 
-def load_tflite(path):
-    """-> the weights dict of cpx.ml_tools.wrresnet (what load_weights returns for an .npz) of a .tflite model file."""
+def load_tflite(path, quantised_math=None):
+    """-> the weights dict of cpx.ml_tools.wrresnet (what load_weights returns for an .npz) of a .tflite model file;
+    quantised_math: convert's."""
     with open(str(path), "rb") as fh:
         g = Graph(fh.read())
-    return convert(g)
+    return convert(g, quantised_math=quantised_math)
+
+
+def has_quantised_filters(path):
+    """A .tflite file holds at least one INT8 filter: it is dynamic-range quantised."""
+    with open(str(path), "rb") as fh:
+        g = Graph(fh.read())
+    return any(g.quantised_filter(op) is not None for op in g.ops)

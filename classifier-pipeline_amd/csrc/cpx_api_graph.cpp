@@ -42,16 +42,20 @@ static const char* graph_check_op(const cpx_graph_op& o, const std::vector<cpx_g
     case CPX_GRAPH_CONV_PRE:
     case CPX_GRAPH_CONV_Q8:
     case CPX_GRAPH_CONV_F16X2:
+    case CPX_GRAPH_CONV_GROUPED:
+    case CPX_GRAPH_CONV_Q8_GROUPED:
     case CPX_GRAPH_DWCONV:
     case CPX_GRAPH_DWCONV_PRE:
     case CPX_GRAPH_DWCONV_Q8:
     case CPX_GRAPH_MAX_POOL:
     case CPX_GRAPH_AVG_POOL: {
       const bool dw = o.kind == CPX_GRAPH_DWCONV || o.kind == CPX_GRAPH_DWCONV_PRE || o.kind == CPX_GRAPH_DWCONV_Q8;
-      const bool conv = dw || o.kind == CPX_GRAPH_CONV || o.kind == CPX_GRAPH_CONV_PRE || o.kind == CPX_GRAPH_CONV_Q8 ||
+      const bool grouped = o.kind == CPX_GRAPH_CONV_GROUPED || o.kind == CPX_GRAPH_CONV_Q8_GROUPED;
+      const bool conv = dw || grouped || o.kind == CPX_GRAPH_CONV || o.kind == CPX_GRAPH_CONV_PRE || o.kind == CPX_GRAPH_CONV_Q8 ||
                         o.kind == CPX_GRAPH_CONV_F16X2;
       if (o.kh < 1 || o.kw < 1 || o.kh > 7 || o.kw > 7) return "kernel sides are 1 to 7";
-      if (o.stride_h < 1 || o.stride_w < 1 || o.stride_h > (conv ? 2 : 7) || o.stride_w > (conv ? 2 : 7)) return "bad stride";
+      if (grouped && (o.stride_h < 1 || o.stride_w < 1 || o.stride_h > 3 || o.stride_w > 3)) return "grouped CONV: strides are 1 to 3";
+      if (!grouped && (o.stride_h < 1 || o.stride_w < 1 || o.stride_h > (conv ? 2 : 7) || o.stride_w > (conv ? 2 : 7))) return "bad stride";
       if (o.pad_top < 0 || o.pad_left < 0 || o.pad_bottom < 0 || o.pad_right < 0 || o.pad_top >= o.kh || o.pad_bottom >= o.kh ||
           o.pad_left >= o.kw || o.pad_right >= o.kw)
         return "bad padding";
@@ -69,6 +73,13 @@ static const char* graph_check_op(const cpx_graph_op& o, const std::vector<cpx_g
       if ((o.kind == CPX_GRAPH_DWCONV || o.kind == CPX_GRAPH_DWCONV_PRE) && (reinterpret_cast<uintptr_t>(o.weights) & 15))
         return "DWCONV weights are not 16-byte aligned";
       if (o.kind == CPX_GRAPH_DWCONV_Q8 && (reinterpret_cast<uintptr_t>(o.weights) & 3)) return "DWCONV_Q8 weights are not 4-byte aligned";
+      if (grouped) {
+        if (o.n_map < 2) return "grouped CONV: n_map carries the number of groups, 2 or more";
+        if (a.C % o.n_map != 0) return "grouped CONV: the groups do not divide the input channels";
+        if (y.C % o.n_map != 0) return "grouped CONV: the groups do not divide the output channels";
+        if (o.kind == CPX_GRAPH_CONV_GROUPED && (reinterpret_cast<uintptr_t>(o.weights) & 15)) return "CONV_GROUPED weights are not 16-byte aligned";
+        if (o.kind == CPX_GRAPH_CONV_Q8_GROUPED && (reinterpret_cast<uintptr_t>(o.weights) & 15)) return "CONV_Q8_GROUPED weights are not 16-byte aligned";
+      }
       if (o.kind == CPX_GRAPH_CONV_F16X2) {
         if (reinterpret_cast<uintptr_t>(o.weights) & 15) return "CONV_F16X2 weights are not 16-byte aligned";
         if (!is_params(o.in1)) return "CONV_F16X2 needs the 1 x 1 x 4 RANGE tensor of its input as in1";
@@ -134,7 +145,7 @@ static const char* graph_check_op(const cpx_graph_op& o, const std::vector<cpx_g
       return "unknown operator kind";
   }
   // what a hybrid operator needs beyond its float32 twin (the caller's message names the operator's kind)
-  if (o.kind == CPX_GRAPH_CONV_Q8 || o.kind == CPX_GRAPH_FC_Q8 || o.kind == CPX_GRAPH_DWCONV_Q8) {
+  if (o.kind == CPX_GRAPH_CONV_Q8 || o.kind == CPX_GRAPH_FC_Q8 || o.kind == CPX_GRAPH_DWCONV_Q8 || o.kind == CPX_GRAPH_CONV_Q8_GROUPED) {
     if (!is_params(o.in1)) return "a hybrid operator needs a 1 x 1 x 4 parameter tensor as in1";
     if (!o.scale || !o.shift) return "a hybrid operator without scale or shift";
   }

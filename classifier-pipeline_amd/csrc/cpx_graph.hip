@@ -15,6 +15,8 @@
 // CONV_PRE is the same kernel with a prologue: the pre-activation act(x * pre_scale[c] + pre_shift[c]) of a DenseNet /
 // ResNetV2 block is applied to the patch on its way from memory to LDS, as the WR-ResNet kernels do (cpx_cnn_bf3.hip), so
 // the AFFINE launch in front of the convolution and its round trip through memory go away.
+// CONV_GROUPED is the same kernel once more with the group as blockIdx.z: one launch for all groups, each group's walk
+// CONV's over its own channel slice and its own weight image (include/cpx.h).
 #include <hip/hip_runtime.h>
 
 #include "cpx_graph_core.h"
@@ -34,27 +36,36 @@ constexpr int AP = BM + 4;         // row stride of the k-major patch image: the
 
 struct ConvGeom {
   long long P;   // N * Ho * Wo
-  int HoWo, cin_pad, cout_pad, vec4;
+  int HoWo, cin_pad, cout_pad, vec4;   // the pads and vec4 of ONE group's walk where the operator is grouped
+  int cg, cog;                         // CONV_GROUPED: input / output channels of a group
 };
 
 // PRE: the input is read as activate(x * pre_scale[c] + pre_shift[c], (int)a.param), the two float32 operations and the
 // activation of graph_affine_kernel; the constants sit behind the filter image, pre_scale[cin_pad] then pre_shift[cin_pad]
-template <int NTN, bool PRE>
+// GRP (CONV_GROUPED): blockIdx.z is the group.  The walk is CONV's over the group's own Cg input channels, with the group's
+// own weight image; only the base channel of the loads, the image and the channel bound / base of the store differ, so a
+// group's outputs are CONV's of that channel slice bit for bit.  scale / shift are indexed by the absolute channel.
+template <int NTN, bool PRE, bool GRP = false>
 __global__ __launch_bounds__(CT) void graph_conv_kernel(GraphOpArgs a, ConvGeom g) {
+  static_assert(!(PRE && GRP), "there is no grouped CONV_PRE");
   constexpr int BN = 32 * NTN;
   __shared__ __attribute__((aligned(16))) float s_a[KC * AP];   // [k][pixel]
   __shared__ __attribute__((aligned(16))) float s_b[KC * BN];   // [k][channel]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const long long p0 = (long long)blockIdx.x * BM;
   const int cout0 = blockIdx.y * BN;
-  const int Cin = a.in0.C, H = a.in0.H, W = a.in0.W;
+  const int grp = GRP ? (int)blockIdx.z : 0;
+  const int Cin = GRP ? g.cg : a.in0.C, H = a.in0.H, W = a.in0.W;     // the channels of the K walk
+  const int Cout = GRP ? g.cog : a.out.C, ch_base = GRP ? grp * g.cog : 0;
+  const float* wimg = GRP ? a.weights + (size_t)grp * a.kh * a.kw * g.cin_pad * g.cout_pad : a.weights;
 
   // staging role: pixel tid / 2 of the tile, channels [8 * half, 8 * half + 8) of the chunk -- the same pixel for the
   // whole K walk, so its coordinates are worked out once
   const int spx = tid >> 1, half = tid & 1;
   const ConvPixel sp = conv_pixel(p0 + spx, g.P, g.HoWo, a.out.W);
   const int iy0 = window_origin(sp.oy, a.stride_h, a.pad_top), ix0 = window_origin(sp.ox, a.stride_w, a.pad_left);
-  const float* in_n = a.in0.p + (size_t)sp.n * a.in0.sample_stride;   // 64-bit over the batch, 32-bit inside a sample
+  // 64-bit over the batch, 32-bit inside a sample; GRP: from the group's first channel on
+  const float* in_n = a.in0.p + (size_t)sp.n * a.in0.sample_stride + (GRP ? grp * g.cg : 0);
   // weight staging: KC rows of BN channels = KC * BN / 4 float4 (one per thread with NTN = 2)
   constexpr int WQ = BN / 4;
   const int wk = tid / WQ, wc4 = tid - wk * WQ;
@@ -115,7 +126,7 @@ __global__ __launch_bounds__(CT) void graph_conv_kernel(GraphOpArgs a, ConvGeom 
       }
     }
     if (wload)
-      pre_w = *reinterpret_cast<const f32x4*>(a.weights + ((size_t)(tap * g.cin_pad + c0 + wk) * g.cout_pad + cout0 + 4 * wc4));
+      pre_w = *reinterpret_cast<const f32x4*>(wimg + ((size_t)(tap * g.cin_pad + c0 + wk) * g.cout_pad + cout0 + 4 * wc4));
   };
 
   fetch(0);
@@ -156,8 +167,9 @@ __global__ __launch_bounds__(CT) void graph_conv_kernel(GraphOpArgs a, ConvGeom 
   const int remb = (int)(pb - nb * g.HoWo);
 #pragma unroll
   for (int t = 0; t < NTN; ++t) {
-    const int ch = cout0 + 32 * t + (lane & 31);
-    if (ch >= a.out.C) continue;
+    const int chl = cout0 + 32 * t + (lane & 31);   // within the group: the bound is the group's own
+    if (chl >= Cout) continue;
+    const int ch = ch_base + chl;
     const float sc = a.scale ? a.scale[ch] : 1.0f;
     const float sh = a.shift ? a.shift[ch] : 0.0f;
 #pragma unroll
@@ -420,6 +432,8 @@ void launch_graph_op(const GraphOpArgs& a, hipStream_t s) {
       g.cin_pad = (a.in0.C + GRAPH_CONV_KC - 1) / GRAPH_CONV_KC * GRAPH_CONV_KC;
       g.cout_pad = (a.out.C + GRAPH_CONV_CO - 1) / GRAPH_CONV_CO * GRAPH_CONV_CO;
       g.vec4 = quads(a.in0);
+      g.cg = a.in0.C;
+      g.cog = a.out.C;
       const unsigned gx = (unsigned)((g.P + BM - 1) / BM);
       const bool pre = a.kind == CPX_GRAPH_CONV_PRE;
       if (g.cout_pad % 64 == 0) {
@@ -435,6 +449,23 @@ void launch_graph_op(const GraphOpArgs& a, hipStream_t s) {
         else
           hipLaunchKernelGGL((graph_conv_kernel<1, false>), grid, dim3(CT), 0, s, a, g);
       }
+      break;
+    }
+    case CPX_GRAPH_CONV_GROUPED: {
+      const int G = a.n_map;
+      ConvGeom g;
+      g.HoWo = a.out.H * a.out.W;
+      g.P = (long long)a.N * g.HoWo;
+      g.cg = a.in0.C / G;
+      g.cog = a.out.C / G;
+      g.cin_pad = (g.cg + GRAPH_CONV_KC - 1) / GRAPH_CONV_KC * GRAPH_CONV_KC;
+      g.cout_pad = (g.cog + GRAPH_CONV_CO - 1) / GRAPH_CONV_CO * GRAPH_CONV_CO;
+      g.vec4 = group_quads(a.in0, g.cg);
+      const unsigned gx = (unsigned)((g.P + BM - 1) / BM);
+      if (g.cout_pad % 64 == 0)
+        hipLaunchKernelGGL((graph_conv_kernel<2, false, true>), dim3(gx, g.cout_pad / 64, G), dim3(CT), 0, s, a, g);
+      else
+        hipLaunchKernelGGL((graph_conv_kernel<1, false, true>), dim3(gx, g.cout_pad / 32, G), dim3(CT), 0, s, a, g);
       break;
     }
     case CPX_GRAPH_MAX_POOL:
@@ -490,6 +521,7 @@ void launch_graph_op(const GraphOpArgs& a, hipStream_t s) {
       hipLaunchKernelGGL(graph_softmax_kernel, dim3(blocks_for((size_t)a.N * a.in0.H * a.in0.W)), dim3(CT), 0, s, a);
       break;
     case CPX_GRAPH_CONV_Q8:
+    case CPX_GRAPH_CONV_Q8_GROUPED:
     case CPX_GRAPH_FC_Q8:
     case CPX_GRAPH_QUANT_PARAMS:
       launch_graph_q8_op(a, s);

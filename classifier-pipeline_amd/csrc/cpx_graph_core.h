@@ -113,6 +113,13 @@ inline bool quads(const View& v) {
   return v.C % 4 == 0 && v.cstride % 4 == 0 && v.sample_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(v.p) & 15) == 0;
 }
 
+// ... and so can every group of a grouped convolution's input of Cg channels per group: the first channel of group g is
+// c_offset + g * Cg, which must lie on a quad for EVERY g -- the view's own alignment does not say that
+template <class View>
+inline bool group_quads(const View& v, int cg) {
+  return quads(v) && cg % 4 == 0;
+}
+
 // ---- CONV / CONV_Q8: M = the output pixels of the whole batch, flattened ----
 // pixel p of P = N * HoWo -> sample, output row and column; p >= P (the last tile's surplus) is sample 0's pixel 0, not valid
 struct ConvPixel {

@@ -59,29 +59,35 @@ __global__ __launch_bounds__(QT) void graph_quant_params_kernel(GraphOpArgs a) {
 
 struct ConvQ8Geom {
   long long P;   // N * Ho * Wo
-  int HoWo, nchunks, ntiles, vec4;
+  int HoWo, nchunks, ntiles, vec4;   // chunks, tiles and vec4 of ONE group's walk where the operator is grouped
+  int cg, cog, G;                    // CONV_Q8_GROUPED: input / output channels of a group, the groups
 };
 
-template <int NTN>
+// GRP (CONV_Q8_GROUPED): blockIdx.z is the group.  The parameters are the whole view's (in1), the walk is CONV_Q8's over
+// the group's own Cg channels with the group's own fragment image; wsum, scale and shift are indexed by the absolute
+// channel (wsum by the padded one: [G][Cog rounded up to 32], behind all G images), the store is bounded by the group.
+template <int NTN, bool GRP = false>
 __global__ __launch_bounds__(CT) void graph_conv_q8_kernel(GraphOpArgs a, ConvQ8Geom g) {
   __shared__ __attribute__((aligned(16))) int s_a[2][BM * KQ / 4];   // [pixel][k], bytes
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const long long p0 = (long long)blockIdx.x * BM;
   const int tile0 = blockIdx.y * NTN;
-  const int Cin = a.in0.C, H = a.in0.H, W = a.in0.W;
+  const int grp = GRP ? (int)blockIdx.z : 0;
+  const int Cin = GRP ? g.cg : a.in0.C, H = a.in0.H, W = a.in0.W;   // the channels of the K walk
+  const int Cout = GRP ? g.cog : a.out.C;
 
   // staging role: pixel tid / 2 of the tile, channels [16 * half, 16 * half + 16) of the chunk -- the same pixel for the
   // whole K walk, so its coordinates and its sample's parameters are worked out once
   const int spx = tid >> 1, half = tid & 1;
   const ConvPixel sp = conv_pixel(p0 + spx, g.P, g.HoWo, a.out.W);
   const int iy0 = window_origin(sp.oy, a.stride_h, a.pad_top), ix0 = window_origin(sp.ox, a.stride_w, a.pad_left);
-  const float* in_n = a.in0.p + (size_t)sp.n * a.in0.sample_stride;
+  const float* in_n = a.in0.p + (size_t)sp.n * a.in0.sample_stride + (GRP ? grp * g.cg : 0);
   const float* sprm = a.in1.p + (size_t)sp.n * a.in1.sample_stride;
   const float inv = sprm[1];
   const int zp = (int)sprm[2];
-  const i32x4* wq = reinterpret_cast<const i32x4*>(a.weights);
-
   const int steps = a.kh * a.kw * g.nchunks;
+  const i32x4* wq0 = reinterpret_cast<const i32x4*>(a.weights);
+  const i32x4* wq = GRP ? wq0 + (size_t)grp * steps * g.ntiles * 64 : wq0;   // the group's image
 
   i32x16 acc[NTN];
 #pragma unroll
@@ -150,16 +156,17 @@ __global__ __launch_bounds__(CT) void graph_conv_q8_kernel(GraphOpArgs a, ConvQ8
   // tile; every pixel takes its own sample's sx and zp
   const long long pb = p0 + 32 * wave;
   if (pb >= g.P) return;
-  const int* wsum = reinterpret_cast<const int*>(wq + (size_t)steps * g.ntiles * 64);
+  const int* wsum = reinterpret_cast<const int*>(wq0 + (size_t)(GRP ? g.G : 1) * steps * g.ntiles * 64) + (GRP ? grp * g.ntiles * 32 : 0);
   const long long nb = pb / g.HoWo;
   const int remb = (int)(pb - nb * g.HoWo);
 #pragma unroll
   for (int t = 0; t < NTN; ++t) {
-    const int ch = (tile0 + t) * 32 + (lane & 31);
-    if (tile0 + t >= g.ntiles || ch >= a.out.C) continue;
+    const int chl = (tile0 + t) * 32 + (lane & 31);   // within the group: the bound is the group's own
+    if (tile0 + t >= g.ntiles || chl >= Cout) continue;
+    const int ch = (GRP ? grp * g.cog : 0) + chl;
     const float sc = a.scale[ch];
     const float sh = a.shift[ch];
-    const int ws = wsum[ch];
+    const int ws = wsum[chl];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int i = acc_row(r, tid);
@@ -220,6 +227,9 @@ void launch_graph_q8_op(const GraphOpArgs& a, hipStream_t s) {
       g.nchunks = (a.in0.C + KQ - 1) / KQ;
       g.ntiles = (a.out.C + GRAPH_CONV_CO - 1) / GRAPH_CONV_CO;
       g.vec4 = vec4;
+      g.cg = a.in0.C;
+      g.cog = a.out.C;
+      g.G = 1;
       const unsigned gx = (unsigned)((g.P + BM - 1) / BM);
       if (g.ntiles == 1)
         hipLaunchKernelGGL(graph_conv_q8_kernel<1>, dim3(gx, 1), dim3(CT), 0, s, a, g);
@@ -227,6 +237,25 @@ void launch_graph_q8_op(const GraphOpArgs& a, hipStream_t s) {
         hipLaunchKernelGGL(graph_conv_q8_kernel<2>, dim3(gx, 1), dim3(CT), 0, s, a, g);
       else
         hipLaunchKernelGGL(graph_conv_q8_kernel<4>, dim3(gx, (g.ntiles + 3) / 4), dim3(CT), 0, s, a, g);
+      break;
+    }
+    case CPX_GRAPH_CONV_Q8_GROUPED: {
+      ConvQ8Geom g;
+      g.G = a.n_map;
+      g.HoWo = a.out.H * a.out.W;
+      g.P = (long long)a.N * g.HoWo;
+      g.cg = a.in0.C / g.G;
+      g.cog = a.out.C / g.G;
+      g.nchunks = (g.cg + KQ - 1) / KQ;
+      g.ntiles = (g.cog + GRAPH_CONV_CO - 1) / GRAPH_CONV_CO;
+      g.vec4 = group_quads(a.in0, g.cg);
+      const unsigned gx = (unsigned)((g.P + BM - 1) / BM);
+      if (g.ntiles == 1)
+        hipLaunchKernelGGL((graph_conv_q8_kernel<1, true>), dim3(gx, 1, g.G), dim3(CT), 0, s, a, g);
+      else if (g.ntiles == 2)
+        hipLaunchKernelGGL((graph_conv_q8_kernel<2, true>), dim3(gx, 1, g.G), dim3(CT), 0, s, a, g);
+      else
+        hipLaunchKernelGGL((graph_conv_q8_kernel<4, true>), dim3(gx, (g.ntiles + 3) / 4, g.G), dim3(CT), 0, s, a, g);
       break;
     }
     case CPX_GRAPH_FC_Q8:

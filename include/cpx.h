@@ -877,13 +877,30 @@ enum {
   /* CONV_2D with float32 in and out on the fp16 matrix pipe: every operand as two fp16 planes, see below. */
   CPX_GRAPH_RANGE = 22,      /* in0 (its own channels only) -> out, a 1 x 1 x 4 tensor [up, down, 0, 0] per sample: the
                                 exact power-of-two scaling that brings the sample's largest magnitude below 2^15 */
-  CPX_GRAPH_CONV_F16X2 = 23  /* CONV_2D, float32 in, float32 out.  in1: the 1 x 1 x 4 RANGE tensor of in0.  `weights`
+  CPX_GRAPH_CONV_F16X2 = 23, /* CONV_2D, float32 in, float32 out.  in1: the 1 x 1 x 4 RANGE tensor of in0.  `weights`
                                 (16-byte aligned) is reinterpreted as BYTES: fp16 [kh * kw][chunks of 32 input
                                 channels][tiles of 32 output channels][plane: wh, wl][k half m: 0, 1][64 lanes][8] --
                                 lane l: output channel l & 31 of the tile, input channels 16 * m + 8 * (l >> 5) + j of
                                 the chunk (the B fragment of v_mfma_f32_32x32x16_f16), zeros beyond Cin / Cout -- and
                                 behind them float32 wdown[Cout rounded up to 32], wdown[c] = 2^-kw[c].  `activation`,
                                 scale, shift: as CONV, NULL included */
+  /* Grouped CONV_2D (a WR-ResNet's convolutions are groups = 2).  n_map carries the number of groups G (channel_map is
+   * unused): G >= 2 divides in C and out C; Cg = in C / G, Cog = out C / G.  Kernel sides 1 to 7, strides 1 to 3 on
+   * either axis, pads as CONV.  One launch covers all groups. */
+  CPX_GRAPH_CONV_GROUPED = 24,/* float32.  `weights` (16-byte aligned): G images in CONV's layout for Cg -> Cog, one after
+                                another, [kh * kw][Cg rounded up to 16][Cog rounded up to 32], zeros beyond; image g
+                                holds filter rows [g * Cog, (g + 1) * Cog).  scale / shift may be NULL, as for CONV, and
+                                are indexed by the absolute output channel.  The output channels of group g are, bit
+                                for bit, what CONV computes from the view of input channels [g * Cg, (g + 1) * Cg)
+                                with image g: the same K walk -- tap x chunk of 16 of the group's own channels x pair
+                                -- and the same chain wherever the pixel, the sample or the group lands */
+  CPX_GRAPH_CONV_Q8_GROUPED = 25 /* hybrid.  in1: the QUANT_PARAMS tensor of in0, taken over the WHOLE view with all its
+                                groups: the input tensor is quantised once per sample, before the groups are walked
+                                (as the TFLite runtime's published hybrid kernels do; taken from their text, not
+                                verified against the runtime).  `weights` as bytes: G images in CONV_Q8's fragment
+                                layout for Cg -> Cog (without their wsum), then int32 wsum[G][Cog rounded up to 32].
+                                q, acc and out are exactly CONV_Q8's with K = kh * kw * Cg.  scale, shift: [out C],
+                                indexed by the absolute output channel, not NULL */
 };
 /* The fp16x2 arithmetic, per sample.  RANGE: m = max |x| over the view in float32.  m == 0 or m not finite (inf, NaN):
  * up = down = 1.  Otherwise m = f * 2^e with f in [0.5, 1) (frexp), k = min(15 - e, 100), up = 2^k, down = 2^-k: both
@@ -928,7 +945,7 @@ typedef struct cpx_graph_op {
   int32_t pad_top, pad_left, pad_bottom, pad_right;
   int32_t activation;
   int32_t out_c_offset, out_c_stride; /* where the output goes: the channel slice of tensors[out] */
-  int32_t n_map, channel_map[4];
+  int32_t n_map, channel_map[4]; /* CONV_GROUPED / CONV_Q8_GROUPED: n_map = the number of groups, channel_map unused */
   float param;
   const float* weights; /* device pointers, owned by the caller, alive as long as the graph (the Q8 kinds: bytes) */
   const float* scale;

@@ -61,7 +61,16 @@ convolution: the yardstick) and with conv_math="fp16x2" (two fp16 planes per ope
 view), both in the same process on the same input, in --rounds alternating rounds: the median over the rounds and their
 scatter.  With --skip-torch the fp16x2 plan alone runs (a run under a profiler); --kernel-trace with --conv-math fp16x2
 splits such a trace by kind, RANGE and the new kernel included, and gives the fp16x2 convolutions' float32-equivalent
-TFLOP/s against the 16 / 3 x 157.3 roof and RANGE's bytes per second against the HBM peak."""
+TFLOP/s against the 16 / 3 x 157.3 roof and RANGE's bytes per second against the HBM peak.
+
+    python tools/bench_tflite.py --wrresnet [--batches 1,8,128]
+
+times the WR-ResNet-22-4 (tests/tflite_build.py: wrresnet, every convolution groups = 2; 160 x 160 x 2) four ways on one
+card in one process: its dynamic-range quantised file on the graph executor (CONV_Q8_GROUPED: TFLite's hybrid arithmetic,
+what get_interpreter runs by default), the float32 file on the graph executor (CONV_GROUPED), the fused kernels in their
+default math (WRResNetDevice: what CPX_TFLITE_QUANT_MATH=float and a float32 file run) and PyTorch-ROCm float32
+(conv2d(groups=2), reduced-precision paths off).  Prints launches per forward and ms per forward (HIP events, median) for
+each; the launches of the last two are counted by torch.profiler over one forward (null where it cannot)."""
 import argparse
 import json
 import os
@@ -73,7 +82,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (os.path.join(REPO, "classifier-pipeline_amd"), os.path.join(REPO, "tests")):
     sys.path.insert(0, p)
 
-KIND_NAMES = {1: "conv", 2: "max_pool", 3: "avg_pool", 4: "add", 5: "affine", 6: "mean", 7: "fc", 8: "logistic", 9: "softmax",
+KIND_NAMES = {24: "conv_grouped", 25: "conv_q8_grouped", 1: "conv", 2: "max_pool", 3: "avg_pool", 4: "add", 5: "affine", 6: "mean", 7: "fc", 8: "logistic", 9: "softmax",
               10: "pad", 11: "channel_map", 12: "conv_q8", 13: "fc_q8", 14: "quant_params", 15: "dwconv", 16: "dwconv_q8", 17: "mul", 18: "input", 19: "conv_pre",
               20: "slice", 21: "dwconv_pre", 22: "range", 23: "conv_f16x2"}
 CONV_KINDS = (1, 12, 19, 23)
@@ -108,7 +117,8 @@ def torch_model(g, device):
                 if pt or pb or pl or pr:
                     a = F.pad(a, (pl, pr, pt, pb))
                 bias = const[ins[2]] if len(ins) > 2 and ins[2] >= 0 else None
-                r = _act(F.conv2d(a, wts[ins[1]], bias, stride=(op["stride_h"], op["stride_w"])), op["act"])
+                r = _act(F.conv2d(a, wts[ins[1]], bias, stride=(op["stride_h"], op["stride_w"]),
+                                  groups=a.shape[1] // wts[ins[1]].shape[1]), op["act"])
             elif name == "DEPTHWISE_CONV_2D":
                 w = dw_wts[ins[1]]
                 pt, pb = _pads(a.shape[2], w.shape[2], op["stride_h"], op["padding"])
@@ -173,6 +183,84 @@ F32_MFMA_PEAK_TFLOPS = 157.3
 # three fp16 plane products per float32 product on a pipe 16 times as fast as v_mfma_f32_32x32x2_f32
 F16X2_ROOF_TFLOPS = F32_MFMA_PEAK_TFLOPS * 16.0 / 3.0
 I8_MFMA_PEAK_TOPS = 5000.0   # 2 x the ~2.5 PFLOP/s dense BF16 peak: the i8 forms have twice the K in the same cycles
+
+
+def count_launches(torch, fn):
+    """Kernels one call of fn launches, by torch.profiler's device events; None where the profiler sees none."""
+    try:
+        from torch.profiler import ProfilerActivity, profile
+
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        n = sum(1 for e in prof.events() if str(getattr(e, "device_type", "")).endswith("CUDA") and "memcpy" not in e.name.lower()
+                and "memset" not in e.name.lower())
+        return n or None
+    except Exception:   # (a profiler that cannot start is no reason to lose the timings)
+        return None
+
+
+def wrresnet_leg(args):
+    """The WR-ResNet-22-4 four ways: hybrid and float32 on the graph executor, the fused kernels, PyTorch-ROCm float32."""
+    import ctypes as C
+
+    import tflite_build as tb
+    import tflite_build_q8 as tq
+    import torch
+    from cpx import _lib
+    from cpx.engine import TrackEngine
+    from cpx.ml_tools import wrresnet as wr
+    from cpx.ml_tools.tflite_graph import GraphDevice, build_plan
+    from cpx.ml_tools.tflite_reader import Graph
+
+    torch.backends.cudnn.allow_tf32 = False
+    torch.backends.cuda.matmul.allow_tf32 = False
+    eng = TrackEngine(model="lepton3", device=0)
+    # BatchNorm statistics fitted to the kind of input that is timed: activations of ordinary size, nothing leaves fp16's range
+    xcal = torch.from_numpy(np.random.default_rng(1).uniform(0, 255, size=(2, 160, 160, 2)).astype(np.float32)).to(eng.device)
+    w = wr.calibrate_bn_device(eng, wr.random_weights(17, seed=3), xcal)
+    blob = tb.wrresnet(w)
+    g = Graph(blob)
+    plans = {"hybrid_graph": build_plan(Graph(tq.quantise(blob)), grouped_convolutions=True, **FOLDS),
+             "float32_graph": build_plan(g, grouped_convolutions=True, **FOLDS)}
+    stream = torch.cuda.ExternalStream(eng.lib.cpx_stream(eng.h), device=eng.device)
+    net = wr.WRResNetDevice(eng, w, 17)
+    ref = torch_model(g, eng.device)
+    out = {"model": "wr-resnet-22-4 groups 2 160x160x2", "batches": [],
+           "launches": {k: len(p.ops) for k, p in plans.items()},
+           "launches_by_kind": {k: {KIND_NAMES[kind]: sum(o.kind == kind for o in p.ops) for kind in sorted(set(o.kind for o in p.ops))}
+                                for k, p in plans.items()}}
+    assert sum(o.kind == _lib.GRAPH_CONV_Q8_GROUPED for o in plans["hybrid_graph"].ops) == 20
+    rng = np.random.default_rng(0)
+    for n in [int(v) for v in args.batches.split(",")]:
+        x = torch.from_numpy(rng.uniform(0, 255, size=(n, 160, 160, 2)).astype(np.float32)).to(eng.device)
+        y = torch.empty((n, 17), dtype=torch.float32, device=eng.device)
+        logits, probs = torch.empty_like(y), torch.empty_like(y)
+        x_nchw = x.permute(0, 3, 1, 2).contiguous()
+        rec = {"N": n}
+        for name, plan in plans.items():
+            dev = GraphDevice(eng, plan)
+
+            def forward():
+                rc = eng.lib.cpx_graph_forward(dev._graph, C.c_void_p(x.data_ptr()), n, C.c_void_p(y.data_ptr()))
+                assert rc == 0, eng._err()
+
+            with torch.cuda.stream(stream):
+                rec[name + "_ms"] = timed(torch, forward, args.steps, args.warmup)
+            dev.close()
+        with torch.cuda.stream(stream):
+            rec["fused_ms"] = timed(torch, lambda: net.forward_async(x, logits, probs), args.steps, args.warmup)
+            if "fused" not in out["launches"]:
+                out["launches"]["fused"] = count_launches(torch, lambda: net.forward_async(x, logits, probs))
+        with torch.no_grad():
+            rec["torch_ms"] = timed(torch, lambda: ref(x_nchw), args.steps, args.warmup)
+            if "torch" not in out["launches"]:
+                out["launches"]["torch"] = count_launches(torch, lambda: ref(x_nchw))
+        out["batches"].append(rec)
+    net.close()
+    eng.close()
+    print(json.dumps(out))
 
 
 def quantised_leg(args):
@@ -735,8 +823,14 @@ def main():
     ap.add_argument("--conv-math", default="f32", choices=("f32", "fp16x2"),
                     help="fp16x2: time the network (default Inception-v3; --mobilenet, --efficientnet, --densenet) with both "
                          "convolution maths in the same process; with --kernel-trace: split a trace of the fp16x2 plan")
+    ap.add_argument("--wrresnet", action="store_true",
+                    help="the WR-ResNet-22-4 (grouped convolutions): hybrid and float32 on the graph executor, the fused kernels, PyTorch-ROCm")
     ap.add_argument("--rounds", type=int, default=3, help="with --conv-math fp16x2: alternating rounds per batch size (median, scatter)")
     args = ap.parse_args()
+    if args.wrresnet:
+        if args.batches == "1,8,32,128":
+            args.batches = "1,8,128"
+        return wrresnet_leg(args)
     if args.conv_math == "fp16x2":
         if (args.mobilenet or args.efficientnet or args.densenet) and args.batches == "1,8,32,128":
             args.batches = "1,128"

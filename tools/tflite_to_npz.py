@@ -4,6 +4,13 @@ flatbuffer is parsed here, TensorFlow is not needed (only NumPy).
 
     python tools/tflite_to_npz.py model.tflite /tmp/wr [--sidecar model.json]
     python tools/tflite_to_npz.py --describe model.tflite
+    python tools/tflite_to_npz.py --dequantise quantised.tflite /tmp/wr
+
+--dequantise writes the .npz of a dynamic-range quantised WR-ResNet (what the reference's converter writes,
+src/tfliteconverter.py:54-62): every INT8 filter multiplied out, float32(int8) * scale -- the float32 network the file
+stands for, which the fused kernels run (CPX_TFLITE_QUANT_MATH=float does the same on load).  Without it such a file is
+refused by the name of its first INT8 tensor.  --describe plans a grouped CONV_2D as LiteInterpreter does
+(grouped_convolutions=True) and prints each grouped convolution's G, the hybrid ones marked and counted in the census.
 
 --describe converts nothing: it prints the operator census, the input and output shapes, the arena bytes per sample and,
 for a dynamic-range quantised file, the number of hybrid operators with the int8 against the float32 weight bytes of ANY graph the device executor runs (cpx/ml_tools/tflite_graph.py: an Inception-v3, a MobileNetV2 or an EfficientNet, say; the launches carry what was folded into them: CONV_2D+SWISH, CONV_2D+LOGISTIC, CONV_2D+MUL+ADD, AFFINE>CONV_2D for a folded pre-activation; a second line gives the launches with the window folds on, as LiteInterpreter runs the file: PAD>DEPTHWISE_CONV_2D, RELU>DEPTHWISE_CONV_2D, PAD>STRIDED_SLICE>AVERAGE_POOL_2D), or the refusal -- the
@@ -59,8 +66,8 @@ def describe(g, sidecar=None, conv_math="f32"):
     print("operators: " + ", ".join("%s: %d" % kv for kv in sorted(census.items())))
     try:
         # every PAD, 1 x 1 pool and slice a launch (CPX_TFLITE_FOLD_WINDOWS=0), and what LiteInterpreter runs
-        unfolded = build_plan(g, fuse_preactivation=True)
-        plan = build_plan(g, fuse_preactivation=True, fuse_preactivation_dw=True, fold_windows=True)
+        unfolded = build_plan(g, fuse_preactivation=True, grouped_convolutions=True)
+        plan = build_plan(g, fuse_preactivation=True, fuse_preactivation_dw=True, fold_windows=True, grouped_convolutions=True)
     except NotImplementedError as e:
         print("refused: %s" % e)
         return 1
@@ -68,8 +75,12 @@ def describe(g, sidecar=None, conv_math="f32"):
     print("launches: " + ", ".join("%s: %d" % kv for kv in sorted(unfolded.census().items())))
     print("folded launches (%d of %d): " % (len(plan.ops), len(unfolded.ops)) + ", ".join("%s: %d" % kv for kv in sorted(plan.census().items())))
     print("arena bytes per sample: %d (unfolded: %d)" % (plan.arena_bytes_per_sample, unfolded.arena_bytes_per_sample))
-    from cpx.ml_tools.tflite_graph import Q8_KINDS
+    from cpx.ml_tools.tflite_graph import GROUPED_KINDS, Q8_KINDS
 
+    grouped = [o for o in plan.ops if o.kind in GROUPED_KINDS]
+    if grouped:
+        print("grouped convolutions: %d (%d hybrid): " % (len(grouped), sum(o.kind in Q8_KINDS for o in grouped))
+              + ", ".join("operator %d: G = %d%s" % (o.source, o.groups, " (hybrid)" if o.kind in Q8_KINDS else "") for o in grouped))
     hybrid = [o for o in plan.ops if o.kind in Q8_KINDS]
     q8 = sum(int(np.prod(o.filter.shape)) for o in hybrid)
     f32 = sum(4 * int(np.prod((o.filter if getattr(o, "filter", None) is not None else o.weights).shape)) for o in plan.ops
@@ -80,8 +91,8 @@ def describe(g, sidecar=None, conv_math="f32"):
         # what CPX_TFLITE_CONV_MATH=fp16x2 makes of the file, with LiteInterpreter's default folds
         from cpx import _lib
 
-        base = build_plan(g, fuse_preactivation=True, fold_windows=True)
-        h2 = build_plan(g, fuse_preactivation=True, fold_windows=True, conv_math=conv_math)
+        base = build_plan(g, fuse_preactivation=True, fold_windows=True, grouped_convolutions=True)
+        h2 = build_plan(g, fuse_preactivation=True, fold_windows=True, conv_math=conv_math, grouped_convolutions=True)
         n_h2 = sum(o.kind == _lib.GRAPH_CONV_F16X2 for o in h2.ops)
         n_range = sum(o.kind == _lib.GRAPH_RANGE for o in h2.ops)
         n_pre = sum(o.kind == _lib.GRAPH_CONV_PRE for o in base.ops)
@@ -108,6 +119,8 @@ def main():
     ap.add_argument("--sidecar", default=None, help="the model's JSON sidecar (default: <model>.json next to it)")
     ap.add_argument("--conv-math", default="f32", choices=("f32", "fp16x2"),
                     help="with --describe: also print how many convolutions go fp16x2 and how many RANGE launches that adds")
+    ap.add_argument("--dequantise", action="store_true",
+                    help="convert a dynamic-range quantised WR-ResNet: the INT8 filters multiplied out by their scales")
     args = ap.parse_args()
     with open(args.model, "rb") as fh:
         g = Graph(fh.read())
@@ -115,7 +128,7 @@ def main():
         return describe(g, args.sidecar or os.path.splitext(args.model)[0] + ".json", conv_math=args.conv_math)
     if args.out_base is None:
         ap.error("out_base is required unless --describe is given")
-    weights = convert(g)
+    weights = convert(g, quantised_math="float" if args.dequantise else None)
     np.savez(args.out_base + ".npz", **weights)
     sidecar = args.sidecar or os.path.splitext(args.model)[0] + ".json"
     if os.path.exists(sidecar):
