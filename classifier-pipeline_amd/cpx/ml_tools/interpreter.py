@@ -389,44 +389,36 @@ class LiteInterpreter(Interpreter):
     DEFAULT_FUSE_PREACT_DW = "0"
     INPUT_MODE_OF = {"resnet": "caffe", "resnet152": "caffe", "vgg16": "caffe", "vgg19": "caffe", "densenet121": "torch"}
 
+    @staticmethod
+    def _env_choice(name, default, allowed):
+        mode = os.environ.get(name, default)
+        if mode not in allowed:
+            raise ValueError("%s=%r: one of %s" % (name, mode, ", ".join(allowed)))
+        return mode
+
     @classmethod
     def quant_math(cls):
         from .tflite_graph import QUANT_MATHS
 
-        mode = os.environ.get("CPX_TFLITE_QUANT_MATH", cls.DEFAULT_QUANT_MATH)
-        if mode not in QUANT_MATHS:
-            raise ValueError("CPX_TFLITE_QUANT_MATH=%r: one of %s" % (mode, ", ".join(QUANT_MATHS)))
-        return mode
+        return cls._env_choice("CPX_TFLITE_QUANT_MATH", cls.DEFAULT_QUANT_MATH, QUANT_MATHS)
 
     @classmethod
     def conv_math(cls):
         from .tflite_graph import CONV_MATHS
 
-        mode = os.environ.get("CPX_TFLITE_CONV_MATH", cls.DEFAULT_CONV_MATH)
-        if mode not in CONV_MATHS:
-            raise ValueError("CPX_TFLITE_CONV_MATH=%r: one of %s" % (mode, ", ".join(CONV_MATHS)))
-        return mode
+        return cls._env_choice("CPX_TFLITE_CONV_MATH", cls.DEFAULT_CONV_MATH, CONV_MATHS)
 
     @classmethod
     def fuse_preact(cls):
-        mode = os.environ.get("CPX_TFLITE_FUSE_PREACT", cls.DEFAULT_FUSE_PREACT)
-        if mode not in ("0", "1"):
-            raise ValueError("CPX_TFLITE_FUSE_PREACT=%r: one of 0, 1" % mode)
-        return mode == "1"
+        return cls._env_choice("CPX_TFLITE_FUSE_PREACT", cls.DEFAULT_FUSE_PREACT, ("0", "1")) == "1"
 
     @classmethod
     def fuse_preact_dw(cls):
-        mode = os.environ.get("CPX_TFLITE_FUSE_PREACT_DW", cls.DEFAULT_FUSE_PREACT_DW)
-        if mode not in ("0", "1"):
-            raise ValueError("CPX_TFLITE_FUSE_PREACT_DW=%r: one of 0, 1" % mode)
-        return mode == "1"
+        return cls._env_choice("CPX_TFLITE_FUSE_PREACT_DW", cls.DEFAULT_FUSE_PREACT_DW, ("0", "1")) == "1"
 
     @classmethod
     def fold_windows(cls):
-        mode = os.environ.get("CPX_TFLITE_FOLD_WINDOWS", cls.DEFAULT_FOLD_WINDOWS)
-        if mode not in ("0", "1"):
-            raise ValueError("CPX_TFLITE_FOLD_WINDOWS=%r: one of 0, 1" % mode)
-        return mode == "1"
+        return cls._env_choice("CPX_TFLITE_FOLD_WINDOWS", cls.DEFAULT_FOLD_WINDOWS, ("0", "1")) == "1"
 
     def get_preprocess_fn(self):
         """The base class's, and the 'caffe' / 'torch' families it refuses: the host statement of what the graph's INPUT
@@ -457,10 +449,11 @@ class LiteInterpreter(Interpreter):
         self._fuse_preact = self.fuse_preact()
         self._fold_windows = self.fold_windows()
         self._fuse_preact_dw = self.fuse_preact_dw() and self._fuse_preact
+        self._plan_options = dict(quantised_math=self._quant_math, fuse_preactivation=self._fuse_preact,
+                                  fuse_preactivation_dw=self._fuse_preact_dw, fold_windows=self._fold_windows,
+                                  conv_math=self._conv_math, grouped_convolutions=True)
         # refuses, by operator, what the executor does not run
-        plan = build_plan(self._graph, quantised_math=self._quant_math, fuse_preactivation=self._fuse_preact,
-                          fuse_preactivation_dw=self._fuse_preact_dw, fold_windows=self._fold_windows,
-                          conv_math=self._conv_math, grouped_convolutions=True)
+        plan = build_plan(self._graph, **self._plan_options)
         self._plans[(plan.graph_input_shape, None)] = plan
         if self.input_mode is not None and plan.graph_input_shape[2] != 3:
             raise NotImplementedError("model_name %r: the %r input mode subtracts the means of three colour channels; the "
@@ -518,10 +511,7 @@ class LiteInterpreter(Interpreter):
         plan = self._plans.get(key)
         if plan is None:
             plan = self._plans[key] = build_plan(self._graph, input_shape=key[0], channel_map=cmap,
-                                                 quantised_math=self._quant_math, fuse_preactivation=self._fuse_preact,
-                                                 fuse_preactivation_dw=self._fuse_preact_dw, fold_windows=self._fold_windows,
-                                                 input_mode=None if cmap is None else self.input_mode,
-                                                 conv_math=self._conv_math, grouped_convolutions=True)
+                                                 input_mode=None if cmap is None else self.input_mode, **self._plan_options)
         return key, plan
 
     def _device(self, engine, hwc):
