@@ -111,7 +111,7 @@ class HeadDesc(C.Structure):  # struct cpx_head_desc
 
 class GraphTensor(C.Structure):  # struct cpx_graph_tensor
     _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("c_offset", C.c_int32), ("c_stride", C.c_int32),
-                ("reserved", C.c_int32), ("arena_offset", C.c_int64)]
+                ("type", C.c_int32), ("arena_offset", C.c_int64)]
 
 
 class GraphOp(C.Structure):  # struct cpx_graph_op
@@ -130,6 +130,13 @@ GRAPH_CONV, GRAPH_MAX_POOL, GRAPH_AVG_POOL, GRAPH_ADD, GRAPH_AFFINE, GRAPH_MEAN,
     GRAPH_PAD, GRAPH_CHANNEL_MAP, GRAPH_CONV_Q8, GRAPH_FC_Q8, GRAPH_QUANT_PARAMS, GRAPH_DWCONV, GRAPH_DWCONV_Q8, GRAPH_MUL, \
     GRAPH_INPUT, GRAPH_CONV_PRE, GRAPH_SLICE, GRAPH_DWCONV_PRE, GRAPH_RANGE, GRAPH_CONV_F16X2, GRAPH_CONV_GROUPED, \
     GRAPH_CONV_Q8_GROUPED = range(1, 26)
+# the full-integer operators (int8 activations); enum CPX_GRAPH_TYPE_* and CPX_GRAPH_I8_HDR_*
+GRAPH_QUANTIZE, GRAPH_DEQUANTIZE, GRAPH_CONV_I8, GRAPH_CONV_I8_GROUPED, GRAPH_DWCONV_I8, GRAPH_FC_I8, GRAPH_ADD_I8, \
+    GRAPH_MUL_I8, GRAPH_MAX_POOL_I8, GRAPH_AVG_POOL_I8, GRAPH_MEAN_I8 = range(26, 37)
+GRAPH_TYPE_FLOAT32, GRAPH_TYPE_INT8 = 0, 1
+GRAPH_I8_HDR_Z_IN, GRAPH_I8_HDR_Z_IN1, GRAPH_I8_HDR_Z_OUT, GRAPH_I8_HDR_LO, GRAPH_I8_HDR_HI, GRAPH_I8_HDR_M0, GRAPH_I8_HDR_S0, \
+    GRAPH_I8_HDR_M1, GRAPH_I8_HDR_S1, GRAPH_I8_HDR_MO, GRAPH_I8_HDR_SO, GRAPH_I8_HDR_LEFT = range(12)
+GRAPH_I8_HDR_WORDS = 16
 # enum CPX_GRAPH_ACT_*: the planner's own activation codes, outside TFLite's ActivationFunctionType
 GRAPH_ACT_SWISH, GRAPH_ACT_LOGISTIC = 16, 17
 GRAPH_MEAN_WIDE_PIXELS = 256   # MEAN: from this many pixels on the striped summation order (csrc/cpx_graph_core.h)

@@ -379,7 +379,10 @@ class LiteInterpreter(Interpreter):
     launch, a PAD folded into the VALID convolution behind it (build_plan: fold_windows), or every one of them a launch --
     again the same bits.
     A grouped CONV_2D runs here as well (build_plan: grouped_convolutions=True, always): the WR-ResNet-22-4's own file,
-    float32 or dynamic-range quantised -- get_interpreter sends the quantised one here."""
+    float32 or dynamic-range quantised -- get_interpreter sends the quantised one here.
+    A full-integer file (INT8 activations between a QUANTIZE and a DEQUANTIZE: a converter given a representative dataset)
+    runs here too (build_plan: integer_activations=True, always): float32 in and out, as the reference feeds it, the
+    interior on the int8 operators with the TFLite reference integer kernels' arithmetic (include/cpx.h)."""
 
     TYPE = "TFLite"
     DEFAULT_QUANT_MATH = "hybrid"
@@ -451,7 +454,7 @@ class LiteInterpreter(Interpreter):
         self._fuse_preact_dw = self.fuse_preact_dw() and self._fuse_preact
         self._plan_options = dict(quantised_math=self._quant_math, fuse_preactivation=self._fuse_preact,
                                   fuse_preactivation_dw=self._fuse_preact_dw, fold_windows=self._fold_windows,
-                                  conv_math=self._conv_math, grouped_convolutions=True)
+                                  conv_math=self._conv_math, grouped_convolutions=True, integer_activations=True)
         # refuses, by operator, what the executor does not run
         plan = build_plan(self._graph, **self._plan_options)
         self._plans[(plan.graph_input_shape, None)] = plan

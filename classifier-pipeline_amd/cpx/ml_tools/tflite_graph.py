@@ -15,6 +15,9 @@ these passes over one _Build, in this order, each described where it stands:
   place_arena          offsets by lifetime
   pack_weights         each kind's weight image
 
+With integer_activations=True lower_ops hands every operator that touches an INT8 activation to tflite_graph_i8 (the int8
+kinds; float32 stays at the graph's two ends), annotate_types marks the int8 tensors and place_arena counts them in bytes.
+
 What an operator kind takes part in is one row of KINDS.  GraphDevice uploads a plan's constants to an engine's device and
 runs it."""
 import collections
@@ -23,7 +26,8 @@ import ctypes as C
 import numpy as np
 
 from .. import _lib
-from .tflite_reader import ACT_NONE, ACT_RELU, ACT_RELU6, FILTER_OPS, PADDING_SAME, SLICE_OPS, resolve_slice
+from . import tflite_graph_i8
+from .tflite_reader import ACT_NONE, ACT_RELU, ACT_RELU6, FILTER_OPS, INTEGER_OPS, PADDING_SAME, SLICE_OPS, resolve_slice
 
 ALIGN = 64   # floats: every tensor of the arena starts on a 256-byte boundary
 
@@ -63,6 +67,8 @@ class PlanTensor:
         self.external = False   # the caller's buffer (the plan's input and output), not the arena
         self.alias = False      # a RESHAPE's view of its input
         self.src_shape = None   # of such a view: its input's (H, W, C)
+        self.dtype = "float32"  # or "int8": an activation of a full-integer graph, with its scale and zero point
+        self.scale = self.zero_point = None
         _set_fields(self, kw)
 
 
@@ -153,6 +159,12 @@ KINDS = {
     _lib.GRAPH_FC: Kind(pack=lambda o: np.ascontiguousarray(o.filter, np.float32)),
     _lib.GRAPH_FC_Q8: Kind(hybrid=True, pack=lambda o: pack_fc_filter_q8(o.filter), scaled=True),
     _lib.GRAPH_QUANT_PARAMS: Kind(params=True), _lib.GRAPH_RANGE: Kind(params=True),
+    # the full-integer kinds (tflite_graph_i8): the hybrid kinds' filter images unchanged; their integers ride in `scale`
+    # and `shift`, which the lowering has already made.  A same-parameter PAD folds into the two that take explicit pads
+    _lib.GRAPH_CONV_I8: Kind(pad=True, pack=lambda o: pack_conv_filter_q8(o.filter)),
+    _lib.GRAPH_CONV_I8_GROUPED: Kind(grouped=True, pack=lambda o: pack_conv_filter_q8_grouped(o.filter, o.groups)),
+    _lib.GRAPH_DWCONV_I8: Kind(pad=True, pack=lambda o: pack_dw_filter_q8(o.filter)),
+    _lib.GRAPH_FC_I8: Kind(pack=lambda o: pack_fc_filter_q8(o.filter)),
 }
 
 
@@ -165,6 +177,7 @@ def _kinds(column):
 
 
 Q8_KINDS, GROUPED_KINDS, PARAM_KINDS = _kinds("hybrid"), _kinds("grouped"), _kinds("params")
+I8_FILTER_KINDS = (_lib.GRAPH_CONV_I8, _lib.GRAPH_CONV_I8_GROUPED, _lib.GRAPH_DWCONV_I8, _lib.GRAPH_FC_I8)
 FOLD_INTO, LOGISTIC_INTO = _kinds("folds"), _kinds("logistic")
 
 QUANT_MATHS = ("hybrid", "float")
@@ -211,7 +224,7 @@ class _Build:
 
 def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_math="hybrid", fuse_activations=True,
                input_mode=None, fuse_preactivation=False, fold_windows=False, fuse_preactivation_dw=False, conv_math="f32",
-               grouped_convolutions=False):
+               grouped_convolutions=False, integer_activations=False):
     """g: tflite_reader.Graph.  input_shape: (H, W, C) of a sample, default: the flatbuffer's.  output: the tensor the
     forward hands out, default the graph's output; the operators it does not need are dropped.  channel_map: up to 4
     indices into the channels of the sample the CALLER brings ([N, H, W, max(map) + 1 or more]): the graph's input
@@ -226,14 +239,17 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
     SLICEs; both keep every bit (fold_window_chains, fuse_preactivations).  conv_math: "f32" runs float32 convolutions on
     the exact float32 kernel, "fp16x2" as two fp16 planes on the fp16 matrix pipe behind one RANGE launch per input view; a
     pre-activation is then not folded into them (no CONV_PRE is planned: the AFFINE stays a launch).  grouped_convolutions:
-    False refuses a grouped CONV_2D by name, True plans it as CONV_GROUPED / CONV_Q8_GROUPED (_lower_filter)."""
+    False refuses a grouped CONV_2D by name, True plans it as CONV_GROUPED / CONV_Q8_GROUPED (_lower_filter).
+    integer_activations: False refuses a full-integer file (INT8 activations, QUANTIZE / DEQUANTIZE) as ever, True plans its
+    interior on the int8 kinds (tflite_graph_i8: float32 stays at the two ends; a float32 operator behind a DEQUANTIZE is
+    the existing kind)."""
     if quantised_math not in QUANT_MATHS:
         raise ValueError("quantised_math %r: one of %s" % (quantised_math, ", ".join(QUANT_MATHS)))
     if conv_math not in CONV_MATHS:
         raise ValueError("conv_math %r: one of %s" % (conv_math, ", ".join(CONV_MATHS)))
     if input_mode is not None and input_mode not in INPUT_MODES:
         raise ValueError("input_mode %r: one of %s" % (input_mode, ", ".join(sorted(INPUT_MODES))))
-    g.check_executable(grouped=grouped_convolutions)
+    g.check_executable(grouped=grouped_convolutions, integer=integer_activations)
     if len(g.inputs) != 1 or len(g.outputs) < 1:
         raise NotImplementedError("graphs with %d inputs" % len(g.inputs))
     gin = g.inputs[0]
@@ -243,12 +259,16 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
         raise NotImplementedError("operator 0: the input has the dynamic shape %s: pass input_shape" % (list(input_shape),))
     s = _Build(g, gin, g.outputs[0] if output is None else int(output))
     s.T[gin] = PlanTensor(gin, *[int(v) for v in input_shape])
-    lower_ops(s, quantised_math, fuse_activations, conv_math, grouped_convolutions)
+    lower_ops(s, quantised_math, fuse_activations, conv_math, grouped_convolutions, integer_activations)
+    if integer_activations:
+        tflite_graph_i8.annotate_types(s)
     resolve_views(s)
     attach_input(s, channel_map, input_mode)
     prune_to_output(s)
     if fold_windows:
         fold_window_chains(s)
+    if integer_activations:
+        tflite_graph_i8.finish_pads(s)
     if fuse_preactivation or fuse_preactivation_dw:
         fuse_preactivations(s, fuse_preactivation, fuse_preactivation_dw)
     check_used_tensors(s)
@@ -425,7 +445,7 @@ def _affine_of(name, c, const_first, what):
     return (-one, c) if const_first else (one, -c)   # c - x; x - c
 
 
-def lower_ops(s, quantised_math, fuse_activations, conv_math, grouped_convolutions):
+def lower_ops(s, quantised_math, fuse_activations, conv_math, grouped_convolutions, integer_activations=False):
     """Every operator of the flatbuffer, in its order, as PlanOps on tensors of inferred shape ([H, W, C] of one sample,
     TensorFlow's SAME / VALID arithmetic):
     * MUL / ADD / SUB / DIV by a per-channel constant behind one of FOLD_INTO (a convolution, or another such operator)
@@ -471,6 +491,9 @@ def lower_ops(s, quantised_math, fuse_activations, conv_math, grouped_convolutio
         x = T[act_ins[0]] if act_ins else None
         if op.get("act", 0) not in (ACT_NONE, ACT_RELU, ACT_RELU6):
             raise NotImplementedError("%s: fused activation %d" % (what, op["act"]))
+        int8 = integer_activations and (name in INTEGER_OPS or any(tflite_graph_i8.is_int8(g, t) for t in act_ins + [y]))
+        if int8 and tflite_graph_i8.lower_integer_op(s, i, op, what, x, y, ins, act_ins, grouped_convolutions):
+            continue
         if name in ("CONV_2D", "DEPTHWISE_CONV_2D"):
             _lower_filter(s, i, op, what, x, y, ins, quantised_math, conv_math, grouped_convolutions)
         elif name in ("MAX_POOL_2D", "AVERAGE_POOL_2D"):
@@ -530,7 +553,11 @@ def lower_ops(s, quantised_math, fuse_activations, conv_math, grouped_convolutio
                 if must_copy:
                     # a slice of the output that an AFFINE operator without constants fills
                     T[(y, off)] = PlanTensor((y, off), x.H, x.W, p.C, root=y, c_offset=off)
-                    s.emit(PlanOp(_lib.GRAPH_AFFINE, "COPY", p.id, (y, off), copy=True), i)
+                    if int8:   # bytes: a SLICE that takes everything
+                        s.emit(PlanOp(_lib.GRAPH_SLICE, "COPY", p.id, (y, off), copy=True,
+                                      shift=tflite_graph_i8.header(z_in=tflite_graph_i8.qparams(g, y)[1])), i)
+                    else:
+                        s.emit(PlanOp(_lib.GRAPH_AFFINE, "COPY", p.id, (y, off), copy=True), i)
                     del s.producer[(y, off)]
                 else:
                     p.root, p.c_offset = y, off
@@ -819,7 +846,9 @@ def place_arena(s):
             life[st] = (min(a, k), max(b, k))
     plan.lifetimes = life
     external = {plan.input, plan.out_storage}
-    sizes = {k: -(-(T[k].H * T[k].W * T[k].C) // ALIGN) * ALIGN for k in life if k not in external}
+    # (floats per sample; an int8 tensor: its bytes rounded up to floats)
+    extent = {k: -(-(T[k].H * T[k].W * T[k].C) // 4) if T[k].dtype == "int8" else T[k].H * T[k].W * T[k].C for k in life}
+    sizes = {k: -(-extent[k] // ALIGN) * ALIGN for k in life if k not in external}
     placed = []   # (offset, size, first, last)
     offsets = {}
     for k in sorted(sizes, key=lambda k: (-sizes[k], life[k][0])):
@@ -832,7 +861,7 @@ def place_arena(s):
             off = max(off, o + z)
         offsets[k] = off
         placed.append((off, sizes[k], a, b))
-    plan.arena_floats = max([offsets[k] + T[k].H * T[k].W * T[k].C for k in offsets] or [0])   # (the last tensor unpadded)
+    plan.arena_floats = max([offsets[k] + extent[k] for k in offsets] or [0])   # (the last tensor unpadded)
     for t in plan.tensors.values():
         t.arena_offset = offsets.get(t.storage, 0)
         t.external = t.storage in external
@@ -1091,6 +1120,7 @@ class GraphDevice:
             p = plan.tensors[tid]
             tens[k].H, tens[k].W, tens[k].C = p.H, p.W, p.C
             tens[k].c_offset, tens[k].c_stride, tens[k].arena_offset = p.c_offset, p.c_stride, p.arena_offset
+            tens[k].type = _lib.GRAPH_TYPE_INT8 if p.dtype == "int8" else _lib.GRAPH_TYPE_FLOAT32
             if out_slice is not None and tid == plan.output:
                 tens[k].c_offset, tens[k].c_stride = out_slice
         out_id = plan.output

@@ -17,7 +17,11 @@ only NumPy.  Two users:
   everything else float32) is read too: an INT8 constant comes with its quantisation table (`quant`: scale, zero_point,
   dim), FULLY_CONNECTED with asymmetric_quantize_inputs.
   check_executable() refuses everything else by operator name and index: a depth multiplier, quantised activations,
-  UINT8 / INT16 or asymmetric filters, an INT8 constant anywhere but as such a filter, DEQUANTIZE / QUANTIZE, grouped
+  UINT8 / INT16 or asymmetric filters, an INT8 constant anywhere but as such a filter, DEQUANTIZE / QUANTIZE
+  (check_executable(integer=True) lets a full-integer graph through -- what the converter writes when it is given a
+  representative dataset: INT8 activations with one scale and one zero point, INT32 biases, INT8 constants as operands of
+  ADD / SUB / MUL, QUANTIZE / DEQUANTIZE at the two ends; cpx/ml_tools/tflite_graph_i8.py plans it.  A DEQUANTIZE of a FLOAT16
+  constant, the converter's float16 mode, is folded on load into a float32 constant either way), grouped
   CONV_2D (check_executable(grouped=True) lets one through where the filter depth divides the input depth and the groups
   divide the output channels: the graph executor's CONV_GROUPED / CONV_Q8_GROUPED), a dynamic shape, an operator outside
   the set.
@@ -42,11 +46,12 @@ import numpy as np
 BN_EPS = np.float32(1e-3)
 OPS = {0: "ADD", 1: "AVERAGE_POOL_2D", 2: "CONCATENATION", 3: "CONV_2D", 4: "DEPTHWISE_CONV_2D", 9: "FULLY_CONNECTED", 14: "LOGISTIC",
        17: "MAX_POOL_2D", 18: "MUL", 19: "RELU", 21: "RELU6", 25: "SOFTMAX", 40: "MEAN", 41: "SUB", 22: "RESHAPE", 34: "PAD",
-       42: "DIV", 45: "STRIDED_SLICE", 65: "SLICE"}
+       42: "DIV", 45: "STRIDED_SLICE", 65: "SLICE", 6: "DEQUANTIZE", 114: "QUANTIZE"}
 SLICE_OPS = ("STRIDED_SLICE", "SLICE")
+# the two ends of a full-integer graph: run with check_executable(integer=True) only, refused by name without
+INTEGER_OPS = ("DEQUANTIZE", "QUANTIZE")
 # operators that are recognised only to be refused by name (check_executable)
-REFUSED_OPS = {6: "DEQUANTIZE", 114: "QUANTIZE", 67: "TRANSPOSE_CONV", 23: "RESIZE_BILINEAR",
-               28: "TANH", 39: "TRANSPOSE", 32: "CUSTOM", 117: "HARD_SWISH"}
+REFUSED_OPS = {67: "TRANSPOSE_CONV", 23: "RESIZE_BILINEAR", 28: "TANH", 39: "TRANSPOSE", 32: "CUSTOM", 117: "HARD_SWISH"}
 TENSOR_TYPES = {0: "FLOAT32", 1: "FLOAT16", 2: "INT32", 3: "UINT8", 4: "INT64", 6: "BOOL", 7: "INT16", 9: "INT8"}
 PADDING_SAME, PADDING_VALID = 0, 1
 ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 3
@@ -136,6 +141,9 @@ class Graph:
             if raw:
                 if ttype == 0:
                     const = np.frombuffer(raw, "<f4").reshape(shape)
+                elif ttype == 1:
+                    # FLOAT16: the weights of the converter's float16 mode, each behind a DEQUANTIZE that is folded below
+                    const = np.frombuffer(raw, "<f2").reshape(shape)
                 elif ttype == 2:
                     const = np.frombuffer(raw, "<i4").reshape(shape)
                 elif ttype in (9, 3, 7):
@@ -219,6 +227,21 @@ class Graph:
                 o.setdefault("beta", 1.0)
             o["code"] = code
             self.ops.append(o)
+        self._fold_float16_constants()
+
+    def _fold_float16_constants(self):
+        """The converter's float16 mode stores every weight as a FLOAT16 constant behind a DEQUANTIZE: such an operator is
+        folded here, on load -- its output becomes the float32 constant (the conversion is exact) and the operator is gone,
+        so the graph plans as the float32 graph of the fp16-rounded weights."""
+        kept = []
+        for o in self.ops:
+            src = self.tensors[o["inputs"][0]] if o["name"] == "DEQUANTIZE" and len(o["inputs"]) == 1 and o["inputs"][0] >= 0 else None
+            if src is not None and src["type"] == 1 and src["const"] is not None and len(o["outputs"]) == 1:
+                out = self.tensors[o["outputs"][0]]
+                out["const"], out["type"] = src["const"].astype(np.float32), 0
+            else:
+                kept.append(o)
+        self.ops = kept
 
     def const(self, idx):
         return self.tensors[idx]["const"]
@@ -243,18 +266,52 @@ class Graph:
         dim = ten["quant"]["dim"] if sc.size > 1 else 0
         return (w * sc.reshape((1,) * dim + (-1,) + (1,) * (w.ndim - 1 - dim))).astype(np.float32)
 
-    def check_executable(self, grouped=False):
+    def _check_integer_tensor(self, i, name, k, t, ten, integer):
+        """check_executable(integer=True): -> True where tensor `t`, input or output k of operator i, is one a full-integer
+        graph may hold: an INT8 activation with exactly one scale and one zero point (not the graph's input or output: the
+        reference feeds and reads float32), the INT32 bias of a filter operator, an INT8 constant with one scale and one
+        zero point as an operand of ADD / SUB / MUL.  What is refused here is refused by the operator's name and index."""
+        if not integer:
+            return False
+        what, tname = "operator %d (%s)" % (i, name), TENSOR_TYPES.get(ten["type"], ten["type"])
+        if ten["const"] is None and ten["type"] in (3, 7):
+            raise NotImplementedError("%s: tensor %r is a %s activation, only INT8 activations are run" % (what, ten["name"], tname))
+        if ten["type"] == 2 and ten["const"] is not None and k == 2 and name in FILTER_OPS:
+            return True
+        if ten["type"] != 9 or (ten["const"] is not None and name not in ("ADD", "SUB", "MUL")):
+            if ten["type"] == 9 and name == "DIV":
+                raise NotImplementedError("%s: a division on INT8 tensors is not run" % what)
+            return False
+        q = ten["quant"]
+        if q is None or q["scale"].size != 1 or q["zero_point"].size != 1:
+            raise NotImplementedError("%s: tensor %r is INT8 with %d scales and %d zero points (per-channel quantised "
+                                      "activations are not run: exactly one of each)"
+                                      % (what, ten["name"], 0 if q is None else q["scale"].size, 0 if q is None else q["zero_point"].size))
+        if not -128 <= int(q["zero_point"][0]) <= 127:
+            raise NotImplementedError("%s: tensor %r has the zero point %d, outside INT8" % (what, ten["name"], q["zero_point"][0]))
+        if t in self.inputs or t in self.outputs:
+            raise NotImplementedError("%s: tensor %r, the graph's %s, is INT8: only float32 inputs and outputs are run "
+                                      "(QUANTIZE in front, DEQUANTIZE behind)" % (what, ten["name"], "input" if t in self.inputs else "output"))
+        if name == "DIV":
+            raise NotImplementedError("%s: a division on INT8 tensors is not run" % what)
+        return True
+
+    def check_executable(self, grouped=False, integer=False):
         """Raises NotImplementedError, naming the operator and its index, for whatever the graph executor
         (cpx/ml_tools/tflite_graph.py) does not run: an operator outside OPS, a STRIDED_SLICE / SLICE that resolve_slice
         refuses, a tensor that is not float32 (int32 constants of MEAN / RESHAPE / PAD / STRIDED_SLICE / SLICE excepted; an INT8 constant as the filter of CONV_2D / FULLY_CONNECTED with
         symmetric scales along dimension 0, or of DEPTHWISE_CONV_2D along dimension 3, excepted), grouped CONV_2D, a
         DEPTHWISE_CONV_2D with a depth multiplier or a dilation other than 1, a dynamic shape.  grouped=True lets a grouped
-        CONV_2D through where the filter depth divides the input depth and the groups divide the output channels."""
+        CONV_2D through where the filter depth divides the input depth and the groups divide the output channels.
+        integer=True lets a full-integer graph through (what a converter given a representative dataset writes): QUANTIZE /
+        DEQUANTIZE, INT8 activations with one scale and one zero point, INT32 biases, INT8 constants as operands of ADD /
+        SUB / MUL (_check_integer_tensor); without it every one of those is refused as ever, with the same texts."""
         for i, op in enumerate(self.ops):
             name = op["name"]
-            if op["code"] not in OPS:
+            if op["code"] not in OPS or (name in INTEGER_OPS and not integer):
                 raise NotImplementedError("operator %d (%s) is not in the set the graph executor runs: %s"
-                                          % (i, REFUSED_OPS.get(op["code"], name), ", ".join(sorted(OPS.values()))))
+                                          % (i, REFUSED_OPS.get(op["code"], name),
+                                             ", ".join(sorted(v for v in OPS.values() if v not in INTEGER_OPS))))
             if name in SLICE_OPS:
                 shape = self.tensors[op["inputs"][0]]["shape"]
                 # (a dynamic H or W: the planner resolves against the shape it plans for, and refuses there)
@@ -279,6 +336,8 @@ class Graph:
                         raise NotImplementedError("operator %d (%s): the INT8 filter %r has %d scales along dimension %d, "
                                                   "only one or one per output channel (dimension %d) are run"
                                                   % (i, name, ten["name"], q["scale"].size, q["dim"], qdim))
+                    continue
+                if self._check_integer_tensor(i, name, k, t, ten, integer):
                     continue
                 if ten["type"] != 0 and not int_const:
                     raise NotImplementedError("operator %d (%s): tensor %r has type %s, only float32 graphs are run"

@@ -36,6 +36,12 @@ static const char* graph_check_op(const cpx_graph_op& o, const std::vector<cpx_g
       o.activation != CPX_GRAPH_ACT_SWISH && o.activation != CPX_GRAPH_ACT_LOGISTIC)
     return "unknown activation";
   const bool same_hw = a.H == y.H && a.W == y.W;
+  // the element types each kind takes: float32 throughout, unless the kind says otherwise below
+  const bool a8 = a.type == CPX_GRAPH_TYPE_INT8, y8 = y.type == CPX_GRAPH_TYPE_INT8;
+  const bool b8 = o.in1 >= 0 && t[o.in1].type == CPX_GRAPH_TYPE_INT8;
+  bool types_ok = !a8 && !y8 && !b8;
+  const bool i8_header = o.kind >= CPX_GRAPH_QUANTIZE && o.kind <= CPX_GRAPH_MEAN_I8;
+  if (i8_header && (!o.shift || (reinterpret_cast<uintptr_t>(o.shift) & 3))) return "a full-integer operator without its int32 header in `shift`";
   auto is_params = [&](int id) { return id >= 0 && t[id].H == 1 && t[id].W == 1 && t[id].C == 4; };
   switch (o.kind) {
     case CPX_GRAPH_CONV:
@@ -131,8 +137,69 @@ static const char* graph_check_op(const cpx_graph_op& o, const std::vector<cpx_g
       if (hh < 0 || ww < 0 || y.H != hh / o.stride_h + 1 || y.W != ww / o.stride_w + 1) return "SLICE: output size does not follow from stride and pads";
       if (a.C != y.C) return "SLICE changes the channel count";
       if (o.param != 0.0f && o.param != 1.0f) return "SLICE: param is 0 (a copy) or 1 (-0.0 becomes +0.0)";
+      if (a8 || y8) {
+        if (!a8 || !y8 || o.in1 >= 0) return "SLICE: input and output are of one type";
+        if (o.activation != CPX_GRAPH_ACT_NONE || o.param != 0.0f) return "SLICE on int8 tensors copies bytes: no activation, param 0";
+        if (!o.shift || (reinterpret_cast<uintptr_t>(o.shift) & 3)) return "SLICE on int8 tensors needs the int32 header (the zero point) in `shift`";
+        types_ok = true;
+      }
       break;
     }
+    case CPX_GRAPH_QUANTIZE:
+      if (!same_hw || a.C != y.C || o.in1 >= 0) return "QUANTIZE keeps the shape and has one input";
+      if (!y8) return "QUANTIZE writes an int8 tensor";
+      if (!a8 && !(o.param > 0.0f)) return "QUANTIZE: param is the output's scale, above 0";
+      types_ok = true;
+      break;
+    case CPX_GRAPH_DEQUANTIZE:
+      if (!same_hw || a.C != y.C || o.in1 >= 0) return "DEQUANTIZE keeps the shape and has one input";
+      if (!a8 || y8) return "DEQUANTIZE reads an int8 tensor and writes a float32 one";
+      if (!(o.param > 0.0f)) return "DEQUANTIZE: param is the input's scale, above 0";
+      types_ok = true;
+      break;
+    case CPX_GRAPH_CONV_I8:
+    case CPX_GRAPH_CONV_I8_GROUPED:
+    case CPX_GRAPH_DWCONV_I8:
+    case CPX_GRAPH_MAX_POOL_I8:
+    case CPX_GRAPH_AVG_POOL_I8: {
+      const bool dw = o.kind == CPX_GRAPH_DWCONV_I8, grouped = o.kind == CPX_GRAPH_CONV_I8_GROUPED;
+      const bool conv = dw || grouped || o.kind == CPX_GRAPH_CONV_I8;
+      if (o.kh < 1 || o.kw < 1 || o.kh > 7 || o.kw > 7) return "kernel sides are 1 to 7";
+      const int smax = grouped ? 3 : conv ? 2 : 7;
+      if (o.stride_h < 1 || o.stride_w < 1 || o.stride_h > smax || o.stride_w > smax) return "bad stride";
+      if (o.pad_top < 0 || o.pad_left < 0 || o.pad_bottom < 0 || o.pad_right < 0 || o.pad_top >= o.kh || o.pad_bottom >= o.kh ||
+          o.pad_left >= o.kw || o.pad_right >= o.kw)
+        return "bad padding";
+      const int hh = a.H + o.pad_top + o.pad_bottom - o.kh, ww = a.W + o.pad_left + o.pad_right - o.kw;
+      if (hh < 0 || ww < 0 || y.H != hh / o.stride_h + 1 || y.W != ww / o.stride_w + 1) return "output size does not follow from kernel, stride and pads";
+      if ((!conv || dw) && a.C != y.C) return "the operator keeps the channel count";
+      if (conv && (!o.weights || !o.scale)) return "a full-integer filter operator without weights or its int32 M / shift / bias in `scale`";
+      if (conv && ((reinterpret_cast<uintptr_t>(o.weights) & 15) || (reinterpret_cast<uintptr_t>(o.scale) & 3))) return "a full-integer filter operator's weights are not 16-byte aligned";
+      if (grouped && (o.n_map < 2 || a.C % o.n_map != 0 || y.C % o.n_map != 0)) return "grouped CONV: n_map carries the number of groups, which divide the input and output channels";
+      if (!a8 || !y8 || o.in1 >= 0) return "the operator takes one int8 tensor and writes one";
+      types_ok = true;
+      break;
+    }
+    case CPX_GRAPH_FC_I8:
+      if (a.H != 1 || a.W != 1 || y.H != 1 || y.W != 1 || !o.weights || !o.scale) return "FULLY_CONNECTED takes and gives 1 x 1 x C";
+      if ((reinterpret_cast<uintptr_t>(o.weights) & 3) || (reinterpret_cast<uintptr_t>(o.scale) & 3)) return "FC_I8 weights are not 4-byte aligned";
+      if (!a8 || !y8 || o.in1 >= 0) return "the operator takes one int8 tensor and writes one";
+      types_ok = true;
+      break;
+    case CPX_GRAPH_ADD_I8:
+    case CPX_GRAPH_MUL_I8:
+      if (!same_hw || a.C != y.C) return "element-wise operator changes the shape";
+      if (o.in1 >= 0 && (t[o.in1].H != y.H || t[o.in1].W != y.W || t[o.in1].C != y.C)) return "ADD_I8 / MUL_I8 of different shapes";
+      if (o.in1 < 0 && !o.weights) return "ADD_I8 / MUL_I8 needs a second tensor or the constant in `weights`";
+      if (o.kind == CPX_GRAPH_ADD_I8 && o.param != 1.0f && o.param != -1.0f) return "ADD_I8: param is 1 (ADD) or -1 (SUB)";
+      if (!a8 || !y8 || (o.in1 >= 0 && !b8)) return "the operator takes int8 tensors and writes one";
+      types_ok = true;
+      break;
+    case CPX_GRAPH_MEAN_I8:
+      if (y.H != 1 || y.W != 1 || a.C != y.C || o.in1 >= 0) return "MEAN gives 1 x 1 x C";
+      if (!a8 || !y8) return "the operator takes one int8 tensor and writes one";
+      types_ok = true;
+      break;
     case CPX_GRAPH_INPUT:
       if (!o.shift || !(o.param > 0.0f)) return "INPUT needs a shift and a positive param";
       /* fall through */
@@ -149,6 +216,7 @@ static const char* graph_check_op(const cpx_graph_op& o, const std::vector<cpx_g
     if (!is_params(o.in1)) return "a hybrid operator needs a 1 x 1 x 4 parameter tensor as in1";
     if (!o.scale || !o.shift) return "a hybrid operator without scale or shift";
   }
+  if (!types_ok) return "a tensor's element type is not what the operator's kind takes";
   return nullptr;
 }
 
@@ -172,11 +240,14 @@ int cpx_graph_create(cpx_handle* h, const cpx_graph_op* ops, int n_ops, const cp
     // a sample is indexed in 32 bits
     if (t.H < 1 || t.W < 1 || t.C < 1 || t.c_offset < 0 || t.c_stride < t.c_offset + t.C ||
         (double)t.H * t.W * t.c_stride >= 2147483648.0 || (!ext && t.arena_offset < 0) ||
-        (i == input_tensor && (t.c_offset != 0 || t.c_stride != t.C))) {
+        (i == input_tensor && (t.c_offset != 0 || t.c_stride != t.C)) ||
+        (t.type != CPX_GRAPH_TYPE_FLOAT32 && t.type != CPX_GRAPH_TYPE_INT8) || (ext && t.type != CPX_GRAPH_TYPE_FLOAT32)) {
       delete g;
       return fail(h, CPX_ERR_INVALID, "cpx_graph_create: bad tensor");
     }
-    if (!ext) g->arena_floats = std::max(g->arena_floats, (size_t)t.arena_offset + (size_t)t.H * t.W * t.c_stride);
+    // (an int8 tensor's extent: its bytes rounded up to floats)
+    const size_t elems = (size_t)t.H * t.W * t.c_stride;
+    if (!ext) g->arena_floats = std::max(g->arena_floats, (size_t)t.arena_offset + (t.type == CPX_GRAPH_TYPE_INT8 ? (elems + 3) / 4 : elems));
   }
   for (int i = 0; i < n_ops; ++i) {
     if (const char* why = graph_check_op(g->ops[i], g->tensors, input_tensor, output_tensor)) {
@@ -230,6 +301,8 @@ int cpx_graph_forward(cpx_graph* g, const float* in_dev, int N, float* out_dev) 
       v.p = const_cast<float*>(in_dev);
     else if (id == g->output)
       v.p = out_dev + t.c_offset;
+    else if (t.type == CPX_GRAPH_TYPE_INT8)   // bytes: the pointer and the sample stride count elements of one byte
+      v.p = reinterpret_cast<float*>(reinterpret_cast<char*>(h->graph_arena.as<float>() + (size_t)t.arena_offset * N) + t.c_offset);
     else
       v.p = h->graph_arena.as<float>() + (size_t)t.arena_offset * N + t.c_offset;
     return v;
@@ -254,6 +327,7 @@ int cpx_graph_forward(cpx_graph* g, const float* in_dev, int N, float* out_dev) 
     a.weights = o.weights;
     a.scale = o.scale;
     a.shift = o.shift;
+    a.in0_int8 = g->tensors[o.in0].type == CPX_GRAPH_TYPE_INT8;
     cpx::launch_graph_op(a, h->stream);
   }
   CPX_HIP(h, hipGetLastError());

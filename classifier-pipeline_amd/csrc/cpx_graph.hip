@@ -526,11 +526,29 @@ void launch_graph_op(const GraphOpArgs& a, hipStream_t s) {
     case CPX_GRAPH_QUANT_PARAMS:
       launch_graph_q8_op(a, s);
       break;
+    case CPX_GRAPH_SLICE:
+      if (a.in0_int8) {
+        launch_graph_i8_op(a, s);
+        break;
+      }
+      /* fall through */
     case CPX_GRAPH_DWCONV:
     case CPX_GRAPH_DWCONV_PRE:
     case CPX_GRAPH_DWCONV_Q8:
-    case CPX_GRAPH_SLICE:
       launch_graph_dw_op(a, s);
+      break;
+    case CPX_GRAPH_QUANTIZE:
+    case CPX_GRAPH_DEQUANTIZE:
+    case CPX_GRAPH_CONV_I8:
+    case CPX_GRAPH_CONV_I8_GROUPED:
+    case CPX_GRAPH_DWCONV_I8:
+    case CPX_GRAPH_FC_I8:
+    case CPX_GRAPH_ADD_I8:
+    case CPX_GRAPH_MUL_I8:
+    case CPX_GRAPH_MAX_POOL_I8:
+    case CPX_GRAPH_AVG_POOL_I8:
+    case CPX_GRAPH_MEAN_I8:
+      launch_graph_i8_op(a, s);
       break;
     case CPX_GRAPH_RANGE:
     case CPX_GRAPH_CONV_F16X2:

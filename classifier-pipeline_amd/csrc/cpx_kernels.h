@@ -402,6 +402,7 @@ struct GraphOpArgs {
   const float* weights;
   const float* scale;
   const float* shift;
+  int in0_int8;  // in0 is an int8 tensor: QUANTIZE requantises, SLICE copies bytes (an int8 view's pointer and strides count bytes)
 };
 void launch_graph_op(const GraphOpArgs& a, hipStream_t s);
 constexpr int GRAPH_CONV_KC = 16;  // CONV weights: Cin padded to this ...
@@ -420,6 +421,9 @@ constexpr int GRAPH_CONV_H2_KC = 32;
 // DEPTHWISE_CONV_2D, float32 (with or without a pre-activation) and hybrid, and SLICE (cpx_graph_dw.hip): weights
 // [tap][C rounded up to 4], float32 or int8 + wsum.
 void launch_graph_dw_op(const GraphOpArgs& a, hipStream_t s);
+// The full-integer operators (cpx_graph_i8.hip; the arithmetic: cpx_graph_i8_core.h) and SLICE on int8 tensors.  An int8
+// view's pointer and sample stride count bytes.
+void launch_graph_i8_op(const GraphOpArgs& a, hipStream_t s);
 
 // Kernels that use more than 64 KB of dynamic LDS need hipFuncAttributeMaxDynamicSharedMemorySize raised once per
 // (kernel, device): `done` is a per-kernel array indexed by the current device ordinal.

@@ -894,13 +894,62 @@ enum {
                                 for bit, what CONV computes from the view of input channels [g * Cg, (g + 1) * Cg)
                                 with image g: the same K walk -- tap x chunk of 16 of the group's own channels x pair
                                 -- and the same chain wherever the pixel, the sample or the group lands */
-  CPX_GRAPH_CONV_Q8_GROUPED = 25 /* hybrid.  in1: the QUANT_PARAMS tensor of in0, taken over the WHOLE view with all its
+  CPX_GRAPH_CONV_Q8_GROUPED = 25,/* hybrid.  in1: the QUANT_PARAMS tensor of in0, taken over the WHOLE view with all its
                                 groups: the input tensor is quantised once per sample, before the groups are walked
                                 (as the TFLite runtime's published hybrid kernels do; taken from their text, not
                                 verified against the runtime).  `weights` as bytes: G images in CONV_Q8's fragment
                                 layout for Cg -> Cog (without their wsum), then int32 wsum[G][Cog rounded up to 32].
                                 q, acc and out are exactly CONV_Q8's with K = kh * kw * Cg.  scale, shift: [out C],
                                 indexed by the absolute output channel, not NULL */
+  /* The full-integer operators of a file converted with a representative dataset (int8 activations, int32 biases,
+   * per-channel int8 filters): see "The full-integer arithmetic" below.  Their int8 tensors carry element type
+   * CPX_GRAPH_TYPE_INT8; `shift` is reinterpreted as the int32 header CPX_GRAPH_I8_HDR_*, not NULL. */
+  CPX_GRAPH_QUANTIZE = 26,   /* float32 -> int8: param = the output's scale, header Z_OUT.  int8 -> int8, the same shape: a
+                                requantisation, header Z_IN, Z_OUT, M0 / S0 = QM(s_in / s_out), LO, HI -- which is also a
+                                stand-alone RELU / RELU6 (the clamp) */
+  CPX_GRAPH_DEQUANTIZE = 27, /* int8 -> float32: param = the input's scale, header Z_IN */
+  CPX_GRAPH_CONV_I8 = 28,    /* CONV_2D, int8 in, int8 out.  `weights`: CONV_Q8's bytes unchanged (fragment image, then
+                                wsum).  `scale` is reinterpreted as int32 [3][out C]: M[c], shift[c], bias[c], not NULL.
+                                Header Z_IN, Z_OUT, LO, HI.  `activation` is ignored: the clamp carries it */
+  CPX_GRAPH_CONV_I8_GROUPED = 29, /* n_map = G; `weights`: CONV_Q8_GROUPED's bytes unchanged; scale, header: as CONV_I8,
+                                indexed by the absolute output channel */
+  CPX_GRAPH_DWCONV_I8 = 30,  /* depth multiplier 1, sides 1 to 7, strides 1 or 2.  `weights`: DWCONV_Q8's bytes unchanged
+                                (16-byte aligned); scale, header: as CONV_I8 */
+  CPX_GRAPH_FC_I8 = 31,      /* 1 x 1 x C -> 1 x 1 x C'.  `weights`: FC_Q8's bytes unchanged; scale, header: as CONV_I8 */
+  CPX_GRAPH_ADD_I8 = 32,     /* param 1 (ADD) or -1 (SUB).  in1: an int8 tensor of in0's shape, or -1: then `weights` is
+                                reinterpreted as int8 [C], the constant per channel.  Header Z_IN, Z_IN1, Z_OUT, LO, HI,
+                                M0 / S0, M1 / S1, MO / SO, LEFT = 20 */
+  CPX_GRAPH_MUL_I8 = 33,     /* operands as ADD_I8.  Header Z_IN, Z_IN1, Z_OUT, LO, HI, M0 / S0 = QM(s1 * s2 / s_out) */
+  CPX_GRAPH_MAX_POOL_I8 = 34,/* window, strides and pads as MAX_POOL; header LO, HI */
+  CPX_GRAPH_AVG_POOL_I8 = 35,/* as AVG_POOL; header LO, HI */
+  CPX_GRAPH_MEAN_I8 = 36     /* over H and W -> 1 x 1 x C.  Header M0 / S0 = QM(s_in / s_out), LEFT = the bias, LO, HI */
+};
+/* The full-integer arithmetic: the TFLite reference integer kernels' as published (parity with a TFLite runtime is not
+ * pinned: its optimised and single-rounding builds differ in the last step).  Written once in csrc/cpx_graph_i8_core.h.
+ * QM(real), on the host in float64: (f, shift) = frexp(real), M = round-half-away(f * 2^31); M == 2^31: M /= 2, ++shift;
+ * shift < -31: (M, shift) = (0, 0).
+ * SRDHM(a, b) = INT32_MAX if a == b == INT32_MIN, else int32((int64(a) * b + nudge) / 2^31) with C's truncating division,
+ * nudge = 2^30 for a product >= 0, else 1 - 2^30.
+ * RDivPOT(x, e): mask = 2^e - 1, rem = x & mask, thr = (mask >> 1) + (x < 0); (x >> e) + (rem > thr).
+ * MBQM(x, M, shift) = RDivPOT(SRDHM(x * 2^max(shift, 0), M), max(-shift, 0)); the caller keeps |x| * 2^max(shift, 0) < 2^31.
+ * The clamp [LO, HI] is the caller's: NONE [-128, 127], RELU [max(-128, z_out), 127], RELU6 [max(-128, z_out),
+ * min(127, z_out + round-half-away(float32(6 / s_out)))].
+ * QUANTIZE float32 -> int8: t = roundf(float32(x / s)), clamped in float to [-128 - z, 127 - z], q = int(t) + z; NaN: q = z.
+ * QUANTIZE int8 -> int8: clamp(z_out + MBQM(q - z_in, M0, S0)).  DEQUANTIZE: float32(s) * float32(q - z).
+ * CONV_I8 / CONV_I8_GROUPED / DWCONV_I8 / FC_I8: acc = sum (q - z_in) * w + bias[c] in int32 (w: zero point 0; a padded
+ * tap contributes nothing; the caller keeps K * 255 * 127 + max |bias| below 2^31), out = clamp(z_out + MBQM(acc, M[c], shift[c])).
+ * ADD_I8: a = MBQM((q1 - z1) << LEFT, M0, S0), b = MBQM((q2 - z2) << LEFT, M1, S1), out = clamp(z_out + MBQM(a +- b, MO, SO)).
+ * MUL_I8: out = clamp(z_out + MBQM((q1 - z1) * (q2 - z2), M0, S0)).
+ * MAX_POOL_I8: the maximum over the in-bounds window, clamped.  AVG_POOL_I8: acc = sum q over the n in-bounds elements,
+ * out = clamp(acc > 0 ? (acc + n / 2) / n : (acc - n / 2) / n), truncating division.
+ * MEAN_I8: acc = MBQM(sum q, M0, S0), divided by n = H * W with AVG_POOL_I8's rounding, + LEFT (the bias), clamped.
+ * SLICE on int8 tensors copies bytes (param 0, activation NONE); its zero region is header Z_IN. */
+enum { CPX_GRAPH_TYPE_FLOAT32 = 0, CPX_GRAPH_TYPE_INT8 = 1 };   /* cpx_graph_tensor.type */
+enum {
+  CPX_GRAPH_I8_HDR_Z_IN = 0, CPX_GRAPH_I8_HDR_Z_IN1 = 1, CPX_GRAPH_I8_HDR_Z_OUT = 2, CPX_GRAPH_I8_HDR_LO = 3,
+  CPX_GRAPH_I8_HDR_HI = 4, CPX_GRAPH_I8_HDR_M0 = 5, CPX_GRAPH_I8_HDR_S0 = 6, CPX_GRAPH_I8_HDR_M1 = 7, CPX_GRAPH_I8_HDR_S1 = 8,
+  CPX_GRAPH_I8_HDR_MO = 9, CPX_GRAPH_I8_HDR_SO = 10, CPX_GRAPH_I8_HDR_LEFT = 11,
+  CPX_GRAPH_I8_HDR_WORDS = 16   /* int32 words of the header; the words not named are 0 */
 };
 /* The fp16x2 arithmetic, per sample.  RANGE: m = max |x| over the view in float32.  m == 0 or m not finite (inf, NaN):
  * up = down = 1.  Otherwise m = f * 2^e with f in [0.5, 1) (frexp), k = min(15 - e, 100), up = 2^k, down = 2^-k: both
@@ -934,8 +983,11 @@ enum {
 typedef struct cpx_graph_tensor {
   int32_t H, W, C;
   int32_t c_offset, c_stride;
-  int32_t reserved;
-  int64_t arena_offset; /* floats per sample; ignored for the input and output tensors */
+  int32_t type;         /* CPX_GRAPH_TYPE_*: 0 float32 (the field every earlier plan left 0), 1 int8 */
+  int64_t arena_offset; /* floats per sample, whatever the type; ignored for the input and output tensors.  An int8
+                           tensor takes ceil(H * W * c_stride / 4) floats per sample: the tensor of a forward over N
+                           samples starts arena_offset * N floats in, its sample n at + n * H * W * c_stride BYTES.  The
+                           input and the output tensor are float32 */
 } cpx_graph_tensor;
 
 typedef struct cpx_graph_op {

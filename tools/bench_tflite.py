@@ -70,7 +70,17 @@ card in one process: its dynamic-range quantised file on the graph executor (CON
 what get_interpreter runs by default), the float32 file on the graph executor (CONV_GROUPED), the fused kernels in their
 default math (WRResNetDevice: what CPX_TFLITE_QUANT_MATH=float and a float32 file run) and PyTorch-ROCm float32
 (conv2d(groups=2), reduced-precision paths off).  Prints launches per forward and ms per forward (HIP events, median) for
-each; the launches of the last two are counted by torch.profiler over one forward (null where it cannot)."""
+each; the launches of the last two are counted by torch.profiler over one forward (null where it cannot).
+
+    python tools/bench_tflite.py --int8 [--batches 1,8,128] [--rounds 3]
+
+times the WR-ResNet-22-4 and a width-1.0 MobileNetV2 as full-integer files (tests/tflite_build_i8.py: quantise_full from a
+calibration batch; INT8 activations between QUANTIZE and DEQUANTIZE) on the int8 kinds, and beside them, in the same
+process on the same card in alternating rounds, the same network's hybrid plan and float32 plan: the median over the
+rounds and their scatter, the launches by kind, the arena bytes per sample.  --int8 --skip-torch runs the full-integer
+plans alone at the last batch size (a run under `rocprofv3 --kernel-trace --stats`, whose per-kernel times give CONV_I8's
+share and the DWCONV_I8 / SLICE bytes per second: the bytes are printed as dwconv_i8_bytes / slice_bytes; --int8-net wr |
+mobilenet keeps one network's kernels in the trace)."""
 import argparse
 import json
 import os
@@ -84,7 +94,9 @@ for p in (os.path.join(REPO, "classifier-pipeline_amd"), os.path.join(REPO, "tes
 
 KIND_NAMES = {24: "conv_grouped", 25: "conv_q8_grouped", 1: "conv", 2: "max_pool", 3: "avg_pool", 4: "add", 5: "affine", 6: "mean", 7: "fc", 8: "logistic", 9: "softmax",
               10: "pad", 11: "channel_map", 12: "conv_q8", 13: "fc_q8", 14: "quant_params", 15: "dwconv", 16: "dwconv_q8", 17: "mul", 18: "input", 19: "conv_pre",
-              20: "slice", 21: "dwconv_pre", 22: "range", 23: "conv_f16x2"}
+              20: "slice", 21: "dwconv_pre", 22: "range", 23: "conv_f16x2", 26: "quantize", 27: "dequantize", 28: "conv_i8",
+              29: "conv_i8_grouped", 30: "dwconv_i8", 31: "fc_i8", 32: "add_i8", 33: "mul_i8", 34: "max_pool_i8", 35: "avg_pool_i8",
+              36: "mean_i8"}
 CONV_KINDS = (1, 12, 19, 23)
 DW_KINDS = (15, 16, 21)
 FOLDS = dict(fold_windows=True, fuse_preactivation_dw=True, fuse_preactivation=True)
@@ -259,6 +271,80 @@ def wrresnet_leg(args):
                 out["launches"]["torch"] = count_launches(torch, lambda: ref(x_nchw))
         out["batches"].append(rec)
     net.close()
+    eng.close()
+    print(json.dumps(out))
+
+
+def int8_leg(args):
+    """The WR-ResNet-22-4 and a MobileNetV2 as full-integer files against their hybrid and float32 plans, interleaved."""
+    import ctypes as C
+
+    import tflite_build as tb
+    import tflite_build_dw as td
+    import tflite_build_i8 as ti
+    import tflite_build_q8 as tq
+    import torch
+    from cpx import _lib
+    from cpx.engine import TrackEngine
+    from cpx.ml_tools import wrresnet as wr
+    from cpx.ml_tools.tflite_graph import GraphDevice, build_plan
+    from cpx.ml_tools.tflite_reader import Graph
+
+    eng = TrackEngine(model="lepton3", device=0)
+    stream = torch.cuda.ExternalStream(eng.lib.cpx_stream(eng.h), device=eng.device)
+    rng = np.random.default_rng(0)
+    xcal = torch.from_numpy(np.random.default_rng(1).uniform(0, 255, size=(2, 160, 160, 2)).astype(np.float32)).to(eng.device)
+    w = wr.calibrate_bn_device(eng, wr.random_weights(17, seed=3), xcal)
+    nets = {"wr-resnet-22-4 groups 2 160x160x2": (tb.wrresnet(w), tq.quantise, (160, 160, 2), (0.0, 255.0)),
+            "mobilenet_v2 width 1.00 160x160x3": (td.mobilenet_v2(17, width=1.0, seed=7), td.quantise, (160, 160, 3), (-1.0, 1.0))}
+    out = {"networks": []}
+    batches = [int(v) for v in args.batches.split(",")]
+    for model, (blob, hybrid_of, shape, (lo, hi)) in nets.items():
+        if args.int8_net not in ("all", model.split("-")[0].split("_")[0]):
+            continue
+        full = ti.quantise_full(blob, np.random.default_rng(2).uniform(lo, hi, size=(1,) + shape))
+        opts = dict(grouped_convolutions=True, **FOLDS)
+        plans = {"int8": build_plan(Graph(full), integer_activations=True, **opts)}
+        if not args.skip_torch:
+            plans.update(hybrid=build_plan(Graph(hybrid_of(blob)), **opts), float32=build_plan(Graph(blob), **opts))
+        p8 = plans["int8"]
+        rec = {"model": model, "launches": {k: len(p.ops) for k, p in plans.items()},
+               "arena_bytes_per_sample": {k: p.arena_bytes_per_sample for k, p in plans.items()},
+               "launches_by_kind": {k: {KIND_NAMES[kind]: sum(o.kind == kind for o in p.ops) for kind in sorted(set(o.kind for o in p.ops))}
+                                    for k, p in plans.items()},
+               # what the HBM-bound int8 launches must move per sample: input and output once (bytes), the weights apart
+               "dwconv_i8_bytes_per_sample": sum(p8.tensors[o.in0].H * p8.tensors[o.in0].W * p8.tensors[o.in0].C +
+                                                 p8.tensors[o.out].H * p8.tensors[o.out].W * p8.tensors[o.out].C
+                                                 for o in p8.ops if o.kind == _lib.GRAPH_DWCONV_I8),
+               "slice_bytes_per_sample": sum(2 * p8.tensors[o.out].H * p8.tensors[o.out].W * p8.tensors[o.out].C
+                                             for o in p8.ops if o.kind == _lib.GRAPH_SLICE),
+               "conv_i8_gop_per_sample": sum(2.0 * p8.tensors[o.out].H * p8.tensors[o.out].W * p8.tensors[o.out].C * o.kh * o.kw *
+                                             p8.tensors[o.in0].C / o.groups for o in p8.ops
+                                             if o.kind in (_lib.GRAPH_CONV_I8, _lib.GRAPH_CONV_I8_GROUPED)) / 1e9,
+               "batches": []}
+        for n in (batches[-1:] if args.skip_torch else batches):
+            x = torch.from_numpy(rng.uniform(lo, hi, size=(n,) + shape).astype(np.float32)).to(eng.device)
+            y = torch.empty((n, 17), dtype=torch.float32, device=eng.device)
+            devs = {k: GraphDevice(eng, p) for k, p in plans.items()}
+            times = {k: [] for k in plans}
+            for _ in range(args.rounds):   # alternating: a drift of the card or the host lands on every plan alike
+                for k, dev in devs.items():
+                    def forward(dev=dev):
+                        rc = eng.lib.cpx_graph_forward(dev._graph, C.c_void_p(x.data_ptr()), n, C.c_void_p(y.data_ptr()))
+                        assert rc == 0, eng._err()
+
+                    with torch.cuda.stream(stream):
+                        times[k].append(timed(torch, forward, args.steps, args.warmup))
+            for dev in devs.values():
+                dev.close()
+            b = {"N": n}
+            for k, v in times.items():
+                b[k + "_ms"] = float(np.median(v))
+                b[k + "_runs_ms"] = [round(t, 4) for t in v]
+            if "hybrid_ms" in b:
+                b["hybrid_over_int8"], b["float32_over_int8"] = b["hybrid_ms"] / b["int8_ms"], b["float32_ms"] / b["int8_ms"]
+            rec["batches"].append(b)
+        out["networks"].append(rec)
     eng.close()
     print(json.dumps(out))
 
@@ -826,7 +912,15 @@ def main():
     ap.add_argument("--wrresnet", action="store_true",
                     help="the WR-ResNet-22-4 (grouped convolutions): hybrid and float32 on the graph executor, the fused kernels, PyTorch-ROCm")
     ap.add_argument("--rounds", type=int, default=3, help="with --conv-math fp16x2: alternating rounds per batch size (median, scatter)")
+    ap.add_argument("--int8", action="store_true",
+                    help="the WR-ResNet-22-4 and a MobileNetV2 as full-integer files beside their hybrid and float32 plans, interleaved")
+    ap.add_argument("--int8-net", default="all", choices=("all", "wr", "mobilenet"),
+                    help="with --int8: one of the two networks alone (a run under a profiler: the kernels of one network in the trace)")
     args = ap.parse_args()
+    if args.int8:
+        if args.batches == "1,8,32,128":
+            args.batches = "1,8,128"
+        return int8_leg(args)
     if args.wrresnet:
         if args.batches == "1,8,32,128":
             args.batches = "1,8,128"

@@ -10,7 +10,9 @@ flatbuffer is parsed here, TensorFlow is not needed (only NumPy).
 src/tfliteconverter.py:54-62): every INT8 filter multiplied out, float32(int8) * scale -- the float32 network the file
 stands for, which the fused kernels run (CPX_TFLITE_QUANT_MATH=float does the same on load).  Without it such a file is
 refused by the name of its first INT8 tensor.  --describe plans a grouped CONV_2D as LiteInterpreter does
-(grouped_convolutions=True) and prints each grouped convolution's G, the hybrid ones marked and counted in the census.
+(grouped_convolutions=True) and prints each grouped convolution's G, the hybrid ones marked and counted in the census.  A
+full-integer file (INT8 activations, QUANTIZE / DEQUANTIZE) is planned as LiteInterpreter plans it too
+(integer_activations=True): the tensor types and the smaller per-sample arena are printed, or the refusal.
 
 --describe converts nothing: it prints the operator census, the input and output shapes, the arena bytes per sample and,
 for a dynamic-range quantised file, the number of hybrid operators with the int8 against the float32 weight bytes of ANY graph the device executor runs (cpx/ml_tools/tflite_graph.py: an Inception-v3, a MobileNetV2 or an EfficientNet, say; the launches carry what was folded into them: CONV_2D+SWISH, CONV_2D+LOGISTIC, CONV_2D+MUL+ADD, AFFINE>CONV_2D for a folded pre-activation; a second line gives the launches with the window folds on, as LiteInterpreter runs the file: PAD>DEPTHWISE_CONV_2D, RELU>DEPTHWISE_CONV_2D, PAD>STRIDED_SLICE>AVERAGE_POOL_2D), or the refusal -- the
@@ -66,8 +68,9 @@ def describe(g, sidecar=None, conv_math="f32"):
     print("operators: " + ", ".join("%s: %d" % kv for kv in sorted(census.items())))
     try:
         # every PAD, 1 x 1 pool and slice a launch (CPX_TFLITE_FOLD_WINDOWS=0), and what LiteInterpreter runs
-        unfolded = build_plan(g, fuse_preactivation=True, grouped_convolutions=True)
-        plan = build_plan(g, fuse_preactivation=True, fuse_preactivation_dw=True, fold_windows=True, grouped_convolutions=True)
+        unfolded = build_plan(g, fuse_preactivation=True, grouped_convolutions=True, integer_activations=True)
+        plan = build_plan(g, fuse_preactivation=True, fuse_preactivation_dw=True, fold_windows=True, grouped_convolutions=True,
+                          integer_activations=True)
     except NotImplementedError as e:
         print("refused: %s" % e)
         return 1
@@ -75,8 +78,14 @@ def describe(g, sidecar=None, conv_math="f32"):
     print("launches: " + ", ".join("%s: %d" % kv for kv in sorted(unfolded.census().items())))
     print("folded launches (%d of %d): " % (len(plan.ops), len(unfolded.ops)) + ", ".join("%s: %d" % kv for kv in sorted(plan.census().items())))
     print("arena bytes per sample: %d (unfolded: %d)" % (plan.arena_bytes_per_sample, unfolded.arena_bytes_per_sample))
-    from cpx.ml_tools.tflite_graph import GROUPED_KINDS, Q8_KINDS
+    from cpx.ml_tools.tflite_graph import GROUPED_KINDS, I8_FILTER_KINDS, Q8_KINDS
 
+    n8 = sum(t.dtype == "int8" for t in plan.tensors.values())
+    if n8:
+        # a full-integer file: int8 activations between QUANTIZE and DEQUANTIZE, an arena counted in bytes
+        full = [o for o in plan.ops if o.kind in I8_FILTER_KINDS]
+        print("tensor types: %d int8, %d float32; full-integer filter operators (int8 in, int8 out): %d, int8 weight bytes: %d"
+              % (n8, len(plan.tensors) - n8, len(full), sum(int(np.prod(o.filter.shape)) for o in full)))
     grouped = [o for o in plan.ops if o.kind in GROUPED_KINDS]
     if grouped:
         print("grouped convolutions: %d (%d hybrid): " % (len(grouped), sum(o.kind in Q8_KINDS for o in grouped))
@@ -84,15 +93,16 @@ def describe(g, sidecar=None, conv_math="f32"):
     hybrid = [o for o in plan.ops if o.kind in Q8_KINDS]
     q8 = sum(int(np.prod(o.filter.shape)) for o in hybrid)
     f32 = sum(4 * int(np.prod((o.filter if getattr(o, "filter", None) is not None else o.weights).shape)) for o in plan.ops
-              if o.kind not in Q8_KINDS and o.weights is not None)
+              if o.kind not in Q8_KINDS and o.kind not in I8_FILTER_KINDS and o.weights is not None and o.weights.dtype != np.uint8)
     print("hybrid operators (int8 filter, activations quantised per sample): %d; int8 weight bytes: %d, float32 weight bytes: %d"
           % (len(hybrid), q8, f32))
     if conv_math != "f32":
         # what CPX_TFLITE_CONV_MATH=fp16x2 makes of the file, with LiteInterpreter's default folds
         from cpx import _lib
 
-        base = build_plan(g, fuse_preactivation=True, fold_windows=True, grouped_convolutions=True)
-        h2 = build_plan(g, fuse_preactivation=True, fold_windows=True, conv_math=conv_math, grouped_convolutions=True)
+        base = build_plan(g, fuse_preactivation=True, fold_windows=True, grouped_convolutions=True, integer_activations=True)
+        h2 = build_plan(g, fuse_preactivation=True, fold_windows=True, conv_math=conv_math, grouped_convolutions=True,
+                        integer_activations=True)
         n_h2 = sum(o.kind == _lib.GRAPH_CONV_F16X2 for o in h2.ops)
         n_range = sum(o.kind == _lib.GRAPH_RANGE for o in h2.ops)
         n_pre = sum(o.kind == _lib.GRAPH_CONV_PRE for o in base.ops)
