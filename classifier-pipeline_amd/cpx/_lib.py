@@ -132,13 +132,14 @@ GRAPH_CONV, GRAPH_MAX_POOL, GRAPH_AVG_POOL, GRAPH_ADD, GRAPH_AFFINE, GRAPH_MEAN,
     GRAPH_CONV_Q8_GROUPED = range(1, 26)
 # the full-integer operators (int8 activations); enum CPX_GRAPH_TYPE_* and CPX_GRAPH_I8_HDR_*
 GRAPH_QUANTIZE, GRAPH_DEQUANTIZE, GRAPH_CONV_I8, GRAPH_CONV_I8_GROUPED, GRAPH_DWCONV_I8, GRAPH_FC_I8, GRAPH_ADD_I8, \
-    GRAPH_MUL_I8, GRAPH_MAX_POOL_I8, GRAPH_AVG_POOL_I8, GRAPH_MEAN_I8 = range(26, 37)
+    GRAPH_MUL_I8, GRAPH_MAX_POOL_I8, GRAPH_AVG_POOL_I8, GRAPH_MEAN_I8, GRAPH_LUT_I8 = range(26, 38)
 GRAPH_TYPE_FLOAT32, GRAPH_TYPE_INT8 = 0, 1
 GRAPH_I8_HDR_Z_IN, GRAPH_I8_HDR_Z_IN1, GRAPH_I8_HDR_Z_OUT, GRAPH_I8_HDR_LO, GRAPH_I8_HDR_HI, GRAPH_I8_HDR_M0, GRAPH_I8_HDR_S0, \
     GRAPH_I8_HDR_M1, GRAPH_I8_HDR_S1, GRAPH_I8_HDR_MO, GRAPH_I8_HDR_SO, GRAPH_I8_HDR_LEFT = range(12)
 GRAPH_I8_HDR_WORDS = 16
+GRAPH_I8_LUT_BYTES = 4 * GRAPH_I8_HDR_WORDS + 256   # the header with a 256-entry int8 table behind it (LUT_I8, ACT_LUT)
 # enum CPX_GRAPH_ACT_*: the planner's own activation codes, outside TFLite's ActivationFunctionType
-GRAPH_ACT_SWISH, GRAPH_ACT_LOGISTIC = 16, 17
+GRAPH_ACT_SWISH, GRAPH_ACT_LOGISTIC, GRAPH_ACT_LUT = 16, 17, 18
 GRAPH_MEAN_WIDE_PIXELS = 256   # MEAN: from this many pixels on the striped summation order (csrc/cpx_graph_core.h)
 GRAPH_CONV_KC, GRAPH_CONV_CO = 16, 32   # CONV weights: Cin / Cout rounded up to these (csrc/cpx_kernels.h)
 GRAPH_CONV_Q8_KC = 32   # CONV_Q8 weights: int8 in MFMA fragment order, Cin rounded up to this (csrc/cpx_kernels.h)

@@ -382,7 +382,12 @@ class LiteInterpreter(Interpreter):
     float32 or dynamic-range quantised -- get_interpreter sends the quantised one here.
     A full-integer file (INT8 activations between a QUANTIZE and a DEQUANTIZE: a converter given a representative dataset)
     runs here too (build_plan: integer_activations=True, always): float32 in and out, as the reference feeds it, the
-    interior on the int8 operators with the TFLite reference integer kernels' arithmetic (include/cpx.h)."""
+    interior on the int8 operators with the TFLite reference integer kernels' arithmetic (include/cpx.h).  That covers the
+    EfficientNet families: the INT8 MUL by a squeeze-and-excite gate is MUL_I8 (integer_gate_mul=True, always), and
+    CPX_TFLITE_I8_LUT=1|0 (default 1) makes every interior INT8 LOGISTIC and swish a 256-entry table, folded into the
+    convolution in front of it where it can be (build_plan: integer_lut) -- the stated arithmetic exactly, where the three
+    launches DEQUANTIZE -> LOGISTIC -> QUANTIZE it replaces (0) may differ by a step at a near-tie of the device's float32
+    expf.  A file without an interior INT8 LOGISTIC keeps every bit under either setting."""
 
     TYPE = "TFLite"
     DEFAULT_QUANT_MATH = "hybrid"
@@ -390,6 +395,7 @@ class LiteInterpreter(Interpreter):
     DEFAULT_FUSE_PREACT = "1"
     DEFAULT_FOLD_WINDOWS = "1"
     DEFAULT_FUSE_PREACT_DW = "0"
+    DEFAULT_I8_LUT = "1"
     INPUT_MODE_OF = {"resnet": "caffe", "resnet152": "caffe", "vgg16": "caffe", "vgg19": "caffe", "densenet121": "torch"}
 
     @staticmethod
@@ -423,6 +429,10 @@ class LiteInterpreter(Interpreter):
     def fold_windows(cls):
         return cls._env_choice("CPX_TFLITE_FOLD_WINDOWS", cls.DEFAULT_FOLD_WINDOWS, ("0", "1")) == "1"
 
+    @classmethod
+    def i8_lut(cls):
+        return cls._env_choice("CPX_TFLITE_I8_LUT", cls.DEFAULT_I8_LUT, ("0", "1")) == "1"
+
     def get_preprocess_fn(self):
         """The base class's, and the 'caffe' / 'torch' families it refuses: the host statement of what the graph's INPUT
         operator does on the device; self.input_mode names the mode (None for every other family)."""
@@ -454,7 +464,8 @@ class LiteInterpreter(Interpreter):
         self._fuse_preact_dw = self.fuse_preact_dw() and self._fuse_preact
         self._plan_options = dict(quantised_math=self._quant_math, fuse_preactivation=self._fuse_preact,
                                   fuse_preactivation_dw=self._fuse_preact_dw, fold_windows=self._fold_windows,
-                                  conv_math=self._conv_math, grouped_convolutions=True, integer_activations=True)
+                                  conv_math=self._conv_math, grouped_convolutions=True, integer_activations=True,
+                                  integer_gate_mul=True, integer_lut=self.i8_lut())
         # refuses, by operator, what the executor does not run
         plan = build_plan(self._graph, **self._plan_options)
         self._plans[(plan.graph_input_shape, None)] = plan

@@ -134,6 +134,8 @@ def _channel_const(g, tid, channels, what):
 #   params    the kind writes the 1 x 1 x 4 per-sample tensor of a view (_view_params)
 #   folds     MUL / ADD / SUB / DIV by constants and a swish fold into it (_fold_into_producer)
 #   logistic  a LOGISTIC folds into it.  Behind a FULLY_CONNECTED it stays a launch
+#   table     a full-integer kind whose int8 result can go through a 256-entry table behind its header (the activation
+#             LUT: integer_lut folds an INT8 LOGISTIC or swish into it, tflite_graph_i8._emit_table).  Not FC_I8
 #   pad       a PAD in front of it, VALID, becomes its four explicit pads (fold_window_chains).  Not the grouped kinds
 #   pre       the kind it becomes behind a dropped pre-activation (fuse_preactivations).  There is no grouped and no fp16x2
 #             CONV_PRE: in front of those kinds the AFFINE stays a launch.  CONV_PRE and DWCONV_PRE are made behind every
@@ -141,8 +143,8 @@ def _channel_const(g, tid, channels, what):
 #   pack      PlanOp -> its weights in the kernel's layout (pack_weights)
 #   scaled    the device multiplies by float32(filter scale x folded scale): pack_weights puts the product into `scale`
 #             (the hybrid kinds: only an INT8 filter has scales)
-Kind = collections.namedtuple("Kind", "hybrid grouped params folds logistic pad pre pack scaled",
-                              defaults=(False, False, False, False, False, False, None, None, False))
+Kind = collections.namedtuple("Kind", "hybrid grouped params folds logistic pad pre pack scaled table",
+                              defaults=(False, False, False, False, False, False, None, None, False, False))
 _CONV_EPILOGUE = dict(folds=True, logistic=True)
 KINDS = {
     _lib.GRAPH_CONV: Kind(pad=True, pre=_lib.GRAPH_CONV_PRE, pack=lambda o: pack_conv_filter(o.filter), **_CONV_EPILOGUE),
@@ -161,9 +163,9 @@ KINDS = {
     _lib.GRAPH_QUANT_PARAMS: Kind(params=True), _lib.GRAPH_RANGE: Kind(params=True),
     # the full-integer kinds (tflite_graph_i8): the hybrid kinds' filter images unchanged; their integers ride in `scale`
     # and `shift`, which the lowering has already made.  A same-parameter PAD folds into the two that take explicit pads
-    _lib.GRAPH_CONV_I8: Kind(pad=True, pack=lambda o: pack_conv_filter_q8(o.filter)),
-    _lib.GRAPH_CONV_I8_GROUPED: Kind(grouped=True, pack=lambda o: pack_conv_filter_q8_grouped(o.filter, o.groups)),
-    _lib.GRAPH_DWCONV_I8: Kind(pad=True, pack=lambda o: pack_dw_filter_q8(o.filter)),
+    _lib.GRAPH_CONV_I8: Kind(pad=True, pack=lambda o: pack_conv_filter_q8(o.filter), table=True),
+    _lib.GRAPH_CONV_I8_GROUPED: Kind(grouped=True, pack=lambda o: pack_conv_filter_q8_grouped(o.filter, o.groups), table=True),
+    _lib.GRAPH_DWCONV_I8: Kind(pad=True, pack=lambda o: pack_dw_filter_q8(o.filter), table=True),
     _lib.GRAPH_FC_I8: Kind(pack=lambda o: pack_fc_filter_q8(o.filter)),
 }
 
@@ -178,7 +180,7 @@ def _kinds(column):
 
 Q8_KINDS, GROUPED_KINDS, PARAM_KINDS = _kinds("hybrid"), _kinds("grouped"), _kinds("params")
 I8_FILTER_KINDS = (_lib.GRAPH_CONV_I8, _lib.GRAPH_CONV_I8_GROUPED, _lib.GRAPH_DWCONV_I8, _lib.GRAPH_FC_I8)
-FOLD_INTO, LOGISTIC_INTO = _kinds("folds"), _kinds("logistic")
+FOLD_INTO, LOGISTIC_INTO, LUT_INTO = _kinds("folds"), _kinds("logistic"), _kinds("table")
 
 QUANT_MATHS = ("hybrid", "float")
 CONV_MATHS = ("f32", "fp16x2")
@@ -224,7 +226,7 @@ class _Build:
 
 def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_math="hybrid", fuse_activations=True,
                input_mode=None, fuse_preactivation=False, fold_windows=False, fuse_preactivation_dw=False, conv_math="f32",
-               grouped_convolutions=False, integer_activations=False):
+               grouped_convolutions=False, integer_activations=False, integer_gate_mul=False, integer_lut=False):
     """g: tflite_reader.Graph.  input_shape: (H, W, C) of a sample, default: the flatbuffer's.  output: the tensor the
     forward hands out, default the graph's output; the operators it does not need are dropped.  channel_map: up to 4
     indices into the channels of the sample the CALLER brings ([N, H, W, max(map) + 1 or more]): the graph's input
@@ -242,7 +244,13 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
     False refuses a grouped CONV_2D by name, True plans it as CONV_GROUPED / CONV_Q8_GROUPED (_lower_filter).
     integer_activations: False refuses a full-integer file (INT8 activations, QUANTIZE / DEQUANTIZE) as ever, True plans its
     interior on the int8 kinds (tflite_graph_i8: float32 stays at the two ends; a float32 operator behind a DEQUANTIZE is
-    the existing kind)."""
+    the existing kind).  integer_gate_mul (with integer_activations; default False refuses it as ever): an INT8 MUL of an
+    [H, W, C] tensor by the [1, 1, C] gate of a squeeze-and-excite block, in either operand order, is MUL_I8 with the gate as
+    in1.  integer_lut (with integer_activations; default False: DEQUANTIZE -> LOGISTIC -> QUANTIZE as ever): an interior INT8
+    LOGISTIC is a 256-entry table, and so is a swish (LOGISTIC + MUL of the same x: both operands are functions of the one
+    byte); the table is folded into x's producer where that is one of KINDS' table column under _fold_into_producer's rules,
+    elsewhere it is ONE LUT_I8 launch.  An INT8 LOGISTIC that a DEQUANTIZE reads (the head) and SOFTMAX keep their three
+    launches.  The arithmetic: include/cpx.h, "Tables"."""
     if quantised_math not in QUANT_MATHS:
         raise ValueError("quantised_math %r: one of %s" % (quantised_math, ", ".join(QUANT_MATHS)))
     if conv_math not in CONV_MATHS:
@@ -259,7 +267,8 @@ def build_plan(g, input_shape=None, output=None, channel_map=None, quantised_mat
         raise NotImplementedError("operator 0: the input has the dynamic shape %s: pass input_shape" % (list(input_shape),))
     s = _Build(g, gin, g.outputs[0] if output is None else int(output))
     s.T[gin] = PlanTensor(gin, *[int(v) for v in input_shape])
-    lower_ops(s, quantised_math, fuse_activations, conv_math, grouped_convolutions, integer_activations)
+    lower_ops(s, quantised_math, fuse_activations, conv_math, grouped_convolutions, integer_activations, integer_gate_mul,
+              integer_lut)
     if integer_activations:
         tflite_graph_i8.annotate_types(s)
     resolve_views(s)
@@ -445,7 +454,8 @@ def _affine_of(name, c, const_first, what):
     return (-one, c) if const_first else (one, -c)   # c - x; x - c
 
 
-def lower_ops(s, quantised_math, fuse_activations, conv_math, grouped_convolutions, integer_activations=False):
+def lower_ops(s, quantised_math, fuse_activations, conv_math, grouped_convolutions, integer_activations=False,
+              integer_gate_mul=False, integer_lut=False):
     """Every operator of the flatbuffer, in its order, as PlanOps on tensors of inferred shape ([H, W, C] of one sample,
     TensorFlow's SAME / VALID arithmetic):
     * MUL / ADD / SUB / DIV by a per-channel constant behind one of FOLD_INTO (a convolution, or another such operator)
@@ -466,16 +476,32 @@ def lower_ops(s, quantised_math, fuse_activations, conv_math, grouped_convolutio
       feeds two concatenations, it is the graph's input, it is a view of another tensor -- is copied (a COPY entry: an
       AFFINE operator without constants);
     * CONV_2D / DEPTHWISE_CONV_2D: _lower_filter.  A FULLY_CONNECTED with an INT8 filter is the hybrid FC_Q8
-      (pack_fc_filter_q8) on the symmetric or asymmetric QUANT_PARAMS of its input view, as the flatbuffer asks."""
+      (pack_fc_filter_q8) on the symmetric or asymmetric QUANT_PARAMS of its input view, as the flatbuffer asks;
+    * integer_activations: an operator on INT8 tensors is tflite_graph_i8's.  A swish of an INT8 x is no float32 activation:
+      with integer_lut it is one table (lower_integer_swish), without it its LOGISTIC and its MUL are lowered as they stand."""
     g, T, gin, gout = s.g, s.T, s.gin, s.gout
-    swish_logistic, swish_mul = _find_swishes(s) if fuse_activations else ({}, {})
+    swish_logistic, swish_mul = _find_swishes(s) if fuse_activations or (integer_activations and integer_lut) else ({}, {})
+    i8_logistic, i8_mul = {}, {}
+    if integer_activations:
+        i8_mul = {m: x for m, x in swish_mul.items() if tflite_graph_i8.is_int8(g, x)}
+        i8_logistic = {lg: m for lg, m in swish_logistic.items() if m in i8_mul}
+        swish_mul = {m: x for m, x in swish_mul.items() if m not in i8_mul} if fuse_activations else {}
+        swish_logistic = {lg: m for lg, m in swish_logistic.items() if m in swish_mul}
+        if not integer_lut:
+            i8_logistic, i8_mul = {}, {}
     for i, op in enumerate(g.ops):
         name = op["name"]
         what = "operator %d (%s)" % (i, name)
         ins = [t for t in op["inputs"] if t >= 0]
         act_ins = [t for t in ins if g.const(t) is None]
-        if i in swish_logistic:
+        if i in swish_logistic or i in i8_logistic:
             continue   # (its MUL does the work)
+        if i in i8_mul:
+            if i8_mul[i] not in T:
+                raise NotImplementedError("%s reads tensor %d, which no earlier operator wrote" % (what, i8_mul[i]))
+            logistic = g.ops[next(lg for lg, m in i8_logistic.items() if m == i)]
+            tflite_graph_i8.lower_integer_swish(s, i, op, logistic, T[i8_mul[i]], op["outputs"][0], what)
+            continue
         if i in swish_mul:
             if swish_mul[i] not in T:
                 raise NotImplementedError("%s reads tensor %d, which no earlier operator wrote" % (what, swish_mul[i]))
@@ -492,7 +518,8 @@ def lower_ops(s, quantised_math, fuse_activations, conv_math, grouped_convolutio
         if op.get("act", 0) not in (ACT_NONE, ACT_RELU, ACT_RELU6):
             raise NotImplementedError("%s: fused activation %d" % (what, op["act"]))
         int8 = integer_activations and (name in INTEGER_OPS or any(tflite_graph_i8.is_int8(g, t) for t in act_ins + [y]))
-        if int8 and tflite_graph_i8.lower_integer_op(s, i, op, what, x, y, ins, act_ins, grouped_convolutions):
+        if int8 and tflite_graph_i8.lower_integer_op(s, i, op, what, x, y, ins, act_ins, grouped_convolutions, integer_gate_mul,
+                                                     integer_lut):
             continue
         if name in ("CONV_2D", "DEPTHWISE_CONV_2D"):
             _lower_filter(s, i, op, what, x, y, ins, quantised_math, conv_math, grouped_convolutions)

@@ -1,11 +1,13 @@
 """The full-integer half of the graph planner (cpx/ml_tools/tflite_graph.py: build_plan(..., integer_activations=True)): the
 operators of a file converted with a representative dataset -- INT8 activations with one scale and one zero point, INT32
 biases, per-channel INT8 filters, QUANTIZE / DEQUANTIZE at the two ends -- lowered to the executor's int8 kinds
-(include/cpx.h: CPX_GRAPH_QUANTIZE .. CPX_GRAPH_MEAN_I8, and SLICE on bytes).  The arithmetic is the TFLite reference
+(include/cpx.h: CPX_GRAPH_QUANTIZE .. CPX_GRAPH_LUT_I8, and SLICE on bytes).  The arithmetic is the TFLite reference
 integer kernels' as published, fixed in include/cpx.h; parity with a TFLite runtime is not pinned.  Everything an operator
 needs beyond its filter is worked out HERE, in float64 from the float32 scales widened to double, and rides as integers:
 the int32 header (`shift`: zero points, clamp, multipliers and shifts) and, for the filter kinds, int32 M[c], shift[c],
-bias[c] per output channel (`scale`).  What cannot be run is refused by the operator's name and index."""
+bias[c] per output channel (`scale`).  With integer_lut an interior LOGISTIC or swish is a 256-entry table made here too
+(logistic_table, swish_table), which rides behind the header.  What cannot be run is refused by the operator's name and
+index."""
 import math
 
 import numpy as np
@@ -81,6 +83,82 @@ def unpack_header(b):
     return np.asarray(b, np.uint8).view(np.int32)
 
 
+def _mbqm(x, m, shift):
+    """MBQM on Python integers (include/cpx.h): SRDHM by m, then the rounding division by 2^max(-shift, 0)."""
+    x <<= max(shift, 0)
+    if x == m == -2 ** 31:
+        v = 2 ** 31 - 1
+    else:
+        ab = x * m
+        ab += 2 ** 30 if ab >= 0 else 1 - 2 ** 30
+        v = abs(ab) // 2 ** 31 * (-1 if ab < 0 else 1)   # C's division: it truncates
+    e = max(-shift, 0)
+    mask = (1 << e) - 1
+    return (v >> e) + (1 if (v & mask) > (mask >> 1) + (1 if v < 0 else 0) else 0)
+
+
+def logistic_table(s_in, z_in, s_out, z_out):
+    """The 256 bytes of an INT8 LOGISTIC (include/cpx.h, "Tables"), entry q + 128 for q = -128 .. 127: the float64 logistic
+    of the dequantised input float32(s_in) * float32(q - z_in), divided by float64(s_out), rounded half away, + z_out,
+    clamped."""
+    q = np.arange(-128, 128)
+    x = (np.float32(s_in) * (q - int(z_in)).astype(np.float32)).astype(np.float32).astype(np.float64)
+    with np.errstate(over="ignore"):
+        t = (1.0 / (1.0 + np.exp(-x))) / float(np.float32(s_out))
+    r = (np.sign(t) * np.floor(np.abs(t) + 0.5)).astype(np.int64)
+    return np.clip(r + int(z_out), -128, 127).astype(np.int8)
+
+
+def swish_table(x_qp, l_qp, out_qp, act, what="MUL"):
+    """The 256 bytes of y = MUL(x, LOGISTIC(x)): S[q + 128] = MUL_I8(q, L[q + 128]) with the MUL's own constants -- the zero
+    points of x and of the LOGISTIC's output, QM(s_x * s_l / s_out), and the clamp of its fused activation `act`."""
+    (s_x, z_x), (s_l, z_l), (s_out, z_out) = x_qp, l_qp, out_qp
+    if not (float(s_x) > 0.0 and float(s_l) > 0.0 and float(s_out) > 0.0):
+        raise NotImplementedError("%s: a scale that is not above 0" % what)
+    L = logistic_table(s_x, z_x, s_l, z_l)
+    m, e = _multiplier(what, float(s_x) * float(s_l) / float(s_out), 255 * 255)
+    lo, hi = clamp_of(act, s_out, z_out, what)
+    return np.array([min(max(z_out + _mbqm((q - z_x) * (int(L[q + 128]) - z_l), m, e), lo), hi) for q in range(-128, 128)], np.int8)
+
+
+def with_table(hdr, table):
+    """The header with the 256-entry table behind it: what `shift` points at for LUT_I8 and for an operator with the
+    activation LUT (include/cpx.h: CPX_GRAPH_I8_LUT_BYTES)."""
+    out = np.concatenate([np.asarray(hdr, np.uint8)[:4 * _lib.GRAPH_I8_HDR_WORDS], np.asarray(table, np.int8).view(np.uint8)])
+    assert out.size == _lib.GRAPH_I8_LUT_BYTES, out.size
+    return out
+
+
+def table_of(shift):
+    """-> the int8 table behind a header made by with_table."""
+    return np.asarray(shift, np.uint8)[4 * _lib.GRAPH_I8_HDR_WORDS:].view(np.int8)
+
+
+def _emit_table(s, i, x, y, table, name, readers):
+    """y = T[x]: folded into x's producer as the activation LUT where _fold_into_producer allows it (a kind of KINDS' table
+    column that carries no table yet; x an own tensor with exactly `readers` readers, not the output), else ONE LUT_I8
+    launch x -> y."""
+    from .tflite_graph import LUT_INTO, PlanOp, _fold_into_producer
+
+    if _fold_into_producer(s, x, y, LUT_INTO, name, _lib.GRAPH_ACT_LUT, readers=readers):
+        p = s.producer[y]
+        p.shift = with_table(p.shift, table)
+    else:
+        s.emit(PlanOp(_lib.GRAPH_LUT_I8, name, x.id, y, shift=with_table(header(), table)), i)
+
+
+def lower_integer_swish(s, i, mul, logistic, x, y, what):
+    """integer_lut: the swish y = MUL(x, LOGISTIC(x)) (tflite_graph._find_swishes) on INT8 tensors as one table of x."""
+    from .tflite_graph import PlanTensor
+
+    g = s.g
+    if not all(is_int8(g, t) for t in (x.id, y, logistic["outputs"][0])):
+        raise NotImplementedError("%s mixes INT8 and float32 activations: only QUANTIZE and DEQUANTIZE change the type" % what)
+    table = swish_table(qparams(g, x.id), qparams(g, logistic["outputs"][0]), qparams(g, y), mul.get("act", 0), what)
+    s.T[y] = PlanTensor(y, x.H, x.W, x.C)
+    _emit_table(s, i, x, y, table, "SWISH", 2)
+
+
 def per_channel(m, shift, bias):
     """int32 [3][C]: M[c], shift[c], bias[c] of a filter kind, as bytes."""
     return np.ascontiguousarray(np.stack([np.asarray(m, np.int64), np.asarray(shift, np.int64), np.asarray(bias, np.int64)])
@@ -135,10 +213,11 @@ def _requantize(s, i, name, x, y, act, what, PlanOp):
     s.emit(PlanOp(_lib.GRAPH_QUANTIZE, name, x.id, y, shift=header(z_in=z_in, z_out=z_out, m0=m, s0=e, lo=lo, hi=hi)), i)
 
 
-def lower_integer_op(s, i, op, what, x, y, ins, act_ins, grouped_convolutions):
+def lower_integer_op(s, i, op, what, x, y, ins, act_ins, grouped_convolutions, integer_gate_mul=False, integer_lut=False):
     """One operator of the flatbuffer that reads or writes INT8 activations -> its PlanOps (tflite_graph.lower_ops calls this
     for such an operator).  -> False for the operators whose float32 lowering serves unchanged (RESHAPE: a view;
-    CONCATENATION: a placement, once the parameters are checked)."""
+    CONCATENATION: a placement, once the parameters are checked).  integer_gate_mul: a MUL by the [1, 1, C] gate of a
+    squeeze-and-excite block is MUL_I8 with the gate as in1; integer_lut: an interior LOGISTIC is a table (_emit_table)."""
     from .tflite_graph import PlanOp, PlanTensor, slice_pads, window
 
     g, T, name = s.g, s.T, op["name"]
@@ -222,8 +301,18 @@ def lower_integer_op(s, i, op, what, x, y, ins, act_ins, grouped_convolutions):
         if len(act_ins) == 2:
             b = T[act_ins[1]]
             if (x.H, x.W, x.C) != (b.H, b.W, b.C):
-                raise NotImplementedError("%s of two INT8 tensors of shapes %s, %s: only one shape is run (a [1, 1, C] gate "
-                                          "is not)" % (what, (x.H, x.W, x.C), (b.H, b.W, b.C)))
+                if not integer_gate_mul:
+                    raise NotImplementedError("%s of two INT8 tensors of shapes %s, %s: only one shape is run (a [1, 1, C] gate "
+                                              "is not); build_plan(integer_gate_mul=True) plans a MUL by such a gate as MUL_I8"
+                                              % (what, (x.H, x.W, x.C), (b.H, b.W, b.C)))
+                # [H, W, C] by the [1, 1, C] gate of its sample, in either order: the gate is in1
+                if name == "MUL" and (x.H, x.W, x.C) == (1, 1, b.C):
+                    x, b = b, x
+                if name != "MUL" or (b.H, b.W, b.C) != (1, 1, x.C):
+                    raise NotImplementedError("%s of two INT8 tensors of shapes %s, %s: only one shape, or for a MUL [H, W, C] "
+                                              "by [1, 1, C]" % (what, (T[act_ins[0]].H, T[act_ins[0]].W, T[act_ins[0]].C),
+                                                                (T[act_ins[1]].H, T[act_ins[1]].W, T[act_ins[1]].C)))
+                s1, z1 = qparams(g, x.id)
             s2, z2 = qparams(g, b.id)
             in1 = b.id
         else:
@@ -304,12 +393,18 @@ def lower_integer_op(s, i, op, what, x, y, ins, act_ins, grouped_convolutions):
                           pads=slice_pads(x.H, x.W, ho, wo, sh, sw, -y0, -x0), shift=header(z_in=z)), i)
         return True
     if name in ("SOFTMAX", "LOGISTIC"):
-        # DEQUANTIZE -> the float32 kernel -> QUANTIZE: three launches on a [N, labels] tensor.  The TFLite runtime's
-        # fixed-point tables may differ from it by a step
         s_in, z_in = qparams(g, x.id)
         s_out, z_out = qparams(g, y)
         if not (float(s_in) > 0.0 and float(s_out) > 0.0):
             raise NotImplementedError("%s: a scale that is not above 0" % what)
+        # integer_lut: an interior LOGISTIC (the gate's sigmoid; a swish's that could not be taken whole) is its table.  The
+        # head -- a DEQUANTIZE among the readers -- stays as below
+        if integer_lut and name == "LOGISTIC" and not any(g.ops[r]["name"] == "DEQUANTIZE" for r in s.consumers.get(y, [])):
+            T[y] = PlanTensor(y, x.H, x.W, x.C)
+            _emit_table(s, i, x, y, logistic_table(s_in, z_in, s_out, z_out), "LOGISTIC", 1)
+            return True
+        # DEQUANTIZE -> the float32 kernel -> QUANTIZE: three launches on a [N, labels] tensor.  The TFLite runtime's
+        # fixed-point tables may differ from it by a step
         t0, t1 = ("float", y, 0), ("float", y, 1)
         T[t0], T[t1], T[y] = PlanTensor(t0, x.H, x.W, x.C), PlanTensor(t1, x.H, x.W, x.C), PlanTensor(y, x.H, x.W, x.C)
         s.emit(PlanOp(_lib.GRAPH_DEQUANTIZE, "DEQUANTIZE", x.id, t0, param=float(s_in), shift=header(z_in=z_in)), i)

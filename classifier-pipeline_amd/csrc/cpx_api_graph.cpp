@@ -33,14 +33,16 @@ static const char* graph_check_op(const cpx_graph_op& o, const std::vector<cpx_g
   const cpx_graph_tensor &a = t[o.in0], &y = t[o.out];
   if (o.out_c_offset != y.c_offset || o.out_c_stride != y.c_stride) return "output slice differs from the tensor's";
   if (o.activation != CPX_GRAPH_ACT_NONE && o.activation != CPX_GRAPH_ACT_RELU && o.activation != CPX_GRAPH_ACT_RELU6 &&
-      o.activation != CPX_GRAPH_ACT_SWISH && o.activation != CPX_GRAPH_ACT_LOGISTIC)
+      o.activation != CPX_GRAPH_ACT_SWISH && o.activation != CPX_GRAPH_ACT_LOGISTIC && o.activation != CPX_GRAPH_ACT_LUT)
     return "unknown activation";
+  if (o.activation == CPX_GRAPH_ACT_LUT && o.kind != CPX_GRAPH_CONV_I8 && o.kind != CPX_GRAPH_CONV_I8_GROUPED && o.kind != CPX_GRAPH_DWCONV_I8)
+    return "the activation LUT (a table behind the int32 header) is taken by CONV_I8, CONV_I8_GROUPED and DWCONV_I8 only";
   const bool same_hw = a.H == y.H && a.W == y.W;
   // the element types each kind takes: float32 throughout, unless the kind says otherwise below
   const bool a8 = a.type == CPX_GRAPH_TYPE_INT8, y8 = y.type == CPX_GRAPH_TYPE_INT8;
   const bool b8 = o.in1 >= 0 && t[o.in1].type == CPX_GRAPH_TYPE_INT8;
   bool types_ok = !a8 && !y8 && !b8;
-  const bool i8_header = o.kind >= CPX_GRAPH_QUANTIZE && o.kind <= CPX_GRAPH_MEAN_I8;
+  const bool i8_header = o.kind >= CPX_GRAPH_QUANTIZE && o.kind <= CPX_GRAPH_LUT_I8;
   if (i8_header && (!o.shift || (reinterpret_cast<uintptr_t>(o.shift) & 3))) return "a full-integer operator without its int32 header in `shift`";
   auto is_params = [&](int id) { return id >= 0 && t[id].H == 1 && t[id].W == 1 && t[id].C == 4; };
   switch (o.kind) {
@@ -189,10 +191,19 @@ static const char* graph_check_op(const cpx_graph_op& o, const std::vector<cpx_g
     case CPX_GRAPH_ADD_I8:
     case CPX_GRAPH_MUL_I8:
       if (!same_hw || a.C != y.C) return "element-wise operator changes the shape";
-      if (o.in1 >= 0 && (t[o.in1].H != y.H || t[o.in1].W != y.W || t[o.in1].C != y.C)) return "ADD_I8 / MUL_I8 of different shapes";
+      if (o.in1 >= 0) {   // the shape of in0, or for MUL_I8 the 1 x 1 x C gate
+        const cpx_graph_tensor& b = t[o.in1];
+        const bool same = b.H == y.H && b.W == y.W, gate = o.kind == CPX_GRAPH_MUL_I8 && b.H == 1 && b.W == 1;
+        if (b.C != y.C || (!same && !gate)) return "ADD_I8 / MUL_I8 of different shapes (MUL_I8: in1 has the shape of in0 or is 1 x 1 x C)";
+      }
       if (o.in1 < 0 && !o.weights) return "ADD_I8 / MUL_I8 needs a second tensor or the constant in `weights`";
       if (o.kind == CPX_GRAPH_ADD_I8 && o.param != 1.0f && o.param != -1.0f) return "ADD_I8: param is 1 (ADD) or -1 (SUB)";
       if (!a8 || !y8 || (o.in1 >= 0 && !b8)) return "the operator takes int8 tensors and writes one";
+      types_ok = true;
+      break;
+    case CPX_GRAPH_LUT_I8:
+      if (!same_hw || a.C != y.C || o.in1 >= 0) return "LUT_I8 keeps the shape and has one input";
+      if (!a8 || !y8) return "the operator takes one int8 tensor and writes one";
       types_ok = true;
       break;
     case CPX_GRAPH_MEAN_I8:

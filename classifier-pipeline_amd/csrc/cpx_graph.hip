@@ -548,6 +548,7 @@ void launch_graph_op(const GraphOpArgs& a, hipStream_t s) {
     case CPX_GRAPH_MAX_POOL_I8:
     case CPX_GRAPH_AVG_POOL_I8:
     case CPX_GRAPH_MEAN_I8:
+    case CPX_GRAPH_LUT_I8:
       launch_graph_i8_op(a, s);
       break;
     case CPX_GRAPH_RANGE:

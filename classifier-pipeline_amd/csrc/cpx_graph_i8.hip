@@ -12,6 +12,10 @@
 // flattened batch per workgroup, the filter fragment image and its wsum unchanged, the group as blockIdx.z) with the A
 // image staged FROM BYTES -- a thread takes its pixel's 16 channels with one 16-byte load, or byte by byte; a masked
 // element is z_in, nothing is quantised -- and an epilogue that requantises in registers and stores bytes.
+//
+// A unary int8 -> int8 function (an interior LOGISTIC, a swish) is a 256-entry table behind the header (include/cpx.h,
+// "Tables"): LUT_I8 looks every byte up, and CONV_I8 / CONV_I8_GROUPED / DWCONV_I8 with CPX_GRAPH_ACT_LUT send their
+// requantised byte through it (the LUT template parameter).  The table sits in 256 bytes of LDS.
 #include <hip/hip_runtime.h>
 
 #include "cpx_graph_core.h"
@@ -105,7 +109,8 @@ __device__ __forceinline__ size_t at(const GraphView& v, size_t n, int rem, int 
   return n * v.sample_stride + (size_t)rem * v.cstride + c;
 }
 
-// ---- the element-wise operators: the two QUANTIZE forms, DEQUANTIZE, ADD_I8, MUL_I8 ----
+// ---- the element-wise operators: the two QUANTIZE forms, DEQUANTIZE, ADD_I8, MUL_I8 (in1 of one shape, the constant, or
+// MUL_I8's per-sample gate) ----
 enum { EW_QUANT = 0, EW_REQUANT = 1, EW_DEQUANT = 2, EW_ADD = 3, EW_MUL = 4 };
 
 template <int VW, int OP>
@@ -136,8 +141,8 @@ __global__ __launch_bounds__(CT) void graph_i8_ew_kernel(GraphOpArgs a, size_t i
       for (int j = 0; j < VW; ++j) q[j] = requantize_i8(q[j], h);
     } else {
       int b[VW];
-      if (a.in1.p)
-        load_q<VW>(bytes_of(a.in1) + at(a.in1, it.n, it.rem, it.c), b);
+      if (a.in1.p)   // (MUL_I8's 1 x 1 x C gate: pixel 0 of its sample, whatever the output's pixel)
+        load_q<VW>(bytes_of(a.in1) + at(a.in1, it.n, OP == EW_MUL && a.in1.H * a.in1.W == 1 ? 0 : it.rem, it.c), b);
       else
         load_q<VW>(reinterpret_cast<const int8_t*>(a.weights) + it.c, b);   // the constant, per channel
       const int sign = a.param < 0.0f ? -1 : 1;
@@ -148,13 +153,44 @@ __global__ __launch_bounds__(CT) void graph_i8_ew_kernel(GraphOpArgs a, size_t i
   }
 }
 
+// ---- the 256-entry table of LUT_I8 and of CPX_GRAPH_ACT_LUT: one byte per thread into LDS (CT == 256); the caller's next
+// barrier publishes it
+static_assert(CT == 256, "a workgroup stages the table one entry per thread");
+__device__ __forceinline__ void stage_table(int8_t (&s_t)[256], const GraphOpArgs& a) {
+  s_t[threadIdx.x] = table_of(&header_of(a))[threadIdx.x];
+}
+
+// LUT_I8: the element-wise kernel's walk with sixteen lookups per lane between one 16-byte load and one 16-byte store.
+// A lookup is one LDS byte read: 16 of them per 32 bytes of HBM traffic, from a table of 64 dwords -- two dwords per
+// bank, so a read is at worst a two-way conflict (DESIGN.md section 5 has the arithmetic)
+template <int VW>
+__global__ __launch_bounds__(CT) void graph_i8_lut_kernel(GraphOpArgs a, size_t items) {
+  __shared__ int8_t s_t[256];
+  stage_table(s_t, a);
+  __syncthreads();
+  const size_t i = (size_t)blockIdx.x * CT + threadIdx.x;
+  if (i >= items) return;
+  const PixelItem it = pixel_item<VW>(i, a.out.C, a.out.H * a.out.W);
+  int q[VW];
+  load_q<VW>(bytes_of(a.in0) + at(a.in0, it.n, it.rem, it.c), q);
+#pragma unroll
+  for (int j = 0; j < VW; ++j) q[j] = lut_i8(s_t, q[j]);
+  store_q<VW>(bytes_of_out(a.out) + at(a.out, it.n, it.rem, it.c), q);
+}
+
 // ---- the window operators: DWCONV_I8, MAX_POOL_I8, AVG_POOL_I8 and SLICE on bytes ----
 enum { WIN_DW = 0, WIN_MAX = 1, WIN_AVG = 2, WIN_SLICE = 3 };
 
 // One output pixel and VW channels per lane.  Every read is masked by the input's size (SLICE's pads are signed).
 // DWCONV_I8 sums (q - z_in) * w over the in-bounds taps: a padded tap contributes nothing and no wsum is needed.
-template <int VW, int OP>
+// LUT (DWCONV_I8 with CPX_GRAPH_ACT_LUT): the finished byte goes through the table, staged before any thread leaves.
+template <int VW, int OP, bool LUT = false>
 __global__ __launch_bounds__(CT) void graph_i8_window_kernel(GraphOpArgs a, size_t items) {
+  __shared__ int8_t s_t[LUT ? 256 : 1];
+  if constexpr (LUT) {
+    stage_table(s_t, a);
+    __syncthreads();
+  }
   const size_t i = (size_t)blockIdx.x * CT + threadIdx.x;
   if (i >= items) return;
   const I8Header& h = header_of(a);
@@ -195,6 +231,7 @@ __global__ __launch_bounds__(CT) void graph_i8_window_kernel(GraphOpArgs a, size
     if constexpr (OP == WIN_DW) {
       // (wsum 0: the zero point is already out of the sum)
       acc[j] = filter_finish_i8(acc[j], 0, prm[2 * C + it.c + j], prm[it.c + j], prm[C + it.c + j], h);
+      if constexpr (LUT) acc[j] = lut_i8(s_t, acc[j]);
     } else if constexpr (OP == WIN_MAX) {
       acc[j] = clamp_i8(acc[j], lo, hi);
     } else if constexpr (OP == WIN_AVG) {
@@ -283,9 +320,13 @@ struct ConvI8Geom {
 
 // V16: the view's channel count per group, channel offsets, row stride and sample stride are multiples of 16 and its
 // pointer is 16-byte aligned -- a thread's 16 channels are one aligned 16-byte load and valid or masked as a whole.
-template <int NTN, bool GRP, bool V16>
+// LUT (CPX_GRAPH_ACT_LUT): the table is staged in front of the K walk -- the walk's first barrier publishes it -- and read
+// in the epilogue behind filter_finish_i8.
+template <int NTN, bool GRP, bool V16, bool LUT>
 __global__ __launch_bounds__(CT) void graph_conv_i8_kernel(GraphOpArgs a, ConvI8Geom g) {
   __shared__ __attribute__((aligned(16))) int s_a[2][BM * KQ / 4];   // [pixel][k], bytes
+  __shared__ int8_t s_t[LUT ? 256 : 1];
+  if constexpr (LUT) stage_table(s_t, a);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const long long p0 = (long long)blockIdx.x * BM;
   const int tile0 = blockIdx.y * NTN;
@@ -385,7 +426,9 @@ __global__ __launch_bounds__(CT) void graph_conv_i8_kernel(GraphOpArgs a, ConvI8
       const int i = acc_row(r, tid);
       if (pb + i >= g.P) continue;
       const SamplePixel o = sample_step(nb, remb + i, g.HoWo);
-      out[(size_t)o.n * a.out.sample_stride + (size_t)o.rem * a.out.cstride + ch] = (int8_t)filter_finish_i8(acc[t][r], ws, bias, M, sh, h);
+      int v = filter_finish_i8(acc[t][r], ws, bias, M, sh, h);
+      if constexpr (LUT) v = lut_i8(s_t, v);
+      out[(size_t)o.n * a.out.sample_stride + (size_t)o.rem * a.out.cstride + ch] = (int8_t)v;
     }
   }
 }
@@ -407,17 +450,17 @@ void launch_ew(const GraphOpArgs& a, bool wide, hipStream_t s) {
     hipLaunchKernelGGL((graph_i8_ew_kernel<1, OP>), dim3(blocks_for(elems)), dim3(CT), 0, s, a, elems);
 }
 
-template <int OP>
+template <int OP, bool LUT = false>
 void launch_window(const GraphOpArgs& a, hipStream_t s) {
   const size_t elems = (size_t)a.N * a.out.H * a.out.W * a.out.C;
   const bool wide = bytes16(a.in0) && bytes16(a.out) && (OP != WIN_DW || (reinterpret_cast<uintptr_t>(a.weights) & 15) == 0);
   if (wide)
-    hipLaunchKernelGGL((graph_i8_window_kernel<16, OP>), dim3(blocks_for(elems / 16)), dim3(CT), 0, s, a, elems / 16);
+    hipLaunchKernelGGL((graph_i8_window_kernel<16, OP, LUT>), dim3(blocks_for(elems / 16)), dim3(CT), 0, s, a, elems / 16);
   else
-    hipLaunchKernelGGL((graph_i8_window_kernel<1, OP>), dim3(blocks_for(elems)), dim3(CT), 0, s, a, elems);
+    hipLaunchKernelGGL((graph_i8_window_kernel<1, OP, LUT>), dim3(blocks_for(elems)), dim3(CT), 0, s, a, elems);
 }
 
-template <bool GRP>
+template <bool GRP, bool LUT>
 void launch_conv(const GraphOpArgs& a, hipStream_t s) {
   ConvI8Geom g;
   g.G = GRP ? a.n_map : 1;
@@ -436,9 +479,9 @@ void launch_conv(const GraphOpArgs& a, hipStream_t s) {
   do {                                                                                                         \
     const dim3 grid(gx, (GY), g.G);                                                                            \
     if (v16)                                                                                                   \
-      hipLaunchKernelGGL((graph_conv_i8_kernel<NTN, GRP, true>), grid, block, 0, s, a, g);                     \
+      hipLaunchKernelGGL((graph_conv_i8_kernel<NTN, GRP, true, LUT>), grid, block, 0, s, a, g);                \
     else                                                                                                       \
-      hipLaunchKernelGGL((graph_conv_i8_kernel<NTN, GRP, false>), grid, block, 0, s, a, g);                    \
+      hipLaunchKernelGGL((graph_conv_i8_kernel<NTN, GRP, false, LUT>), grid, block, 0, s, a, g);               \
   } while (0)
   if (g.ntiles == 1)
     CPX_CONV_I8(1, 1);
@@ -473,8 +516,19 @@ void launch_graph_i8_op(const GraphOpArgs& a, hipStream_t s) {
       break;
     }
     case CPX_GRAPH_DWCONV_I8:
-      launch_window<WIN_DW>(a, s);
+      if (a.act == CPX_GRAPH_ACT_LUT)
+        launch_window<WIN_DW, true>(a, s);
+      else
+        launch_window<WIN_DW>(a, s);
       break;
+    case CPX_GRAPH_LUT_I8: {
+      const size_t elems = (size_t)a.N * a.out.H * a.out.W * a.out.C;
+      if (bytes16(a.in0) && bytes16(a.out))
+        hipLaunchKernelGGL(graph_i8_lut_kernel<16>, dim3(blocks_for(elems / 16)), dim3(CT), 0, s, a, elems / 16);
+      else
+        hipLaunchKernelGGL(graph_i8_lut_kernel<1>, dim3(blocks_for(elems)), dim3(CT), 0, s, a, elems);
+      break;
+    }
     case CPX_GRAPH_MAX_POOL_I8:
       launch_window<WIN_MAX>(a, s);
       break;
@@ -502,10 +556,16 @@ void launch_graph_i8_op(const GraphOpArgs& a, hipStream_t s) {
       break;
     }
     case CPX_GRAPH_CONV_I8:
-      launch_conv<false>(a, s);
+      if (a.act == CPX_GRAPH_ACT_LUT)
+        launch_conv<false, true>(a, s);
+      else
+        launch_conv<false, false>(a, s);
       break;
     case CPX_GRAPH_CONV_I8_GROUPED:
-      launch_conv<true>(a, s);
+      if (a.act == CPX_GRAPH_ACT_LUT)
+        launch_conv<true, true>(a, s);
+      else
+        launch_conv<true, false>(a, s);
       break;
     default:
       break;

@@ -101,4 +101,9 @@ CPX_HD inline int32_t filter_finish_i8(int32_t acc, int32_t wsum, int32_t bias, 
   return clamp_i8(h.v[CPX_GRAPH_I8_HDR_Z_OUT] + mbqm(v, M, shift), h.v[CPX_GRAPH_I8_HDR_LO], h.v[CPX_GRAPH_I8_HDR_HI]);
 }
 
+// LUT_I8 and CPX_GRAPH_ACT_LUT: the 256-entry table rides behind the header; a sign-extended byte q reads entry q + 128
+CPX_HD inline const int8_t* table_of(const I8Header* h) { return reinterpret_cast<const int8_t*>(h + 1); }
+CPX_HD inline int lut_index(int32_t q) { return q + 128; }
+CPX_HD inline int32_t lut_i8(const int8_t* table, int32_t q) { return table[lut_index(q)]; }
+
 }  // namespace cpx

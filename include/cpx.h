@@ -910,7 +910,8 @@ enum {
   CPX_GRAPH_DEQUANTIZE = 27, /* int8 -> float32: param = the input's scale, header Z_IN */
   CPX_GRAPH_CONV_I8 = 28,    /* CONV_2D, int8 in, int8 out.  `weights`: CONV_Q8's bytes unchanged (fragment image, then
                                 wsum).  `scale` is reinterpreted as int32 [3][out C]: M[c], shift[c], bias[c], not NULL.
-                                Header Z_IN, Z_OUT, LO, HI.  `activation` is ignored: the clamp carries it */
+                                Header Z_IN, Z_OUT, LO, HI.  `activation`: CPX_GRAPH_ACT_LUT (see there), every other
+                                value is ignored: the clamp carries a RELU / RELU6 */
   CPX_GRAPH_CONV_I8_GROUPED = 29, /* n_map = G; `weights`: CONV_Q8_GROUPED's bytes unchanged; scale, header: as CONV_I8,
                                 indexed by the absolute output channel */
   CPX_GRAPH_DWCONV_I8 = 30,  /* depth multiplier 1, sides 1 to 7, strides 1 or 2.  `weights`: DWCONV_Q8's bytes unchanged
@@ -919,10 +920,15 @@ enum {
   CPX_GRAPH_ADD_I8 = 32,     /* param 1 (ADD) or -1 (SUB).  in1: an int8 tensor of in0's shape, or -1: then `weights` is
                                 reinterpreted as int8 [C], the constant per channel.  Header Z_IN, Z_IN1, Z_OUT, LO, HI,
                                 M0 / S0, M1 / S1, MO / SO, LEFT = 20 */
-  CPX_GRAPH_MUL_I8 = 33,     /* operands as ADD_I8.  Header Z_IN, Z_IN1, Z_OUT, LO, HI, M0 / S0 = QM(s1 * s2 / s_out) */
+  CPX_GRAPH_MUL_I8 = 33,     /* operands as ADD_I8; in1 may also be a 1 x 1 x C int8 tensor, the per-sample gate of a
+                                squeeze-and-excite block broadcast over H and W (as CPX_GRAPH_MUL's).  Header Z_IN, Z_IN1,
+                                Z_OUT, LO, HI, M0 / S0 = QM(s1 * s2 / s_out) */
   CPX_GRAPH_MAX_POOL_I8 = 34,/* window, strides and pads as MAX_POOL; header LO, HI */
   CPX_GRAPH_AVG_POOL_I8 = 35,/* as AVG_POOL; header LO, HI */
-  CPX_GRAPH_MEAN_I8 = 36     /* over H and W -> 1 x 1 x C.  Header M0 / S0 = QM(s_in / s_out), LEFT = the bias, LO, HI */
+  CPX_GRAPH_MEAN_I8 = 36,    /* over H and W -> 1 x 1 x C.  Header M0 / S0 = QM(s_in / s_out), LEFT = the bias, LO, HI */
+  CPX_GRAPH_LUT_I8 = 37      /* a unary int8 -> int8 function as its 256-entry table: out = T[in0 + 128], element-wise, the
+                                same shape; in0 and out are int8 views (channel slices included).  `shift`: the header
+                                (unused, zeros) followed by the table, CPX_GRAPH_I8_LUT_BYTES in all */
 };
 /* The full-integer arithmetic: the TFLite reference integer kernels' as published (parity with a TFLite runtime is not
  * pinned: its optimised and single-rounding builds differ in the last step).  Written once in csrc/cpx_graph_i8_core.h.
@@ -943,13 +949,25 @@ enum {
  * MAX_POOL_I8: the maximum over the in-bounds window, clamped.  AVG_POOL_I8: acc = sum q over the n in-bounds elements,
  * out = clamp(acc > 0 ? (acc + n / 2) / n : (acc - n / 2) / n), truncating division.
  * MEAN_I8: acc = MBQM(sum q, M0, S0), divided by n = H * W with AVG_POOL_I8's rounding, + LEFT (the bias), clamped.
- * SLICE on int8 tensors copies bytes (param 0, activation NONE); its zero region is header Z_IN. */
+ * SLICE on int8 tensors copies bytes (param 0, activation NONE); its zero region is header Z_IN.
+ * Tables.  A function of ONE int8 value is 256 int8 entries T[q + 128], q = -128 .. 127, made by the caller on the host:
+ * - an INT8 LOGISTIC with input (s_in, z_in) and output (s_out, z_out), in float64: x = float64(float32(s_in) *
+ *   float32(q - z_in)), p = 1 / (1 + exp(-x)), L[q + 128] = clamp(round-half-away(p / float64(s_out)) + z_out, -128, 127):
+ *   the float64 function of the dequantised input, rounded half away;
+ * - a swish y = MUL(x, LOGISTIC(x)): S[q + 128] = MUL_I8(q, L[q + 128]) with the MUL's own header (Z_IN of x, Z_IN1 of the
+ *   LOGISTIC's output, Z_OUT, M0 / S0, LO / HI: the MUL's fused activation lives in the table).
+ * LUT_I8: out = T[in0 + 128].  CPX_GRAPH_ACT_LUT as the `activation` of CONV_I8, CONV_I8_GROUPED or DWCONV_I8 (no other
+ * kind takes it): out = T[r + 128], r the operator's requantised, clamped result -- header Z_OUT / LO / HI and the
+ * per-channel M / shift are those of the tensor the convolution wrote before the table was folded into it.  For LUT_I8
+ * and for an operator with ACT_LUT `shift` points at the CPX_GRAPH_I8_HDR_WORDS header words followed by the 256 table
+ * bytes: CPX_GRAPH_I8_LUT_BYTES = 320 bytes of device memory. */
 enum { CPX_GRAPH_TYPE_FLOAT32 = 0, CPX_GRAPH_TYPE_INT8 = 1 };   /* cpx_graph_tensor.type */
 enum {
   CPX_GRAPH_I8_HDR_Z_IN = 0, CPX_GRAPH_I8_HDR_Z_IN1 = 1, CPX_GRAPH_I8_HDR_Z_OUT = 2, CPX_GRAPH_I8_HDR_LO = 3,
   CPX_GRAPH_I8_HDR_HI = 4, CPX_GRAPH_I8_HDR_M0 = 5, CPX_GRAPH_I8_HDR_S0 = 6, CPX_GRAPH_I8_HDR_M1 = 7, CPX_GRAPH_I8_HDR_S1 = 8,
   CPX_GRAPH_I8_HDR_MO = 9, CPX_GRAPH_I8_HDR_SO = 10, CPX_GRAPH_I8_HDR_LEFT = 11,
-  CPX_GRAPH_I8_HDR_WORDS = 16   /* int32 words of the header; the words not named are 0 */
+  CPX_GRAPH_I8_HDR_WORDS = 16,  /* int32 words of the header; the words not named are 0 */
+  CPX_GRAPH_I8_LUT_BYTES = 4 * 16 + 256   /* the header with a 256-entry int8 table behind it */
 };
 /* The fp16x2 arithmetic, per sample.  RANGE: m = max |x| over the view in float32.  m == 0 or m not finite (inf, NaN):
  * up = down = 1.  Otherwise m = f * 2^e with f in [0.5, 1) (frexp), k = min(15 - e, 100), up = 2^k, down = 2^-k: both
@@ -977,7 +995,9 @@ enum {
    * LOGISTIC and the MUL behind it, into.  Each operation in float32 as written: a fused SWISH is the same float32
    * operations as a LOGISTIC launch followed by a MUL launch. */
   CPX_GRAPH_ACT_SWISH = 16,    /* v * (1 / (1 + expf(-v))) */
-  CPX_GRAPH_ACT_LOGISTIC = 17  /* 1 / (1 + expf(-v)): what CPX_GRAPH_LOGISTIC computes */
+  CPX_GRAPH_ACT_LOGISTIC = 17, /* 1 / (1 + expf(-v)): what CPX_GRAPH_LOGISTIC computes */
+  CPX_GRAPH_ACT_LUT = 18       /* CONV_I8 / CONV_I8_GROUPED / DWCONV_I8 only: the int8 result goes through the 256-entry
+                                  table behind the header ("Tables" above) */
 };
 
 typedef struct cpx_graph_tensor {

@@ -80,7 +80,17 @@ process on the same card in alternating rounds, the same network's hybrid plan a
 rounds and their scatter, the launches by kind, the arena bytes per sample.  --int8 --skip-torch runs the full-integer
 plans alone at the last batch size (a run under `rocprofv3 --kernel-trace --stats`, whose per-kernel times give CONV_I8's
 share and the DWCONV_I8 / SLICE bytes per second: the bytes are printed as dwconv_i8_bytes / slice_bytes; --int8-net wr |
-mobilenet keeps one network's kernels in the trace)."""
+mobilenet keeps one network's kernels in the trace).
+
+    python tools/bench_tflite.py --int8 --int8-net efficientnet [--batches 1,8,128] [--rounds 3]
+
+is the same for a width-1.0 EfficientNet-B0 (tests/tflite_build_se.py through quantise_full), with FOUR legs interleaved:
+the full-integer plan with its tables (`int8`: integer_gate_mul and integer_lut, every swish and gate sigmoid folded into
+its convolution), the full-integer plan with integer_lut=False (`int8_no_lut`: the gate MUL_I8 only, every LOGISTIC as
+DEQUANTIZE -> LOGISTIC -> QUANTIZE), the hybrid plan and the float32 plan.  With --skip-torch the tabled plan runs alone,
+followed by one forward of a probe graph whose only int8 launch is a LUT_I8 (the EfficientNet's own plan has none: every
+table folds) -- under `rocprofv3 --kernel-trace --stats` graph_i8_lut_kernel's time against lut_i8_probe_bytes and
+graph_i8_ew_kernel<16, 4>'s against gate_mul_i8_bytes_per_sample x N are the two launches' bytes per second."""
 import argparse
 import json
 import os
@@ -96,7 +106,7 @@ KIND_NAMES = {24: "conv_grouped", 25: "conv_q8_grouped", 1: "conv", 2: "max_pool
               10: "pad", 11: "channel_map", 12: "conv_q8", 13: "fc_q8", 14: "quant_params", 15: "dwconv", 16: "dwconv_q8", 17: "mul", 18: "input", 19: "conv_pre",
               20: "slice", 21: "dwconv_pre", 22: "range", 23: "conv_f16x2", 26: "quantize", 27: "dequantize", 28: "conv_i8",
               29: "conv_i8_grouped", 30: "dwconv_i8", 31: "fc_i8", 32: "add_i8", 33: "mul_i8", 34: "max_pool_i8", 35: "avg_pool_i8",
-              36: "mean_i8"}
+              36: "mean_i8", 37: "lut_i8"}
 CONV_KINDS = (1, 12, 19, 23)
 DW_KINDS = (15, 16, 21)
 FOLDS = dict(fold_windows=True, fuse_preactivation_dw=True, fuse_preactivation=True)
@@ -276,13 +286,15 @@ def wrresnet_leg(args):
 
 
 def int8_leg(args):
-    """The WR-ResNet-22-4 and a MobileNetV2 as full-integer files against their hybrid and float32 plans, interleaved."""
+    """The WR-ResNet-22-4, a MobileNetV2 and (where it is named) an EfficientNet-B0 as full-integer files against their hybrid
+    and float32 plans, interleaved."""
     import ctypes as C
 
     import tflite_build as tb
     import tflite_build_dw as td
     import tflite_build_i8 as ti
     import tflite_build_q8 as tq
+    import tflite_build_se as ts
     import torch
     from cpx import _lib
     from cpx.engine import TrackEngine
@@ -293,18 +305,27 @@ def int8_leg(args):
     eng = TrackEngine(model="lepton3", device=0)
     stream = torch.cuda.ExternalStream(eng.lib.cpx_stream(eng.h), device=eng.device)
     rng = np.random.default_rng(0)
-    xcal = torch.from_numpy(np.random.default_rng(1).uniform(0, 255, size=(2, 160, 160, 2)).astype(np.float32)).to(eng.device)
-    w = wr.calibrate_bn_device(eng, wr.random_weights(17, seed=3), xcal)
-    nets = {"wr-resnet-22-4 groups 2 160x160x2": (tb.wrresnet(w), tq.quantise, (160, 160, 2), (0.0, 255.0)),
-            "mobilenet_v2 width 1.00 160x160x3": (td.mobilenet_v2(17, width=1.0, seed=7), td.quantise, (160, 160, 3), (-1.0, 1.0))}
+    nets = {}
+    if args.int8_net in ("all", "wr"):
+        xcal = torch.from_numpy(np.random.default_rng(1).uniform(0, 255, size=(2, 160, 160, 2)).astype(np.float32)).to(eng.device)
+        w = wr.calibrate_bn_device(eng, wr.random_weights(17, seed=3), xcal)
+        nets["wr-resnet-22-4 groups 2 160x160x2"] = (tb.wrresnet(w), tq.quantise, (160, 160, 2), (0.0, 255.0))
+    if args.int8_net in ("all", "mobilenet"):
+        nets["mobilenet_v2 width 1.00 160x160x3"] = (td.mobilenet_v2(17, width=1.0, seed=7), td.quantise, (160, 160, 3), (-1.0, 1.0))
+    if args.int8_net == "efficientnet":   # (the model rescales and normalises its 0 .. 255 input itself)
+        nets["efficientnet_b0 width 1.00 160x160x3"] = (ts.efficientnet_b0(17, (), seed=7, width=1.0, size=160), td.quantise,
+                                                        (160, 160, 3), (0.0, 255.0))
     out = {"networks": []}
     batches = [int(v) for v in args.batches.split(",")]
     for model, (blob, hybrid_of, shape, (lo, hi)) in nets.items():
-        if args.int8_net not in ("all", model.split("-")[0].split("_")[0]):
-            continue
         full = ti.quantise_full(blob, np.random.default_rng(2).uniform(lo, hi, size=(1,) + shape))
         opts = dict(grouped_convolutions=True, **FOLDS)
-        plans = {"int8": build_plan(Graph(full), integer_activations=True, **opts)}
+        if model.startswith("efficientnet"):
+            plans = {"int8": build_plan(Graph(full), integer_activations=True, integer_gate_mul=True, integer_lut=True, **opts)}
+            if not args.skip_torch:
+                plans["int8_no_lut"] = build_plan(Graph(full), integer_activations=True, integer_gate_mul=True, **opts)
+        else:
+            plans = {"int8": build_plan(Graph(full), integer_activations=True, **opts)}
         if not args.skip_torch:
             plans.update(hybrid=build_plan(Graph(hybrid_of(blob)), **opts), float32=build_plan(Graph(blob), **opts))
         p8 = plans["int8"]
@@ -318,6 +339,13 @@ def int8_leg(args):
                                                  for o in p8.ops if o.kind == _lib.GRAPH_DWCONV_I8),
                "slice_bytes_per_sample": sum(2 * p8.tensors[o.out].H * p8.tensors[o.out].W * p8.tensors[o.out].C
                                              for o in p8.ops if o.kind == _lib.GRAPH_SLICE),
+               # (a gate MUL_I8 reads and writes the map once; the gate itself is C bytes)
+               "gate_mul_i8_bytes_per_sample": sum(2 * p8.tensors[o.out].H * p8.tensors[o.out].W * p8.tensors[o.out].C + p8.tensors[o.in1].C
+                                                   for o in p8.ops if o.kind == _lib.GRAPH_MUL_I8 and o.in1 != -1 and
+                                                   p8.tensors[o.in1].H * p8.tensors[o.in1].W == 1 < p8.tensors[o.out].H * p8.tensors[o.out].W),
+               "lut_i8_bytes_per_sample": sum(2 * p8.tensors[o.out].H * p8.tensors[o.out].W * p8.tensors[o.out].C
+                                              for o in p8.ops if o.kind == _lib.GRAPH_LUT_I8),
+               "folded_tables": sum(o.act == _lib.GRAPH_ACT_LUT for o in p8.ops),
                "conv_i8_gop_per_sample": sum(2.0 * p8.tensors[o.out].H * p8.tensors[o.out].W * p8.tensors[o.out].C * o.kh * o.kw *
                                              p8.tensors[o.in0].C / o.groups for o in p8.ops
                                              if o.kind in (_lib.GRAPH_CONV_I8, _lib.GRAPH_CONV_I8_GROUPED)) / 1e9,
@@ -343,10 +371,41 @@ def int8_leg(args):
                 b[k + "_runs_ms"] = [round(t, 4) for t in v]
             if "hybrid_ms" in b:
                 b["hybrid_over_int8"], b["float32_over_int8"] = b["hybrid_ms"] / b["int8_ms"], b["float32_ms"] / b["int8_ms"]
+            if "int8_no_lut_ms" in b:
+                b["no_lut_over_int8"] = b["int8_no_lut_ms"] / b["int8_ms"]
             rec["batches"].append(b)
+        if args.skip_torch and model.startswith("efficientnet"):
+            rec["lut_i8_probe_bytes"] = lut_i8_probe(eng, stream, batches[-1])
         out["networks"].append(rec)
     eng.close()
     print(json.dumps(out))
+
+
+def lut_i8_probe(eng, stream, n):
+    """One forward of QUANTIZE -> swish -> DEQUANTIZE on [n, 80, 80, 96] (the EfficientNet-B0's widest expanded map): the
+    swish has nothing to fold into, so it is ONE LUT_I8 launch, the only graph_i8_lut_kernel of a trace.  -> the bytes that
+    launch moves (in and out once)."""
+    import ctypes as C
+
+    import tflite_build_i8_se as tis
+    import torch
+    from cpx.ml_tools.tflite_graph import GraphDevice, build_plan
+    from cpx.ml_tools.tflite_reader import Graph
+
+    shape = (80, 80, 96)
+    m, q = tis.start([1] + list(shape), (np.float32(0.05), 7))
+    plan = build_plan(Graph(tis.finish(m, m.swish_i8(q, (np.float32(0.026), -117)))), integer_activations=True, integer_lut=True)
+    assert [KIND_NAMES[o.kind] for o in plan.ops] == ["quantize", "lut_i8", "dequantize"]
+    x = torch.from_numpy(np.random.default_rng(3).uniform(-6, 6, size=(n,) + shape).astype(np.float32)).to(eng.device)
+    y = torch.empty((n,) + shape, dtype=torch.float32, device=eng.device)
+    dev = GraphDevice(eng, plan)
+    with torch.cuda.stream(stream):
+        for _ in range(3):
+            rc = eng.lib.cpx_graph_forward(dev._graph, C.c_void_p(x.data_ptr()), n, C.c_void_p(y.data_ptr()))
+            assert rc == 0, eng._err()
+    torch.cuda.synchronize()
+    dev.close()
+    return 2 * n * int(np.prod(shape))
 
 
 def quantised_leg(args):
@@ -914,8 +973,9 @@ def main():
     ap.add_argument("--rounds", type=int, default=3, help="with --conv-math fp16x2: alternating rounds per batch size (median, scatter)")
     ap.add_argument("--int8", action="store_true",
                     help="the WR-ResNet-22-4 and a MobileNetV2 as full-integer files beside their hybrid and float32 plans, interleaved")
-    ap.add_argument("--int8-net", default="all", choices=("all", "wr", "mobilenet"),
-                    help="with --int8: one of the two networks alone (a run under a profiler: the kernels of one network in the trace)")
+    ap.add_argument("--int8-net", default="all", choices=("all", "wr", "mobilenet", "efficientnet"),
+                    help="with --int8: one network alone (a run under a profiler: the kernels of one network in the trace).  all: the "
+                         "WR-ResNet and the MobileNetV2; efficientnet: an EfficientNet-B0, with and without its tables, when named")
     args = ap.parse_args()
     if args.int8:
         if args.batches == "1,8,32,128":

@@ -12,7 +12,9 @@ stands for, which the fused kernels run (CPX_TFLITE_QUANT_MATH=float does the sa
 refused by the name of its first INT8 tensor.  --describe plans a grouped CONV_2D as LiteInterpreter does
 (grouped_convolutions=True) and prints each grouped convolution's G, the hybrid ones marked and counted in the census.  A
 full-integer file (INT8 activations, QUANTIZE / DEQUANTIZE) is planned as LiteInterpreter plans it too
-(integer_activations=True): the tensor types and the smaller per-sample arena are printed, or the refusal.
+(integer_activations=True, integer_gate_mul=True, integer_lut=True): the tensor types and the smaller per-sample arena are
+printed, the 256-entry tables an INT8 LOGISTIC or swish became -- folded into the convolution in front (CONV_2D+SWISH,
+CONV_2D+LOGISTIC in the census) or a LUT_I8 launch of their own (SWISH, LOGISTIC) -- or the refusal.
 
 --describe converts nothing: it prints the operator census, the input and output shapes, the arena bytes per sample and,
 for a dynamic-range quantised file, the number of hybrid operators with the int8 against the float32 weight bytes of ANY graph the device executor runs (cpx/ml_tools/tflite_graph.py: an Inception-v3, a MobileNetV2 or an EfficientNet, say; the launches carry what was folded into them: CONV_2D+SWISH, CONV_2D+LOGISTIC, CONV_2D+MUL+ADD, AFFINE>CONV_2D for a folded pre-activation; a second line gives the launches with the window folds on, as LiteInterpreter runs the file: PAD>DEPTHWISE_CONV_2D, RELU>DEPTHWISE_CONV_2D, PAD>STRIDED_SLICE>AVERAGE_POOL_2D), or the refusal -- the
@@ -62,15 +64,15 @@ def input_mode_of(sidecar):
 def describe(g, sidecar=None, conv_math="f32"):
     from cpx.ml_tools.tflite_graph import build_plan
 
+    I8 = dict(integer_activations=True, integer_gate_mul=True, integer_lut=True)   # a full-integer file, as LiteInterpreter plans it
     census = {}
     for op in g.ops:
         census[op["name"]] = census.get(op["name"], 0) + 1
     print("operators: " + ", ".join("%s: %d" % kv for kv in sorted(census.items())))
     try:
         # every PAD, 1 x 1 pool and slice a launch (CPX_TFLITE_FOLD_WINDOWS=0), and what LiteInterpreter runs
-        unfolded = build_plan(g, fuse_preactivation=True, grouped_convolutions=True, integer_activations=True)
-        plan = build_plan(g, fuse_preactivation=True, fuse_preactivation_dw=True, fold_windows=True, grouped_convolutions=True,
-                          integer_activations=True)
+        unfolded = build_plan(g, fuse_preactivation=True, grouped_convolutions=True, **I8)
+        plan = build_plan(g, fuse_preactivation=True, fuse_preactivation_dw=True, fold_windows=True, grouped_convolutions=True, **I8)
     except NotImplementedError as e:
         print("refused: %s" % e)
         return 1
@@ -86,6 +88,12 @@ def describe(g, sidecar=None, conv_math="f32"):
         full = [o for o in plan.ops if o.kind in I8_FILTER_KINDS]
         print("tensor types: %d int8, %d float32; full-integer filter operators (int8 in, int8 out): %d, int8 weight bytes: %d"
               % (n8, len(plan.tensors) - n8, len(full), sum(int(np.prod(o.filter.shape)) for o in full)))
+        from cpx import _lib
+
+        print("tables (an INT8 LOGISTIC or swish as 256 entries): %d folded into their convolutions, %d LUT_I8 launches; gate MUL_I8: %d"
+              % (sum(o.act == _lib.GRAPH_ACT_LUT for o in plan.ops), sum(o.kind == _lib.GRAPH_LUT_I8 for o in plan.ops),
+                 sum(o.kind == _lib.GRAPH_MUL_I8 and o.in1 != -1 and plan.tensors[o.in1].H * plan.tensors[o.in1].W == 1
+                     < plan.tensors[o.out].H * plan.tensors[o.out].W for o in plan.ops)))
     grouped = [o for o in plan.ops if o.kind in GROUPED_KINDS]
     if grouped:
         print("grouped convolutions: %d (%d hybrid): " % (len(grouped), sum(o.kind in Q8_KINDS for o in grouped))
@@ -100,9 +108,8 @@ def describe(g, sidecar=None, conv_math="f32"):
         # what CPX_TFLITE_CONV_MATH=fp16x2 makes of the file, with LiteInterpreter's default folds
         from cpx import _lib
 
-        base = build_plan(g, fuse_preactivation=True, fold_windows=True, grouped_convolutions=True, integer_activations=True)
-        h2 = build_plan(g, fuse_preactivation=True, fold_windows=True, conv_math=conv_math, grouped_convolutions=True,
-                        integer_activations=True)
+        base = build_plan(g, fuse_preactivation=True, fold_windows=True, grouped_convolutions=True, **I8)
+        h2 = build_plan(g, fuse_preactivation=True, fold_windows=True, conv_math=conv_math, grouped_convolutions=True, **I8)
         n_h2 = sum(o.kind == _lib.GRAPH_CONV_F16X2 for o in h2.ops)
         n_range = sum(o.kind == _lib.GRAPH_RANGE for o in h2.ops)
         n_pre = sum(o.kind == _lib.GRAPH_CONV_PRE for o in base.ops)
