@@ -24,6 +24,20 @@ void graph_free(cpx_graph* g) { delete g; }
 
 extern "C" {
 
+// the window of a convolution or a pool: kernel sides, strides (1 to smax; `bad_stride` names a miss), pads and the
+// output size that follows from them.  NULL: it fits.
+static const char* graph_check_window(const cpx_graph_op& o, const cpx_graph_tensor& a, const cpx_graph_tensor& y, int smax,
+                                      const char* bad_stride) {
+  if (o.kh < 1 || o.kw < 1 || o.kh > 7 || o.kw > 7) return "kernel sides are 1 to 7";
+  if (o.stride_h < 1 || o.stride_w < 1 || o.stride_h > smax || o.stride_w > smax) return bad_stride;
+  if (o.pad_top < 0 || o.pad_left < 0 || o.pad_bottom < 0 || o.pad_right < 0 || o.pad_top >= o.kh || o.pad_bottom >= o.kh ||
+      o.pad_left >= o.kw || o.pad_right >= o.kw)
+    return "bad padding";
+  const int hh = a.H + o.pad_top + o.pad_bottom - o.kh, ww = a.W + o.pad_left + o.pad_right - o.kw;
+  if (hh < 0 || ww < 0 || y.H != hh / o.stride_h + 1 || y.W != ww / o.stride_w + 1) return "output size does not follow from kernel, stride and pads";
+  return nullptr;
+}
+
 // what one operator asks of its tensors; every kernel masks by these sizes, so a graph that passes cannot reach outside
 // the views it names (the weights' extents are the caller's: device pointers cannot be measured)
 static const char* graph_check_op(const cpx_graph_op& o, const std::vector<cpx_graph_tensor>& t, int input, int output) {
@@ -61,14 +75,7 @@ static const char* graph_check_op(const cpx_graph_op& o, const std::vector<cpx_g
       const bool grouped = o.kind == CPX_GRAPH_CONV_GROUPED || o.kind == CPX_GRAPH_CONV_Q8_GROUPED;
       const bool conv = dw || grouped || o.kind == CPX_GRAPH_CONV || o.kind == CPX_GRAPH_CONV_PRE || o.kind == CPX_GRAPH_CONV_Q8 ||
                         o.kind == CPX_GRAPH_CONV_F16X2;
-      if (o.kh < 1 || o.kw < 1 || o.kh > 7 || o.kw > 7) return "kernel sides are 1 to 7";
-      if (grouped && (o.stride_h < 1 || o.stride_w < 1 || o.stride_h > 3 || o.stride_w > 3)) return "grouped CONV: strides are 1 to 3";
-      if (!grouped && (o.stride_h < 1 || o.stride_w < 1 || o.stride_h > (conv ? 2 : 7) || o.stride_w > (conv ? 2 : 7))) return "bad stride";
-      if (o.pad_top < 0 || o.pad_left < 0 || o.pad_bottom < 0 || o.pad_right < 0 || o.pad_top >= o.kh || o.pad_bottom >= o.kh ||
-          o.pad_left >= o.kw || o.pad_right >= o.kw)
-        return "bad padding";
-      const int hh = a.H + o.pad_top + o.pad_bottom - o.kh, ww = a.W + o.pad_left + o.pad_right - o.kw;
-      if (hh < 0 || ww < 0 || y.H != hh / o.stride_h + 1 || y.W != ww / o.stride_w + 1) return "output size does not follow from kernel, stride and pads";
+      if (const char* bad = graph_check_window(o, a, y, grouped ? 3 : conv ? 2 : 7, grouped ? "grouped CONV: strides are 1 to 3" : "bad stride")) return bad;
       if (conv && !o.weights) return "CONV without weights";
       if (!conv && a.C != y.C) return "pool changes the channel count";
       if (dw && a.C != y.C) return "DWCONV changes the channel count (depth multiplier 1 only)";
@@ -166,14 +173,7 @@ static const char* graph_check_op(const cpx_graph_op& o, const std::vector<cpx_g
     case CPX_GRAPH_AVG_POOL_I8: {
       const bool dw = o.kind == CPX_GRAPH_DWCONV_I8, grouped = o.kind == CPX_GRAPH_CONV_I8_GROUPED;
       const bool conv = dw || grouped || o.kind == CPX_GRAPH_CONV_I8;
-      if (o.kh < 1 || o.kw < 1 || o.kh > 7 || o.kw > 7) return "kernel sides are 1 to 7";
-      const int smax = grouped ? 3 : conv ? 2 : 7;
-      if (o.stride_h < 1 || o.stride_w < 1 || o.stride_h > smax || o.stride_w > smax) return "bad stride";
-      if (o.pad_top < 0 || o.pad_left < 0 || o.pad_bottom < 0 || o.pad_right < 0 || o.pad_top >= o.kh || o.pad_bottom >= o.kh ||
-          o.pad_left >= o.kw || o.pad_right >= o.kw)
-        return "bad padding";
-      const int hh = a.H + o.pad_top + o.pad_bottom - o.kh, ww = a.W + o.pad_left + o.pad_right - o.kw;
-      if (hh < 0 || ww < 0 || y.H != hh / o.stride_h + 1 || y.W != ww / o.stride_w + 1) return "output size does not follow from kernel, stride and pads";
+      if (const char* bad = graph_check_window(o, a, y, grouped ? 3 : conv ? 2 : 7, "bad stride")) return bad;
       if ((!conv || dw) && a.C != y.C) return "the operator keeps the channel count";
       if (conv && (!o.weights || !o.scale)) return "a full-integer filter operator without weights or its int32 M / shift / bias in `scale`";
       if (conv && ((reinterpret_cast<uintptr_t>(o.weights) & 15) || (reinterpret_cast<uintptr_t>(o.scale) & 3))) return "a full-integer filter operator's weights are not 16-byte aligned";

@@ -1,44 +1,29 @@
 // cpx_graph.hip -- the float32 kernels of the TFLite graph executor (cpx_graph_forward, include/cpx.h; what the
 // reference's LiteInterpreter hands to the TFLite runtime, ml_tools/interpreter.py:520-560; the hybrid operators are
-// cpx_graph_q8.hip's, the fp16x2 convolution is cpx_graph_h2.hip's, DEPTHWISE_CONV_2D is cpx_graph_dw.hip's, what they share is cpx_graph_core.h).  One launch per planned
+// cpx_graph_q8.hip's, the fp16x2 convolution is cpx_graph_h2.hip's, DEPTHWISE_CONV_2D is cpx_graph_dw.hip's, what they share is cpx_graph_core.h and cpx_graph_conv_core.h).  One launch per planned
 // operator; every kernel reads and writes NHWC views with a channel offset and a row stride, so that the producers of a
 // CONCATENATION write straight into their slice of the concatenated tensor.
 //
 // CONV_2D is an implicit GEMM on v_mfma_f32_32x32x2_f32 (exact float32 in, float32 accumulate: a k-ordered fmaf chain
-// per output, the same chain wherever the pixel sits in a tile or a batch):
-//   M = output pixels of the WHOLE batch, flattened (128 per workgroup, 32 per wave): the 8 x 8 and 17 x 17 maps of an
-//       Inception-v3 fill their tiles from the next sample instead of wasting them
-//   N = output channels (32 per MFMA tile, NTN tiles per wave)
-//   K = kh * kw * Cin walked as (tap) x (chunk of 16 input channels) x (pair of channels)
+// per output, the same chain wherever the pixel sits in a tile or a batch) over the shared walk (cpx_graph_conv_core.h),
+// K as (tap) x (chunk of 16 input channels) x (pair of channels), NTN = 1 or 2 tiles per wave.
 // Weights arrive [tap][Cin rounded up to 16][Cout rounded up to 32] with zeros beyond, so only the activation side is
 // masked.  Scale / shift (bias, folded MUL / ADD), the activation and the channel-sliced store happen from the accumulators.
 // CONV_PRE is the same kernel with a prologue: the pre-activation act(x * pre_scale[c] + pre_shift[c]) of a DenseNet /
 // ResNetV2 block is applied to the patch on its way from memory to LDS, as the WR-ResNet kernels do (cpx_cnn_bf3.hip), so
 // the AFFINE launch in front of the convolution and its round trip through memory go away.
-// CONV_GROUPED is the same kernel once more with the group as blockIdx.z: one launch for all groups, each group's walk
-// CONV's over its own channel slice and its own weight image (include/cpx.h).
+// CONV_GROUPED is the same kernel once more: one launch for all groups, each with its own weight image (include/cpx.h).
 #include <hip/hip_runtime.h>
 
-#include "cpx_graph_core.h"
+#include "cpx_graph_conv_core.h"
 #include "cpx_kernels.h"
 
 namespace cpx {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int CT = 256;
-constexpr int BM = 128;            // output pixels of a workgroup
 constexpr int KC = GRAPH_CONV_KC;  // input channels per staged chunk
 constexpr int AP = BM + 4;         // row stride of the k-major patch image: the two 8-channel halves of a pixel land 32 banks apart
-
-struct ConvGeom {
-  long long P;   // N * Ho * Wo
-  int HoWo, cin_pad, cout_pad, vec4;   // the pads and vec4 of ONE group's walk where the operator is grouped
-  int cg, cog;                         // CONV_GROUPED: input / output channels of a group
-};
 
 // PRE: the input is read as activate(x * pre_scale[c] + pre_shift[c], (int)a.param), the two float32 operations and the
 // activation of graph_affine_kernel; the constants sit behind the filter image, pre_scale[cin_pad] then pre_shift[cin_pad]
@@ -55,24 +40,19 @@ __global__ __launch_bounds__(CT) void graph_conv_kernel(GraphOpArgs a, ConvGeom 
   const long long p0 = (long long)blockIdx.x * BM;
   const int cout0 = blockIdx.y * BN;
   const int grp = GRP ? (int)blockIdx.z : 0;
-  const int Cin = GRP ? g.cg : a.in0.C, H = a.in0.H, W = a.in0.W;     // the channels of the K walk
+  const int Cin = GRP ? g.cg : a.in0.C;     // the channels of the K walk
   const int Cout = GRP ? g.cog : a.out.C, ch_base = GRP ? grp * g.cog : 0;
-  const float* wimg = GRP ? a.weights + (size_t)grp * a.kh * a.kw * g.cin_pad * g.cout_pad : a.weights;
+  const int cin_pad = g.nchunks * KC, cout_pad = g.ntiles * GRAPH_CONV_CO;   // the filter image's
+  const float* wimg = GRP ? a.weights + (size_t)grp * a.kh * a.kw * cin_pad * cout_pad : a.weights;
 
-  // staging role: pixel tid / 2 of the tile, channels [8 * half, 8 * half + 8) of the chunk -- the same pixel for the
-  // whole K walk, so its coordinates are worked out once
-  const int spx = tid >> 1, half = tid & 1;
-  const ConvPixel sp = conv_pixel(p0 + spx, g.P, g.HoWo, a.out.W);
-  const int iy0 = window_origin(sp.oy, a.stride_h, a.pad_top), ix0 = window_origin(sp.ox, a.stride_w, a.pad_left);
-  // 64-bit over the batch, 32-bit inside a sample; GRP: from the group's first channel on
-  const float* in_n = a.in0.p + (size_t)sp.n * a.in0.sample_stride + (GRP ? grp * g.cg : 0);
+  const ConvStager<float> st = conv_stager(a, g, a.in0.p, p0, tid, GRP ? grp * g.cg : 0);
+  const int spx = st.spx, half = st.half;
   // weight staging: KC rows of BN channels = KC * BN / 4 float4 (one per thread with NTN = 2)
   constexpr int WQ = BN / 4;
   const int wk = tid / WQ, wc4 = tid - wk * WQ;
   const bool wload = tid < KC * WQ;
 
-  const int nchunks = g.cin_pad / KC;
-  const int steps = a.kh * a.kw * nchunks;
+  const int steps = a.kh * a.kw * g.nchunks;
 
   f32x16 acc[NTN];
 #pragma unroll
@@ -82,25 +62,20 @@ __global__ __launch_bounds__(CT) void graph_conv_kernel(GraphOpArgs a, ConvGeom 
 
   float pre[8];
   f32x4 pre_w = {0.0f, 0.0f, 0.0f, 0.0f};
-  const float* pre_scale = a.weights + (size_t)a.kh * a.kw * g.cin_pad * g.cout_pad;
+  const float* pre_scale = a.weights + (size_t)a.kh * a.kw * cin_pad * cout_pad;
   // activate() for the two codes a pre-activation has, without its branches: fminf(fmaxf(v, 0), 6 or inf), the same bits
   const float pre_hi = (int)a.param == CPX_GRAPH_ACT_RELU6 ? 6.0f : INFINITY;
   f32x4 pre_sc[2], pre_sh[2];
   bool pre_in = false;
 
-  // global -> registers of step s (branch-free: a masked element reads the sample's first element and is zeroed)
+  // global -> registers of step s
   auto fetch = [&](int s) {
-    const int tap = s / nchunks, c0 = (s - tap * nchunks) * KC;
-    const int ky = tap / a.kw, kx = tap - ky * a.kw;
-    const int iy = iy0 + ky, ix = ix0 + kx;
-    const bool inside = sp.valid && iy >= 0 && iy < H && ix >= 0 && ix < W;
-    const int c = c0 + 8 * half;
-    const int pix = inside ? (iy * W + ix) * a.in0.cstride : 0;
-    if (g.vec4) {
+    const ConvPatch f = conv_patch(a, st, s, g.nchunks, KC);
+    if (g.vec) {
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
-        const bool ok = inside && (c + 4 * q) < Cin;   // Cin % 4 == 0: a quad is valid as a whole
-        const f32x4 v = *reinterpret_cast<const f32x4*>(in_n + (ok ? pix + c + 4 * q : 0));
+        const bool ok = f.inside && (f.c + 4 * q) < Cin;   // Cin % 4 == 0: a quad is valid as a whole
+        const f32x4 v = *reinterpret_cast<const f32x4*>(st.in_n + (ok ? f.pix + f.c + 4 * q : 0));
         pre[4 * q + 0] = ok ? v.x : 0.0f;
         pre[4 * q + 1] = ok ? v.y : 0.0f;
         pre[4 * q + 2] = ok ? v.z : 0.0f;
@@ -109,8 +84,8 @@ __global__ __launch_bounds__(CT) void graph_conv_kernel(GraphOpArgs a, ConvGeom 
     } else {
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const bool ok = inside && (c + j) < Cin;
-        const float v = in_n[ok ? pix + c + j : 0];
+        const bool ok = f.inside && (f.c + j) < Cin;
+        const float v = st.in_n[ok ? f.pix + f.c + j : 0];
         pre[j] = ok ? v : 0.0f;
       }
     }
@@ -118,15 +93,15 @@ __global__ __launch_bounds__(CT) void graph_conv_kernel(GraphOpArgs a, ConvGeom 
       // the constants of this step's channels travel with the patch, and whether the mask let the pixel through: the
       // prologue itself waits until the values are needed (below), so the loads stay in flight under the MFMAs.
       // c + 8 <= cin_pad and the image in front is a multiple of 16 x 32 floats: the quads are in bounds and aligned
-      pre_in = inside;
+      pre_in = f.inside;
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
-        pre_sc[q] = *reinterpret_cast<const f32x4*>(pre_scale + c + 4 * q);
-        pre_sh[q] = *reinterpret_cast<const f32x4*>(pre_scale + g.cin_pad + c + 4 * q);
+        pre_sc[q] = *reinterpret_cast<const f32x4*>(pre_scale + f.c + 4 * q);
+        pre_sh[q] = *reinterpret_cast<const f32x4*>(pre_scale + cin_pad + f.c + 4 * q);
       }
     }
     if (wload)
-      pre_w = *reinterpret_cast<const f32x4*>(wimg + ((size_t)(tap * g.cin_pad + c0 + wk) * g.cout_pad + cout0 + 4 * wc4));
+      pre_w = *reinterpret_cast<const f32x4*>(wimg + ((size_t)(f.tap * cin_pad + f.c0 + wk) * cout_pad + cout0 + 4 * wc4));
   };
 
   fetch(0);
@@ -417,55 +392,24 @@ __global__ __launch_bounds__(CT) void graph_softmax_kernel(GraphOpArgs a) {
   for (int c = 0; c < a.in0.C; ++c) dst[c] = expf(a.param * (src[c] - m)) / sum;
 }
 
-unsigned blocks_for(size_t items) { return (unsigned)((items + CT - 1) / CT); }
-
 }  // namespace
 
 void launch_graph_op(const GraphOpArgs& a, hipStream_t s) {
   const size_t out_elems = (size_t)a.N * a.out.H * a.out.W * a.out.C;
   switch (a.kind) {
     case CPX_GRAPH_CONV:
-    case CPX_GRAPH_CONV_PRE: {
-      ConvGeom g;
-      g.HoWo = a.out.H * a.out.W;
-      g.P = (long long)a.N * g.HoWo;
-      g.cin_pad = (a.in0.C + GRAPH_CONV_KC - 1) / GRAPH_CONV_KC * GRAPH_CONV_KC;
-      g.cout_pad = (a.out.C + GRAPH_CONV_CO - 1) / GRAPH_CONV_CO * GRAPH_CONV_CO;
-      g.vec4 = quads(a.in0);
-      g.cg = a.in0.C;
-      g.cog = a.out.C;
-      const unsigned gx = (unsigned)((g.P + BM - 1) / BM);
-      const bool pre = a.kind == CPX_GRAPH_CONV_PRE;
-      if (g.cout_pad % 64 == 0) {
-        const dim3 grid(gx, g.cout_pad / 64);
-        if (pre)
-          hipLaunchKernelGGL((graph_conv_kernel<2, true>), grid, dim3(CT), 0, s, a, g);
-        else
-          hipLaunchKernelGGL((graph_conv_kernel<2, false>), grid, dim3(CT), 0, s, a, g);
-      } else {
-        const dim3 grid(gx, g.cout_pad / 32);
-        if (pre)
-          hipLaunchKernelGGL((graph_conv_kernel<1, true>), grid, dim3(CT), 0, s, a, g);
-        else
-          hipLaunchKernelGGL((graph_conv_kernel<1, false>), grid, dim3(CT), 0, s, a, g);
-      }
-      break;
-    }
+    case CPX_GRAPH_CONV_PRE:
     case CPX_GRAPH_CONV_GROUPED: {
-      const int G = a.n_map;
-      ConvGeom g;
-      g.HoWo = a.out.H * a.out.W;
-      g.P = (long long)a.N * g.HoWo;
-      g.cg = a.in0.C / G;
-      g.cog = a.out.C / G;
-      g.cin_pad = (g.cg + GRAPH_CONV_KC - 1) / GRAPH_CONV_KC * GRAPH_CONV_KC;
-      g.cout_pad = (g.cog + GRAPH_CONV_CO - 1) / GRAPH_CONV_CO * GRAPH_CONV_CO;
-      g.vec4 = group_quads(a.in0, g.cg);
-      const unsigned gx = (unsigned)((g.P + BM - 1) / BM);
-      if (g.cout_pad % 64 == 0)
-        hipLaunchKernelGGL((graph_conv_kernel<2, false, true>), dim3(gx, g.cout_pad / 64, G), dim3(CT), 0, s, a, g);
-      else
-        hipLaunchKernelGGL((graph_conv_kernel<1, false, true>), dim3(gx, g.cout_pad / 32, G), dim3(CT), 0, s, a, g);
+      typedef void (*Kernel)(GraphOpArgs, ConvGeom);
+      // [CONV, CONV_PRE, CONV_GROUPED][an even number of tiles: two per wave]
+      static const Kernel kernels[3][2] = {{graph_conv_kernel<1, false>, graph_conv_kernel<2, false>},
+                                           {graph_conv_kernel<1, true>, graph_conv_kernel<2, true>},
+                                           {graph_conv_kernel<1, false, true>, graph_conv_kernel<2, false, true>}};
+      const int which = a.kind == CPX_GRAPH_CONV ? 0 : a.kind == CPX_GRAPH_CONV_PRE ? 1 : 2;
+      const ConvGeom g = conv_geom(a.N, a.in0, a.out, GRAPH_CONV_KC, which == 2 ? a.n_map : 1, group_quads<GraphView>);
+      const int two = g.ntiles % 2 == 0;   // (the padded output channels are a multiple of 64)
+      const dim3 grid((unsigned)((g.P + BM - 1) / BM), g.ntiles / (two ? 2 : 1), g.G);
+      hipLaunchKernelGGL(kernels[which][two], grid, dim3(CT), 0, s, a, g);
       break;
     }
     case CPX_GRAPH_MAX_POOL:

@@ -1,7 +1,8 @@
 // cpx_graph_core.h -- the arithmetic and the index maps the TFLite graph executor's kernels share (cpx_graph.hip,
 // cpx_graph_q8.hip, cpx_graph_dw.hip): the activation, the hybrid operators' quantisation, parameters and finish
 // (include/cpx.h fixes them "each operation in float32 as written"; the build has -ffp-contract=off), the test for views
-// of aligned quads, the flattened-pixel walks of the two implicit-GEMM convolutions and the depthwise work item.
+// of aligned quads, the flattened-pixel maps of the implicit-GEMM convolutions (their walk: cpx_graph_conv_core.h), the
+// window's origin and the depthwise work item.
 // Host and device: tests/native/graph_core_host.cpp compiles it without HIP and tests/test_graph_core_host.py holds it,
 // bit for bit, to the NumPy restatement (tests/tflite_eval_q8.py) and to divmod.
 #pragma once
@@ -120,7 +121,7 @@ inline bool group_quads(const View& v, int cg) {
   return quads(v) && cg % 4 == 0;
 }
 
-// ---- CONV / CONV_Q8: M = the output pixels of the whole batch, flattened ----
+// ---- the implicit-GEMM convolutions (cpx_graph_conv_core.h): M = the output pixels of the whole batch, flattened ----
 // pixel p of P = N * HoWo -> sample, output row and column; p >= P (the last tile's surplus) is sample 0's pixel 0, not valid
 struct ConvPixel {
   long long n;
@@ -136,8 +137,6 @@ CPX_HD inline ConvPixel conv_pixel(long long p, long long P, int HoWo, int Wo) {
   c.ox = rem - c.oy * Wo;
   return c;
 }
-// the first input row (column) of the window of output row (column) o
-CPX_HD inline int window_origin(int o, int stride, int pad) { return o * stride - pad; }
 
 // the 32 x 32 accumulator of the MFMAs: register r (0..15) of a lane holds row acc_row, column lane & 31.  Bit 5 of `lane`
 // alone is read, so a thread's index in its workgroup does as well as its lane
@@ -155,6 +154,10 @@ CPX_HD inline SamplePixel sample_step(long long n, int rem, int HoWo) {
   }
   return SamplePixel{n, rem};
 }
+
+// ---- windows ----
+// the first input row (column) of the window of output row (column) o
+CPX_HD inline int window_origin(int o, int stride, int pad) { return o * stride - pad; }
 
 // ---- DWCONV / DWCONV_Q8 ----
 // work item idx of N * Ho * runs * groups, channel group fastest, then run, output row and sample -> sample, output row,

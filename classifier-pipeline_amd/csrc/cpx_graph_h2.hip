@@ -4,11 +4,9 @@
 // arithmetic is fixed in include/cpx.h (CPX_GRAPH_RANGE / CONV_F16X2) so that a NumPy restatement can follow it
 // (tests/tflite_eval_h2.py); the build has -ffp-contract=off.
 //
-// CONV_F16X2 is an implicit GEMM on v_mfma_f32_32x32x16_f16, modelled on graph_conv_q8_kernel:
-//   M = output pixels of the WHOLE batch, flattened (128 per workgroup, 32 per wave)
-//   N = output channels (32 per MFMA tile, up to NTN tiles per wave)
-//   K = kh * kw * Cin walked as (tap) x (chunk of 32 input channels); a chunk is two K blocks m = 0, 1 of 16 channels, a
-//       block three MFMAs per tile: wl * xh, wh * xl, wh * xh, the small terms first
+// CONV_F16X2 is an implicit GEMM on v_mfma_f32_32x32x16_f16 over the walk of cpx_graph_conv_core.h, K in chunks of 32 input
+// channels; a chunk is two K blocks m = 0, 1 of 16 channels, a block three MFMAs per tile: wl * xh, wh * xl, wh * xh, the
+// small terms first.
 // A: two threads per pixel load 16 float32 channels each (4 x 128 bits), multiply by their pixel's own sample's `up`,
 //    split into xh and xl and write 4 x 16 bytes into a [pixel][plane][k] image of 128-byte rows, double buffered: one
 //    barrier per step.  No fp16 copy of the activation goes to memory.
@@ -31,7 +29,7 @@
 // which together with the half in bit 1 makes 8 different slots: no conflict either.
 #include <hip/hip_runtime.h>
 
-#include "cpx_graph_core.h"
+#include "cpx_graph_conv_core.h"
 #include "cpx_graph_minmax.h"
 #include "cpx_kernels.h"
 
@@ -40,13 +38,9 @@ namespace cpx {
 namespace {
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
-constexpr int CT = 256;
-constexpr int BM = 128;               // output pixels of a workgroup
 constexpr int KH = GRAPH_CONV_H2_KC;  // input channels per step
 constexpr int ROW = 32;               // dwords of a pixel's row of the A image: 2 planes x KH fp16
 
@@ -77,27 +71,20 @@ __global__ __launch_bounds__(GRAPH_MINMAX_THREADS) void graph_range_kernel(Graph
   out[3] = 0.0f;
 }
 
-struct ConvH2Geom {
-  long long P;   // N * Ho * Wo
-  int HoWo, nchunks, ntiles, vec4;
-};
-
 template <int NTN>
-__global__ __launch_bounds__(CT) void graph_conv_h2_kernel(GraphOpArgs a, ConvH2Geom g) {
+__global__ __launch_bounds__(CT) void graph_conv_h2_kernel(GraphOpArgs a, ConvGeom g) {
   __shared__ __attribute__((aligned(16))) unsigned s_a[2][BM * ROW];   // [pixel][plane][k], swizzled slots
   __shared__ __attribute__((aligned(16))) u32x4 s_b[2][NTN * CT];      // [tile][2 * plane + m][lane]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const long long p0 = (long long)blockIdx.x * BM;
   const int tile0 = blockIdx.y * NTN;
-  const int Cin = a.in0.C, H = a.in0.H, W = a.in0.W;
+  const int Cin = a.in0.C;
 
-  // staging role: pixel tid / 2 of the tile, channels [16 * half, 16 * half + 16) of the chunk = K block m = half -- the
-  // same pixel for the whole K walk, so its coordinates and its sample's `up` are worked out once
-  const int spx = tid >> 1, half = tid & 1;
-  const ConvPixel sp = conv_pixel(p0 + spx, g.P, g.HoWo, a.out.W);
-  const int iy0 = window_origin(sp.oy, a.stride_h, a.pad_top), ix0 = window_origin(sp.ox, a.stride_w, a.pad_left);
-  const float* in_n = a.in0.p + (size_t)sp.n * a.in0.sample_stride;
-  const float up = a.in1.p[(size_t)sp.n * a.in1.sample_stride];
+  // the stager's 16 channels are K block m = half; its sample's `up` is read once
+  const ConvStager<float> st = conv_stager(a, g, a.in0.p, p0, tid, 0);
+  const int spx = st.spx, half = st.half;
+  const float* in_n = st.in_n;
+  const float up = a.in1.p[(size_t)st.px.n * a.in1.sample_stride];
   const u32x4* wq = reinterpret_cast<const u32x4*>(a.weights);
   const int wbase = spx * ROW, wsw = swz(spx);
   // fragment role: row 32 * wave + (lane & 31), k half lane >> 5 (32 * wave changes no bit that swz reads)
@@ -116,13 +103,10 @@ __global__ __launch_bounds__(CT) void graph_conv_h2_kernel(GraphOpArgs a, ConvH2
 
   // global -> registers of step s.  A masked element (outside the image or the tile, beyond Cin) is 0 in both planes
   auto fetch = [&](int s) {
-    const int tap = s / g.nchunks, c0 = (s - tap * g.nchunks) * KH;
-    const int ky = tap / a.kw, kx = tap - ky * a.kw;
-    const int iy = iy0 + ky, ix = ix0 + kx;
-    const bool inside = sp.valid && iy >= 0 && iy < H && ix >= 0 && ix < W;
-    const int c = c0 + 16 * half;
-    const int pix = inside ? (iy * W + ix) * a.in0.cstride : 0;
-    if (g.vec4) {
+    const ConvPatch f = conv_patch(a, st, s, g.nchunks, KH);
+    const bool inside = f.inside;
+    const int c = f.c, pix = f.pix;
+    if (g.vec) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const bool ok = inside && (c + 4 * q) < Cin;   // Cin % 4 == 0: a quad is valid as a whole
@@ -140,11 +124,7 @@ __global__ __launch_bounds__(CT) void graph_conv_h2_kernel(GraphOpArgs a, ConvH2
         pre[j >> 2][j & 3] = ok ? v : 0.0f;
       }
     }
-#pragma unroll
-    for (int t = 0; t < NTN; ++t) {
-      const int tile = min(tile0 + t, g.ntiles - 1);   // a tile beyond the last is not multiplied: load the last
-      bnext[t] = wq[((size_t)s * g.ntiles + tile) * CT + tid];
-    }
+    prefetch_fragments<NTN>(wq, s, g.ntiles, tile0, CT, tid, bnext);
   };
 
   fetch(0);
@@ -226,19 +206,11 @@ void launch_graph_h2_op(const GraphOpArgs& a, hipStream_t s) {
         hipLaunchKernelGGL(graph_range_kernel<1>, dim3((unsigned)a.N), dim3(GRAPH_MINMAX_THREADS), 0, s, a);
       break;
     case CPX_GRAPH_CONV_F16X2: {
-      ConvH2Geom g;
-      g.HoWo = a.out.H * a.out.W;
-      g.P = (long long)a.N * g.HoWo;
-      g.nchunks = (a.in0.C + KH - 1) / KH;
-      g.ntiles = (a.out.C + GRAPH_CONV_CO - 1) / GRAPH_CONV_CO;
-      g.vec4 = vec4;
+      const ConvGeom g = conv_geom(a.N, a.in0, a.out, KH, 1, group_quads<GraphView>);
       const unsigned gx = (unsigned)((g.P + BM - 1) / BM);
-      if (g.ntiles == 1)
-        hipLaunchKernelGGL(graph_conv_h2_kernel<1>, dim3(gx, 1), dim3(CT), 0, s, a, g);
-      else if (g.ntiles == 2)
-        hipLaunchKernelGGL(graph_conv_h2_kernel<2>, dim3(gx, 1), dim3(CT), 0, s, a, g);
-      else
-        hipLaunchKernelGGL(graph_conv_h2_kernel<4>, dim3(gx, (g.ntiles + 3) / 4), dim3(CT), 0, s, a, g);
+      conv_dispatch_ntn(g.ntiles, [&](auto ntn, int rows) {
+        hipLaunchKernelGGL(graph_conv_h2_kernel<decltype(ntn)::value>, dim3(gx, rows), dim3(CT), 0, s, a, g);
+      });
       break;
     }
     default:

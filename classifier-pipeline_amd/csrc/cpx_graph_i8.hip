@@ -8,8 +8,8 @@
 // one 16-byte load / store where the views allow (bytes16 / floats16: channels, row stride, sample stride and pointer all
 // multiples of 16 elements), VW = 1 goes element by element.  Both run the same arithmetic on the same integers.
 //
-// CONV_I8 is graph_conv_q8_kernel's implicit GEMM on v_mfma_i32_32x32x32_i8 (cpx_graph_q8.hip: 128 output pixels of the
-// flattened batch per workgroup, the filter fragment image and its wsum unchanged, the group as blockIdx.z) with the A
+// CONV_I8 is graph_conv_q8_kernel's implicit GEMM on v_mfma_i32_32x32x32_i8 (cpx_graph_q8.hip; the walk: cpx_graph_conv_core.h;
+// the filter fragment image and its wsum unchanged) with the A
 // image staged FROM BYTES -- a thread takes its pixel's 16 channels with one 16-byte load, or byte by byte; a masked
 // element is z_in, nothing is quantised -- and an epilogue that requantises in registers and stores bytes.
 //
@@ -18,7 +18,7 @@
 // requantised byte through it (the LUT template parameter).  The table sits in 256 bytes of LDS.
 #include <hip/hip_runtime.h>
 
-#include "cpx_graph_core.h"
+#include "cpx_graph_conv_core.h"
 #include "cpx_graph_i8_core.h"
 #include "cpx_kernels.h"
 
@@ -26,17 +26,8 @@ namespace cpx {
 
 namespace {
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int CT = 256;
-constexpr int BM = 128;               // output pixels of a CONV_I8 workgroup
 constexpr int KQ = GRAPH_CONV_Q8_KC;  // input channels (bytes of a row of the A image) per step
 
-__device__ __forceinline__ int pack4(int q0, int q1, int q2, int q3) {
-  return (q0 & 255) | ((q1 & 255) << 8) | ((q2 & 255) << 16) | (int)((unsigned)q3 << 24);
-}
 __device__ __forceinline__ int byte_of(int word, int j) { return (int)(word << (24 - 8 * j)) >> 24; }   // sign extended
 
 __device__ __forceinline__ const int8_t* bytes_of(const GraphView& v) { return reinterpret_cast<const int8_t*>(v.p); }
@@ -312,18 +303,12 @@ __global__ __launch_bounds__(CT) void graph_fc_i8_kernel(GraphOpArgs a) {
 }
 
 // ---- CONV_I8 / CONV_I8_GROUPED ----
-struct ConvI8Geom {
-  long long P;   // N * Ho * Wo
-  int HoWo, nchunks, ntiles;   // chunks and tiles of ONE group's walk where the operator is grouped
-  int cg, cog, G;              // input / output channels of a group, the groups
-};
-
 // V16: the view's channel count per group, channel offsets, row stride and sample stride are multiples of 16 and its
 // pointer is 16-byte aligned -- a thread's 16 channels are one aligned 16-byte load and valid or masked as a whole.
 // LUT (CPX_GRAPH_ACT_LUT): the table is staged in front of the K walk -- the walk's first barrier publishes it -- and read
 // in the epilogue behind filter_finish_i8.
 template <int NTN, bool GRP, bool V16, bool LUT>
-__global__ __launch_bounds__(CT) void graph_conv_i8_kernel(GraphOpArgs a, ConvI8Geom g) {
+__global__ __launch_bounds__(CT) void graph_conv_i8_kernel(GraphOpArgs a, ConvGeom g) {
   __shared__ __attribute__((aligned(16))) int s_a[2][BM * KQ / 4];   // [pixel][k], bytes
   __shared__ int8_t s_t[LUT ? 256 : 1];
   if constexpr (LUT) stage_table(s_t, a);
@@ -331,18 +316,14 @@ __global__ __launch_bounds__(CT) void graph_conv_i8_kernel(GraphOpArgs a, ConvI8
   const long long p0 = (long long)blockIdx.x * BM;
   const int tile0 = blockIdx.y * NTN;
   const int grp = GRP ? (int)blockIdx.z : 0;
-  const int Cin = g.cg, H = a.in0.H, W = a.in0.W;   // the channels of the K walk
+  const int Cin = g.cg;   // the channels of the K walk
   const int Cout = g.cog;
   const I8Header& h = header_of(a);
   const int z_in = h.v[CPX_GRAPH_I8_HDR_Z_IN];
   const int zword = pack4(z_in, z_in, z_in, z_in);
 
-  // staging role: pixel tid / 2 of the tile, channels [16 * half, 16 * half + 16) of the chunk -- the same pixel for the
-  // whole K walk
-  const int spx = tid >> 1, half = tid & 1;
-  const ConvPixel sp = conv_pixel(p0 + spx, g.P, g.HoWo, a.out.W);
-  const int iy0 = window_origin(sp.oy, a.stride_h, a.pad_top), ix0 = window_origin(sp.ox, a.stride_w, a.pad_left);
-  const int8_t* in_n = bytes_of(a.in0) + (size_t)sp.n * a.in0.sample_stride + grp * g.cg;
+  const ConvStager<int8_t> st = conv_stager(a, g, bytes_of(a.in0), p0, tid, grp * g.cg);
+  const int8_t* in_n = st.in_n;
   const int steps = a.kh * a.kw * g.nchunks;
   const i32x4* wq0 = reinterpret_cast<const i32x4*>(a.weights);
   const i32x4* wq = wq0 + (size_t)grp * steps * g.ntiles * 64;   // the group's image
@@ -359,12 +340,10 @@ __global__ __launch_bounds__(CT) void graph_conv_i8_kernel(GraphOpArgs a, ConvI8
   // global -> registers of step s.  A masked element (outside the image or the tile, beyond Cin) is z_in: a real 0, what
   // TFLite's padding contributes (acc - z_in * wsum takes it out again); beyond Cin the weights are zero
   auto fetch = [&](int s) {
-    const int tap = s / g.nchunks, c0 = (s - tap * g.nchunks) * KQ;
-    const int ky = tap / a.kw, kx = tap - ky * a.kw;
-    const int iy = iy0 + ky, ix = ix0 + kx;
-    const bool inside = sp.valid && iy >= 0 && iy < H && ix >= 0 && ix < W;
-    const int c = c0 + 16 * half;
-    const size_t pix = inside ? (size_t)(iy * W + ix) * a.in0.cstride : 0;
+    const ConvPatch f = conv_patch(a, st, s, g.nchunks, KQ);
+    const bool inside = f.inside;
+    const int c = f.c;
+    const size_t pix = f.pix;
     if (V16) {
       const bool ok = inside && c < Cin;   // Cin % 16 == 0: the sixteen are valid as a whole
       const i32x4 v = *reinterpret_cast<const i32x4*>(in_n + (ok ? pix + c : 0));
@@ -383,11 +362,7 @@ __global__ __launch_bounds__(CT) void graph_conv_i8_kernel(GraphOpArgs a, ConvI8
         pre[k] = pack4(q[0], q[1], q[2], q[3]);
       }
     }
-#pragma unroll
-    for (int t = 0; t < NTN; ++t) {
-      const int tile = min(tile0 + t, g.ntiles - 1);   // a tile beyond the last is not multiplied: load the last
-      bnext[t] = wq[((size_t)s * g.ntiles + tile) * 64 + lane];
-    }
+    prefetch_fragments<NTN>(wq, s, g.ntiles, tile0, 64, lane, bnext);
   };
 
   fetch(0);
@@ -433,8 +408,6 @@ __global__ __launch_bounds__(CT) void graph_conv_i8_kernel(GraphOpArgs a, ConvI8
   }
 }
 
-unsigned blocks_for(size_t items) { return (unsigned)((items + CT - 1) / CT); }
-
 // the view can be read and written sixteen channels at a time with aligned 16-byte accesses
 bool bytes16(const GraphView& v) {
   return v.C % 16 == 0 && v.cstride % 16 == 0 && v.sample_stride % 16 == 0 && (reinterpret_cast<uintptr_t>(v.p) & 15) == 0;
@@ -462,34 +435,15 @@ void launch_window(const GraphOpArgs& a, hipStream_t s) {
 
 template <bool GRP, bool LUT>
 void launch_conv(const GraphOpArgs& a, hipStream_t s) {
-  ConvI8Geom g;
-  g.G = GRP ? a.n_map : 1;
-  g.HoWo = a.out.H * a.out.W;
-  g.P = (long long)a.N * g.HoWo;
-  g.cg = a.in0.C / g.G;
-  g.cog = a.out.C / g.G;
-  g.nchunks = (g.cg + KQ - 1) / KQ;
-  g.ntiles = (g.cog + GRAPH_CONV_CO - 1) / GRAPH_CONV_CO;
-  // (the first channel of group grp is c_offset + grp * Cg: on a sixteen for every group only where Cg is a multiple)
-  const bool v16 = g.cg % 16 == 0 && a.in0.cstride % 16 == 0 && a.in0.sample_stride % 16 == 0 &&
-                   (reinterpret_cast<uintptr_t>(a.in0.p) & 15) == 0;
+  const ConvGeom g = conv_geom(a.N, a.in0, a.out, KQ, GRP ? a.n_map : 1, group_bytes16<GraphView>);
   const unsigned gx = (unsigned)((g.P + BM - 1) / BM);
-  const dim3 block(CT);
-#define CPX_CONV_I8(NTN, GY)                                                                                   \
-  do {                                                                                                         \
-    const dim3 grid(gx, (GY), g.G);                                                                            \
-    if (v16)                                                                                                   \
-      hipLaunchKernelGGL((graph_conv_i8_kernel<NTN, GRP, true, LUT>), grid, block, 0, s, a, g);                \
-    else                                                                                                       \
-      hipLaunchKernelGGL((graph_conv_i8_kernel<NTN, GRP, false, LUT>), grid, block, 0, s, a, g);               \
-  } while (0)
-  if (g.ntiles == 1)
-    CPX_CONV_I8(1, 1);
-  else if (g.ntiles == 2)
-    CPX_CONV_I8(2, 1);
-  else
-    CPX_CONV_I8(4, (g.ntiles + 3) / 4);
-#undef CPX_CONV_I8
+  conv_dispatch_ntn(g.ntiles, [&](auto ntn, int rows) {
+    constexpr int NTN = decltype(ntn)::value;
+    if (g.vec)
+      hipLaunchKernelGGL((graph_conv_i8_kernel<NTN, GRP, true, LUT>), dim3(gx, rows, g.G), dim3(CT), 0, s, a, g);
+    else
+      hipLaunchKernelGGL((graph_conv_i8_kernel<NTN, GRP, false, LUT>), dim3(gx, rows, g.G), dim3(CT), 0, s, a, g);
+  });
 }
 
 }  // namespace

@@ -4,10 +4,8 @@
 // restatement reproduces it bit for bit: every float32 operation is written as one operation in cpx_graph_core.h
 // (quantise, quant_params, hybrid_finish; the build has -ffp-contract=off), the integer sums are exact in any order.
 //
-// CONV_Q8 is an implicit GEMM on v_mfma_i32_32x32x32_i8:
-//   M = output pixels of the WHOLE batch, flattened (128 per workgroup, 32 per wave), as graph_conv_kernel
-//   N = output channels (32 per MFMA tile, up to NTN tiles per wave)
-//   K = kh * kw * Cin walked as (tap) x (chunk of 32 input channels): one MFMA per step and tile
+// CONV_Q8 is an implicit GEMM on v_mfma_i32_32x32x32_i8 over the walk of cpx_graph_conv_core.h (M, N, K, the staging role,
+// the step ahead), K in chunks of 32 input channels: one MFMA per step and tile.
 // A: two threads per pixel load 16 float32 channels each (4 x 128 bits), quantise them with their pixel's sample's
 //    parameters and write 16 bytes with one ds_write_b128 into a [pixel][k] image of 32-byte rows.  Thread t writes bytes
 //    [16 t, 16 t + 16) and lane l of wave w reads bytes [1024 w + 32 (l & 31) + 16 (l >> 5), + 16): both sides touch one
@@ -19,7 +17,7 @@
 // l & 31 and sixteen consecutive k of half l >> 5 of A and of B; C / D is the map of the other 32 x 32 forms.
 #include <hip/hip_runtime.h>
 
-#include "cpx_graph_core.h"
+#include "cpx_graph_conv_core.h"
 #include "cpx_graph_minmax.h"
 #include "cpx_kernels.h"
 
@@ -27,17 +25,7 @@ namespace cpx {
 
 namespace {
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int CT = 256;
-constexpr int BM = 128;               // output pixels of a workgroup
 constexpr int KQ = GRAPH_CONV_Q8_KC;  // input channels (bytes of a row of the A image) per step
-
-__device__ __forceinline__ int pack4(int q0, int q1, int q2, int q3) {
-  return (q0 & 255) | ((q1 & 255) << 8) | ((q2 & 255) << 16) | (int)((unsigned)q3 << 24);
-}
 
 // QUANT_PARAMS: one workgroup per sample; out = [sx, inv, zp, 0].  The reduction is sample_min_max (cpx_graph_minmax.h),
 // which RANGE shares.
@@ -57,32 +45,23 @@ __global__ __launch_bounds__(QT) void graph_quant_params_kernel(GraphOpArgs a) {
   out[3] = 0.0f;
 }
 
-struct ConvQ8Geom {
-  long long P;   // N * Ho * Wo
-  int HoWo, nchunks, ntiles, vec4;   // chunks, tiles and vec4 of ONE group's walk where the operator is grouped
-  int cg, cog, G;                    // CONV_Q8_GROUPED: input / output channels of a group, the groups
-};
-
 // GRP (CONV_Q8_GROUPED): blockIdx.z is the group.  The parameters are the whole view's (in1), the walk is CONV_Q8's over
 // the group's own Cg channels with the group's own fragment image; wsum, scale and shift are indexed by the absolute
 // channel (wsum by the padded one: [G][Cog rounded up to 32], behind all G images), the store is bounded by the group.
 template <int NTN, bool GRP = false>
-__global__ __launch_bounds__(CT) void graph_conv_q8_kernel(GraphOpArgs a, ConvQ8Geom g) {
+__global__ __launch_bounds__(CT) void graph_conv_q8_kernel(GraphOpArgs a, ConvGeom g) {
   __shared__ __attribute__((aligned(16))) int s_a[2][BM * KQ / 4];   // [pixel][k], bytes
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const long long p0 = (long long)blockIdx.x * BM;
   const int tile0 = blockIdx.y * NTN;
   const int grp = GRP ? (int)blockIdx.z : 0;
-  const int Cin = GRP ? g.cg : a.in0.C, H = a.in0.H, W = a.in0.W;   // the channels of the K walk
+  const int Cin = GRP ? g.cg : a.in0.C;   // the channels of the K walk
   const int Cout = GRP ? g.cog : a.out.C;
 
-  // staging role: pixel tid / 2 of the tile, channels [16 * half, 16 * half + 16) of the chunk -- the same pixel for the
-  // whole K walk, so its coordinates and its sample's parameters are worked out once
-  const int spx = tid >> 1, half = tid & 1;
-  const ConvPixel sp = conv_pixel(p0 + spx, g.P, g.HoWo, a.out.W);
-  const int iy0 = window_origin(sp.oy, a.stride_h, a.pad_top), ix0 = window_origin(sp.ox, a.stride_w, a.pad_left);
-  const float* in_n = a.in0.p + (size_t)sp.n * a.in0.sample_stride + (GRP ? grp * g.cg : 0);
-  const float* sprm = a.in1.p + (size_t)sp.n * a.in1.sample_stride;
+  // the stager's 16 channels of every chunk; its sample's parameters are worked out once
+  const ConvStager<float> st = conv_stager(a, g, a.in0.p, p0, tid, GRP ? grp * g.cg : 0);
+  const float* in_n = st.in_n;
+  const float* sprm = a.in1.p + (size_t)st.px.n * a.in1.sample_stride;
   const float inv = sprm[1];
   const int zp = (int)sprm[2];
   const int steps = a.kh * a.kw * g.nchunks;
@@ -101,13 +80,10 @@ __global__ __launch_bounds__(CT) void graph_conv_q8_kernel(GraphOpArgs a, ConvQ8
   // global -> registers of step s.  A masked element (outside the image or the tile, beyond Cin) is a real 0, which
   // quantises to zp: what TFLite's padding contributes; beyond Cin the weights are zero and any value would do
   auto fetch = [&](int s) {
-    const int tap = s / g.nchunks, c0 = (s - tap * g.nchunks) * KQ;
-    const int ky = tap / a.kw, kx = tap - ky * a.kw;
-    const int iy = iy0 + ky, ix = ix0 + kx;
-    const bool inside = sp.valid && iy >= 0 && iy < H && ix >= 0 && ix < W;
-    const int c = c0 + 16 * half;
-    const int pix = inside ? (iy * W + ix) * a.in0.cstride : 0;
-    if (g.vec4) {
+    const ConvPatch f = conv_patch(a, st, s, g.nchunks, KQ);
+    const bool inside = f.inside;
+    const int c = f.c, pix = f.pix;
+    if (g.vec) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const bool ok = inside && (c + 4 * q) < Cin;   // Cin % 4 == 0: a quad is valid as a whole
@@ -125,11 +101,7 @@ __global__ __launch_bounds__(CT) void graph_conv_q8_kernel(GraphOpArgs a, ConvQ8
         pre[j >> 2][j & 3] = ok ? v : 0.0f;
       }
     }
-#pragma unroll
-    for (int t = 0; t < NTN; ++t) {
-      const int tile = min(tile0 + t, g.ntiles - 1);   // a tile beyond the last is not multiplied: load the last
-      bnext[t] = wq[((size_t)s * g.ntiles + tile) * 64 + lane];
-    }
+    prefetch_fragments<NTN>(wq, s, g.ntiles, tile0, 64, lane, bnext);
   };
 
   fetch(0);
@@ -220,42 +192,18 @@ void launch_graph_q8_op(const GraphOpArgs& a, hipStream_t s) {
       else
         hipLaunchKernelGGL(graph_quant_params_kernel<1>, dim3((unsigned)a.N), dim3(QT), 0, s, a);
       break;
-    case CPX_GRAPH_CONV_Q8: {
-      ConvQ8Geom g;
-      g.HoWo = a.out.H * a.out.W;
-      g.P = (long long)a.N * g.HoWo;
-      g.nchunks = (a.in0.C + KQ - 1) / KQ;
-      g.ntiles = (a.out.C + GRAPH_CONV_CO - 1) / GRAPH_CONV_CO;
-      g.vec4 = vec4;
-      g.cg = a.in0.C;
-      g.cog = a.out.C;
-      g.G = 1;
-      const unsigned gx = (unsigned)((g.P + BM - 1) / BM);
-      if (g.ntiles == 1)
-        hipLaunchKernelGGL(graph_conv_q8_kernel<1>, dim3(gx, 1), dim3(CT), 0, s, a, g);
-      else if (g.ntiles == 2)
-        hipLaunchKernelGGL(graph_conv_q8_kernel<2>, dim3(gx, 1), dim3(CT), 0, s, a, g);
-      else
-        hipLaunchKernelGGL(graph_conv_q8_kernel<4>, dim3(gx, (g.ntiles + 3) / 4), dim3(CT), 0, s, a, g);
-      break;
-    }
+    case CPX_GRAPH_CONV_Q8:
     case CPX_GRAPH_CONV_Q8_GROUPED: {
-      ConvQ8Geom g;
-      g.G = a.n_map;
-      g.HoWo = a.out.H * a.out.W;
-      g.P = (long long)a.N * g.HoWo;
-      g.cg = a.in0.C / g.G;
-      g.cog = a.out.C / g.G;
-      g.nchunks = (g.cg + KQ - 1) / KQ;
-      g.ntiles = (g.cog + GRAPH_CONV_CO - 1) / GRAPH_CONV_CO;
-      g.vec4 = group_quads(a.in0, g.cg);
+      const bool grouped = a.kind == CPX_GRAPH_CONV_Q8_GROUPED;
+      const ConvGeom g = conv_geom(a.N, a.in0, a.out, KQ, grouped ? a.n_map : 1, group_quads<GraphView>);
       const unsigned gx = (unsigned)((g.P + BM - 1) / BM);
-      if (g.ntiles == 1)
-        hipLaunchKernelGGL((graph_conv_q8_kernel<1, true>), dim3(gx, 1, g.G), dim3(CT), 0, s, a, g);
-      else if (g.ntiles == 2)
-        hipLaunchKernelGGL((graph_conv_q8_kernel<2, true>), dim3(gx, 1, g.G), dim3(CT), 0, s, a, g);
-      else
-        hipLaunchKernelGGL((graph_conv_q8_kernel<4, true>), dim3(gx, (g.ntiles + 3) / 4, g.G), dim3(CT), 0, s, a, g);
+      conv_dispatch_ntn(g.ntiles, [&](auto ntn, int rows) {
+        constexpr int NTN = decltype(ntn)::value;
+        if (grouped)
+          hipLaunchKernelGGL((graph_conv_q8_kernel<NTN, true>), dim3(gx, rows, g.G), dim3(CT), 0, s, a, g);
+        else
+          hipLaunchKernelGGL((graph_conv_q8_kernel<NTN, false>), dim3(gx, rows), dim3(CT), 0, s, a, g);
+      });
       break;
     }
     case CPX_GRAPH_FC_Q8:

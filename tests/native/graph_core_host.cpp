@@ -1,18 +1,20 @@
-// TEST INFRASTRUCTURE ONLY: host build of classifier-pipeline_amd/csrc/cpx_graph_core.h (tests/test_graph_core_host.py),
+// TEST INFRASTRUCTURE ONLY: host build of classifier-pipeline_amd/csrc/cpx_graph_core.h and of the host part of
+// cpx_graph_conv_core.h (tests/test_graph_core_host.py),
 // with -ffp-contract=off as the product.  As a shared object it hands the hybrid arithmetic (over arrays) and the index
 // maps of the graph executor's kernels to Python; with -DGRAPH_CORE_HOST_MAIN it is a program of its own that walks the
 // same ground, for a sanitizer build.  The product never loads either.
 #include <stdint.h>
 #include <stdio.h>
 
-#include "cpx_graph_core.h"
+#include "cpx_graph_conv_core.h"
 
 namespace {
 constexpr int RUN = 4;  // cpx_graph_dw.hip's GRAPH_DW_RUN
-struct View {           // the fields of GraphView that quads reads
+struct View {           // the fields of GraphView that quads and conv_geom read
   const float* p;
   int C, cstride;
   size_t sample_stride;
+  int H, W;
 };
 }  // namespace
 
@@ -33,7 +35,7 @@ extern "C" void hybrid_finish_host(const int* acc, const int* zp, const int* wsu
 }
 
 extern "C" int quads_host(int C, int cstride, unsigned long long sample_stride, unsigned long long address) {
-  return cpx::quads(View{reinterpret_cast<const float*>((uintptr_t)address), C, cstride, (size_t)sample_stride});
+  return cpx::quads(View{reinterpret_cast<const float*>((uintptr_t)address), C, cstride, (size_t)sample_stride, 1, 1});
 }
 
 // out: n, oy, ox, valid
@@ -47,6 +49,25 @@ extern "C" int acc_row_host(int r, int lane) { return cpx::acc_row(r, lane); }
 extern "C" void sample_step_host(long long n, int rem, int HoWo, long long* out) {
   const cpx::SamplePixel s = cpx::sample_step(n, rem, HoWo);
   out[0] = s.n, out[1] = s.rem;
+}
+
+// the geometry of a convolution's launch over dense views at `address`; bytes: the int8 path's 16-byte test, else the
+// float32 one.  out: P, HoWo, nchunks, ntiles, vec, cg, cog, G
+extern "C" void conv_geom_host(int N, int Ho, int Wo, int Cin, int Cout, int kc, int G, int bytes, unsigned long long address,
+                               long long* out) {
+  const float* p = reinterpret_cast<const float*>((uintptr_t)address);
+  const View in{p, Cin, Cin, (size_t)Cin * 49, 7, 7}, y{p, Cout, Cout, (size_t)Cout * Ho * Wo, Ho, Wo};
+  const cpx::ConvGeom g = bytes ? cpx::conv_geom(N, in, y, kc, G, cpx::group_bytes16<View>) : cpx::conv_geom(N, in, y, kc, G, cpx::group_quads<View>);
+  out[0] = g.P, out[1] = g.HoWo, out[2] = g.nchunks, out[3] = g.ntiles, out[4] = g.vec, out[5] = g.cg, out[6] = g.cog, out[7] = g.G;
+}
+// out: tap, c0, ky, kx
+extern "C" void conv_step_host(int s, int nchunks, int kw, int kc, int* out) {
+  const cpx::ConvStep k = cpx::conv_step(s, nchunks, kw, kc);
+  out[0] = k.tap, out[1] = k.c0, out[2] = k.ky, out[3] = k.kx;
+}
+// what conv_dispatch_ntn hands its launch: out = NTN, grid rows
+extern "C" void conv_tiling_host(int ntiles, int* out) {
+  cpx::conv_dispatch_ntn(ntiles, [&](auto ntn, int rows) { out[0] = decltype(ntn)::value, out[1] = rows; });
 }
 
 // `items` below 2^32 takes the 32-bit divisions, from 2^32 on the 64-bit ones (whatever idx is).  out: n, oy, ox0, c.
@@ -122,6 +143,23 @@ int main() {
     EXPECT(cpx::acc_row(5, 255) == cpx::acc_row(5, 63) && cpx::acc_row(5, 192) == cpx::acc_row(5, 0));
     EXPECT(seen == 0xffffffffu);
   }
+  {  // the convolutions' launch geometry, K steps and tiles
+    long long g[8];
+    conv_geom_host(3, 5, 4, 33, 65, 32, 1, 0, 4096, g);
+    EXPECT(g[0] == 60 && g[1] == 20 && g[2] == 2 && g[3] == 3 && g[4] == 0 && g[5] == 33 && g[6] == 65 && g[7] == 1);
+    conv_geom_host(1, 1, 1, 48, 96, 16, 3, 1, 4096, g);
+    EXPECT(g[2] == 1 && g[3] == 1 && g[4] == 1 && g[5] == 16 && g[6] == 32 && g[7] == 3);
+    int k[4], n[2];
+    for (int s = 0; s < 3 * 7 * 5; ++s) {
+      conv_step_host(s, 5, 7, 16, k);
+      EXPECT(k[0] == s / 5 && k[1] == 16 * (s % 5) && k[2] == s / 35 && k[3] == s / 5 % 7);
+    }
+    const int tiles[] = {1, 2, 3, 4, 5, 9}, ntn[] = {1, 2, 4, 4, 4, 4}, rows[] = {1, 1, 1, 1, 2, 3};
+    for (int i = 0; i < 6; ++i) {
+      conv_tiling_host(tiles[i], n);
+      EXPECT(n[0] == ntn[i] && n[1] == rows[i]);
+    }
+  }
   {  // the depthwise item: both paths below 2^32, the 64-bit one above
     unsigned long long a[4], b[4];
     const unsigned long long items = 7ull * 9 * 3 * 5;
@@ -136,8 +174,8 @@ int main() {
     EXPECT(a[3] == 4 * (big % 48) && a[2] == RUN * (big / 48 % 28) && a[1] == big / (48 * 28) % 112 && a[0] == big / (48ull * 28 * 112));
   }
   alignas(16) float buf[8];
-  EXPECT(cpx::quads(View{buf, 8, 8, 64}) && !cpx::quads(View{buf + 1, 8, 8, 64}) && !cpx::quads(View{buf, 6, 8, 64}) &&
-         !cpx::quads(View{buf, 8, 10, 64}) && !cpx::quads(View{buf, 8, 8, 66}));
+  EXPECT(cpx::quads(View{buf, 8, 8, 64, 1, 1}) && !cpx::quads(View{buf + 1, 8, 8, 64, 1, 1}) && !cpx::quads(View{buf, 6, 8, 64, 1, 1}) &&
+         !cpx::quads(View{buf, 8, 10, 64, 1, 1}) && !cpx::quads(View{buf, 8, 8, 66, 1, 1}));
   return failures ? 1 : 0;
 }
 #endif

@@ -1,5 +1,5 @@
-"""The arithmetic and the index maps the graph executor's kernels share (classifier-pipeline_amd/csrc/cpx_graph_core.h)
-compiled for the HOST, with -ffp-contract=off as the product, and held bit for bit (float32 viewed as uint32) to the NumPy
+"""The arithmetic and the index maps the graph executor's kernels share (classifier-pipeline_amd/csrc/cpx_graph_core.h and
+the host part of cpx_graph_conv_core.h) compiled for the HOST, with -ffp-contract=off as the product, and held bit for bit (float32 viewed as uint32) to the NumPy
 restatement of the hybrid arithmetic (tests/tflite_eval_q8.py, which is not translated from the C++) and to divmod.
 Needs no GPU; the product never loads this build."""
 import ctypes as C
@@ -31,6 +31,9 @@ def lib(tmp_path_factory):
     lib.conv_pixel_host.argtypes = [i64, i64, C.c_int, C.c_int, C.c_void_p]
     lib.sample_step_host.argtypes = [i64, C.c_int, C.c_int, C.c_void_p]
     lib.dw_item_host.argtypes = [u64, u64, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    lib.conv_geom_host.argtypes = [C.c_int] * 8 + [u64, C.c_void_p]
+    lib.conv_step_host.argtypes = [C.c_int] * 4 + [C.c_void_p]
+    lib.conv_tiling_host.argtypes = [C.c_int, C.c_void_p]
     return lib
 
 
@@ -246,6 +249,55 @@ def test_accumulator_row_map_is_a_permutation(lib):
     for lane in range(256):   # only bit 5 matters, of a lane or of a thread's index; a register quad is four consecutive rows
         assert [lib.acc_row_host(r, lane) for r in range(16)] == [lib.acc_row_host(r, lane & 32) for r in range(16)]
     assert [lib.acc_row_host(r, 0) for r in range(8)] == [0, 1, 2, 3, 8, 9, 10, 11] and lib.acc_row_host(0, 32) == 4
+
+
+# ---- the convolutions' launch geometry, K steps and tiles (cpx_graph_conv_core.h) ----
+def around(m):
+    """one below, at and one above a multiple of m, and m's neighbourhood itself"""
+    return sorted({v for k in (1, 3) for v in (k * m - 1, k * m, k * m + 1) if v >= 1})
+
+
+@pytest.mark.parametrize("kc", [16, 32])
+@pytest.mark.parametrize("groups", [1, 2, 3])
+def test_conv_geometry_is_plain_arithmetic(lib, groups, kc):
+    """P, HoWo, the group's channels, its chunks of kc input channels and tiles of 32 output channels, and the 16-byte
+    test of either element type, over Cin and Cout per group around the multiples of the chunk and the tile."""
+    out = np.zeros(8, np.int64)
+    N, Ho, Wo = 3, 5, 4
+    for cg in around(kc) + [4, 8, 20]:
+        for cog in around(32):
+            cin, cout = groups * cg, groups * cog
+            for as_bytes, address in ((0, 4096), (1, 4096), (0, 4096 + 4), (1, 4096 + 8)):
+                lib.conv_geom_host(N, Ho, Wo, cin, cout, kc, groups, as_bytes, address, ptr(out))
+                # (the views are dense: row stride Cin, sample stride 49 Cin, so the strides are aligned where Cin is)
+                lanes = 16 if as_bytes else 4
+                vec = cg % lanes == 0 and cin % lanes == 0 and address % 16 == 0
+                want = [N * Ho * Wo, Ho * Wo, -(-cg // kc), -(-cog // 32), int(vec), cg, cog, groups]
+                assert out.tolist() == want, (cin, cout, groups, kc, as_bytes, address)
+
+
+@pytest.mark.parametrize("nchunks", [1, 2, 5])
+@pytest.mark.parametrize("kw", [1, 3, 7])
+@pytest.mark.parametrize("kh", [1, 3, 7])
+def test_conv_step_is_divmod(lib, kh, kw, nchunks):
+    out = np.zeros(4, I32)
+    for kc in (16, 32):
+        for s in range(kh * kw * nchunks):
+            lib.conv_step_host(s, nchunks, kw, kc, ptr(out))
+            tap, chunk = divmod(s, nchunks)
+            assert out.tolist() == [tap, chunk * kc, *divmod(tap, kw)], (s, kc)
+            assert 0 <= out[2] < kh
+
+
+def test_conv_tiles_per_wave_and_grid_rows(lib):
+    out = np.zeros(2, I32)
+    table = {1: (1, 1), 2: (2, 1), 3: (4, 1), 4: (4, 1), 5: (4, 2), 9: (4, 3)}
+    for ntiles, want in table.items():
+        lib.conv_tiling_host(ntiles, ptr(out))
+        assert tuple(out.tolist()) == want, ntiles
+    for ntiles in range(1, 70):   # every tile is some wave's: NTN * rows covers them, with less than a row to spare
+        lib.conv_tiling_host(ntiles, ptr(out))
+        assert out[0] in (1, 2, 4) and out[0] * (out[1] - 1) < ntiles <= out[0] * out[1]
 
 
 # ---- the depthwise work item ----

@@ -177,6 +177,17 @@ def test_conv_i8_grouped(engine, cg):
                   ["QUANTIZE", "CONV_I8_GROUPED", "DEQUANTIZE"])
 
 
+@pytest.mark.parametrize("cg", [8, 32])
+@pytest.mark.parametrize("cog", [40, 72])
+def test_conv_i8_grouped_over_several_tiles(engine, cog, cg):
+    """The grouped kernel with two tiles per wave (Cog = 40: the second one partial) and with four (Cog = 72: three tiles,
+    above 64 channels per group), byte by byte and sixteen bytes at a time; N = 3 samples of 10 x 10 at stride 3."""
+    rng = np.random.default_rng([34, cg, cog])
+    blob = conv_graph(rng, 3, 3, 3, tb.SAME, 2 * cg, 2 * cog, (10, 10), IN_QPS[2], groups=2)
+    check(engine, blob, levels(rng, (3, 10, 10, 2 * cg), IN_QPS[2]), "grouped Cg %d Cog %d" % (cg, cog),
+          ["QUANTIZE", "CONV_I8_GROUPED", "DEQUANTIZE"])
+
+
 @pytest.mark.parametrize("c_first", [16, 5])
 def test_conv_i8_inside_a_concatenation(engine, c_first):
     """Two convolutions write into the channel slices of a concatenated tensor (the second at channel offset 16 or 5 of a

@@ -96,6 +96,12 @@ CONV_LUT_CASES = [
     (1, 2, 32, 40, 1),      # sixteen bytes at a time
     (3, 1, 16, 48, 2),      # CONV_I8_GROUPED
     (1, 1, 24, 160, 1),     # four tiles per workgroup, gridDim.y = 2
+    (1, 1, 32, 160, 1),     # ... sixteen bytes at a time
+    (3, 1, 32, 48, 2),      # CONV_I8_GROUPED, sixteen bytes at a time
+    (3, 1, 16, 80, 2),      # ... two tiles per group, byte by byte
+    (1, 1, 32, 80, 2),      # ... and sixteen bytes at a time
+    (3, 1, 16, 144, 2),     # ... three tiles per group (above 64 channels): four per workgroup, byte by byte
+    (1, 1, 32, 144, 2),     # ... and sixteen bytes at a time
 ]
 
 
