@@ -17,12 +17,18 @@
 //   weights pre-split on the device into the same entry format, [chunk][plane][tap][k half][column]; staging is
 //           a straight copy and a B fragment is one ds_read_b128 per plane
 // Activations stay float32 in HBM; the split happens on the way into LDS.
+//
+// Shared with cpx_cnn_rw.hip and cpx_cnn_blk.hip, each stated once: the device vocabulary -- vector types, 32-bit addressing,
+// the splits, the plane products of a K step -- in cpx_cnn_dev.h; the tile division (tile_div, tile_split, Tiles, fill_tiles)
+// and the persistent grid's width in cpx_conv_layout_core.h; the launch of this file's three split-operand kernels in
+// launch_bf3_tiles below.  What stayed per kernel, and why: profiles/cnn_conv_shared_refactor.md.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 
+#include "cpx_cnn_dev.h"
 #include "cpx_conv_layout_core.h"
 #include "cpx_kernels.h"
 
@@ -30,112 +36,6 @@ namespace cpx {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-// a native vector, not HIP's uint4 struct: struct copies become memcpy calls that keep a staging array in scratch
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-  bf16x2 v = {(__bf16)a, (__bf16)b};  // v_cvt_pk_bf16_f32: round to nearest even
-  return __builtin_bit_cast(unsigned, v);
-}
-// uniform base + 32-bit unsigned byte offset: the form the compiler turns into `global_load v, v_off, s[base]` (one
-// offset register per lane instead of 64-bit address arithmetic per access; everything addressed here stays inside
-// one sample or one weight image: < 2^32 bytes)
-template <typename T>
-__device__ __forceinline__ const T* at_off(const T* base, unsigned bytes) {
-  return reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + bytes);
-}
-template <typename T>
-__device__ __forceinline__ T* at_off(T* base, unsigned bytes) {
-  return reinterpret_cast<T*>(reinterpret_cast<char*>(base) + bytes);
-}
-// element offset of pixel (y, x) in an NHWC sample: both products stay below 2^24 (y * W + x < 2^17 pixels, x C <= 256
-// channels), so the full-rate 24-bit multiply does (a 32-bit v_mul_lo_u32 / v_mad_u64_u32 takes four issue slots)
-__device__ __forceinline__ unsigned pix_off(int y, int x, int W, int C) {
-  return __umul24(__umul24((unsigned)y, (unsigned)W) + (unsigned)x, (unsigned)C);
-}
-// ReLU of a float as an integer maximum: one instruction (fmaxf(x, 0) on a value of unknown origin is canonicalised first)
-__device__ __forceinline__ float relu_bits(float x) { return __int_as_float(max(__float_as_int(x), 0)); }
-__device__ __forceinline__ float bf_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bf_hi(unsigned u) { return __uint_as_float(u & 0xFFFF0000u); }
-// two float32 -> their three bf16 planes (packed pairs)
-__device__ __forceinline__ void split_pair(float a, float b, unsigned& p0, unsigned& p1, unsigned& p2) {
-  p0 = pack2(a, b);
-  // (opaque: seeing through the pack, the compiler converts `a` a second time just to shift it -- one vector
-  // instruction more per level and pair; the halves of the packed word are what is wanted)
-  asm volatile("" : "+v"(p0));
-  const float ra = a - bf_lo(p0), rb = b - bf_hi(p0);  // exact
-  p1 = pack2(ra, rb);
-  asm volatile("" : "+v"(p1));
-  const float sa = ra - bf_lo(p1), sb = rb - bf_hi(p1);  // exact
-  p2 = pack2(sa, sb);
-}
-
-// two float32 -> TWO bf16 planes, each rounded to nearest (v_cvt_pk_bf16_f32): hi + lo carries 16 significand bits,
-// |x - hi - lo| <= 2^-16 |x| (CPX_CNN_MATH_BF16X2: three products per K step instead of six)
-__device__ __forceinline__ unsigned pack2_rne(float a, float b) {
-  unsigned r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-__device__ __forceinline__ void split_pair2(float a, float b, unsigned& p0, unsigned& p1) {
-  p0 = pack2_rne(a, b);
-  const float ra = a - bf_lo(p0), rb = b - bf_hi(p0);  // exact
-  p1 = pack2_rne(ra, rb);
-}
-
-// CPX_CNN_MATH_FP16X2: two float32 -> two fp16 planes, each rounded to nearest (v_cvt_pk_f16_f32): 11 + 11 significand
-// bits and the sign of the remainder, |x - hi - lo| <= 2^-22 |x| while lo is a normal fp16 (|x| >= 2^-3 after the
-// caller's scaling) and <= 2^-25 absolute below that (v_mfma_*_f16 keeps subnormal inputs: scratch/fp16_probe.hip)
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ unsigned pack2_h(float a, float b) {
-  f16x2 v = {(_Float16)a, (_Float16)b};  // v_cvt_pk_f16_f32: round to nearest even
-  return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ void split_pair2_h(float a, float b, unsigned& p0, unsigned& p1) {
-  p0 = pack2_h(a, b);
-  // lo = fp16(x - hi): the difference is exact in float32, so ONE mixed-precision fused multiply-add per element (x * 1.0 - hi,
-  // float32 inside, rounded to nearest fp16 once, into the low / high half of p1) is the same value as convert-back, subtract,
-  // convert -- three instructions per pair instead of six
-  asm("v_fma_mixlo_f16 %0, %1, 1.0, -%2 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(p1) : "v"(a), "v"(p0));
-  asm("v_fma_mixhi_f16 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(p1) : "v"(b), "v"(p0));
-}
-// the two-plane split of the chosen kind (H: fp16, else bf16)
-template <bool H>
-__device__ __forceinline__ void split2(float a, float b, unsigned& p0, unsigned& p1) {
-  if (H) split_pair2_h(a, b, p0, p1);
-  else split_pair2(a, b, p0, p1);
-}
-// one plane product on the matrix pipe: 16-byte fragments as they come out of LDS
-template <bool H>
-__device__ __forceinline__ f32x4 mfma16(u32x4 w, u32x4 x, f32x4 c) {
-  if (H) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, w), __builtin_bit_cast(f16x8, x), c, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), c, 0, 0, 0);
-}
-template <bool H>
-__device__ __forceinline__ f32x16 mfma32(u32x4 x, u32x4 w, f32x16 c) {
-  if (H) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, x), __builtin_bit_cast(f16x8, w), c, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, x), __builtin_bit_cast(bf16x8, w), c, 0, 0, 0);
-}
-constexpr float F16_MAX = 65504.0f;
-// producer-side split (ConvArgs::out_planes): four consecutive channels of one pixel, activated and already multiplied by
-// the consumer's act_scale, as the consumer stages them: [hi 0..3 | lo 0..3] in the 16 bytes the float32 values would take
-__device__ __forceinline__ u32x4 planes_of(f32x4 v) {
-  unsigned h0, h1, l0, l1;
-  split_pair2_h(v.x, v.y, h0, l0);
-  split_pair2_h(v.z, v.w, h1, l1);
-  return u32x4{h0, h1, l0, l1};
-}
-__device__ __forceinline__ unsigned pk_max_u16(unsigned a, unsigned b) {
-  unsigned r;
-  asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-__device__ __forceinline__ float max_abs4(f32x4 v) { return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))); }
 // entry test shared by the split-operand kernels: a fp16 layer is skipped once the network's overflow word is set (its
 // three-plane rerun follows), the rerun is skipped while it is clear
 #define BF3_ENTRY_GUARD(H_)                          \
@@ -149,13 +49,16 @@ constexpr int KC = 16;  // channels per K step of the bf16 MFMA = per staged chu
 
 // NB bands of 128 output pixels per workgroup, CT threads: four waves share a band (32 pixels each); with CT = 512
 // the second set of four waves takes every other band, so NTM = NB / (CT / 256) bands per wave
-// q = n / d with a host-computed multiplier (cpx_conv_layout_core.h: fill_tiles), four divisions per workgroup otherwise
+// q = n / d with a host-computed multiplier (cpx_conv_layout_core.h: tile_div, fill_tiles), four divisions per workgroup
+// otherwise.  Tiles's fields and the column split, in an order of its own: the offsets of a kernel's arguments are part of its
+// instruction stream, and these kernels keep theirs (profiles/cnn_conv_shared_refactor.md: as Tiles + nsplit every one changed)
 struct TileDiv {
   unsigned long long m_nsplit, m_tx, m_ty;
   int nsplit, tiles_x, tiles_y;
-  int run;  // conv_bf3w_kernel: tiles per workgroup along x (tiles_x then counts runs)
+  int _pad;   // (where the retired `run` was: `total` keeps byte 40)
   int total;  // PERSIST: workgroup-sized units of work along x (the grid then is smaller and each workgroup walks its share)
 };
+static_assert(sizeof(TileDiv) == 48 && offsetof(TileDiv, total) == 40, "the argument layout the kernels were tuned with");
 // PERSIST (last template parameter of the three kernels): the form the guarded bf16x3 rerun of a fp16x2 layer is launched
 // in.  A rerun that has nothing to do must cost nothing: 409,600 workgroups that load one word and leave take 174 us
 // (two resident per CU: each costs a dispatch round trip), 1,024 take 2.5 us (profiles/r05_fp16_probe.txt) -- so the
@@ -168,7 +71,6 @@ struct TileDiv {
   if (bid0 >= td.total) break;   \
   __syncthreads();               \
   }
-__device__ __forceinline__ int div_magic(int n, unsigned long long m) { return (int)(((unsigned long long)n * m) >> 42); }
 
 // (two workgroups per CU is what the LDS footprint allows: the register budget is pinned to match)
 // C8: the layer with 8 input channels per group (one 16-byte k half per pixel).  A K = 16 step then pairs two TAPS
@@ -204,15 +106,10 @@ __global__ __launch_bounds__(CT) __attribute__((amdgpu_waves_per_eu(S > 1 ? CT /
   int bid = bid0;
   if (!PERSIST && (gridDim.x & 7) == 0) bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);  // XCD-contiguous tiles (cpx_cnn.hip)
   const int cin_g = a.Cin / a.groups, cout_g = a.Cout / a.groups;
-  int q = div_magic(bid, td.m_nsplit);
-  const int ns = bid - q * td.nsplit;  // the column slices of one tile run next to each other: they share the patch in L2
-  bid = q;
-  q = div_magic(bid, td.m_tx);
-  const int txi = bid - q * td.tiles_x;
-  bid = q;
-  q = div_magic(bid, td.m_ty);
-  const int tyi = bid - q * td.tiles_y;
-  const int n = q;
+  const int ns = tile_split(bid, td.m_nsplit, td.nsplit);  // the column slices of one tile run next to each other: they share the patch in L2
+  const int txi = tile_split(bid, td.m_tx, td.tiles_x);
+  const int tyi = tile_split(bid, td.m_ty, td.tiles_y);
+  const int n = bid;
   const int g = blockIdx.y;
   const int oy0 = tyi * TH, ox0 = txi * TW;
   const int iy0 = oy0 * S - a.pad_top, ix0 = ox0 * S - a.pad_left;
@@ -418,7 +315,8 @@ __global__ __launch_bounds__(CT) __attribute__((amdgpu_waves_per_eu(S > 1 ? CT /
         for (int m = 0; m < NTM; ++m)
 #pragma unroll
           for (int t = 0; t < NTN; ++t) {
-            // smallest terms first: x1*y1, x0*y2, x2*y0, x0*y1, x1*y0, x0*y0
+            // plane_products32's text, written out: through the helper the four PERSIST forms of this kernel compile to other
+            // code (profiles/cnn_conv_shared_refactor.md)
             if (PL == 3) {
               acc[m][t] = mfma32<false>(av[m][1], bv[t][1], acc[m][t]);
               acc[m][t] = mfma32<false>(av[m][0], bv[t][PL - 1], acc[m][t]);
@@ -574,6 +472,8 @@ template <int NTN, int NPXC, int PL, bool H = false, bool PERSIST = false, int C
 __global__ __launch_bounds__(CT) void conv_bf3flat_kernel(ConvArgs a, const uint4* __restrict__ wimg, TileDiv td) {
   constexpr int KS = 3, BAND = CT / 2;
   constexpr int COGW = 32 * NTN;
+  // (retired: other N tiles, patch capacities and thread counts.  Still in the list: traces and profiles name the instantiations)
+  static_assert(NTN == 2 && NPXC == 256 && CT == 256, "launched in one geometry");
   static_assert(!H || PL == 2, "fp16 planes come in twos");
   static_assert(!SC || (H && !PERSIST && CT == 256 && 4 * 2 * 2 * BAND + 4 * 2 * 2 * COGW <= 2 * PL * NPXC + 18 * PL * COGW),
                 "the shortcut's planes reuse the LDS of the patch and the weights");
@@ -587,12 +487,9 @@ __global__ __launch_bounds__(CT) void conv_bf3flat_kernel(ConvArgs a, const uint
   int bid = bid0;
   if (!PERSIST && (gridDim.x & 7) == 0) bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);
   const int cin_g = a.Cin / a.groups, cout_g = a.Cout / a.groups;
-  int q = div_magic(bid, td.m_nsplit);
-  const int ns = bid - q * td.nsplit;
-  bid = q;
-  q = div_magic(bid, td.m_tx);
-  const int ti = bid - q * td.tiles_x;  // band of 128 positions inside the sample
-  const int n = q;
+  const int ns = tile_split(bid, td.m_nsplit, td.nsplit);
+  const int ti = tile_split(bid, td.m_tx, td.tiles_x);  // band of 128 positions inside the sample
+  const int n = bid;
   const int g = blockIdx.y;
   const int M = a.Ho * a.Wo;
   const int p0 = ti * BAND;
@@ -742,16 +639,7 @@ __global__ __launch_bounds__(CT) void conv_bf3flat_kernel(ConvArgs a, const uint
             bv[t][p] = __builtin_bit_cast(u32x4, s_w[(p * 9 + tap) * 2 * COGW + b_base + t * 32]);
         }
 #pragma unroll
-        for (int t = 0; t < NTN; ++t) {
-          if (PL == 3) {
-            acc[t] = mfma32<false>(av[1], bv[t][1], acc[t]);
-            acc[t] = mfma32<false>(av[0], bv[t][PL - 1], acc[t]);
-            acc[t] = mfma32<false>(av[PL - 1], bv[t][0], acc[t]);
-          }
-          acc[t] = mfma32<H>(av[0], bv[t][1], acc[t]);
-          acc[t] = mfma32<H>(av[1], bv[t][0], acc[t]);
-          acc[t] = mfma32<H>(av[0], bv[t][0], acc[t]);
-        }
+        for (int t = 0; t < NTN; ++t) plane_products32<PL, H>(av, bv[t], acc[t]);
       }
       __syncthreads();
     }
@@ -811,11 +699,7 @@ __global__ __launch_bounds__(CT) void conv_bf3flat_kernel(ConvArgs a, const uint
         for (int t = 0; t < NTN; ++t) bv[t][p] = __builtin_bit_cast(u32x4, s_scw[((c * 2 + p) * 2 + kh) * COGW + (lane & 31) + t * 32]);
       }
 #pragma unroll
-      for (int t = 0; t < NTN; ++t) {
-        acc[t] = mfma32<true>(av[0], bv[t][1], acc[t]);
-        acc[t] = mfma32<true>(av[1], bv[t][0], acc[t]);
-        acc[t] = mfma32<true>(av[0], bv[t][0], acc[t]);
-      }
+      for (int t = 0; t < NTN; ++t) plane_products32<2, true>(av, bv[t], acc[t]);
     }
     __syncthreads();  // (the epilogue's tiles reuse the same LDS)
   } else if (a.sc_in) {  // fused 1x1 shortcut (see conv_bf3_kernel)
@@ -922,12 +806,10 @@ constexpr int W_NPXP = 326;  // pixels per (plane, quarter pair) region: 326 * 3
 constexpr int w_patch_entries(int planes) { return planes * 2 * W_NPXP * 2; }
 constexpr int w_rows_resident(int planes) { return planes == 2 ? 3 : 1; }
 constexpr int w_wsub_entries(int planes) { return w_rows_resident(planes) * planes * 3 * 4 * 32; }  // a weight sub-chunk
-// WALK: the workgroup walks a run of td.run tiles along x (launched false: exactly one tile, the loop and the per-use
-// laundering of the staging bases fold away); LDSBN: BatchNorm scale / shift read back from LDS at each patch commit
-// instead of living in eight registers; NH: 32-column slices of the group's output channels the workgroup computes from
-// ONE staged patch (NH = 2 for 64 columns per group: the patch of a tile is loaded, normalised and split once instead
-// of once per slice -- the slices' weights alternate through the same 18 KB, twice the accumulators)
-// NG: GROUPS the workgroup walks on its tile, one after the other (launched 1; 2 ran 171 vs 183 TFLOP/s on stage 2)
+// LDSBN: BatchNorm scale / shift read back from LDS at each patch commit instead of living in eight registers;
+// NH: 32-column slices of the group's output channels the workgroup computes from ONE staged patch (NH = 2 for 64 columns
+// per group: the patch of a tile is loaded, normalised and split once instead of once per slice -- the slices' weights
+// alternate through the same 18 KB, twice the accumulators)
 // PL: bf16 planes per operand.  3 = the exact split (six products per K step: every term down to 2^-24 of the float32
 // product); 2 = CPX_CNN_MATH_BF16X2: both operands as hi + lo rounded to nearest (16 significand bits, relative error
 // <= 2^-16 each), three products w0 x1 + w1 x0 + w0 x0 -- half the matrix work, two thirds of the staging and LDS.
@@ -936,7 +818,10 @@ constexpr int w_wsub_entries(int planes) { return w_rows_resident(planes) * plan
 // fp16's range and the accumulators scaled back in the epilogue (ConvArgs::half)
 template <bool WALK, bool LDSBN, int NH, int NG, int PL, bool H = false, bool PERSIST = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void conv_bf3w_kernel(ConvArgs a, const uint4* __restrict__ wimg, TileDiv td) {
-  static_assert(NG == 1 || (!WALK && !LDSBN && NH == 1), "the group walk is built for the one-slice, one-tile form");
+  // (retired: a run of tiles along x, and two groups, per workgroup.  Still in the list: traces and profiles name the instantiations.
+  // What is left of them below -- the loop of one pass, the `txi < txr` arms, `gn` -- is in the compiled code: before removing it,
+  // compare the listings as profiles/cnn_conv_shared_refactor.md does)
+  static_assert(!WALK && NG == 1, "one tile and one group per workgroup");
   static_assert(PL == 2 || PL == 3, "two or three bf16 planes per operand");
   static_assert(!H || (PL == 2 && LDSBN), "fp16 planes come in twos (and with the BatchNorm parameters in LDS)");
   BF3_ENTRY_GUARD(H)
@@ -948,10 +833,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   constexpr int W_WROW = PL * 3 * 4 * 32;       // entries of one kernel row's weights (32 columns)
   constexpr int W_WSUB = WR * W_WROW;           // entries of a weight sub-chunk
   constexpr int CT = 512;
-  // per-thread staging / output indices are re-derived from the thread index at each use (WALK: they would be carried
-  // across the tile loop; NH > 1: sixteen more accumulator registers leave no room to keep them across the products --
-  // kept, the compiler spills eight of them to scratch per tile: +22 % HBM traffic on the stage-3 launches, measured)
-  constexpr bool LAUNDER = WALK || NH > 1 || NG > 1 || PL == 2;  // (PL == 2: twenty prefetch registers for the three weight rows)
+  // per-thread staging / output indices are re-derived from the thread index at each use (NH > 1: sixteen more accumulator
+  // registers leave no room to keep them across the products -- kept, the compiler spills eight of them to scratch per
+  // tile: +22 % HBM traffic on the stage-3 launches, measured)
+  constexpr bool LAUNDER = NH > 1 || PL == 2;  // (PL == 2: twenty prefetch registers for the three weight rows)
   extern __shared__ __attribute__((aligned(16))) uint4 lds4[];
   uint4* s_patch = lds4;
   uint4* s_w = lds4 + W_PATCH;
@@ -961,20 +846,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   int bid = bid0;
   if (!PERSIST && (gridDim.x & 7) == 0) bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);  // XCD-contiguous tiles (cpx_cnn.hip)
   const int cin_g = a.Cin / a.groups, cout_g = a.Cout / a.groups;
-  int qd = div_magic(bid, td.m_nsplit);
-  const int ns = bid - qd * td.nsplit;
-  bid = qd;
-  qd = div_magic(bid, td.m_tx);
-  const int txr = bid - qd * td.tiles_x;  // run of td.run consecutive tiles of one tile row (td.tiles_x counts runs)
-  bid = qd;
-  qd = div_magic(bid, td.m_ty);
-  const int tyi = bid - qd * td.tiles_y;
-  const int n = qd;
-  const int g0 = blockIdx.y * NG;
+  const int ns = tile_split(bid, td.m_nsplit, td.nsplit);
+  const int txr = tile_split(bid, td.m_tx, td.tiles_x);
+  const int tyi = tile_split(bid, td.m_ty, td.tiles_y);
+  const int n = bid;
+  const int g = blockIdx.y;
   const int oy0 = tyi * W_TH;
   const int iy0 = oy0 - a.pad_top;
-  const int run = WALK ? td.run : 1;
-  const int tx_end = WALK ? min((txr + 1) * run, (a.Wo + W_TW - 1) / W_TW) : txr + 1;
   const float* in_n = a.in + (size_t)n * a.H * a.W * a.Cin;
   const int nch = cin_g / KW;
   const uint4* wg = wimg + (size_t)ns * (32 * NH);
@@ -1002,8 +880,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   f32x4 psc_r, psh_r;
   if (LDSBN && a.in_scale) {
     if (tid < cin_g) {  // (H: relu(x s + b) 2^k = relu(x (s 2^k) + b 2^k), exactly)
-      reinterpret_cast<float*>(s_bn)[tid] = a.in_scale[g0 * cin_g + tid] * (H ? a.act_scale : 1.0f);
-      reinterpret_cast<float*>(s_bn)[cin_g + tid] = a.in_shift[g0 * cin_g + tid] * (H ? a.act_scale : 1.0f);
+      reinterpret_cast<float*>(s_bn)[tid] = a.in_scale[g * cin_g + tid] * (H ? a.act_scale : 1.0f);
+      reinterpret_cast<float*>(s_bn)[cin_g + tid] = a.in_shift[g * cin_g + tid] * (H ? a.act_scale : 1.0f);
     }
     __syncthreads();
   }
@@ -1046,12 +924,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
       pre_p[i] = *reinterpret_cast<const u32x4*>(at_off(in_n, (pix_off(cy, cx, a.W, a.Cin) + coff) << 2)); \
     }                                                                                                     \
   }
-  BF3W_ISSUE_W(g0, 0, 0, 0)
-  BF3W_ISSUE_P(g0, 0, txr * run * W_TW - a.pad_left)
-  // The workgroup walks a run of tiles along x: the next tile's patch and first weights are in flight under the
-  // current tile's products exactly as the next chunk's are, so only the first tile of a run waits for its loads
-  // with nothing else to do (the other workgroup of the CU aside).
-  for (int txi = txr * run; txi < tx_end; ++txi) {
+  BF3W_ISSUE_W(g, 0, 0, 0)
+  BF3W_ISSUE_P(g, 0, txr * W_TW - a.pad_left)
+  // One tile per workgroup.  What is left of the retired walk along x is this loop of one pass and the two `txi < txr`
+  // arms further down, which would request the next tile's first weights and patch and are never reached: the compiler
+  // keeps their code in every instantiation, and the instruction streams measured are the ones with it -- written
+  // without the loop or the arms all eight instantiations compile to other code (profiles/cnn_conv_shared_refactor.md)
+  for (int txi = txr; txi < txr + 1; ++txi) {
   const int ox0 = txi * W_TW, ix0 = ox0 - a.pad_left;
   const bool interior = iy0 >= 0 && iy0 + 18 <= a.H && ix0 >= 0 && ix0 + 18 <= a.W;
   const bool full_tile = oy0 + W_TH <= a.Ho && ox0 + W_TW <= a.Wo;
@@ -1060,7 +939,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   int ch_l;
   unsigned opix[2];  // element offsets of the (clamped) pixels in the output map
   bool ovalid[2];
-  auto out_pixels = [&](const int g) __attribute__((always_inline)) {
+  auto out_pixels = [&]() __attribute__((always_inline)) {
     int t = tid;
     if (LAUNDER) asm volatile("" : "+v"(t));
     const int i16_ = t & 15, q_ = (t >> 4) & 3, wave_ = t >> 6;
@@ -1074,8 +953,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   };
   const bool res_in_acc = a.residual != nullptr && a.out_scale == nullptr;  // see conv_bf3_kernel
   f32x4 acc[NH][2][2];
-  auto init_acc = [&](const int g) __attribute__((always_inline)) {  // a group's accumulators: zero, or its residual
-  out_pixels(g);
+  auto init_acc = [&]() __attribute__((always_inline)) {  // a group's accumulators: zero, or its residual
+  out_pixels();
   if (res_in_acc) {
     const float* res_n = a.residual + (size_t)n * a.Ho * a.Wo * a.Cout;
 #pragma unroll
@@ -1103,7 +982,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   }
   };
   // a group's fused shortcut, affine, residual, ReLU and stores
-  auto finish = [&](const int g) __attribute__((always_inline)) {
+  auto finish = [&]() __attribute__((always_inline)) {
 
   // ---- fused 1x1 shortcut (see conv_bf3_kernel), on v_mfma_f32_16x16x4_f32: A = weights [column][k], B = pixels ----
   if (a.sc_in) {
@@ -1145,7 +1024,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   // ---- epilogue: affine, residual, ReLU and one 16-byte store per accumulator tile, straight from the registers ----
   float* out_n = a.out + (size_t)n * a.Ho * a.Wo * a.Cout;
   const float* res_n = (a.residual && !res_in_acc) ? a.residual + (size_t)n * a.Ho * a.Wo * a.Cout : nullptr;
-  if (LAUNDER) out_pixels(g);  // (re-derived: see LAUNDER)
+  if (LAUNDER) out_pixels();  // (re-derived: see LAUNDER)
 #pragma unroll
   for (int hc = 0; hc < 2 * NH; ++hc) {
     const int hf = hc >> 1, ct = hc & 1;
@@ -1183,11 +1062,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     }
   }
   };
-  init_acc(g0);
+  init_acc();
 
-  for (int cc = 0; cc < NG * nch; ++cc) {
-  const int gi = (NG > 1 && cc >= nch) ? 1 : 0;  // (NG <= 2)
-  const int c = cc - gi * nch, g = g0 + gi;
+  for (int c = 0; c < nch; ++c) {
   {
     // phases of a chunk: (kernel row, column slice) with one row resident, (column slice) with all three
     constexpr int NPH = (3 / WR) * NH;
@@ -1195,7 +1072,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     for (int ph = 0; ph < NPH; ++ph) {
     {
       const int r0 = WR == 3 ? 0 : ph / NH, hf = WR == 3 ? ph : ph % NH;
-      if (cc > 0 || ph > 0 || txi > txr * run) __syncthreads();  // every wave has read the previous phase's fragments
+      if (c > 0 || ph > 0 || txi > txr) __syncthreads();  // every wave has read the previous phase's fragments
       // ---- registers -> LDS: the kernel row's weights (a straight copy) ----
 #pragma unroll
       for (int i = 0; i < NWI; ++i) {
@@ -1283,20 +1160,21 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         }
       }
       // ---- global -> registers for what comes next (in flight under this phase's products) ----
-      // (the chunk after this one: the same group's next 32 channels, or the next group's first)
-      const int gn = (c + 1 < nch) ? g : g + 1, cn = (c + 1 < nch) ? c + 1 : 0;
+      // (the chunk after this one: the group's next 32 channels.  gn is g wherever it is used -- as plain g the selects
+      // the compiler emits for it are gone and every instantiation changes: the same record)
+      const int gn = (c + 1 < nch) ? g : g + 1;
       if (ph + 1 < NPH) {
         BF3W_ISSUE_W(g, c, (WR == 3 ? 0 : (ph + 1) / NH), (WR == 3 ? ph + 1 : (ph + 1) % NH))
-      } else if (cc + 1 < NG * nch) {
-        BF3W_ISSUE_W(gn, cn, 0, 0)
-      } else if (txi + 1 < tx_end) {
-        BF3W_ISSUE_W(g0, 0, 0, 0)
+      } else if (c + 1 < nch) {
+        BF3W_ISSUE_W(gn, c + 1, 0, 0)
+      } else if (txi < txr) {
+        BF3W_ISSUE_W(g, 0, 0, 0)
       }
       if (ph == 0) {
-        if (cc + 1 < NG * nch) {
-          BF3W_ISSUE_P(gn, cn, ix0)
-        } else if (txi + 1 < tx_end) {
-          BF3W_ISSUE_P(g0, 0, ix0 + W_TW)
+        if (c + 1 < nch) {
+          BF3W_ISSUE_P(gn, c + 1, ix0)
+        } else if (txi < txr) {
+          BF3W_ISSUE_P(g, 0, ix0 + W_TW)
         }
       }
       __syncthreads();
@@ -1317,29 +1195,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
-          for (int pt = 0; pt < 2; ++pt) {
-            // smallest terms first, as conv_bf3_kernel (x = activation planes, w = weight planes)
-            if (PL == 3) {
-              acc[hf][ct][pt] = mfma16<false>(wv[ct][1], xv[pt][1], acc[hf][ct][pt]);
-              acc[hf][ct][pt] = mfma16<false>(wv[ct][PL - 1], xv[pt][0], acc[hf][ct][pt]);
-              acc[hf][ct][pt] = mfma16<false>(wv[ct][0], xv[pt][PL - 1], acc[hf][ct][pt]);
-            }
-            acc[hf][ct][pt] = mfma16<H>(wv[ct][1], xv[pt][0], acc[hf][ct][pt]);
-            acc[hf][ct][pt] = mfma16<H>(wv[ct][0], xv[pt][1], acc[hf][ct][pt]);
-            acc[hf][ct][pt] = mfma16<H>(wv[ct][0], xv[pt][0], acc[hf][ct][pt]);
-          }
+          for (int pt = 0; pt < 2; ++pt) plane_products16<PL, H>(xv[pt], wv[ct], acc[hf][ct][pt]);
       }
       }  // resident kernel rows
     }
     }  // phases of the chunk
   }
-  if (NG > 1 && c + 1 == nch && cc + 1 < NG * nch) {  // a group but the last is done: its stores, the next one's accumulators
-    finish(g);
-    init_acc(g + 1);
-  }
-  }  // chunks of the tile's groups
-  finish(g0 + NG - 1);
-  }  // tiles of the run
+  }  // chunks
+  finish();
+  }  // (the loop of one pass)
   BF3_TILE_LOOP_END
 }
 #undef BF3W_ISSUE_W
@@ -1421,10 +1285,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   auto tile_of = [&](int t) { return (t & 7) * per_xcd + (t >> 3); };
   int n, oy0, ox0;
   auto decode = [&](int tile) {
-    int qd = div_magic(tile, td.m_tx);
+    int qd = tile_div(tile, td.m_tx);
     ox0 = (tile - qd * td.tiles_x) * W_TW;
     tile = qd;
-    qd = div_magic(tile, td.m_ty);
+    qd = tile_div(tile, td.m_ty);
     oy0 = (tile - qd * td.tiles_y) * W_TH;
     n = qd;
   };
@@ -1715,9 +1579,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
             for (int ct = 0; ct < 2; ++ct) {
               if (j < 2 || third_full || ct == wave - 4) {
-                acc1[j][ct] = mfma16<true>(wv[ct][1], xv[0], acc1[j][ct]);
-                acc1[j][ct] = mfma16<true>(wv[ct][0], xv[1], acc1[j][ct]);
-                acc1[j][ct] = mfma16<true>(wv[ct][0], xv[0], acc1[j][ct]);
+                plane_products16<2, true>(xv, wv[ct], acc1[j][ct]);
               }
             }
           }
@@ -1760,9 +1622,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
           for (int ct = 0; ct < 2; ++ct) {
             if (j < 2 || third_full || ct == wave - 4) {
-              acc1[j][ct] = mfma16<true>(wv[bf][ct][1], xv[bf][j][0], acc1[j][ct]);
-              acc1[j][ct] = mfma16<true>(wv[bf][ct][0], xv[bf][j][1], acc1[j][ct]);
-              acc1[j][ct] = mfma16<true>(wv[bf][ct][0], xv[bf][j][0], acc1[j][ct]);
+              plane_products16<2, true>(xv[bf][j], wv[bf][ct], acc1[j][ct]);
             }
           }
         }
@@ -1833,11 +1693,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
-          for (int pt = 0; pt < 2; ++pt) {
-            acc[ct][pt] = mfma16<true>(wv[bf][ct][1], xv[bf][pt][0], acc[ct][pt]);
-            acc[ct][pt] = mfma16<true>(wv[bf][ct][0], xv[bf][pt][1], acc[ct][pt]);
-            acc[ct][pt] = mfma16<true>(wv[bf][ct][0], xv[bf][pt][0], acc[ct][pt]);
-          }
+          for (int pt = 0; pt < 2; ++pt) plane_products16<2, true>(xv[bf][pt], wv[bf][ct], acc[ct][pt]);
         if constexpr (C1) {
           if (tp < 3 && more) convert_c1(tp, oy0 - 2, ox0 - 2, interior_next, cbuf ^ 1);  // (in one lump on the first tap: 24,641 against 24,691 samples/s)
         } else {
@@ -1889,23 +1745,35 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   if ((hmax & 0xFFFFu) >= 0x7C00u || (hmax >> 16) >= 0x7C00u) atomicOr(a.ovf, 1);  // (infinity or NaN)
 }
 
+// The launch conv_bf3_kernel, conv_bf3flat_kernel and conv_bf3w_kernel share.  `kernel`: one workgroup of `threads` per
+// (tile, slice of `cols` output columns of a group); `rerun`: its PERSIST form, which a launch with ConvArgs::guard -- the
+// guarded rerun of a fp16x2 layer -- takes instead, on a small grid that walks the tiles (nullptr: the instantiation has
+// none).  `ready`: the instantiation's own table for cpx_dyn_lds_ready, [kernel, rerun] per device
+using Bf3Kernel = void (*)(ConvArgs, const uint4*, TileDiv);
 constexpr long long RERUN_GRID = 1024;  // workgroups along x of a guarded rerun (four per CU and group row)
-template <int NTN, int NPXC, int PL, bool H = false, int CT = 256, bool SC = false>
-int launch_bf3flat_t(const ConvArgs& a, const uint4* wimg, hipStream_t s) {
-  constexpr int BAND = CT / 2;
-  const size_t lds = std::max(((size_t)2 * PL * NPXC + (size_t)18 * PL * 32 * NTN) * 16, (size_t)(CT / 64) * 32 * 32 * sizeof(float));
-  static bool lds_ready[64], lds_ready_p[64];
-  if (!cpx_dyn_lds_ready(reinterpret_cast<const void*>(conv_bf3flat_kernel<NTN, NPXC, PL, H, false, CT, SC>), lds_ready, 160 * 1024 - 1024)) return -1;
+static int launch_bf3_tiles(Bf3Kernel kernel, Bf3Kernel rerun, bool (&ready)[2][64], const ConvArgs& a, const uint4* wimg, int tiles_x,
+                            int tiles_y, int cols, unsigned threads, size_t lds, hipStream_t s) {
+  if (!cpx_dyn_lds_ready(reinterpret_cast<const void*>(kernel), ready[0], 160 * 1024 - 1024)) return -1;
   TileDiv td{};
-  if (const int rc = fill_tiles(td, (a.Ho * a.Wo + BAND - 1) / BAND, 1, a.N, (a.Cout / a.groups) / (32 * NTN), TILES_PER_LAUNCH)) return rc;
-  const long long blocks = td.total;
-  if constexpr (PL == 3 && !H) if (a.guard != nullptr) {  // the guarded rerun of a fp16x2 layer: a small grid that walks the tiles (PERSIST)
-    if (!cpx_dyn_lds_ready(reinterpret_cast<const void*>(conv_bf3flat_kernel<NTN, NPXC, PL, false, true, CT>), lds_ready_p, 160 * 1024 - 1024)) return -1;
-    hipLaunchKernelGGL((conv_bf3flat_kernel<NTN, NPXC, PL, false, true, CT>), dim3((unsigned)std::min<long long>(blocks, RERUN_GRID), a.groups), dim3(CT), lds, s, a, wimg, td);
+  if (const int rc = fill_tiles(td, tiles_x, tiles_y, a.N, (a.Cout / a.groups) / cols, TILES_PER_LAUNCH)) return rc;
+  if (rerun != nullptr && a.guard != nullptr) {
+    if (!cpx_dyn_lds_ready(reinterpret_cast<const void*>(rerun), ready[1], 160 * 1024 - 1024)) return -1;
+    hipLaunchKernelGGL(rerun, dim3((unsigned)std::min<long long>(td.total, RERUN_GRID), a.groups), dim3(threads), lds, s, a, wimg, td);
     return 0;
   }
-  hipLaunchKernelGGL((conv_bf3flat_kernel<NTN, NPXC, PL, H, false, CT, SC>), dim3((unsigned)blocks, a.groups), dim3(CT), lds, s, a, wimg, td);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)td.total, a.groups), dim3(threads), lds, s, a, wimg, td);
   return 0;
+}
+template <int PL, bool H = false, bool SC = false>
+int launch_bf3flat_t(const ConvArgs& a, const uint4* wimg, hipStream_t s) {
+  constexpr int NTN = 2, NPXC = 256, CT = 256;  // (the one geometry the kernel is launched in)
+  constexpr int BAND = CT / 2;
+  const size_t lds = std::max(((size_t)2 * PL * NPXC + (size_t)18 * PL * 32 * NTN) * 16, (size_t)(CT / 64) * 32 * 32 * sizeof(float));
+  static bool lds_ready[2][64];
+  Bf3Kernel rerun = nullptr;
+  if constexpr (PL == 3 && !H) rerun = conv_bf3flat_kernel<NTN, NPXC, PL, false, true, CT>;
+  return launch_bf3_tiles(conv_bf3flat_kernel<NTN, NPXC, PL, H, false, CT, SC>, rerun, lds_ready, a, wimg, (a.Ho * a.Wo + BAND - 1) / BAND, 1,
+                          32 * NTN, CT, lds, s);
 }
 // the flattened tiling applies to stride-1 SAME 3 x 3 layers whose staged rows fit the LDS cap and pays when the
 // rectangular bands waste more than 8 % over it
@@ -1937,10 +1805,7 @@ __global__ __launch_bounds__(256) void split_weights8_kernel(const float* __rest
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = tap < 9 ? w[(((size_t)g * 9 + tap) * 8 + j) * cout_g + col] : 0.0f;
     uint4 p0, p1, p2;
-    split_pair(v[0], v[1], p0.x, p1.x, p2.x);
-    split_pair(v[2], v[3], p0.y, p1.y, p2.y);
-    split_pair(v[4], v[5], p0.z, p1.z, p2.z);
-    split_pair(v[6], v[7], p0.w, p1.w, p2.w);
+    split8<false>(v, 1.0f, 3, p0, p1, p2);
     const size_t base = (size_t)g * 30 * cout_g;
     out[base + ((size_t)(0 * 5 + st) * 2 + h) * cout_g + col] = p0;
     out[base + ((size_t)(1 * 5 + st) * 2 + h) * cout_g + col] = p1;
@@ -1978,12 +1843,9 @@ __global__ __launch_bounds__(256) void split_weights8h_kernel(const float* __res
     const float ws = wscale[g * 32 + col];
     float v[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = tap < 9 ? w[(((size_t)g * 9 + tap) * 8 + j) * 32 + col] * ws : 0.0f;
-    uint4 p0, p1;
-    split_pair2_h(v[0], v[1], p0.x, p1.x);
-    split_pair2_h(v[2], v[3], p0.y, p1.y);
-    split_pair2_h(v[4], v[5], p0.z, p1.z);
-    split_pair2_h(v[6], v[7], p0.w, p1.w);
+    for (int j = 0; j < 8; ++j) v[j] = tap < 9 ? w[(((size_t)g * 9 + tap) * 8 + j) * 32 + col] : 0.0f;
+    uint4 p0, p1, p2;
+    split8<true>(v, ws, 2, p0, p1, p2);
     const size_t base = (size_t)g * B8_WIMG;
     out[base + (size_t)(t * 2 + 0) * 128 + qq * 32 + col] = p0;
     out[base + (size_t)(t * 2 + 1) * 128 + qq * 32 + col] = p1;
@@ -2011,23 +1873,8 @@ __global__ __launch_bounds__(256) void split_weights_kernel(const float* __restr
     for (int j = 0; j < 8; ++j)
       v[j] = w[(((size_t)g * 9 + tap) * cin_g + chunk * KC + 8 * h + j) * cout_g + col];
     uint4 p0, p1, p2;
-    if (wscale) {
-      const float ws = wscale[g * cout_g + col];
-      split_pair2_h(v[0] * ws, v[1] * ws, p0.x, p1.x);
-      split_pair2_h(v[2] * ws, v[3] * ws, p0.y, p1.y);
-      split_pair2_h(v[4] * ws, v[5] * ws, p0.z, p1.z);
-      split_pair2_h(v[6] * ws, v[7] * ws, p0.w, p1.w);
-    } else if (planes == 3) {
-      split_pair(v[0], v[1], p0.x, p1.x, p2.x);
-      split_pair(v[2], v[3], p0.y, p1.y, p2.y);
-      split_pair(v[4], v[5], p0.z, p1.z, p2.z);
-      split_pair(v[6], v[7], p0.w, p1.w, p2.w);
-    } else {
-      split_pair2(v[0], v[1], p0.x, p1.x);
-      split_pair2(v[2], v[3], p0.y, p1.y);
-      split_pair2(v[4], v[5], p0.z, p1.z);
-      split_pair2(v[6], v[7], p0.w, p1.w);
-    }
+    if (wscale) split8<true>(v, wscale[g * cout_g + col], 2, p0, p1, p2);
+    else split8<false>(v, 1.0f, planes, p0, p1, p2);
     const size_t base = ((size_t)g * nchunks + chunk) * (18 * planes) * cout_g;
     out[base + ((size_t)(0 * 9 + tap) * 2 + h) * cout_g + col] = p0;
     out[base + ((size_t)(1 * 9 + tap) * 2 + h) * cout_g + col] = p1;
@@ -2060,23 +1907,8 @@ __global__ __launch_bounds__(256) void split_weights32_kernel(const float* __res
     for (int j = 0; j < 8; ++j)
       v[j] = w[(((size_t)g * 9 + ky * 3 + kx) * cin_g + chunk * KW + 8 * qq + j) * cout_g + col];
     uint4 p0, p1, p2;
-    if (wscale) {
-      const float ws = wscale[g * cout_g + col];
-      split_pair2_h(v[0] * ws, v[1] * ws, p0.x, p1.x);
-      split_pair2_h(v[2] * ws, v[3] * ws, p0.y, p1.y);
-      split_pair2_h(v[4] * ws, v[5] * ws, p0.z, p1.z);
-      split_pair2_h(v[6] * ws, v[7] * ws, p0.w, p1.w);
-    } else if (planes == 3) {
-      split_pair(v[0], v[1], p0.x, p1.x, p2.x);
-      split_pair(v[2], v[3], p0.y, p1.y, p2.y);
-      split_pair(v[4], v[5], p0.z, p1.z, p2.z);
-      split_pair(v[6], v[7], p0.w, p1.w, p2.w);
-    } else {
-      split_pair2(v[0], v[1], p0.x, p1.x);
-      split_pair2(v[2], v[3], p0.y, p1.y);
-      split_pair2(v[4], v[5], p0.z, p1.z);
-      split_pair2(v[6], v[7], p0.w, p1.w);
-    }
+    if (wscale) split8<true>(v, wscale[g * cout_g + col], 2, p0, p1, p2);
+    else split8<false>(v, 1.0f, planes, p0, p1, p2);
     const size_t base = (((size_t)g * nch + chunk) * 3 + ky) * (12 * planes) * cout_g;
     out[base + ((size_t)(0 * 3 + kx) * 4 + qq) * cout_g + col] = p0;
     out[base + ((size_t)(1 * 3 + kx) * 4 + qq) * cout_g + col] = p1;
@@ -2087,21 +1919,13 @@ __global__ __launch_bounds__(256) void split_weights32_kernel(const float* __res
 template <int NH, int PL, bool H = false>
 static int launch_bf3w_t(const ConvArgs& a, const uint4* wimg, hipStream_t s) {
   const size_t lds = (size_t)(w_patch_entries(PL) + w_wsub_entries(PL)) * 16 + (size_t)(a.Cin / a.groups) * 8;  // + BatchNorm scale / shift
-  static bool lds_ready[64], lds_ready_p[64];
+  static bool lds_ready[2][64];
   // (NH = 2 carries 16 more accumulator registers: the BatchNorm parameters go to LDS there)
   constexpr bool LDSBN = NH > 1 || PL == 2;
-  if (!cpx_dyn_lds_ready(reinterpret_cast<const void*>(conv_bf3w_kernel<false, LDSBN, NH, 1, PL, H>), lds_ready, 160 * 1024 - 1024)) return -1;
-  TileDiv td{};
-  td.run = 1;
-  if (const int rc = fill_tiles(td, (a.Wo + W_TW - 1) / W_TW, (a.Ho + W_TH - 1) / W_TH, a.N, (a.Cout / a.groups) / (32 * NH), TILES_PER_LAUNCH)) return rc;
-  const long long blocks = td.total;
-  if constexpr (PL == 3 && !H) if (a.guard != nullptr) {  // the guarded rerun of a fp16x2 layer: a small grid that walks the tiles (PERSIST)
-    if (!cpx_dyn_lds_ready(reinterpret_cast<const void*>(conv_bf3w_kernel<false, LDSBN, NH, 1, PL, false, true>), lds_ready_p, 160 * 1024 - 1024)) return -1;
-    hipLaunchKernelGGL((conv_bf3w_kernel<false, LDSBN, NH, 1, PL, false, true>), dim3((unsigned)std::min<long long>(blocks, RERUN_GRID), a.groups), dim3(512), lds, s, a, wimg, td);
-    return 0;
-  }
-  hipLaunchKernelGGL((conv_bf3w_kernel<false, LDSBN, NH, 1, PL, H>), dim3((unsigned)blocks, a.groups), dim3(512), lds, s, a, wimg, td);
-  return 0;
+  Bf3Kernel rerun = nullptr;
+  if constexpr (PL == 3 && !H) rerun = conv_bf3w_kernel<false, LDSBN, NH, 1, PL, false, true>;
+  return launch_bf3_tiles(conv_bf3w_kernel<false, LDSBN, NH, 1, PL, H>, rerun, lds_ready, a, wimg, (a.Wo + W_TW - 1) / W_TW,
+                          (a.Ho + W_TH - 1) / W_TH, 32 * NH, 512, lds, s);
 }
 // The math mode of a launch and the image it reads, chosen once: two fp16 planes, two bf16 planes where the layer has them,
 // else three.  launch(planes, half, image) gets the first two as integral constants.
@@ -2136,18 +1960,11 @@ int launch_bf3_t(const ConvArgs& a, const uint4* wimg, hipStream_t s) {
   constexpr int PH = (TH - 1) * S + 3, PW = (TW - 1) * S + 3;
   size_t lds = ((size_t)(C8 ? 3 : 2 * PL) * PH * PW + (size_t)(C8 ? 30 : 18 * PL) * 32 * NTN) * 16;
   if (lds < (CT / 64) * 32 * 32 * sizeof(float)) lds = (CT / 64) * 32 * 32 * sizeof(float);
-  static bool lds_ready[64], lds_ready_p[64];
-  if (!cpx_dyn_lds_ready(reinterpret_cast<const void*>(conv_bf3_kernel<NTN, S, NB, TW, CT, C8, PL, H>), lds_ready, 160 * 1024 - 1024)) return -1;
-  TileDiv td{};
-  if (const int rc = fill_tiles(td, (a.Wo + TW - 1) / TW, (a.Ho + TH - 1) / TH, a.N, (a.Cout / a.groups) / (32 * NTN), TILES_PER_LAUNCH)) return rc;
-  const long long blocks = td.total;
-  if constexpr (PL == 3 && !H) if (a.guard != nullptr) {  // the guarded rerun of a fp16x2 layer: a small grid that walks the tiles (PERSIST)
-    if (!cpx_dyn_lds_ready(reinterpret_cast<const void*>(conv_bf3_kernel<NTN, S, NB, TW, CT, C8, PL, false, true>), lds_ready_p, 160 * 1024 - 1024)) return -1;
-    hipLaunchKernelGGL((conv_bf3_kernel<NTN, S, NB, TW, CT, C8, PL, false, true>), dim3((unsigned)std::min<long long>(blocks, RERUN_GRID), a.groups), dim3(CT), lds, s, a, wimg, td);
-    return 0;
-  }
-  hipLaunchKernelGGL((conv_bf3_kernel<NTN, S, NB, TW, CT, C8, PL, H>), dim3((unsigned)blocks, a.groups), dim3(CT), lds, s, a, wimg, td);
-  return 0;
+  static bool lds_ready[2][64];
+  Bf3Kernel rerun = nullptr;
+  if constexpr (PL == 3 && !H) rerun = conv_bf3_kernel<NTN, S, NB, TW, CT, C8, PL, false, true>;
+  return launch_bf3_tiles(conv_bf3_kernel<NTN, S, NB, TW, CT, C8, PL, H>, rerun, lds_ready, a, wimg, (a.Wo + TW - 1) / TW, (a.Ho + TH - 1) / TH,
+                          32 * NTN, CT, lds, s);
 }
 
 // band width: with 32-pixel bands a wave's 32 pixels are one row, i.e. 32 consecutive 16-byte LDS entries -- the
@@ -2155,9 +1972,9 @@ int launch_bf3_t(const ConvArgs& a, const uint4* wimg, hipStream_t s) {
 // bands lanes 12-13 and 26-27 (4-5 and 20-21) share bank slots and every A read takes two LDS passes.  Measured:
 // no difference on the 160-wide maps (LDS is not the limit), and the 80-wide maps of stage 3 lose 17 % of a 3 x 32
 // tiling to padding, so both stay at 16
-// (conv_bf3_kernel's band width, column tiles, bands and threads per workgroup for 32, 64 and 128 columns per group)
+// (conv_bf3_kernel's band width, bands and threads per workgroup for 32 and 64 columns per group -- one 32-column tile per
+// workgroup either way -- and its bands, threads and column tiles for 128)
 constexpr int TW_S2 = 16, NB_S2 = 2, CT_S2 = 512;
-constexpr int TW_S3 = 16, NB_S3 = 2, CT_S3 = 512, NTN_S3 = 1;
 constexpr int NB_S4 = 1, CT_S4 = 256, NTN_S4 = 2;
 static_assert(B8_WIMG == (int)WeightImages::C8_HALF_ENTRIES, "conv_block32_kernel<true> and the layout agree on the tap-quad image");
 
@@ -2265,8 +2082,7 @@ int launch_conv_bf3(const ConvArgs& a_in, const void* wimg, hipStream_t s) {
     if (a.sc_in && ((a.sc_cin / a.groups) & 3)) return -2;  // the fused shortcut walks K in fours
     return launch_bf3w(a, im, w, s);
   }
-  if (a.Cout / a.groups == 32) return launch_bf3_t<1, 1, NB_S2, TW_S2, CT_S2>(a, w, s);
-  if (a.Cout / a.groups == 64) return launch_bf3_t<NTN_S3, 1, NB_S3, TW_S3, CT_S3>(a, w, s);
+  if (cls == ConvClass::Plain) return launch_bf3_t<1, 1, NB_S2, TW_S2, CT_S2>(a, w, s);  // (32 or 64 columns: a 32-column slice per workgroup)
   // Flat at stride 1 (128 columns, stage 4): the flattened kernel takes it when the map is small (flat_pays, a property of the
   // launch), in every math mode.  256 staged pixels + two N tiles = 80 KB: two workgroups per CU.  (Wider maps -- 54 x 54 at
   // frame size 64 -- would need 384 staged pixels and then fit only one N tile per workgroup: measured slower than the
@@ -2276,9 +2092,9 @@ int launch_conv_bf3(const ConvArgs& a_in, const void* wimg, hipStream_t s) {
     if (a.planes == 2 && a.half && a.sc_in && a.sc_planes && conv_shortcut_planes_layer(a, a.sc_cin / a.groups) && !a.residual &&
         a.sc_stride >= 1 && a.sc_xscale > 0.0f && (a.sc_H - 1) / a.sc_stride + 1 == a.Ho && (a.sc_W - 1) / a.sc_stride + 1 == a.Wo &&
         (long long)a.sc_H * a.sc_W * a.sc_cin < (1ll << 31))
-      return launch_bf3flat_t<2, 256, 2, true, 256, true>(a, w + im.half / 16, s);
+      return launch_bf3flat_t<2, true, true>(a, w + im.half / 16, s);
     return with_math(a, im, w, [&](auto pl, auto h, const uint4* wi) {
-      return launch_bf3flat_t<2, 256, decltype(pl)::value, decltype(h)::value>(a, wi, s);
+      return launch_bf3flat_t<decltype(pl)::value, decltype(h)::value>(a, wi, s);
     });
   }
   return with_math(a, im, w, [&](auto pl, auto h, const uint4* wi) {
@@ -2333,10 +2149,8 @@ int launch_conv_block32(const ConvArgs& a_in, const ConvArgs& b_in, const void* 
            : !cpx_dyn_lds_ready(reinterpret_cast<const void*>(conv_block32_kernel<false>), lds_ready, 160 * 1024 - 1024))
     return -1;
   // one workgroup per CU (125 KB of LDS), shared among the groups; a multiple of eight per group so that blockIdx.x & 7 is the XCD
-  const int cus = cpx_device_cus();
-  if (cus == 0) return -1;
-  const char* e = std::getenv("CPX_BLOCK32_GRID");
-  const int gx = e ? persistent_grid_x(std::atoi(e), 1, td.total) : persistent_grid_x(cus, a.groups, td.total);
+  const int gx = persistent_grid(cpx_device_cus(), a.groups, td.total, "CPX_BLOCK32_GRID");
+  if (gx < 0) return -1;
   if (c1) hipLaunchKernelGGL((conv_block32_kernel<true, true>), dim3((unsigned)gx, a.groups), dim3(512), lds, s, a, b, wa, wb, td);
   else if (c8) hipLaunchKernelGGL(conv_block32_kernel<true>, dim3((unsigned)gx, a.groups), dim3(512), lds, s, a, b, wa, wb, td);
   else hipLaunchKernelGGL(conv_block32_kernel<false>, dim3((unsigned)gx, a.groups), dim3(512), lds, s, a, b, wa, wb, td);

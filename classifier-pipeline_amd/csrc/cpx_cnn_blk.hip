@@ -30,12 +30,15 @@
 // Arithmetic: conv_block32_kernel's (fp16x2, the same planes and scales); the taps are summed kx-major, another float32
 // order of the same terms -- logits within 1e-5 of the two-launch form (tests/test_cnn_gpu.py).
 // Reference semantics: /root/reference/src/ml_tools/resnet/wr_resnet.py:49-98 (wr_block).
+// The device vocabulary (vector types, at_off / pix_off, split_pair2_h, mfma16<true>, pk_max_u16, med3, static_for) is
+// cpx_cnn_dev.h's, the tiles, their walk and the grid's width cpx_conv_layout_core.h's: shared with cpx_cnn_bf3.hip and cpx_cnn_rw.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 
+#include "cpx_cnn_dev.h"
 #include "cpx_conv_layout_core.h"
 #include "cpx_kernels.h"
 
@@ -43,49 +46,6 @@ namespace cpx {
 
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-template <typename T>
-__device__ __forceinline__ const T* at_off(const T* base, unsigned bytes) {
-  return reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + bytes);
-}
-template <typename T>
-__device__ __forceinline__ T* at_off(T* base, unsigned bytes) {
-  return reinterpret_cast<T*>(reinterpret_cast<char*>(base) + bytes);
-}
-__device__ __forceinline__ unsigned pix_off(int y, int x, int W, int C) {
-  return __umul24(__umul24((unsigned)y, (unsigned)W) + (unsigned)x, (unsigned)C);
-}
-__device__ __forceinline__ float relu_bits(float x) { return __int_as_float(max(__float_as_int(x), 0)); }
-__device__ __forceinline__ void split_h(float a, float b, unsigned& hi, unsigned& lo) {
-  f16x2 v = {(_Float16)a, (_Float16)b};
-  hi = __builtin_bit_cast(unsigned, v);
-  asm("v_fma_mixlo_f16 %0, %1, 1.0, -%2 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(lo) : "v"(a), "v"(hi));
-  asm("v_fma_mixhi_f16 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lo) : "v"(b), "v"(hi));
-}
-__device__ __forceinline__ f32x4 mfma_h(u32x4 w, u32x4 x, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, w), __builtin_bit_cast(f16x8, x), c, 0, 0, 0);
-}
-__device__ __forceinline__ unsigned pk_max_u16(unsigned x, unsigned y) {
-  unsigned r;
-  asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
-  return r;
-}
-__device__ __forceinline__ int med3(int x, int lo, int hi) {
-  int r;
-  asm("v_med3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "v"(lo), "s"(hi));
-  return r;
-}
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
 constexpr int K_T = 16;                          // output tile: 16 x 16
 constexpr int K_PP = 20, K_PNPX = 400;           // the staged input patch: 20 x 20
 constexpr int K_PNPXP = 402;                     // pixels per (plane, quarter pair) region, x 32 B = 64 mod 128 (cpx_cnn_bf3.hip: B_NPXP)
@@ -185,8 +145,8 @@ __global__ __launch_bounds__(K_CT) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
 #pragma unroll
     for (int j = 0; j < 4; ++j) v[j] = inside ? v[j] : 0.0f;
     unsigned h0, h1, l0, l1;
-    split_h(v[0], v[1], h0, l0);
-    split_h(v[2], v[3], h1, l1);
+    split_pair2_h(v[0], v[1], h0, l0);
+    split_pair2_h(v[2], v[3], h1, l1);
     hmax = pk_max_u16(pk_max_u16(hmax, h0), h1);
     pre_p[i] = u32x4{h0, h1, l0, l1};  // (in place: the store follows at once)
   };
@@ -225,9 +185,9 @@ __global__ __launch_bounds__(K_CT) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
         static_for<0, 3>([&](auto rc) __attribute__((always_inline)) {
           constexpr int r = decltype(rc)::value, o = i - r;
           if constexpr (o >= 0 && o < 9) {
-            if constexpr (pr == 0) acc[o] = mfma_h(Wr[r * 3 + kx][1], xh[bf], acc[o]);
-            if constexpr (pr == 1) acc[o] = mfma_h(Wr[r * 3 + kx][0], xl[bf], acc[o]);
-            if constexpr (pr == 2) acc[o] = mfma_h(Wr[r * 3 + kx][0], xh[bf], acc[o]);
+            if constexpr (pr == 0) acc[o] = mfma16<true>(Wr[r * 3 + kx][1], xh[bf], acc[o]);
+            if constexpr (pr == 1) acc[o] = mfma16<true>(Wr[r * 3 + kx][0], xl[bf], acc[o]);
+            if constexpr (pr == 2) acc[o] = mfma16<true>(Wr[r * 3 + kx][0], xh[bf], acc[o]);
           }
         });
       });
@@ -255,9 +215,9 @@ __global__ __launch_bounds__(K_CT) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
         if (k == 0 || hh) {
-          acc[9 + k] = mfma_h(Wr[ky * 3 + kx][1], eh[k], acc[9 + k]);
-          acc[9 + k] = mfma_h(Wr[ky * 3 + kx][0], el[k], acc[9 + k]);
-          acc[9 + k] = mfma_h(Wr[ky * 3 + kx][0], eh[k], acc[9 + k]);
+          acc[9 + k] = mfma16<true>(Wr[ky * 3 + kx][1], eh[k], acc[9 + k]);
+          acc[9 + k] = mfma16<true>(Wr[ky * 3 + kx][0], el[k], acc[9 + k]);
+          acc[9 + k] = mfma16<true>(Wr[ky * 3 + kx][0], eh[k], acc[9 + k]);
         }
       }
       between(std::integral_constant<int, 33 + tp>{});
@@ -274,8 +234,8 @@ __global__ __launch_bounds__(K_CT) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
 #pragma unroll
     for (int j = 0; j < 4; ++j) v[j] = inside ? v[j] : 0.0f;
     unsigned h0, h1, l0, l1;
-    split_h(v[0], v[1], h0, l0);
-    split_h(v[2], v[3], h1, l1);
+    split_pair2_h(v[0], v[1], h0, l0);
+    split_pair2_h(v[2], v[3], h1, l1);
     hmax = pk_max_u16(pk_max_u16(hmax, h0), h1);
     // channels ct 16 + 4 q .. of the 32: piece 4 ct + q -> quarter pair ct, 8-byte slot q of the pixel's 32 bytes
     const unsigned off = (unsigned)(((ct * K_MNPXP + mrow * K_MP + mcol) * 4 + q) * 8);
@@ -337,9 +297,9 @@ __global__ __launch_bounds__(K_CT) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
         static_for<0, 3>([&](auto rc) __attribute__((always_inline)) {
           constexpr int r = decltype(rc)::value, o = i - r;
           if constexpr (o >= 0 && o < 8) {
-            if constexpr (pr == 0) acc[o] = mfma_h(Wr[r * 3 + kx][1], xh[bf], acc[o]);
-            if constexpr (pr == 1) acc[o] = mfma_h(Wr[r * 3 + kx][0], xl[bf], acc[o]);
-            if constexpr (pr == 2) acc[o] = mfma_h(Wr[r * 3 + kx][0], xh[bf], acc[o]);
+            if constexpr (pr == 0) acc[o] = mfma16<true>(Wr[r * 3 + kx][1], xh[bf], acc[o]);
+            if constexpr (pr == 1) acc[o] = mfma16<true>(Wr[r * 3 + kx][0], xl[bf], acc[o]);
+            if constexpr (pr == 2) acc[o] = mfma16<true>(Wr[r * 3 + kx][0], xh[bf], acc[o]);
           }
         });
       });
@@ -465,10 +425,8 @@ int launch_conv_block32s(const ConvArgs& a, const ConvArgs& b, const void* wa, c
   if (const int rc = fill_tiles(td, (a.W + K_T - 1) / K_T, (a.H + K_T - 1) / K_T, a.N, TILES_PERSISTENT)) return rc;
   static bool lds_ready[64];
   if (!cpx_dyn_lds_ready(reinterpret_cast<const void*>(conv_block32s_kernel), lds_ready, 160 * 1024 - 1024)) return -1;
-  const int cus = cpx_device_cus();
-  if (cus == 0) return -1;
-  const char* e = std::getenv("CPX_BLOCK32_GRID");
-  const int gx = e ? persistent_grid_x(std::atoi(e), 1, td.total) : persistent_grid_x(cus, a.groups, td.total);
+  const int gx = persistent_grid(cpx_device_cus(), a.groups, td.total, "CPX_BLOCK32_GRID");
+  if (gx < 0) return -1;
   // CPX_BLOCK32_CARRY=0: every tile computes its own halo columns; CPX_BLOCK32_WALK=0 | 1: the tile-interleaved walk or the
   // row runs whatever choose_walk says (both read at every launch, as the grid: for the bitwise tests and the timing)
   const char* ec = std::getenv("CPX_BLOCK32_CARRY");

@@ -42,11 +42,14 @@
 // profiles/r06_conv_rw_experiments.md; counters of the shipped forms: profiles/r06_conv_sq_counters.json, r06_conv_traffic.json.
 // Reference semantics: /root/reference/src/ml_tools/resnet/wr_resnet.py:49-98 (wr_block: BN -> ReLU -> conv3x3 -> BN -> ReLU ->
 // conv3x3 -> add), kerasmodel.py:441-454.
+// The device vocabulary (vector types, at_off / pix_off, split_pair2_h, mfma16<true>, pk_max_u16, med3, static_for) is
+// cpx_cnn_dev.h's, the tile argument and the grid's width cpx_conv_layout_core.h's: shared with cpx_cnn_bf3.hip and cpx_cnn_blk.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <type_traits>
 
+#include "cpx_cnn_dev.h"
 #include "cpx_conv_layout_core.h"
 #include "cpx_kernels.h"
 
@@ -54,48 +57,7 @@ namespace cpx {
 
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-template <typename T>
-__device__ __forceinline__ const T* at_off(const T* base, unsigned bytes) {
-  return reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + bytes);
-}
-template <typename T>
-__device__ __forceinline__ T* at_off(T* base, unsigned bytes) {
-  return reinterpret_cast<T*>(reinterpret_cast<char*>(base) + bytes);
-}
-// element offset of pixel (y, x) in an NHWC sample (24-bit multiplies: see cpx_cnn_bf3.hip)
-__device__ __forceinline__ unsigned pix_off(int y, int x, int W, int C) {
-  return __umul24(__umul24((unsigned)y, (unsigned)W) + (unsigned)x, (unsigned)C);
-}
-__device__ __forceinline__ float relu_bits(float x) { return __int_as_float(max(__float_as_int(x), 0)); }
-// two float32 -> two fp16 planes, each rounded to nearest (cpx_cnn_bf3.hip: split_pair2_h)
-__device__ __forceinline__ void split_h(float a, float b, unsigned& hi, unsigned& lo) {
-  f16x2 v = {(_Float16)a, (_Float16)b};
-  hi = __builtin_bit_cast(unsigned, v);
-  asm("v_fma_mixlo_f16 %0, %1, 1.0, -%2 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(lo) : "v"(a), "v"(hi));
-  asm("v_fma_mixhi_f16 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lo) : "v"(b), "v"(hi));
-}
-__device__ __forceinline__ f32x4 mfma_h(u32x4 w, u32x4 x, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, w), __builtin_bit_cast(f16x8, x), c, 0, 0, 0);
-}
-
-struct RwTiles {
-  unsigned long long m_tx, m_ty;  // div_magic's multipliers (cpx_conv_layout_core.h: fill_tiles)
-  int tiles_x, tiles_y, total;
-};
-// a loop whose index is a compile-time constant in every iteration (register arrays indexed by it stay registers)
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
-__device__ __forceinline__ int div_magic(int n, unsigned long long m) { return (int)(((unsigned long long)n * m) >> 42); }
+struct RwTiles : Tiles {};  // (a name of its own: the kernels' signatures as a trace prints them)
 
 constexpr int RW_TW = 16;                      // output columns of a tile = the pixels of one B fragment
 constexpr int RW_CT = 256;                     // threads: four waves, one per SIMD
@@ -187,10 +149,10 @@ __global__ __launch_bounds__(RW_CT) __attribute__((amdgpu_waves_per_eu(1, 1))) v
   const int per_xcd = (td.total + 7) >> 3;
   auto tile_of = [&](int t) { return (t & 7) * per_xcd + (t >> 3); };
   auto decode = [&](int tile, int& n_, int& oy_, int& ox_) {
-    int qd = div_magic(tile, td.m_tx);
+    int qd = tile_div(tile, td.m_tx);
     ox_ = (tile - qd * td.tiles_x) * RW_TW;
     tile = qd;
-    qd = div_magic(tile, td.m_ty);
+    qd = tile_div(tile, td.m_ty);
     oy_ = (tile - qd * td.tiles_y) * ROWS;
     n_ = qd;
   };
@@ -226,11 +188,6 @@ __global__ __launch_bounds__(RW_CT) __attribute__((amdgpu_waves_per_eu(1, 1))) v
   const unsigned st_base = (unsigned)((((q8 >> 2) * NPXP + (tid >> 3)) * 4 + (q8 & 3)) * 8);
   f32x4 psc[NCH], psh[NCH];  // filled behind the barrier that publishes s_bn
   const unsigned coff0 = (unsigned)(g * CING + 4 * q8);
-  auto med3 = [](int x, int lo, int hi) __attribute__((always_inline)) {
-    int r;
-    asm("v_med3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "v"(lo), "s"(hi));
-    return r;
-  };
   const int Hm1 = a.H - 1, Wm1 = a.W - 1;
   auto issue_item = [&](const int i, const int c, const int n_, const int oy_, const int ox_) __attribute__((always_inline)) {
     const float* in_n = a.in + (size_t)n_ * a.H * a.W * a.Cin;  // (uniform)
@@ -241,11 +198,6 @@ __global__ __launch_bounds__(RW_CT) __attribute__((amdgpu_waves_per_eu(1, 1))) v
   // out of fp16's range = a high plane that came out infinite: the running maximum of the high planes' magnitudes, two
   // packed halves per instruction (conv_block32_kernel's test; the sign bits are masked off where no ReLU precedes)
   unsigned hmax = 0u;
-  auto pk_max_u16 = [](unsigned x, unsigned y) __attribute__((always_inline)) {
-    unsigned r;
-    asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
-    return r;
-  };
   // registers -> the chunk's fp16 planes in LDS buffer `bsel`, in two stages that ride on different steps of the product
   // stream (a step of nine products hides ~18 vector instructions; an item's 35 in one lump left the matrix pipe idle):
   // activate = BatchNorm + ReLU prologue and zero padding, in place; store = fp16 split + the two 8-byte LDS stores
@@ -266,8 +218,8 @@ __global__ __launch_bounds__(RW_CT) __attribute__((amdgpu_waves_per_eu(1, 1))) v
   };
   auto store_item = [&](const int i, const int bsel) __attribute__((always_inline)) {
     unsigned h0, h1, l0, l1;
-    split_h(__uint_as_float(pre_p[i][0]), __uint_as_float(pre_p[i][1]), h0, l0);
-    split_h(__uint_as_float(pre_p[i][2]), __uint_as_float(pre_p[i][3]), h1, l1);
+    split_pair2_h(__uint_as_float(pre_p[i][0]), __uint_as_float(pre_p[i][1]), h0, l0);
+    split_pair2_h(__uint_as_float(pre_p[i][2]), __uint_as_float(pre_p[i][3]), h1, l1);
     if (has_bn) hmax = pk_max_u16(pk_max_u16(hmax, h0), h1);
     else hmax = pk_max_u16(pk_max_u16(hmax, h0 & 0x7FFF7FFFu), h1 & 0x7FFF7FFFu);
     unsigned char* sp = reinterpret_cast<unsigned char*>(s_buf) + st_base;
@@ -295,8 +247,8 @@ __global__ __launch_bounds__(RW_CT) __attribute__((amdgpu_waves_per_eu(1, 1))) v
   auto store_sc = [&](const int i) __attribute__((always_inline)) {
     if constexpr (SC) {
       unsigned h0, h1, l0, l1;
-      split_h(__uint_as_float(pre_s[i][0]) * a.sc_xscale, __uint_as_float(pre_s[i][1]) * a.sc_xscale, h0, l0);
-      split_h(__uint_as_float(pre_s[i][2]) * a.sc_xscale, __uint_as_float(pre_s[i][3]) * a.sc_xscale, h1, l1);
+      split_pair2_h(__uint_as_float(pre_s[i][0]) * a.sc_xscale, __uint_as_float(pre_s[i][1]) * a.sc_xscale, h0, l0);
+      split_pair2_h(__uint_as_float(pre_s[i][2]) * a.sc_xscale, __uint_as_float(pre_s[i][3]) * a.sc_xscale, h1, l1);
       hmax = pk_max_u16(pk_max_u16(hmax, h0 & 0x7FFF7FFFu), h1 & 0x7FFF7FFFu);  // (the residual stream has both signs)
       unsigned char* sp = reinterpret_cast<unsigned char*>(s_sc) + sc_st_base;
       *reinterpret_cast<uint2*>(sp + i * (RW_PPI * 32)) = make_uint2(h0, h1);
@@ -350,9 +302,9 @@ __global__ __launch_bounds__(RW_CT) __attribute__((amdgpu_waves_per_eu(1, 1))) v
         static_for<0, 3>([&](auto rc) __attribute__((always_inline)) {
           constexpr int r = decltype(rc)::value, d = i - r, o = d / S;
           if constexpr (d >= 0 && d % S == 0 && o < ROWS) {
-            if constexpr (pr == 0) acc[o] = mfma_h(Wr[C][r * 3 + kx][1], xh[bf], acc[o]);
-            if constexpr (pr == 1) acc[o] = mfma_h(Wr[C][r * 3 + kx][0], xl[bf], acc[o]);
-            if constexpr (pr == 2) acc[o] = mfma_h(Wr[C][r * 3 + kx][0], xh[bf], acc[o]);
+            if constexpr (pr == 0) acc[o] = mfma16<true>(Wr[C][r * 3 + kx][1], xh[bf], acc[o]);
+            if constexpr (pr == 1) acc[o] = mfma16<true>(Wr[C][r * 3 + kx][0], xl[bf], acc[o]);
+            if constexpr (pr == 2) acc[o] = mfma16<true>(Wr[C][r * 3 + kx][0], xh[bf], acc[o]);
           }
         });
       });
@@ -388,9 +340,9 @@ __global__ __launch_bounds__(RW_CT) __attribute__((amdgpu_waves_per_eu(1, 1))) v
         // plane order of the taps; then the next tile's operand is requested into the registers the first chunk emptied
         if constexpr (s % 3 == 0 && s >= 3 && s / 3 - 1 < ROWS) {
           constexpr int o = s / 3 - 1;
-          acc[o] = mfma_h(Wsc[1], xsh[o & 1], acc[o]);
-          acc[o] = mfma_h(Wsc[0], xsl[o & 1], acc[o]);
-          acc[o] = mfma_h(Wsc[0], xsh[o & 1], acc[o]);
+          acc[o] = mfma16<true>(Wsc[1], xsh[o & 1], acc[o]);
+          acc[o] = mfma16<true>(Wsc[0], xsl[o & 1], acc[o]);
+          acc[o] = mfma16<true>(Wsc[0], xsh[o & 1], acc[o]);
         }
         if constexpr (s % 3 == 0 && s / 3 < ROWS) {
           constexpr int o = s / 3;
@@ -546,10 +498,10 @@ __global__ __launch_bounds__(256) void split_shortcut_kernel(const float* __rest
 #pragma unroll
   for (int j = 0; j < 8; ++j) v[j] = w[((size_t)g * cin_g + chunk * 32 + 8 * qq + j) * cout_g + col] * f;
   uint4 hi, lo;
-  split_h(v[0], v[1], hi.x, lo.x);
-  split_h(v[2], v[3], hi.y, lo.y);
-  split_h(v[4], v[5], hi.z, lo.z);
-  split_h(v[6], v[7], hi.w, lo.w);
+  split_pair2_h(v[0], v[1], hi.x, lo.x);
+  split_pair2_h(v[2], v[3], hi.y, lo.y);
+  split_pair2_h(v[4], v[5], hi.z, lo.z);
+  split_pair2_h(v[6], v[7], hi.w, lo.w);
   const size_t base = (size_t)(g * nch + chunk) * 8 * cout_g + (size_t)qq * cout_g + col;
   out[base] = hi;
   out[base + (size_t)4 * cout_g] = lo;
@@ -590,10 +542,9 @@ int launch_rw_t(const ConvArgs& a, const uint4* wimg, hipStream_t s) {
   // one workgroup per CU (four waves, each with a SIMD's whole register file), shared among the (group, 64-channel half)
   // pairs; a multiple of eight per pair so that blockIdx.x & 7 names the XCD -- the halves of a group then walk the same tiles
   // on the same XCD at the same time and share the patch in its L2
-  const int cus = cpx_device_cus();
-  if (cus == 0) return -1;
   const int ny = a.groups * ((a.Cout / a.groups) / RW_WC);
-  const int gx = persistent_grid_x(cus, ny, td.total);
+  const int gx = persistent_grid(cpx_device_cus(), ny, td.total);
+  if (gx < 0) return -1;
   hipLaunchKernelGGL((conv_rw_kernel<S, NCH, ROWS, BN, RES, SC>), dim3((unsigned)gx, (unsigned)ny), dim3(RW_CT), LDS, s, a, wimg, td);
   return 0;
 }

@@ -6,6 +6,7 @@
 // cpx_cnn_bf3.hip, cpx_cnn_rw.hip and cpx_cnn_blk.hip are its users in the product.
 #pragma once
 #include <stddef.h>
+#include <stdlib.h>
 
 #include <algorithm>
 
@@ -104,11 +105,31 @@ constexpr int TILE_AXIS_LIMIT = 4096;
 constexpr long long TILES_PER_LAUNCH = 1ll << 22;
 constexpr long long TILES_PERSISTENT = (1ll << 22) - 8;
 inline unsigned long long tile_magic(int d) { return (1ull << 42) / (unsigned long long)d + 1; }
+#if defined(__HIPCC__)
+#define CPX_WALK_HD __host__ __device__ __forceinline__
+#else
+#define CPX_WALK_HD inline
+#endif
+CPX_WALK_HD int tile_div(int n, unsigned long long m) { return (int)(((unsigned long long)n * m) >> 42); }
+// one step of an index decode: the remainder of n by d (m = tile_magic(d)); n becomes the quotient
+CPX_WALK_HD int tile_split(int& n, unsigned long long m, int d) {
+  const int q = tile_div(n, m), r = n - q * d;
+  n = q;
+  return r;
+}
+// A kernel's tile argument: the tile counts along x and y, their product with the samples, and tile_div's multipliers.
+// conv_rw_kernel takes it as it is.  BlkTiles (below) and TileDiv (cpx_cnn_bf3.hip) state the same fields themselves, with the
+// walk and the column split: the byte offsets of a kernel's arguments are part of its instruction stream, and as structs
+// derived from this one theirs move (profiles/cnn_conv_shared_refactor.md).  fill_tiles fills all three
+struct Tiles {
+  unsigned long long m_tx, m_ty;
+  int tiles_x, tiles_y, total;
+};
 
-// fills tiles_x / tiles_y / total (= tiles_x tiles_y n) and their multipliers of a kernel's tile argument (TileDiv, RwTiles,
-// BlkTiles: schedule_point's way); -3: out of div_magic's range
-template <class Tiles>
-int fill_tiles(Tiles& td, int tiles_x, int tiles_y, long long n, long long limit) {
+// fills tiles_x / tiles_y / total (= tiles_x tiles_y n) and their multipliers of a kernel's tile argument (schedule_point's
+// way); -3: out of tile_div's range
+template <class T>
+int fill_tiles(T& td, int tiles_x, int tiles_y, long long n, long long limit) {
   if (tiles_x < 1 || tiles_y < 1 || tiles_x >= TILE_AXIS_LIMIT || tiles_y >= TILE_AXIS_LIMIT) return -3;
   const long long total = (long long)tiles_x * tiles_y * n;  // (< 2^24 n: no overflow for any int n)
   if (total >= limit) return -3;
@@ -118,8 +139,8 @@ int fill_tiles(Tiles& td, int tiles_x, int tiles_y, long long n, long long limit
   return 0;
 }
 // ... and with the columns of a group split among nsplit workgroups per tile (TileDiv): the split is the innermost index
-template <class Tiles>
-int fill_tiles(Tiles& td, int tiles_x, int tiles_y, long long n, int nsplit, long long limit) {
+template <class T>
+int fill_tiles(T& td, int tiles_x, int tiles_y, long long n, int nsplit, long long limit) {
   if (nsplit < 1 || nsplit >= TILE_AXIS_LIMIT) return -3;
   td.nsplit = nsplit, td.m_nsplit = tile_magic(nsplit);
   return fill_tiles(td, tiles_x, tiles_y, n * nsplit, limit);
@@ -131,6 +152,13 @@ inline int persistent_grid_x(int cus, int ny, long long tiles) {
   const int gx = std::max(8, cus / std::max(ny, 1) / 8 * 8);
   return (int)std::min<long long>(gx, (tiles + 7) / 8 * 8);
 }
+// ... on a device of `cus` compute units (0: no current device; -1).  `width_env`: an environment variable that, where
+// set, gives the compute units of the whole grid instead (CPX_BLOCK32_GRID: read at every launch, for the bitwise tests and the timing)
+inline int persistent_grid(int cus, int ny, long long tiles, const char* width_env = nullptr) {
+  if (cus == 0) return -1;
+  const char* e = width_env ? getenv(width_env) : nullptr;
+  return e ? persistent_grid_x(atoi(e), 1, tiles) : persistent_grid_x(cus, ny, tiles);
+}
 
 // ---- the order in which conv_block32s_kernel's persistent workgroups walk the tiles (cpx_cnn_blk.hip), host + device ----
 // Both walks hand out UNITS: every XCD (blockIdx.x & 7) owns a contiguous eighth of the units, its gx / 8 workgroups
@@ -139,18 +167,15 @@ inline int persistent_grid_x(int cus, int ny, long long tiles) {
 //   WALK_ROWS   one tile row of one sample, walked from its rightmost tile to its leftmost: every tile but a row's first has
 //               its right neighbour as the workgroup's previous tile, which is what the kernel's halo carry needs, and
 //               vertically adjacent rows of a sample are in flight in the same XCD at the same time.
-#if defined(__HIPCC__)
-#define CPX_WALK_HD __host__ __device__ __forceinline__
-#else
-#define CPX_WALK_HD inline
-#endif
 enum { WALK_TILES = 0, WALK_ROWS = 1 };
 struct BlkTiles {
-  unsigned long long m_tx, m_ty;  // tile_div's multipliers (fill_tiles)
+  unsigned long long m_tx, m_ty;  // Tiles's fields (fill_tiles), at Tiles's offsets
   int tiles_x, tiles_y, total;
   int walk, units;                // WALK_*; units = total (WALK_TILES) or total / tiles_x (WALK_ROWS): set_walk
 };
-CPX_WALK_HD int tile_div(int n, unsigned long long m) { return (int)(((unsigned long long)n * m) >> 42); }
+static_assert(sizeof(BlkTiles) == 40 && offsetof(BlkTiles, total) == offsetof(Tiles, total) && offsetof(BlkTiles, walk) == 28 &&
+                  offsetof(BlkTiles, units) == 32,
+              "the argument layout conv_block32s_kernel was tuned with");
 inline void set_walk(BlkTiles& td, int walk) {
   td.walk = walk;
   td.units = walk == WALK_ROWS ? td.total / td.tiles_x : td.total;

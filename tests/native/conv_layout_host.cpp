@@ -11,7 +11,7 @@ namespace {
 struct Layer {  // the fields of ConvArgs that conv_shape_of reads
   int Cin, Cout, groups, ksize, stride;
 };
-struct Tiles {  // the fields of TileDiv / RwTiles / BlkTiles that fill_tiles writes
+struct SplitTiles {  // TileDiv's fields (cpx_cnn_bf3.hip): cpx::Tiles's and the column split, in that struct's order
   unsigned long long m_nsplit, m_tx, m_ty;
   int nsplit, tiles_x, tiles_y, total;
 };
@@ -31,15 +31,26 @@ extern "C" int conv_layout_host(int Cin, int Cout, int groups, int ksize, int st
 // persistent = 0: the limit of the one-unit-per-workgroup launches, 1: of the persistent ones.  nsplit = 0: the form without
 // a column split.  out: m_nsplit, m_tx, m_ty, nsplit, tiles_x, tiles_y, total.
 extern "C" int tile_fill_host(int tiles_x, int tiles_y, long long n, int nsplit, int persistent, uint64_t* out) {
-  Tiles td{};
+  SplitTiles td{};
   const long long limit = persistent ? cpx::TILES_PERSISTENT : cpx::TILES_PER_LAUNCH;
-  const int rc = nsplit ? cpx::fill_tiles(td, tiles_x, tiles_y, n, nsplit, limit) : cpx::fill_tiles(td, tiles_x, tiles_y, n, limit);
+  int rc;
+  if (nsplit) {
+    rc = cpx::fill_tiles(td, tiles_x, tiles_y, n, nsplit, limit);
+  } else {  // the struct the kernels without a column split take
+    cpx::Tiles t{};
+    rc = cpx::fill_tiles(t, tiles_x, tiles_y, n, limit);
+    td.m_tx = t.m_tx, td.m_ty = t.m_ty, td.tiles_x = t.tiles_x, td.tiles_y = t.tiles_y, td.total = t.total;
+  }
   const uint64_t v[7] = {td.m_nsplit, td.m_tx, td.m_ty, (uint64_t)td.nsplit, (uint64_t)td.tiles_x, (uint64_t)td.tiles_y, (uint64_t)td.total};
   for (int i = 0; i < 7; ++i) out[i] = v[i];
   return rc;
 }
 
 extern "C" uint64_t tile_magic_host(int d) { return cpx::tile_magic(d); }
+extern "C" int tile_div_host(int n, int d) { return cpx::tile_div(n, cpx::tile_magic(d)); }  // the kernels' n / d
+extern "C" int persistent_grid_host(int cus, int ny, long long tiles, const char* width_env) {
+  return cpx::persistent_grid(cus, ny, tiles, width_env);
+}
 extern "C" int persistent_grid_x_host(int cus, int ny, long long tiles) { return cpx::persistent_grid_x(cus, ny, tiles); }
 
 #ifdef CONV_LAYOUT_HOST_MAIN
@@ -85,8 +96,9 @@ int main() {
       const unsigned long long ns[] = {0, (unsigned long long)d - 1, (unsigned long long)d, (unsigned long long)d + 1,
                                        1000ull * d - 1, 1000ull * d, (1ull << 22) - 1};
       for (unsigned long long n : ns)
-        if (n < (1ull << 22)) EXPECT(((n * m) >> 42) == n / d);
+        if (n < (1ull << 22)) EXPECT(((n * m) >> 42) == n / d && (unsigned long long)tile_div_host((int)n, d) == n / d);
     }
+    EXPECT(tile_div_host((1 << 22) - 9, 4095) == ((1 << 22) - 9) / 4095 && tile_div_host((1 << 22) - 1, 4095) == ((1 << 22) - 1) / 4095);
   }
   {  // the range errors
     uint64_t o[7];
@@ -97,6 +109,8 @@ int main() {
   }
   EXPECT(persistent_grid_x_host(256, 2, 1 << 20) == 128 && persistent_grid_x_host(256, 64, 1 << 20) == 8 &&
          persistent_grid_x_host(256, 2, 9) == 16 && persistent_grid_x_host(256, 0, 0) == 0);
+  EXPECT(persistent_grid_host(256, 2, 1 << 20, nullptr) == 128 && persistent_grid_host(0, 2, 1 << 20, nullptr) == -1 &&
+         persistent_grid_host(256, 2, 1 << 20, "CPX_TEST_NO_SUCH_VARIABLE") == 128);
   return failures ? 1 : 0;
 }
 #endif

@@ -24,6 +24,7 @@ def host_lib(tmp_path_factory):
     lib.tile_magic_host.restype = C.c_uint64
     lib.tile_fill_host.argtypes = [C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_void_p]
     lib.persistent_grid_x_host.argtypes = [C.c_int, C.c_int, C.c_longlong]
+    lib.persistent_grid_host.argtypes = [C.c_int, C.c_int, C.c_longlong, C.c_char_p]
     return lib
 
 
@@ -136,6 +137,16 @@ def test_tile_magic_exact_to_the_edge_of_its_range(host_lib):
             assert n * m < 2 ** 64 and (n * m) >> 42 == n // d, (n, d)  # (n * m < 2^64: what the device's 64-bit product holds)
 
 
+def test_tile_div_at_the_edges_of_its_range(host_lib):
+    """The one division the kernels and the block walk share (tile_div), at the largest index a persistent grid forms
+    (2^22 - 9, + 7 for the walk's rounding) and the largest count along an axis (4095)."""
+    div = host_lib.tile_div_host
+    for d in (1, 2, 3, 7, 10, 4094, 4095):
+        for n in (0, d - 1, d, min(4095 * d, 2 ** 22) - 1, 2 ** 22 - 9, 2 ** 22 - 2, 2 ** 22 - 1):
+            assert 0 <= n < 2 ** 22 and div(n, d) == n // d, (n, d)
+    assert div(2 ** 22 - 9, 4095) == 1024
+
+
 def fill(lib, tx, ty, n, nsplit=0, persistent=0):
     out = np.zeros(7, np.uint64)
     rc = lib.tile_fill_host(tx, ty, n, nsplit, persistent, out.ctypes.data_as(C.c_void_p))
@@ -173,6 +184,18 @@ def test_persistent_grid_x(host_lib):
                 g = gx(cus, ny, tiles)
                 assert g % 8 == 0 and g >= 8 and g <= (tiles + 7) // 8 * 8
                 assert g == min(max(8, cus // ny // 8 * 8), (tiles + 7) // 8 * 8)
+
+
+def test_persistent_grid_width_and_its_override(host_lib, monkeypatch):
+    """persistent_grid: persistent_grid_x on the device's CUs shared among the rows; -1 without a device; where the named
+    variable is set, its value as the CUs of the whole grid (what CPX_BLOCK32_GRID means to the block launchers)."""
+    pg = host_lib.persistent_grid_host
+    monkeypatch.delenv("CPX_TEST_GRID", raising=False)
+    assert pg(256, 2, 10 ** 6, None) == 128 and pg(256, 2, 10 ** 6, b"CPX_TEST_GRID") == 128
+    assert pg(0, 2, 10 ** 6, None) == -1 and pg(256, 2, 9, None) == 16
+    monkeypatch.setenv("CPX_TEST_GRID", "64")
+    assert pg(256, 2, 10 ** 6, b"CPX_TEST_GRID") == 64 and pg(256, 2, 10 ** 6, None) == 128
+    assert pg(256, 2, 9, b"CPX_TEST_GRID") == 16 and pg(0, 2, 10 ** 6, b"CPX_TEST_GRID") == -1
 
 
 def test_standalone_under_sanitizers(tmp_path):
