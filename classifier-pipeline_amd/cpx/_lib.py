@@ -147,21 +147,81 @@ GRAPH_CONV_H2_KC = 32   # CONV_F16X2 weights: two fp16 planes in MFMA fragment o
 HEAD_SIGMOID, HEAD_SOFTMAX = 0, 1
 
 
-EXPORTS = [
-    "cpx_abi_version", "cpx_create", "cpx_destroy", "cpx_last_error", "cpx_stream", "cpx_synchronize", "cpx_join_medians", "cpx_release_memory",
-    "cpx_track_batch", "cpx_track_workspace_bytes", "cpx_last_kernel_timing", "cpx_associate_batch",
-    "cpx_track_limits_batch", "cpx_crop_tile", "cpx_conv2d", "cpx_cnn_head",
-    "cpx_finalize_tracks", "cpx_counts_prefix", "cpx_plan_segments", "cpx_aggregate_predictions",
-    "cpx_conv_timing_enable", "cpx_conv_timing_report", "cpx_cptv_unpack", "cpx_thumb_stats", "cpx_trackless_thumb",
-    "cpx_trackless_thumb_batch", "cpx_thumb_stats_ex",
-    "cpx_track_frame", "cpx_associate_frame", "cpx_cnn_create", "cpx_cnn_destroy", "cpx_cnn_forward", "cpx_ir_detect", "cpx_set_cnn_math", "cpx_get_cnn_math",
-    "cpx_mog2_create", "cpx_mog2_apply", "cpx_mog2_background", "cpx_mog2_destroy",
-    "cpx_track_batch_ex", "cpx_track_frame_ex", "cpx_set_background", "cpx_get_background", "cpx_track_limits_batch_ex",
-    "cpx_cnn_head_ex", "cpx_ir_delta_variance", "cpx_cptv_inflate", "cpx_cptv_gather_index", "cpx_format_regions", "cpx_json_indent", "cpx_ir_merge", "cpx_ir_resize_area",
-    "cpx_ir_frame_statistics", "cpx_cnn_last_overflow", "cpx_cnn_set_activation_bounds", "cpx_cnn_overflow_forwards", "cpx_cnn_forward_taps",
-    "cpx_graph_create", "cpx_graph_forward", "cpx_graph_arena_bytes", "cpx_graph_arena_allocated", "cpx_graph_destroy",
-    "cpx_cnn_set_residual_bounds", "cpx_cnn_shortcut_scale",
-]
+# One entry per function of include/cpx.h: name -> (restype, [argtypes]).  load() declares the prototypes from it, call() and
+# status() marshal by it, tests/test_binding_cpu.py holds it against the header.
+def _signatures():
+    i, vp = C.c_int, C.c_void_p
+    i32p, intp, f32p, vpp, sizep = (C.POINTER(ty) for ty in (C.c_int32, C.c_int, C.c_float, C.c_void_p, C.c_size_t))
+    return {
+        "cpx_abi_version": (i, []),
+        "cpx_create": (i, [i, C.POINTER(Config), vpp]),
+        "cpx_destroy": (None, [vp]),
+        "cpx_last_error": (C.c_char_p, [vp]),
+        "cpx_stream": (vp, [vp]),
+        "cpx_synchronize": (i, [vp]),
+        "cpx_join_medians": (i, [vp]),
+        "cpx_release_memory": (i, [vp]),
+        "cpx_track_batch": (i, [vp, vp, i32p, vp, i, vp, vp, vp, vp, vp]),
+        "cpx_track_workspace_bytes": (C.c_size_t, [vp, i, i]),
+        "cpx_last_kernel_timing": (i, [vp, f32p, intp]),
+        "cpx_associate_batch": (i, [vp, vp, i32p, vp, i, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "cpx_track_limits_batch": (i, [vp, vp, vp, vp, vp, vp, i, vp]),
+        "cpx_crop_tile": (i, [vp, vp, vp, vp, vp, i, vp, i, i, vp]),
+        "cpx_conv2d": (i, [vp, vp]),
+        "cpx_cnn_head": (i, [vp, vp, i, i, i, vp, vp, vp, vp, i, vp, vp]),
+        "cpx_finalize_tracks": (i, [vp, vp, i32p, vp, i, vp, vp, vp, vp, vp]),
+        "cpx_counts_prefix": (i, [vp, vp, i, vp]),
+        "cpx_plan_segments": (i, [vp, vp, i32p, vp, i, vp, vp, vp, vp, i, vp, vp, vp, vp, vp]),
+        "cpx_aggregate_predictions": (i, [vp, vp, vp, i, vp, i, i, i, i, vp, vp]),
+        "cpx_conv_timing_enable": (i, [vp, i]),
+        "cpx_conv_timing_report": (i, [vp, vp, i, intp]),
+        "cpx_cptv_unpack": (i, [vp, vp, vp, vp, vp, i, vp]),
+        "cpx_thumb_stats": (i, [vp, vp, vp, vp, vp, i, vp]),
+        "cpx_trackless_thumb": (i, [vp, vp, i, i, vp]),
+        "cpx_trackless_thumb_batch": (i, [vp, vp, vp, i, vp]),
+        "cpx_thumb_stats_ex": (i, [vp, vp, vp, vp, vp, i, vp, i, i, i]),
+        "cpx_track_frame": (i, [vp, vp, vp, i, i, vp, vp, vp, vp, vp]),
+        "cpx_associate_frame": (i, [vp, vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "cpx_cnn_create": (i, [vp, C.POINTER(WRResNetParams), vpp]),
+        "cpx_cnn_destroy": (None, [vp]),
+        "cpx_cnn_forward": (i, [vp, vp, i, i, i, vp, vp]),
+        "cpx_ir_detect": (i, [vp, vp, i, i, i, i, i, vp, vp, vp, vp]),
+        "cpx_set_cnn_math": (i, [vp, i]),
+        "cpx_get_cnn_math": (i, [vp]),
+        "cpx_mog2_create": (i, [vp, i, i, i, i, C.c_float, vpp]),
+        "cpx_mog2_apply": (i, [vp, vp, C.c_double, vp]),
+        "cpx_mog2_background": (i, [vp, vp]),
+        "cpx_mog2_destroy": (None, [vp]),
+        "cpx_track_batch_ex": (i, [vp, vp, i32p, vp, i, vp, vp, vp, vp, vp, i]),
+        "cpx_track_frame_ex": (i, [vp, vp, vp, i, i, vp, vp, vp, vp, vp, i]),
+        "cpx_set_background": (i, [vp, i, vp, vp, C.c_double]),
+        "cpx_get_background": (i, [vp, i, vp, vp, C.POINTER(C.c_double)]),
+        "cpx_track_limits_batch_ex": (i, [vp, vp, vp, vp, vp, vp, i, vp, i]),
+        "cpx_cnn_head_ex": (i, [vp, C.POINTER(HeadDesc)]),
+        "cpx_ir_delta_variance": (i, [vp, vp, vp, i, i, vp, i, vp]),
+        "cpx_cptv_inflate": (i, [vp, vp, vp, i, vp, vp, vp, vp]),
+        "cpx_cptv_gather_index": (i, [vp, vp, vp, vp, i, vp, vp, vp]),
+        "cpx_format_regions": (C.c_long, [vp, i, C.c_long, i, i, i, vp, C.c_long]),
+        "cpx_json_indent": (C.c_long, [C.c_char_p, C.c_long, i, i, vp, C.c_long]),
+        "cpx_ir_merge": (i, [vp, vp, vp, i, i, i, vp, vp, i, i, i, i, vp, vp, vp]),
+        "cpx_ir_resize_area": (i, [vp, vp, i, i, i, i, vp]),
+        "cpx_ir_frame_statistics": (i, [vp, vp, vp, i, i, vp, vp]),
+        "cpx_cnn_last_overflow": (i, [vp, intp]),
+        "cpx_cnn_set_activation_bounds": (i, [vp, f32p, i]),
+        "cpx_cnn_overflow_forwards": (i, [vp, intp, i]),
+        "cpx_cnn_forward_taps": (i, [vp, vp, i, i, i, vp, vp, vpp, i, vp]),
+        "cpx_graph_create": (i, [vp, C.POINTER(GraphOp), i, C.POINTER(GraphTensor), i, i, i, vpp]),
+        "cpx_graph_forward": (i, [vp, vp, i, vp]),
+        "cpx_graph_arena_bytes": (i, [vp, i, sizep]),
+        "cpx_graph_arena_allocated": (i, [vp, sizep]),
+        "cpx_graph_destroy": (None, [vp]),
+        "cpx_cnn_set_residual_bounds": (i, [vp, f32p, i]),
+        "cpx_cnn_shortcut_scale": (i, [C.c_float, C.c_float, f32p]),
+    }
+
+
+SIGNATURES = _signatures()
+EXPORTS = list(SIGNATURES)
 
 IR_FRAME_STATS_DTYPE = np.dtype([("min", "<i4"), ("max", "<i4"), ("sum", "<i8"), ("median_x2", "<i4"), ("reserved", "<i4"),
                                  ("filtered_sum", "<i8")])
@@ -191,136 +251,68 @@ def load():
     except ImportError:  # pure ctypes use without torch: the system runtime is fine
         pass
     lib = C.CDLL(LIB_PATH)
-    vp, i32p = C.c_void_p, C.POINTER(C.c_int32)
-    lib.cpx_abi_version.restype = C.c_int
-    lib.cpx_create.argtypes = [C.c_int, C.POINTER(Config), C.POINTER(vp)]
-    lib.cpx_create.restype = C.c_int
-    lib.cpx_destroy.argtypes = [vp]
-    lib.cpx_destroy.restype = None
-    lib.cpx_last_error.argtypes = [vp]
-    lib.cpx_last_error.restype = C.c_char_p
-    lib.cpx_stream.argtypes = [vp]
-    lib.cpx_stream.restype = vp
-    lib.cpx_synchronize.argtypes = [vp]
-    lib.cpx_synchronize.restype = C.c_int
-    lib.cpx_join_medians.argtypes = [vp]
-    lib.cpx_join_medians.restype = C.c_int
-    lib.cpx_release_memory.argtypes = [vp]
-    lib.cpx_release_memory.restype = C.c_int
-    lib.cpx_track_batch.argtypes = [vp, vp, i32p, vp, C.c_int, vp, vp, vp, vp, vp]
-    lib.cpx_track_batch.restype = C.c_int
-    lib.cpx_associate_batch.argtypes = [vp, vp, i32p, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.cpx_associate_batch.restype = C.c_int
-    lib.cpx_track_limits_batch.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp]
-    lib.cpx_track_limits_batch.restype = C.c_int
-    lib.cpx_crop_tile.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp]
-    lib.cpx_crop_tile.restype = C.c_int
-    lib.cpx_conv2d.argtypes = [vp, vp]
-    lib.cpx_conv2d.restype = C.c_int
-    lib.cpx_cnn_head.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp]
-    lib.cpx_cnn_head.restype = C.c_int
-    lib.cpx_cnn_head_ex.argtypes = [vp, C.POINTER(HeadDesc)]
-    lib.cpx_cnn_head_ex.restype = C.c_int
-    lib.cpx_finalize_tracks.argtypes = [vp, vp, i32p, vp, C.c_int, vp, vp, vp, vp, vp]
-    lib.cpx_finalize_tracks.restype = C.c_int
-    lib.cpx_plan_segments.argtypes = [vp, vp, i32p, vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]
-    lib.cpx_plan_segments.restype = C.c_int
-    lib.cpx_counts_prefix.argtypes = [vp, vp, C.c_int, vp]
-    lib.cpx_counts_prefix.restype = C.c_int
-    lib.cpx_aggregate_predictions.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
-    lib.cpx_aggregate_predictions.restype = C.c_int
-    lib.cpx_conv_timing_enable.argtypes = [vp, C.c_int]
-    lib.cpx_conv_timing_enable.restype = C.c_int
-    lib.cpx_conv_timing_report.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int)]
-    lib.cpx_conv_timing_report.restype = C.c_int
-    lib.cpx_set_cnn_math.argtypes = [vp, C.c_int]
-    lib.cpx_set_cnn_math.restype = C.c_int
-    lib.cpx_get_cnn_math.argtypes = [vp]
-    lib.cpx_get_cnn_math.restype = C.c_int
-    lib.cpx_cnn_last_overflow.argtypes = [vp, C.POINTER(C.c_int)]
-    lib.cpx_cnn_last_overflow.restype = C.c_int
-    lib.cpx_cnn_overflow_forwards.argtypes = [vp, C.POINTER(C.c_int), C.c_int]
-    lib.cpx_cnn_overflow_forwards.restype = C.c_int
-    lib.cpx_cnn_set_activation_bounds.argtypes = [vp, C.POINTER(C.c_float), C.c_int]
-    lib.cpx_cnn_set_activation_bounds.restype = C.c_int
-    lib.cpx_cnn_set_residual_bounds.argtypes = [vp, C.POINTER(C.c_float), C.c_int]
-    lib.cpx_cnn_set_residual_bounds.restype = C.c_int
-    lib.cpx_cnn_shortcut_scale.argtypes = [C.c_float, C.c_float, C.POINTER(C.c_float)]
-    lib.cpx_cnn_shortcut_scale.restype = C.c_int
-    lib.cpx_mog2_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(vp)]
-    lib.cpx_mog2_create.restype = C.c_int
-    lib.cpx_mog2_apply.argtypes = [vp, vp, C.c_double, vp]
-    lib.cpx_mog2_apply.restype = C.c_int
-    lib.cpx_mog2_background.argtypes = [vp, vp]
-    lib.cpx_mog2_background.restype = C.c_int
-    lib.cpx_mog2_destroy.argtypes = [vp]
-    lib.cpx_mog2_destroy.restype = None
-    lib.cpx_ir_detect.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
-    lib.cpx_ir_detect.restype = C.c_int
-    lib.cpx_ir_delta_variance.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp]
-    lib.cpx_ir_delta_variance.restype = C.c_int
-    lib.cpx_ir_merge.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
-    lib.cpx_ir_merge.restype = C.c_int
-    lib.cpx_ir_resize_area.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
-    lib.cpx_ir_resize_area.restype = C.c_int
-    lib.cpx_ir_frame_statistics.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp]
-    lib.cpx_ir_frame_statistics.restype = C.c_int
-    lib.cpx_cnn_create.argtypes = [vp, C.POINTER(WRResNetParams), C.POINTER(vp)]
-    lib.cpx_cnn_create.restype = C.c_int
-    lib.cpx_cnn_destroy.argtypes = [vp]
-    lib.cpx_cnn_destroy.restype = None
-    lib.cpx_graph_create.argtypes = [vp, C.POINTER(GraphOp), C.c_int, C.POINTER(GraphTensor), C.c_int, C.c_int, C.c_int,
-                                     C.POINTER(vp)]
-    lib.cpx_graph_create.restype = C.c_int
-    lib.cpx_graph_forward.argtypes = [vp, vp, C.c_int, vp]
-    lib.cpx_graph_forward.restype = C.c_int
-    lib.cpx_graph_arena_bytes.argtypes = [vp, C.c_int, C.POINTER(C.c_size_t)]
-    lib.cpx_graph_arena_bytes.restype = C.c_int
-    lib.cpx_graph_arena_allocated.argtypes = [vp, C.POINTER(C.c_size_t)]
-    lib.cpx_graph_arena_allocated.restype = C.c_int
-    lib.cpx_graph_destroy.argtypes = [vp]
-    lib.cpx_graph_destroy.restype = None
-    lib.cpx_cnn_forward.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
-    lib.cpx_cnn_forward.restype = C.c_int
-    lib.cpx_cnn_forward_taps.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.POINTER(vp), C.c_int, vp]
-    lib.cpx_cnn_forward_taps.restype = C.c_int
-    lib.cpx_track_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
-    lib.cpx_track_frame.restype = C.c_int
-    lib.cpx_track_batch_ex.argtypes = [vp, vp, i32p, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int]
-    lib.cpx_track_batch_ex.restype = C.c_int
-    lib.cpx_track_frame_ex.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int]
-    lib.cpx_track_frame_ex.restype = C.c_int
-    lib.cpx_set_background.argtypes = [vp, C.c_int, vp, vp, C.c_double]
-    lib.cpx_set_background.restype = C.c_int
-    lib.cpx_get_background.argtypes = [vp, C.c_int, vp, vp, C.POINTER(C.c_double)]
-    lib.cpx_get_background.restype = C.c_int
-    lib.cpx_track_limits_batch_ex.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int]
-    lib.cpx_track_limits_batch_ex.restype = C.c_int
-    lib.cpx_associate_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.cpx_associate_frame.restype = C.c_int
-    lib.cpx_thumb_stats.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp]
-    lib.cpx_thumb_stats.restype = C.c_int
-    lib.cpx_thumb_stats_ex.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int]
-    lib.cpx_thumb_stats_ex.restype = C.c_int
-    lib.cpx_trackless_thumb.argtypes = [vp, vp, C.c_int, C.c_int, vp]
-    lib.cpx_trackless_thumb.restype = C.c_int
-    lib.cpx_trackless_thumb_batch.argtypes = [vp, vp, vp, C.c_int, vp]
-    lib.cpx_trackless_thumb_batch.restype = C.c_int
-    lib.cpx_cptv_unpack.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp]
-    lib.cpx_cptv_unpack.restype = C.c_int
-    lib.cpx_cptv_inflate.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp, vp]
-    lib.cpx_cptv_inflate.restype = C.c_int
-    lib.cpx_cptv_gather_index.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp]
-    lib.cpx_cptv_gather_index.restype = C.c_int
-    lib.cpx_format_regions.argtypes = [vp, C.c_int, C.c_long, C.c_int, C.c_int, C.c_int, vp, C.c_long]
-    lib.cpx_format_regions.restype = C.c_long
-    lib.cpx_json_indent.argtypes = [C.c_char_p, C.c_long, C.c_int, C.c_int, vp, C.c_long]
-    lib.cpx_json_indent.restype = C.c_long
-    lib.cpx_track_workspace_bytes.argtypes = [vp, C.c_int, C.c_int]
-    lib.cpx_track_workspace_bytes.restype = C.c_size_t
-    lib.cpx_last_kernel_timing.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]
-    lib.cpx_last_kernel_timing.restype = C.c_int
+    for name, (restype, argtypes) in SIGNATURES.items():
+        declare(getattr(lib, name), restype, argtypes)
     if lib.cpx_abi_version() != 3:
         raise ImportError("libcpx_hip.so ABI version mismatch")
     _lib = lib
     return lib
+
+
+def ptr(x, what="a cpx call"):
+    """What a call site holds -> what ctypes takes for a pointer parameter: None -> NULL, a torch tensor -> its
+    data_ptr(), a numpy array -> its ctypes.data, a ctypes Structure -> byref; ctypes pointers, byref objects, ints,
+    floats and bytes pass through.  The kernels index densely, so a tensor or array that is not contiguous is refused."""
+    if x is None or type(x) is C.c_void_p:   # (the two cheapest first: this runs per argument of every call)
+        return x
+    data_ptr = getattr(x, "data_ptr", None)
+    if data_ptr is not None:
+        if not x.is_contiguous():
+            raise ValueError("%s: tensor of shape %s, strides %s is not contiguous" % (what, tuple(x.shape), x.stride()))
+        return C.c_void_p(data_ptr())
+    if isinstance(x, np.ndarray):
+        if not x.flags.c_contiguous:
+            raise ValueError("%s: array of shape %s, strides %s is not C-contiguous" % (what, x.shape, x.strides))
+        return C.c_void_p(x.ctypes.data)
+    if isinstance(x, C.Structure):
+        return C.byref(x)
+    return x
+
+
+def declare(fn, restype, argtypes):
+    """Give a function of the library its entry of the table: the prototype ctypes converts by, and -- worked out here,
+    once, not per call -- how many parameters it takes and where the pointers among them stand: fn.pointers = ((position,
+    the POINTER type an address is cast to, or None for void * / char *), ...).  Both live on the function object that
+    load() fetched (the one `lib.<name>` hands out from then on): status() takes no other."""
+    fn.restype, fn.argtypes, fn.arity = restype, argtypes, len(argtypes)
+    fn.pointers = tuple((k, None if ty in (C.c_void_p, C.c_char_p) else ty) for k, ty in enumerate(argtypes)
+                        if ty in (C.c_void_p, C.c_char_p) or issubclass(ty, C._Pointer))
+
+
+def status(lib, name, *args):
+    """lib.<name>(...) with ptr() applied to every argument the function declares as a pointer -> its integer status."""
+    fn = getattr(lib, name)
+    try:
+        pointers = fn.pointers
+    except AttributeError:
+        raise TypeError("%s has no declared prototype: take the library from cpx._lib.load()" % name) from None
+    if len(args) != fn.arity:
+        raise TypeError("%s takes %d arguments, %d given" % (name, fn.arity, len(args)))
+    args = list(args)
+    for k, typed in pointers:
+        a = ptr(args[k], name)
+        if typed is not None and type(a) is C.c_void_p:   # an address for a typed pointer (int32_t *clip_offsets)
+            a = C.cast(a, typed)
+        args[k] = a
+    return fn(*args)
+
+
+def check(lib, err_handle, rc):
+    """Raise CpxError with cpx_last_error(err_handle) as its text when the status rc is not CPX_OK."""
+    if rc != 0:
+        raise CpxError(rc, (lib.cpx_last_error(err_handle) or b"").decode())
+
+
+def call(lib, err_handle, name, *args):
+    """status(), checked."""
+    check(lib, err_handle, status(lib, name, *args))

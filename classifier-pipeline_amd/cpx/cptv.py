@@ -391,9 +391,7 @@ def inflate_files_on_device(engine, blobs, names=None):
     """The bytes of whole .cptv files -> frames on the device, without the host touching their content: upload,
     cpx_cptv_inflate (one wavefront per file: gzip + DEFLATE + section walk), cpx_cptv_gather_index,
     cpx_cptv_unpack.  A file that fails is reported in ``errors`` and leaves the others alone."""
-    import ctypes as C
-
-    from ._lib import (CPTV_FILE_DTYPE, CPTV_HEADER_BYTES, CPTV_RESULT_DTYPE, CPTV_SLOT_DTYPE, CPTV_STATUS, CpxError)
+    from ._lib import CPTV_FILE_DTYPE, CPTV_HEADER_BYTES, CPTV_RESULT_DTYPE, CPTV_SLOT_DTYPE, CPTV_STATUS
 
     t = engine.torch
     dev = engine.device
@@ -435,11 +433,7 @@ def inflate_files_on_device(engine, blobs, names=None):
     header_dev = t.empty((n, CPTV_HEADER_BYTES), dtype=t.uint8, device=dev)
     results_dev = t.zeros(n * 10, dtype=t.int32, device=dev)
     engine.sync_inputs()
-    p = lambda x: C.c_void_p(x.data_ptr())
-    rc = engine.lib.cpx_cptv_inflate(engine.h, p(in_dev), p(files_dev), n, p(out_dev), p(slots_dev), p(header_dev),
-                                     p(results_dev))
-    if rc != 0:
-        raise CpxError(rc, engine._err())
+    engine.call("cpx_cptv_inflate", in_dev, files_dev, n, out_dev, slots_dev, header_dev, results_dev)
     engine.synchronize()
     res = results_dev.cpu().numpy().view(CPTV_RESULT_DTYPE).reshape(-1)
     out.results = res
@@ -474,13 +468,8 @@ def inflate_files_on_device(engine, blobs, names=None):
     dense_dev = t.empty(total * 8, dtype=t.int32, device=dev)
     frames_dev = t.empty((total, engine.height, engine.width), dtype=t.int16, device=dev)
     engine.sync_inputs()
-    rc = engine.lib.cpx_cptv_gather_index(engine.h, p(slots_dev), p(so_dev), p(offs_dev), len(ok), p(fo_dev), p(bw_dev),
-                                          p(dense_dev))
-    if rc != 0:
-        raise CpxError(rc, engine._err())
-    rc = engine.lib.cpx_cptv_unpack(engine.h, p(out_dev), p(fo_dev), p(bw_dev), p(offs_dev), len(ok), p(frames_dev))
-    if rc != 0:
-        raise CpxError(rc, engine._err())
+    engine.call("cpx_cptv_gather_index", slots_dev, so_dev, offs_dev, len(ok), fo_dev, bw_dev, dense_dev)
+    engine.call("cpx_cptv_unpack", out_dev, fo_dev, bw_dev, offs_dev, len(ok), frames_dev)
     engine.synchronize()
     out.slots = dense_dev.cpu().numpy().view(CPTV_SLOT_DTYPE).reshape(-1)
     out.frames_dev = frames_dev

@@ -167,9 +167,11 @@ class TrackStream:
         self.n_tracked = 0      # frames the track kernels have consumed
         self.result = TrackBatchResult(engine, n, cap, self.comps, self.info, self.labels, self.filtered,
                                        self.background)
-
-    def _p(self, tensor):
-        return C.c_void_p(tensor.data_ptr() if tensor is not None else None)
+        # the buffers live as long as the stream: their addresses are taken (and their layout checked) once, here, not per frame
+        self._frames_p, self._meta_p, self._params_p = (_lib.ptr(x) for x in (self.frames_dev, self.meta, self.params))
+        self._track_out = tuple(_lib.ptr(x) for x in (self.comps, self.info, self.labels, self.filtered, self.background))
+        self._assoc_out = tuple(_lib.ptr(x) for x in (self.comps, self.info, self.pool, self.tracks, self.ntracks,
+                                                      self.status, self.regions, self.rcounts))
 
     def append(self, pix, time_on=None, last_ffc=None, init_only=False, associate=True, flags=0):
         """Upload one frame and process it.  init_only: the frame only initialises the background
@@ -191,21 +193,11 @@ class TrackStream:
             return f  # consumed together with the first real frame
         eng.sync_inputs()
         eng.track_calls = getattr(eng, "track_calls", 0) + 1
-        mp = C.c_void_p(self.meta.ctypes.data)
-        rc = eng.lib.cpx_track_frame_ex(eng.h, self._p(self.frames_dev), mp, self.n_tracked, self.n,
-                                        self._p(self.comps), self._p(self.info), self._p(self.labels),
-                                        self._p(self.filtered), self._p(self.background), int(flags))
-        if rc != 0:
-            raise CpxError(rc, eng._err())
+        eng.call("cpx_track_frame_ex", self._frames_p, self._meta_p, self.n_tracked, self.n, *self._track_out, int(flags))
         n_prev = self.n_tracked
         self.n_tracked = self.n
         if associate and not init_only:
-            rc = eng.lib.cpx_associate_frame(eng.h, C.byref(self.params), mp, n_prev, self.n, self._p(self.comps),
-                                             self._p(self.info), self._p(self.pool), self._p(self.tracks),
-                                             self._p(self.ntracks), self._p(self.status), self._p(self.regions),
-                                             self._p(self.rcounts))
-            if rc != 0:
-                raise CpxError(rc, eng._err())
+            eng.call("cpx_associate_frame", self._params_p, self._meta_p, n_prev, self.n, *self._assoc_out)
         eng.synchronize()
         return f
 
@@ -222,18 +214,10 @@ class TrackStream:
             return
         eng.torch.cuda.current_stream(eng.device).synchronize()
         eng.track_calls = getattr(eng, "track_calls", 0) + 1
-        mp = C.c_void_p(self.meta.ctypes.data)
-        rc = eng.lib.cpx_track_frame_ex(eng.h, self._p(self.frames_dev), mp, 0, n, self._p(self.comps), self._p(self.info),
-                                        self._p(self.labels), self._p(self.filtered), self._p(self.background), int(flags))
-        if rc != 0:
-            raise CpxError(rc, eng._err())
+        eng.call("cpx_track_frame_ex", self._frames_p, self._meta_p, 0, n, *self._track_out, int(flags))
         self.n_tracked = n
         if associate:
-            rc = eng.lib.cpx_associate_frame(eng.h, C.byref(self.params), mp, 0, n, self._p(self.comps), self._p(self.info),
-                                             self._p(self.pool), self._p(self.tracks), self._p(self.ntracks),
-                                             self._p(self.status), self._p(self.regions), self._p(self.rcounts))
-            if rc != 0:
-                raise CpxError(rc, eng._err())
+            eng.call("cpx_associate_frame", self._params_p, self._meta_p, 0, n, *self._assoc_out)
         eng.synchronize()
 
     def overflow(self):
@@ -286,6 +270,9 @@ class ComponentStream:
         self.rcounts = t.zeros(n, dtype=t.int32, device=dev)
         self.meta = np.zeros(n, dtype=FRAME_META_DTYPE)
         self.n = 0
+        self._params_p, self._meta_p = _lib.ptr(self.params), _lib.ptr(self.meta)   # (taken once, as in TrackStream)
+        self._assoc_out = tuple(_lib.ptr(x) for x in (self.comps, self.info, self.pool, self.tracks, self.ntracks,
+                                                      self.status, self.regions, self.rcounts))
 
     def append(self, components, ffc_affected=False):
         """components: COMPONENT_DTYPE rows of this frame (label order = region ids).  -> the frame's index."""
@@ -305,12 +292,7 @@ class ComponentStream:
             self.meta[f]["time_on_ms"], self.meta[f]["last_ffc_ms"], self.meta[f]["has_times"] = 100, 100, 1
         self.n = f + 1
         eng.sync_inputs()
-        p = lambda x: C.c_void_p(x.data_ptr())
-        rc = eng.lib.cpx_associate_frame(eng.h, C.byref(self.params), C.c_void_p(self.meta.ctypes.data), f, self.n,
-                                         p(self.comps), p(self.info), p(self.pool), p(self.tracks), p(self.ntracks),
-                                         p(self.status), p(self.regions), p(self.rcounts))
-        if rc != 0:
-            raise CpxError(rc, eng._err())
+        eng.call("cpx_associate_frame", self._params_p, self._meta_p, f, self.n, *self._assoc_out)
         eng.synchronize()
         return f
 
@@ -468,7 +450,21 @@ class TrackEngine:
         except Exception:
             pass
 
-    def _err(self):
+    def call(self, name, *args, on=None):
+        """lib.<name>(handle, *args), tensors / arrays / structures marshalled by _lib.ptr; raises CpxError with this
+        handle's last error on a non-zero status.  on: the first argument where it is not the handle but a child object
+        of it (a cpx_mog2, cpx_cnn or cpx_graph)."""
+        _lib.check(self.lib, self.h, _lib.status(self.lib, name, self.h if on is None else on, *args))
+
+    def status(self, name, *args, on=None):
+        """call() that returns the status and leaves the decision to the caller."""
+        return _lib.status(self.lib, name, self.h if on is None else on, *args)
+
+    def check(self, rc):
+        """Raise CpxError with this handle's last error when a status() is not CPX_OK."""
+        _lib.check(self.lib, self.h, rc)
+
+    def _err(self):  # (not used in cpx/ any more: bench.py, tools/ and the tests read the handle's message through it)
         return (self.lib.cpx_last_error(self.h) or b"").decode()
 
     def torch_stream(self):
@@ -478,9 +474,7 @@ class TrackEngine:
         return self._torch_stream
 
     def synchronize(self):
-        rc = self.lib.cpx_synchronize(self.h)
-        if rc != 0:
-            raise CpxError(rc, self._err())
+        self.call("cpx_synchronize")
 
     def sync_inputs(self):
         """Order this handle's next kernels behind what torch has enqueued: a host wait on torch's current stream --
@@ -509,11 +503,7 @@ class TrackEngine:
         fo_d, bw_d, offs_d = (t.from_numpy(a).to(self.device) for a in (fo, bw, offs))
         out = t.empty((total, self.height, self.width), dtype=t.int16, device=self.device)
         self.sync_inputs()
-        rc = self.lib.cpx_cptv_unpack(self.h, C.c_void_p(pay.data_ptr()), C.c_void_p(fo_d.data_ptr()),
-                                      C.c_void_p(bw_d.data_ptr()), C.c_void_p(offs_d.data_ptr()), offs.size - 1,
-                                      C.c_void_p(out.data_ptr()))
-        if rc != 0:
-            raise CpxError(rc, self._err())
+        self.call("cpx_cptv_unpack", pay, fo_d, bw_d, offs_d, offs.size - 1, out)
         self.synchronize()  # the staging tensors go out of scope here
         return out
 
@@ -535,8 +525,7 @@ class TrackEngine:
         refs_dev = self._to_dev(refs)
         out = t.zeros(n * 4, dtype=t.int32, device=self.device)
         self.sync_inputs()
-        args = (C.c_void_p(frames_dev.data_ptr()), C.c_void_p(track_result.labels_dev.data_ptr()),
-                C.c_void_p(track_result.info_dev.data_ptr()))
+        args = (frames_dev, track_result.labels_dev, track_result.info_dev)
         # Tiers: the kernel keeps a region's mask and border chain in LDS, one wavefront per region, and a CU works on
         # as many regions as fit its LDS -- sized for ordinary regions (<= 46 x 46, the animals of the path) seven run
         # per CU, at 80 x 80 three, in the whole-frame form one.  A region goes to the first tier that holds it; one
@@ -558,13 +547,9 @@ class TrackEngine:
             sub_out = out if whole else t.zeros(take.size * 4, dtype=t.int32, device=self.device)
             self.sync_inputs()
             if side is None:
-                rc = self.lib.cpx_thumb_stats(self.h, *args, C.c_void_p(sub_dev.data_ptr()), int(take.size),
-                                              C.c_void_p(sub_out.data_ptr()))
+                self.call("cpx_thumb_stats", *args, sub_dev, int(take.size), sub_out)
             else:
-                rc = self.lib.cpx_thumb_stats_ex(self.h, *args, C.c_void_p(sub_dev.data_ptr()), int(take.size),
-                                                 C.c_void_p(sub_out.data_ptr()), side, side, chain)
-            if rc != 0:
-                raise CpxError(rc, self._err())
+                self.call("cpx_thumb_stats_ex", *args, sub_dev, int(take.size), sub_out, side, side, chain)
             self.synchronize()
             res = sub_out.cpu().numpy().view(THUMB_STAT_DTYPE)
             got[take] = res
@@ -588,25 +573,19 @@ class TrackEngine:
         rounded fp16 planes (11 + 11 bits: 2^-22 per operand, the float32 kernels' own error level against a float64
         convolution), operands scaled by powers of two into fp16's range, a device-side rerun in bf16x3 if an
         activation leaves it (include/cpx.h: cpx_set_cnn_math).  Same inputs, outputs and logit tolerance."""
-        rc = self.lib.cpx_set_cnn_math(self.h, self.CNN_MATH[mode])
-        if rc != 0:
-            raise CpxError(rc, self._err())
+        self.call("cpx_set_cnn_math", self.CNN_MATH[mode])
 
     def cnn_last_overflow(self):
         """fp16x2: True when the last forward / convolution on this engine fell back to the bf16x3 kernels because an
         activation left fp16's range (cpx_cnn_last_overflow; synchronises)."""
         out = C.c_int(0)
-        rc = self.lib.cpx_cnn_last_overflow(self.h, C.byref(out))
-        if rc != 0:
-            raise CpxError(rc, self._err())
+        self.call("cpx_cnn_last_overflow", C.byref(out))
         return bool(out.value)
 
     def cnn_overflow_forwards(self, reset=False):
         """fp16x2: forwards on this engine that fell back to the bf16x3 kernels so far (cpx_cnn_overflow_forwards)."""
         out = C.c_int(0)
-        rc = self.lib.cpx_cnn_overflow_forwards(self.h, C.byref(out), 1 if reset else 0)
-        if rc != 0:
-            raise CpxError(rc, self._err())
+        self.call("cpx_cnn_overflow_forwards", C.byref(out), 1 if reset else 0)
         return int(out.value)
 
     def get_cnn_math(self):
@@ -625,12 +604,7 @@ class TrackEngine:
             counts = t.zeros(n, dtype=t.int32, device=self.device)
             status = t.zeros(n, dtype=t.int32, device=self.device)
             labels = t.empty((n, H, W), dtype=t.int32, device=self.device) if want_labels else None
-        rc = self.lib.cpx_ir_detect(self.h, C.c_void_p(images_dev.data_ptr()), n, W, H, int(threshold),
-                                    int(max_components), C.c_void_p(comps.data_ptr()), C.c_void_p(counts.data_ptr()),
-                                    C.c_void_p(status.data_ptr()),
-                                    C.c_void_p(labels.data_ptr()) if want_labels else None)
-        if rc != 0:
-            raise CpxError(rc, self._err())
+        self.call("cpx_ir_detect", images_dev, n, W, H, int(threshold), int(max_components), comps, counts, status, labels)
         self.synchronize()
         st = status.cpu().numpy()
         cnt = counts.cpu().numpy()
@@ -652,9 +626,7 @@ class TrackEngine:
         n, H, W = (int(v) for v in src.shape)
         with self._own_stream():
             out = t.empty((n, H // factor, W // factor), dtype=t.uint8, device=self.device)
-        rc = self.lib.cpx_ir_resize_area(self.h, C.c_void_p(src.data_ptr()), n, W, H, int(factor), C.c_void_p(out.data_ptr()))
-        if rc != 0:
-            raise CpxError(rc, self._err())
+        self.call("cpx_ir_resize_area", src, n, W, H, int(factor), out)
         wo = W // factor
         if pad_width_to > 1 and wo % pad_width_to:
             with t.cuda.stream(self.torch_stream()):
@@ -675,10 +647,7 @@ class TrackEngine:
         r_dev = t.from_numpy(rects).to(self.device)
         out = t.empty(n, dtype=t.float64, device=self.device)
         self.sync_inputs()
-        rc = self.lib.cpx_ir_delta_variance(self.h, C.c_void_p(cur_dev.data_ptr()), C.c_void_p(prev_dev.data_ptr()), W, H,
-                                            C.c_void_p(r_dev.data_ptr()), n, C.c_void_p(out.data_ptr()))
-        if rc != 0:
-            raise CpxError(rc, self._err())
+        self.call("cpx_ir_delta_variance", cur_dev, prev_dev, W, H, r_dev, n, out)
         self.synchronize()
         return out.cpu().numpy()
 
@@ -687,10 +656,7 @@ class TrackEngine:
         t = self.torch
         out = t.zeros(2, dtype=t.int32, device=self.device)
         self.sync_inputs()
-        rc = self.lib.cpx_trackless_thumb(self.h, C.c_void_p(frames_dev.data_ptr()), int(frame), int(background),
-                                          C.c_void_p(out.data_ptr()))
-        if rc != 0:
-            raise CpxError(rc, self._err())
+        self.call("cpx_trackless_thumb", frames_dev, int(frame), int(background), out)
         self.synchronize()
         x, y = out.cpu().numpy()
         return int(x), int(y)
@@ -722,10 +688,7 @@ class TrackEngine:
                 raise ValueError("weights must cover the cropped interior")
         if average is None:
             average = float(np.average(bg[e:self.height - e, e:self.width - e]))
-        rc = self.lib.cpx_set_background(self.h, int(clip), C.c_void_p(bg.ctypes.data),
-                                         C.c_void_p(w.ctypes.data if w is not None else None), float(average))
-        if rc != 0:
-            raise CpxError(rc, self._err())
+        self.call("cpx_set_background", int(clip), bg, w, float(average))
 
     def get_background(self, clip=0):
         """-> (background float32 [H,W], weights float64 [H-2e,W-2e], average) the last track call left for `clip`."""
@@ -733,10 +696,7 @@ class TrackEngine:
         bg = np.empty((self.height, self.width), np.float32)
         w = np.empty((self.height - 2 * e, self.width - 2 * e), np.float64)
         avg = C.c_double()
-        rc = self.lib.cpx_get_background(self.h, int(clip), C.c_void_p(bg.ctypes.data), C.c_void_p(w.ctypes.data),
-                                         C.byref(avg))
-        if rc != 0:
-            raise CpxError(rc, self._err())
+        self.call("cpx_get_background", int(clip), bg, w, C.byref(avg))
         return bg, w, float(avg.value)
 
     def track_batch(self, frames_dev, clip_offsets, meta, want_labels=False, want_filtered=False,
@@ -760,14 +720,7 @@ class TrackEngine:
             comps, info, labels, filt, bgo = outputs
             self.sync_inputs()  # inputs were produced on torch's stream
         self.track_calls = getattr(self, "track_calls", 0) + 1  # whose state cpx_get_background would read
-        rc = self.lib.cpx_track_batch_ex(
-            self.h, C.c_void_p(frames_dev.data_ptr()), offs.ctypes.data_as(C.POINTER(C.c_int32)),
-            C.c_void_p(meta.ctypes.data), B, C.c_void_p(comps.data_ptr()), C.c_void_p(info.data_ptr()),
-            C.c_void_p(labels.data_ptr() if labels is not None else None),
-            C.c_void_p(filt.data_ptr() if filt is not None else None),
-            C.c_void_p(bgo.data_ptr() if bgo is not None else None), int(flags))
-        if rc != 0:
-            raise CpxError(rc, self._err())
+        self.call("cpx_track_batch_ex", frames_dev, offs, meta, B, comps, info, labels, filt, bgo, int(flags))
         return TrackBatchResult(self, total, self.cap, comps, info, labels, filt, bgo)
 
     def associate_batch(self, track_result, clip_offsets, meta, params=None, want_regions=True):
@@ -786,15 +739,8 @@ class TrackEngine:
             status = t.zeros(B, dtype=t.int32, device=self.device)
             regions = t.zeros(total * self.cap * 14, dtype=t.int32, device=self.device) if want_regions else None
             rcounts = t.zeros(total, dtype=t.int32, device=self.device) if want_regions else None
-        rc = self.lib.cpx_associate_batch(
-            self.h, C.byref(params), offs.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(meta.ctypes.data), B,
-            C.c_void_p(track_result.comps_dev.data_ptr()), C.c_void_p(track_result.info_dev.data_ptr()),
-            C.c_void_p(pool.data_ptr()), C.c_void_p(tracks.data_ptr()), C.c_void_p(ntr.data_ptr()),
-            C.c_void_p(status.data_ptr()),
-            C.c_void_p(regions.data_ptr() if regions is not None else None),
-            C.c_void_p(rcounts.data_ptr() if rcounts is not None else None))
-        if rc != 0:
-            raise CpxError(rc, self._err())
+        self.call("cpx_associate_batch", params, offs, meta, B, track_result.comps_dev, track_result.info_dev, pool, tracks,
+                  ntr, status, regions, rcounts)
         return AssocBatchResult(self, offs, params, pool, tracks, ntr, status, regions, rcounts)
 
     def _to_dev(self, arr):
@@ -840,19 +786,11 @@ class TrackEngine:
         if out is None:
             out = t.empty((n_samples, side, side, 2), dtype=t.float32, device=self.device)
         self.sync_inputs()
-        rc = self.lib.cpx_track_limits_batch_ex(
-            self.h, C.c_void_p(frames_dev.data_ptr()), C.c_void_p(track_result.filtered_dev.data_ptr()),
-            C.c_void_p(track_result.info_dev.data_ptr()), C.c_void_p(refs_dev.data_ptr()),
-            C.c_void_p(offs_dev.data_ptr()), n_tracks, C.c_void_p(limits_dev.data_ptr()), int(limits_flags))
-        if rc != 0:
-            raise CpxError(rc, self._err())
+        self.call("cpx_track_limits_batch_ex", frames_dev, track_result.filtered_dev, track_result.info_dev, refs_dev,
+                  offs_dev, n_tracks, limits_dev, int(limits_flags))
         if reqs.size:  # limits only when there is nothing to crop
-            rc = self.lib.cpx_crop_tile(
-                self.h, C.c_void_p(frames_dev.data_ptr()), C.c_void_p(track_result.filtered_dev.data_ptr()),
-                C.c_void_p(track_result.info_dev.data_ptr()), C.c_void_p(reqs_dev.data_ptr()), int(reqs.size),
-                C.c_void_p(limits_dev.data_ptr()), frame_size, square_width, C.c_void_p(out.data_ptr()))
-            if rc != 0:
-                raise CpxError(rc, self._err())
+            self.call("cpx_crop_tile", frames_dev, track_result.filtered_dev, track_result.info_dev, reqs_dev,
+                      int(reqs.size), limits_dev, frame_size, square_width, out)
         self.synchronize()
         limits = limits_dev.cpu().numpy().view(TRACK_LIMITS_DTYPE).reshape(-1)[:n_tracks]
         return out, limits
@@ -863,21 +801,15 @@ class TrackEngine:
         from ._lib import CONV_TIMING_DTYPE
 
         if enable is not None:
-            rc = self.lib.cpx_conv_timing_enable(self.h, 1 if enable else 0)
-            if rc != 0:
-                raise CpxError(rc, self._err())
+            self.call("cpx_conv_timing_enable", 1 if enable else 0)
             return None
         out = np.zeros(32, CONV_TIMING_DTYPE)
         n = C.c_int(0)
-        rc = self.lib.cpx_conv_timing_report(self.h, C.c_void_p(out.ctypes.data), 32, C.byref(n))
-        if rc != 0:
-            raise CpxError(rc, self._err())
+        self.call("cpx_conv_timing_report", out, 32, C.byref(n))
         return {int(r["key"]): (int(r["launches"]), float(r["total_ms"]), float(r["flops"])) for r in out[: n.value]}
 
     def last_kernel_timing(self):
         ms = C.c_float()
         n = C.c_int()
-        rc = self.lib.cpx_last_kernel_timing(self.h, C.byref(ms), C.byref(n))
-        if rc != 0:
-            raise CpxError(rc, self._err())
+        self.call("cpx_last_kernel_timing", C.byref(ms), C.byref(n))
         return float(ms.value), int(n.value)

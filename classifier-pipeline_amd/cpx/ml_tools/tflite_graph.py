@@ -1167,23 +1167,19 @@ class GraphDevice:
             if kind_of(o.kind).grouped:
                 n.n_map = o.groups   # (a convolution has no channel map: the field carries the number of groups)
             n.weights, n.scale, n.shift = up(o.weights), up(o.scale), up(o.shift)
-        self._graph = C.c_void_p()
-        rc = self.lib.cpx_graph_create(engine.h, ops, len(plan.ops), tens, len(ids), ids[plan.input], ids[out_id],
-                                       C.byref(self._graph))
-        if rc != 0:
-            self._graph = None
-            raise _lib.CpxError(rc, engine._err())
+        self._graph = None   # (what close() finds when the creation below refuses the plan)
+        graph = C.c_void_p()
+        engine.call("cpx_graph_create", ops, len(plan.ops), tens, len(ids), ids[plan.input], ids[out_id], C.byref(graph))
+        self._graph = graph
 
     def arena_bytes(self, N):
         v = C.c_size_t()
-        rc = self.lib.cpx_graph_arena_bytes(self._graph, int(N), C.byref(v))
-        if rc != 0:
-            raise _lib.CpxError(rc, self.eng._err())
+        self.eng.call("cpx_graph_arena_bytes", int(N), C.byref(v), on=self._graph)
         return int(v.value)
 
     def arena_allocated(self):
         v = C.c_size_t()
-        self.lib.cpx_graph_arena_allocated(self.eng.h, C.byref(v))
+        self.eng.status("cpx_graph_arena_allocated", C.byref(v))
         return int(v.value)
 
     def forward(self, x, out=None):
@@ -1204,14 +1200,13 @@ class GraphDevice:
 
     def _enqueue(self, x, N, out):
         for attempt in range(2):
-            rc = self.lib.cpx_graph_forward(self._graph, C.c_void_p(x.data_ptr()), N, C.c_void_p(out.data_ptr()))
+            rc = self.eng.status("cpx_graph_forward", x, N, out, on=self._graph)
             if rc == -6 and attempt == 0:   # CPX_ERR_NOMEM: the arena is a plain hipMalloc; torch's cache is invisible to it
                 self.eng.synchronize()
                 self.torch.cuda.empty_cache()
                 continue
             break
-        if rc != 0:
-            raise _lib.CpxError(rc, self.eng._err())
+        self.eng.check(rc)
 
     def forward_async(self, x, out):
         """forward() for a caller that orders its work by the engine's stream (the batched pipeline): the launches are

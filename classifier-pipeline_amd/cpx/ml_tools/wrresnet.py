@@ -19,7 +19,8 @@ import json
 
 import numpy as np
 
-from .._lib import CpxError, WRResNetParams
+from .. import _lib
+from .._lib import WRResNetParams
 
 BN_EPS = 1e-3  # tf.keras.layers.BatchNormalization default
 FILTERS = (16, 64, 128, 256)
@@ -150,6 +151,11 @@ class ConvDesc(C.Structure):
 assert C.sizeof(ConvDesc) == 104
 
 
+def _field(tensor):
+    """A tensor's address for a pointer field of ConvDesc (cpx_conv2d takes its buffers inside the structure)."""
+    return _lib.ptr(tensor, "cpx_conv2d")
+
+
 class WRResNetDevice:
     """The network resident on one GPU: the parameters are uploaded once and handed to the native network
     object (cpx_cnn_create); forward() is one cpx_cnn_forward call = 23 kernel launches on the engine's stream."""
@@ -243,24 +249,18 @@ class WRResNetDevice:
     def _create_native(self):
         prm = self._native_params()
         out = C.c_void_p()
-        rc = self.lib.cpx_cnn_create(self.eng.h, C.byref(prm), C.byref(out))
-        if rc != 0:
-            raise CpxError(rc, self.eng._err())
+        self.eng.call("cpx_cnn_create", prm, C.byref(out))
         self._cnn = out
         self._set_activation_bounds()
         self._set_residual_bounds()
 
     def _set_activation_bounds(self):
         bounds = (C.c_float * len(self.act_bounds))(*self.act_bounds)
-        rc = self.lib.cpx_cnn_set_activation_bounds(self._cnn, bounds, len(self.act_bounds))
-        if rc != 0:
-            raise CpxError(rc, self.eng._err())
+        self.eng.call("cpx_cnn_set_activation_bounds", bounds, len(self.act_bounds), on=self._cnn)
 
     def _set_residual_bounds(self):
         bounds = (C.c_float * len(self.res_bounds))(*self.res_bounds)
-        rc = self.lib.cpx_cnn_set_residual_bounds(self._cnn, bounds, len(self.res_bounds))
-        if rc != 0:
-            raise CpxError(rc, self.eng._err())
+        self.eng.call("cpx_cnn_set_residual_bounds", bounds, len(self.res_bounds), on=self._cnn)
 
     def _measure_activation_bounds(self, headroom=32.0, n=2, seed=12345):
         """The largest activated input of every 3x3 convolution on a seeded probe batch (uniform 0..255 tiles through the
@@ -302,15 +302,12 @@ class WRResNetDevice:
 
     def _conv(self, x, out, wkey, N, H, W, Cin, Cout, ksize, stride, same, relu, in_affine=None, out_scale=None,
               out_shift=None, residual=None):
-        ptr = lambda v: None if v is None else C.c_void_p(v.data_ptr())
         d = ConvDesc(N, H, W, Cin, Cout, GROUPS, ksize, stride, 1 if same else 0, 1 if relu else 0,
-                     ptr(x), ptr(out), ptr(self.p[wkey]),
-                     ptr(self.p[in_affine + "/in_scale"]) if in_affine else None,
-                     ptr(self.p[in_affine + "/in_shift"]) if in_affine else None,
-                     ptr(out_scale), ptr(out_shift), ptr(residual))
-        rc = self.lib.cpx_conv2d(self.eng.h, C.byref(d))
-        if rc != 0:
-            raise CpxError(rc, self.eng._err())
+                     _field(x), _field(out), _field(self.p[wkey]),
+                     _field(self.p[in_affine + "/in_scale"]) if in_affine else None,
+                     _field(self.p[in_affine + "/in_shift"]) if in_affine else None,
+                     _field(out_scale), _field(out_shift), _field(residual))
+        self.eng.call("cpx_conv2d", d)
 
     def forward(self, x, want_probs=True, taps=False):
         """x: device float32 [N, H, W, 2] (values 0..255, no input scaling) -> (logits, probs) [N, n_labels].
@@ -323,10 +320,9 @@ class WRResNetDevice:
         dev = self.eng.device
         logits = t.empty((N, self.n_labels), dtype=t.float32, device=dev)
         probs = t.empty((N, self.n_labels), dtype=t.float32, device=dev) if want_probs else None
-        args = (self._cnn, C.c_void_p(x.data_ptr()), N, H, W, C.c_void_p(logits.data_ptr()),
-                C.c_void_p(probs.data_ptr()) if probs is not None else None)
+        args = (x, N, H, W, logits, probs)
         if not taps:
-            rc = self.lib.cpx_cnn_forward(*args)
+            self.eng.call("cpx_cnn_forward", *args, on=self._cnn)
         else:
             blocks, h, w_ = [], H, W
             for si in range(3):
@@ -336,9 +332,7 @@ class WRResNetDevice:
                     blocks.append(t.full((N, h, w_, FILTERS[si + 1]), float("nan"), dtype=t.float32, device=dev))
             ovf = t.full((len(blocks),), -1, dtype=t.int32, device=dev)
             ptrs = (C.c_void_p * len(blocks))(*[b.data_ptr() for b in blocks])
-            rc = self.lib.cpx_cnn_forward_taps(*args, ptrs, len(blocks), C.c_void_p(ovf.data_ptr()))
-        if rc != 0:
-            raise CpxError(rc, self.eng._err())
+            self.eng.call("cpx_cnn_forward_taps", *args, ptrs, len(blocks), ovf, on=self._cnn)
         self.eng.synchronize()
         if taps:
             return logits, probs, blocks, ovf.cpu().numpy()
@@ -350,16 +344,14 @@ class WRResNetDevice:
         N, H, W, cin = x.shape
         assert cin == 2 and x.is_contiguous() and logits.is_contiguous()
         for attempt in range(2):
-            rc = self.lib.cpx_cnn_forward(self._cnn, C.c_void_p(x.data_ptr()), N, H, W, C.c_void_p(logits.data_ptr()),
-                                          C.c_void_p(probs.data_ptr()) if probs is not None else None)
+            rc = self.eng.status("cpx_cnn_forward", x, N, H, W, logits, probs, on=self._cnn)
             if rc == -6 and attempt == 0:   # CPX_ERR_NOMEM: the handle's activation buffers are a plain hipMalloc, and what
                 # torch's allocator holds in its cache is invisible to it -- hand that back and try once more
                 self.eng.synchronize()
                 self.torch.cuda.empty_cache()
                 continue
             break
-        if rc != 0:
-            raise CpxError(rc, self.eng._err())
+        self.eng.check(rc)
 
     def forward_layerwise(self, x, want_probs=True, _probe=None, _probe_res=None):
         """The same network issued layer by layer through cpx_conv2d / cpx_cnn_head (what a caller binding the
@@ -417,9 +409,7 @@ class WRResNetDevice:
         hd.dense_w_dev, hd.dense_b_dev = self.p["dense/w"].data_ptr(), self.p["dense/b"].data_ptr()
         hd.logits_dev = logits.data_ptr()
         hd.probs_dev = probs.data_ptr() if probs is not None else None
-        rc = self.lib.cpx_cnn_head_ex(self.eng.h, C.byref(hd))
-        if rc != 0:
-            raise CpxError(rc, self.eng._err())
+        self.eng.call("cpx_cnn_head_ex", hd)
         self.eng.synchronize()
         return logits, probs
 

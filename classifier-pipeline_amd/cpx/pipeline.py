@@ -3,12 +3,11 @@ round trip of image data -- track stage, association, end-of-clip filtering, seg
 crop / tile, CNN forward, per-track aggregation.  This is what bench.py times; the per-clip
 drop-in classes (cpx.track / cpx.classify) run the same kernels one clip at a time."""
 
-import ctypes as C
 import os
 
 import numpy as np
 
-from ._lib import CROP_REQ_DTYPE, REGION_REF_DTYPE, TRACK_DEFER_MEDIANS, CpxError
+from ._lib import TRACK_DEFER_MEDIANS
 from .tracking import TRACK_SUMMARY_DTYPE, make_filter_params, make_track_params
 
 
@@ -57,10 +56,6 @@ class BatchPipeline:
         # arena_bytes_per_sample) gets chunks that keep it inside this many bytes; None: cnn_chunk alone decides
         self.network_bytes = network_bytes
         self._sample_buf = None
-
-    def _check(self, rc):
-        if rc != 0:
-            raise CpxError(rc, self.eng._err())
 
     def sample_chunk(self):
         """Samples per network call at the most: cnn_chunk, clamped by network_bytes for a network that states its
@@ -150,7 +145,6 @@ class BatchPipeline:
         """Stages 5b-7 for a _front result: crop / tile, network, aggregation (on the current stream = the handle's).
         Callable again on the same `out` from a pipeline with another network / frame size (one per model)."""
         eng, t = self.eng, self.eng.torch
-        lib, h = eng.lib, eng.h
         dev = eng.device
         n_tracks, n_samples = out.n_tracks, out.n_samples
         reqs, limits, per = out.reqs_dev, out.limits_dev, self.sq * self.sq
@@ -179,10 +173,9 @@ class BatchPipeline:
             buf = out.samples_dev[s0:s1] if keep_samples else self._sample_buf[: s1 - s0]
             # the chunk's requests carry absolute sample indices: hand the kernel the address sample 0 WOULD have
             # (it only writes the samples of these requests), instead of rewriting the requests
-            self._check(lib.cpx_crop_tile(
-                h, C.c_void_p(frames_dev.data_ptr()), C.c_void_p(out.track.filtered_dev.data_ptr()),
-                C.c_void_p(out.track.info_dev.data_ptr()), C.c_void_p(reqs.data_ptr() + s0 * per * 32), (s1 - s0) * per,
-                C.c_void_p(limits.data_ptr()), self.fs, self.sq, C.c_void_p(buf.data_ptr() - s0 * sample_bytes)))
+            eng.call("cpx_crop_tile", frames_dev, out.track.filtered_dev, out.track.info_dev,
+                     reqs.data_ptr() + s0 * per * 32, (s1 - s0) * per, limits, self.fs, self.sq,
+                     buf.data_ptr() - s0 * sample_bytes)
             if self.net is not None:
                 if two_streams:
                     ev = t.cuda.Event()
@@ -206,10 +199,8 @@ class BatchPipeline:
         # ---- 7. per-track aggregation ----
         out.scores = t.empty((n_tracks, self.n_labels), dtype=t.float32, device=dev)
         out.best = t.empty(n_tracks, dtype=t.int32, device=dev)
-        self._check(lib.cpx_aggregate_predictions(
-            h, C.c_void_p(probs.data_ptr()), C.c_void_p(out.sample_track_dev.data_ptr()), n_samples,
-            C.c_void_p(reqs.data_ptr()), n_tracks, self.n_labels, self.fp_index, self.sq,
-            C.c_void_p(out.scores.data_ptr()), C.c_void_p(out.best.data_ptr())))
+        eng.call("cpx_aggregate_predictions", probs, out.sample_track_dev, n_samples, reqs, n_tracks, self.n_labels,
+                 self.fp_index, self.sq, out.scores, out.best)
         out.probs = probs
         out.logits = logits
         eng.synchronize()  # results are complete when run() returns (callers read them from any stream)
@@ -240,19 +231,16 @@ class BatchPipeline:
         mt = self.tp.max_tracks
         summ = t.zeros(B * mt * 30, dtype=t.int32, device=dev)
         counts = t.zeros((B, 4), dtype=t.int32, device=dev)
-        offs_p = offs.ctypes.data_as(C.POINTER(C.c_int32))
         eng.sync_inputs()
-        self._check(lib.cpx_finalize_tracks(
-            h, C.byref(self.fp), offs_p, C.c_void_p(meta.ctypes.data), B, C.c_void_p(out.assoc.pool_dev.data_ptr()),
-            C.c_void_p(out.assoc.tracks_dev.data_ptr()), C.c_void_p(out.assoc.ntracks_dev.data_ptr()),
-            C.c_void_p(summ.data_ptr()), C.c_void_p(counts.data_ptr())))
+        eng.call("cpx_finalize_tracks", self.fp, offs, meta, B, out.assoc.pool_dev, out.assoc.tracks_dev,
+                 out.assoc.ntracks_dev, summ, counts)
         out.summaries_dev = summ
         on_stream = int(t.cuda.current_stream(dev).cuda_stream) == int(lib.cpx_stream(h) or 0)
         if not on_stream:
             eng.synchronize()  # torch runs on another stream (the overlapped form): the kernels must have finished
         # exclusive prefix sums of the counts on the handle's stream (cpx_counts_prefix: the step launches no torch kernel)
         prefix = t.empty((B + 1, 4), dtype=t.int32, device=dev)
-        self._check(lib.cpx_counts_prefix(h, C.c_void_p(counts.data_ptr()), B, C.c_void_p(prefix.data_ptr())))
+        eng.call("cpx_counts_prefix", counts, B, prefix)
         if not on_stream:
             eng.synchronize()
         out.counts = counts.cpu().numpy()   # the one host wait of a run: the work counts size what follows
@@ -274,28 +262,23 @@ class BatchPipeline:
         sample_track = t.empty(n_samples, dtype=t.int32, device=dev)
         track_clip = t.empty((n_tracks, 2), dtype=t.int32, device=dev)
         eng.sync_inputs()
-        self._check(lib.cpx_plan_segments(
-            h, C.byref(self.fp), offs_p, C.c_void_p(meta.ctypes.data), B, C.c_void_p(out.assoc.pool_dev.data_ptr()),
-            C.c_void_p(summ.data_ptr()), C.c_void_p(out.assoc.ntracks_dev.data_ptr()), C.c_void_p(prefix.data_ptr()),
-            self.sq, C.c_void_p(refs.data_ptr()), C.c_void_p(toffs.data_ptr()), C.c_void_p(reqs.data_ptr()),
-            C.c_void_p(sample_track.data_ptr()), C.c_void_p(track_clip.data_ptr())))
+        eng.call("cpx_plan_segments", self.fp, offs, meta, B, out.assoc.pool_dev, summ, out.assoc.ntracks_dev, prefix,
+                 self.sq, refs, toffs, reqs, sample_track, track_clip)
         if not on_stream:
             eng.synchronize()
         out.track_clip, out.reqs_dev, out.sample_track_dev = track_clip, reqs, sample_track
         # ---- 5a. per-track limits ----
         limits = t.zeros(n_tracks * 8, dtype=t.int32, device=dev)
         eng.sync_inputs()
-        self._check(lib.cpx_track_limits_batch_ex(
-            h, C.c_void_p(frames_dev.data_ptr()), C.c_void_p(out.track.filtered_dev.data_ptr()),
-            C.c_void_p(out.track.info_dev.data_ptr()), C.c_void_p(refs.data_ptr()), C.c_void_p(toffs.data_ptr()),
-            n_tracks, C.c_void_p(limits.data_ptr()), int(self.limits_flags)))
+        eng.call("cpx_track_limits_batch_ex", frames_dev, out.track.filtered_dev, out.track.info_dev, refs, toffs,
+                 n_tracks, limits, int(self.limits_flags))
         out.limits_dev = limits
         out._keep = (refs, toffs, prefix)
         return out
 
     def _run_overlapped(self, frames_dev, clip_offsets, meta, outputs, n_sub):
         eng, ceng, t = self.eng, self.net.eng, self.eng.torch
-        lib, dev = eng.lib, eng.device
+        dev = eng.device
         offs = np.ascontiguousarray(clip_offsets, dtype=np.int32)
         meta = np.ascontiguousarray(meta)
         B = offs.size - 1
@@ -329,10 +312,8 @@ class BatchPipeline:
             part.scores = t.empty((nt, self.n_labels), dtype=t.float32, device=dev)
             part.best = t.empty(nt, dtype=t.int32, device=dev)
             eng.sync_inputs()
-            self._check(lib.cpx_crop_tile(
-                eng.h, C.c_void_p(fr.data_ptr()), C.c_void_p(part.track.filtered_dev.data_ptr()),
-                C.c_void_p(part.track.info_dev.data_ptr()), C.c_void_p(part.reqs_dev.data_ptr()), ns * per,
-                C.c_void_p(part.limits_dev.data_ptr()), self.fs, self.sq, C.c_void_p(samples.data_ptr())))
+            eng.call("cpx_crop_tile", fr, part.track.filtered_dev, part.track.info_dev, part.reqs_dev, ns * per,
+                     part.limits_dev, self.fs, self.sq, samples)
             ev = t.cuda.Event()
             ev.record(s_track)
             s_cnn.wait_event(ev)
@@ -342,12 +323,8 @@ class BatchPipeline:
             for s0 in range(0, ns, chunk):
                 s1 = min(s0 + chunk, ns)
                 self.net.forward_async(samples[s0:s1], logits[s0:s1], part.probs[s0:s1])
-            rc = lib.cpx_aggregate_predictions(
-                ceng.h, C.c_void_p(part.probs.data_ptr()), C.c_void_p(part.sample_track_dev.data_ptr()), ns,
-                C.c_void_p(part.reqs_dev.data_ptr()), nt, self.n_labels, self.fp_index, self.sq,
-                C.c_void_p(part.scores.data_ptr()), C.c_void_p(part.best.data_ptr()))
-            if rc != 0:
-                raise CpxError(rc, ceng._err())
+            ceng.call("cpx_aggregate_predictions", part.probs, part.sample_track_dev, ns, part.reqs_dev, nt, self.n_labels,
+                      self.fp_index, self.sq, part.scores, part.best)
             part._keep2 = (samples, logits, ev)
         eng.synchronize()
         ceng.synchronize()

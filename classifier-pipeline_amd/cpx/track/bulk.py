@@ -31,7 +31,7 @@ import numpy as np
 
 from .._lib import (CPTV_BACKGROUND_FRAME, CPTV_FILE_DTYPE, CPTV_HAS_LAST_FFC, CPTV_HAS_TIME_ON, CPTV_HEADER_BYTES,
                     CPTV_RESULT_DTYPE, CPTV_SLOT_DTYPE, CPTV_STATUS, FRAME_INFO_DTYPE, FRAME_META_DTYPE,
-                    REGION_REF_DTYPE, THUMB_STAT_DTYPE, CpxError)
+                    REGION_REF_DTYPE, THUMB_STAT_DTYPE, ptr)
 from ..ml_tools import tools
 from ..tracking import (REGION_DTYPE, TRACK_SUMMARY_DTYPE, make_filter_params, make_track_params)
 from .clip import Clip
@@ -243,12 +243,8 @@ def inflate_launch(eng, staged, min_pixels=160 * 120):
     slots_dev = t.empty(max(int(slot_off[-1]), 1) * 8, dtype=t.int32, device=dev)
     header_dev = t.empty((n, CPTV_HEADER_BYTES), dtype=t.uint8, device=dev)
     results_dev = t.zeros(n * 10, dtype=t.int32, device=dev)
-    p = lambda x: C.c_void_p(x.data_ptr())
     eng.sync_inputs()
-    rc = eng.lib.cpx_cptv_inflate(eng.h, p(in_dev), p(files_dev), n, p(out_dev), p(slots_dev), p(header_dev),
-                                  p(results_dev))
-    if rc != 0:
-        raise CpxError(rc, eng._err())
+    eng.call("cpx_cptv_inflate", in_dev, files_dev, n, out_dev, slots_dev, header_dev, results_dev)
     done = t.cuda.Event()
     done.record(eng.torch_stream())
     return dict(n=n, slot_off=slot_off, in_dev=in_dev, files_dev=files_dev, out_dev=out_dev, slots_dev=slots_dev,
@@ -264,7 +260,6 @@ def inflate_finish(eng, staged, ctx, unpack_engine=None):
     t, dev = eng.torch, eng.device
     n, slot_off = ctx["n"], ctx["slot_off"]
     out_dev, slots_dev, header_dev, results_dev = ctx["out_dev"], ctx["slots_dev"], ctx["header_dev"], ctx["results_dev"]
-    p = lambda x: C.c_void_p(x.data_ptr())
     out = DecodedBatch()
     out.errors.update(staged.errors)
     ctx["done"].synchronize()
@@ -307,7 +302,6 @@ def _unpack_group(eng, unpack_engine, key, members, headers, res, slot_off, slot
     from .cliptrackextractor import get_engine
 
     t, dev = eng.torch, eng.device
-    p = lambda x: C.c_void_p(x.data_ptr())
     W, H, _ = key
     ok = np.asarray(members)
     offs = np.zeros(len(ok) + 1, np.int32)
@@ -323,12 +317,10 @@ def _unpack_group(eng, unpack_engine, key, members, headers, res, slot_off, slot
     dense_dev = t.empty(total * 8, dtype=t.int32, device=dev)
     frames_dev = t.empty((total, H, W), dtype=t.int16, device=dev)
     ueng.sync_inputs()
-    rc = ueng.lib.cpx_cptv_gather_index(ueng.h, p(slots_dev), p(so_dev), p(offs_dev), len(ok), p(fo_dev), p(bw_dev),
-                                        p(dense_dev))
+    rc = ueng.status("cpx_cptv_gather_index", slots_dev, so_dev, offs_dev, len(ok), fo_dev, bw_dev, dense_dev)
     if rc == 0:
-        rc = ueng.lib.cpx_cptv_unpack(ueng.h, p(out_dev), p(fo_dev), p(bw_dev), p(offs_dev), len(ok), p(frames_dev))
-    if rc != 0:
-        raise CpxError(rc, ueng._err())
+        rc = ueng.status("cpx_cptv_unpack", out_dev, fo_dev, bw_dev, offs_dev, len(ok), frames_dev)
+    ueng.check(rc)
     ueng.synchronize()
     slots = dense_dev.cpu().numpy().view(CPTV_SLOT_DTYPE).reshape(-1)
     return DecodedGroup(key, members, [headers[i] for i in members], offs, slots, frames_dev)
@@ -598,10 +590,7 @@ class BulkTracker:
                 pairs_dev = t.from_numpy(np.asarray(pairs, np.int32)).to(dev)
                 xy = t.zeros((len(pairs), 2), dtype=t.int32, device=dev)
                 eng.sync_inputs()
-                rc = eng.lib.cpx_trackless_thumb_batch(eng.h, C.c_void_p(group.frames_dev.data_ptr()),
-                                                       C.c_void_p(pairs_dev.data_ptr()), len(pairs), C.c_void_p(xy.data_ptr()))
-                if rc != 0:
-                    raise CpxError(rc, eng._err())
+                eng.call("cpx_trackless_thumb_batch", group.frames_dev, pairs_dev, len(pairs), xy)
                 eng.synchronize()
                 xy_h = xy.cpu().numpy()
                 for k, (b, q) in enumerate(rows):
@@ -613,12 +602,12 @@ class BulkTracker:
         n = len(regs)
         cap = 512 + 420 * max(n, 1)
         buf = C.create_string_buffer(cap)
-        got = self.lib.cpx_format_regions(C.c_void_p(regs.ctypes.data), n, REGION_DTYPE.itemsize, indent, depth,
-                                          1 if as_list else 0, buf, cap)
+        regs_p = ptr(regs, "cpx_format_regions")
+        got = self.lib.cpx_format_regions(regs_p, n, REGION_DTYPE.itemsize, indent, depth, 1 if as_list else 0, buf, cap)
         if got < 0:
             buf = C.create_string_buffer(-got + 16)
-            got = self.lib.cpx_format_regions(C.c_void_p(regs.ctypes.data), n, REGION_DTYPE.itemsize, indent, depth,
-                                              1 if as_list else 0, buf, -got + 16)
+            got = self.lib.cpx_format_regions(regs_p, n, REGION_DTYPE.itemsize, indent, depth, 1 if as_list else 0, buf,
+                                              -got + 16)
         return buf.raw[:got].decode("ascii")
 
     def thumbnail_of(self, regs, use, st):

@@ -15,7 +15,7 @@ from datetime import datetime
 
 import numpy as np
 
-from .._lib import TRACK_FREEZE_BACKGROUND
+from .._lib import TRACK_FREEZE_BACKGROUND, CpxError
 from ..cptv import CptvReader, decode_clips_on_device
 from ..engine import TrackEngine
 from ..ml_tools.rectangle import Rectangle
@@ -511,7 +511,6 @@ class ClipTrackExtractor(ClipTracker):
         has no such limit): a new stream with tables grown to fit takes over the frames consumed so far and runs them
         again, so the clip stands where it stood, on larger tables.  A caller-owned background model cannot be replayed
         (its past states are gone): that case reports the overflow."""
-        from ..engine import CpxError
         from ..tracking import TrackParams
 
         if self._external_bg is not None:

@@ -98,11 +98,7 @@ class MOG2Background:
         self._frames = 0
         self._background = None  # the foreground mask of the last update, as the reference names it
         m = C.c_void_p()
-        rc = engine.lib.cpx_mog2_create(engine.h, n_streams, width, height, history, float(var_threshold), C.byref(m))
-        if rc != 0:
-            from .._lib import CpxError
-
-            raise CpxError(rc, engine._err())
+        engine.call("cpx_mog2_create", n_streams, width, height, history, float(var_threshold), C.byref(m))
         self._m = m
 
     def _as_batch(self, frame):
@@ -117,19 +113,12 @@ class MOG2Background:
         self.update_background(background, learning_rate=1)
 
     def update_background(self, thermal, filtered=None, learning_rate=-1):
-        import ctypes as C
-
         t = self.eng.torch
         single = thermal.dim() == 2
         frame = self._as_batch(thermal)
         mask = t.empty(self.shape, dtype=t.uint8, device=self.eng.device)
         t.cuda.current_stream(self.eng.device).synchronize()
-        rc = self.eng.lib.cpx_mog2_apply(self._m, C.c_void_p(frame.data_ptr()), float(learning_rate),
-                                         C.c_void_p(mask.data_ptr()))
-        if rc != 0:
-            from .._lib import CpxError
-
-            raise CpxError(rc, self.eng._err())
+        self.eng.call("cpx_mog2_apply", frame, float(learning_rate), mask, on=self._m)
         self.eng.synchronize()
         self._background = mask[0] if single else mask
         self._frames += 1
@@ -137,15 +126,9 @@ class MOG2Background:
 
     @property
     def background(self):
-        import ctypes as C
-
         t = self.eng.torch
         out = t.empty(self.shape, dtype=t.uint8, device=self.eng.device)
-        rc = self.eng.lib.cpx_mog2_background(self._m, C.c_void_p(out.data_ptr()))
-        if rc != 0:
-            from .._lib import CpxError
-
-            raise CpxError(rc, self.eng._err())
+        self.eng.call("cpx_mog2_background", out, on=self._m)
         self.eng.synchronize()
         return out[0] if self.shape[0] == 1 else out
 

@@ -237,8 +237,6 @@ class IRTrackExtractor(ClipTracker):
         frame and those steps are not recorded).  Same tracks as parse_frames clip by clip
         (tests/test_irtrack_gpu.py), with the region variances in float32 (the device's component record) instead of
         float64."""
-        import ctypes as C
-
         from .._lib import IR_FRAME_STATS_DTYPE, CpxError
         from ..engine import AssocBatchResult
 
@@ -265,7 +263,7 @@ class IRTrackExtractor(ClipTracker):
             self._engine.close()
         eng = self._engine = TrackEngine(width=160, height=120, device=self.device, max_components=256,
                                          max_frames=max(T, 1024))
-        t, dev, lib, h = eng.torch, eng.device, eng.lib, eng.h
+        t, dev = eng.torch, eng.device
         for clip in clips:
             clip.type = self.type
             clip.set_frame_buffer(False, self.cache_to_disk, False, False, max_frames=51)
@@ -298,29 +296,22 @@ class IRTrackExtractor(ClipTracker):
         if calc_stats:   # one 32-byte cpx_ir_frame_stats record per (step, video)
             stats = t.empty((T, V, 32), dtype=t.uint8, device=dev)
             hist = t.empty((V, 256), dtype=t.int32, device=dev)
-        p = lambda x: C.c_void_p(x.data_ptr())
-
-        def check(rc):
-            if rc != 0:
-                raise CpxError(rc, eng._err())
-
         t.cuda.current_stream(dev).synchronize()
         with t.cuda.stream(eng.torch_stream()):
-            check(lib.cpx_mog2_apply(bg._m, p(video[0]), 1.0, p(mask)))   # start_tracking: the first frame seeds the model
+            eng.call("cpx_mog2_apply", video[0], 1.0, mask, on=bg._m)   # start_tracking: the first frame seeds the model
             for q in range(T):
                 cur = video[q]
-                check(lib.cpx_mog2_apply(bg._m, p(cur), float(self.learning_rate), p(mask)))
+                eng.call("cpx_mog2_apply", cur, float(self.learning_rate), mask, on=bg._m)
                 if q == 0:   # clip.background is the model's image after the first frame (irtrackextractor.py:415-416)
                     first_background = bg.background.clone()
-                check(lib.cpx_ir_detect(h, p(mask), V, W, H, 0, cap_det, p(det), p(counts[q]), p(dstatus[q]), None))
+                eng.call("cpx_ir_detect", mask, V, W, H, 0, cap_det, det, counts[q], dstatus[q], None)
                 # get_delta_frame (irtrackextractor.py:638-659): the frame FRAMES_AGO back, frame 1 before that
                 prev_i = q - 1 if q < self.FRAMES_AGO else self.FRAMES_AGO
                 want = q - prev_i
                 prev = video[want] if (prev_i != q and want != q and 0 <= want < q and q - want <= self.FRAMES_AGO) else None
-                check(lib.cpx_ir_merge(h, p(det), p(counts[q]), V, cap_det, cap, p(cur), p(prev) if prev is not None else None,
-                                       W, H, q, T, p(comps), p(info), p(mstatus[q])))
+                eng.call("cpx_ir_merge", det, counts[q], V, cap_det, cap, cur, prev, W, H, q, T, comps, info, mstatus[q])
                 if stats is not None:
-                    check(lib.cpx_ir_frame_statistics(h, p(cur), p(mask), V, H * W, p(hist), p(stats[q])))
+                    eng.call("cpx_ir_frame_statistics", cur, mask, V, H * W, hist, stats[q])
             eng.synchronize()
         bad = t.nonzero((dstatus != 0) | (mstatus != 0))
         if bad.numel():

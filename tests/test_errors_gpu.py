@@ -46,6 +46,20 @@ def test_null_and_out_of_sequence_arguments():
     eng.close()
 
 
+def test_checked_call_raises_with_the_handles_message():
+    """TrackEngine.call: a refused call raises CpxError with the status as its code and the text cpx_last_error holds
+    for THIS handle -- the handle reaches both the function and the error lookup."""
+    from cpx._lib import CpxError
+    from cpx.engine import TrackEngine
+
+    eng = TrackEngine(model="lepton3", width=160, height=120, max_frames=8)
+    with pytest.raises(CpxError) as e:
+        eng.call("cpx_counts_prefix", None, 0, None)
+    assert e.value.code == -1 and "cpx_counts_prefix: bad argument" in str(e.value)
+    assert eng.status("cpx_counts_prefix", None, 0, None) == -1
+    eng.close()
+
+
 def test_track_capacity_overflow_is_reported():
     """More simultaneous objects than max_active_tracks: status CPX_ERR_OVERFLOW for that clip only."""
     from cpx._lib import CpxError
