@@ -174,6 +174,7 @@ int cpx_create(int device_id, const cpx_config* cfg, cpx_handle** out) {
   if (const char* env = std::getenv("CPX_TRACK_PER_STEP")) h->track_per_step = std::atoi(env) != 0;
   if (const char* env = std::getenv("CPX_CNN_FUSE_SHORTCUT")) h->fuse_shortcut = std::atoi(env) != 0;
   if (const char* env = std::getenv("CPX_CNN_SHORTCUT_FP16")) h->shortcut_fp16 = std::atoi(env) != 0;
+  if (const char* env = std::getenv("CPX_CNN_FLAT16")) h->flat16 = std::atoi(env) != 0;
   if (const char* env = std::getenv("CPX_CNN_BLOCK_FUSION")) h->block_fusion = std::min(std::max(std::atoi(env), 0), 2);
   if (const char* env = std::getenv("CPX_CNN_MATH")) {
     if (!std::strcmp(env, "f32")) h->cnn_math = CPX_CNN_MATH_F32;

@@ -211,6 +211,7 @@ static int conv_run(cpx_handle* h, const cpx_conv_desc* d, const void* split_wei
       first.act_scale = k.act_scale;
       first.act_unscale = 1.0f / first.act_scale;  // (a power of two: exact)
       first.in_planes = k.in_planes;
+      first.flat16 = h->flat16;
     }
     first.ovf = word;
     if (planes_out) {

@@ -30,6 +30,7 @@
 
 #include "cpx_cnn_dev.h"
 #include "cpx_conv_layout_core.h"
+#include "cpx_flat_band_core.h"
 #include "cpx_kernels.h"
 
 namespace cpx {
@@ -1780,8 +1781,7 @@ int launch_bf3flat_t(const ConvArgs& a, const uint4* wimg, hipStream_t s) {
 static bool flat_pays(const ConvArgs& a, int TW, int TH, int npx_cap, int band = 128) {
   if (a.stride != 1 || a.ksize != 3 || a.pad_top != 1 || a.pad_left != 1 || a.H != a.Ho || a.W != a.Wo) return false;
   const int M = a.Ho * a.Wo;
-  const int rows = (band - 1 + a.Wo - 1) / a.Wo + 1;
-  if ((rows + 2) * (a.W + 2) > npx_cap) return false;
+  if (flat_band_max_pixels(band, a.Wo) > npx_cap) return false;  // (cpx_flat_band_core.h: a band's geometry)
   const double rect = (double)M / ((double)((a.Wo + TW - 1) / TW) * TW * ((a.Ho + TH - 1) / TH) * TH);
   const double flat = (double)M / ((double)((M + band - 1) / band) * band);
   return flat > rect + 0.08;
@@ -2088,6 +2088,12 @@ int launch_conv_bf3(const ConvArgs& a_in, const void* wimg, hipStream_t s) {
   // frame size 64 -- would need 384 staged pixels and then fit only one N tile per workgroup: measured slower than the
   // rectangular bands, 399 vs 371 ms, the patch being activated and split by four column slices instead of two.)
   if (flat_pays(a, 32, 4 * NB_S4, 256)) {
+    // fp16x2 with float32 in and out, shortcut (if any) as fp16 planes, not the rerun: conv_flat16_kernel (cpx_cnn_flat.hip:
+    // 16x16x32 products, all 128 columns from one staged patch) unless CPX_CNN_FLAT16=0; -2: a launch it leaves to the kernels here
+    if (a.flat16 && a.planes == 2 && a.half) {
+      const int rc = launch_conv_flat16(a, w + im.half / 16, s);
+      if (rc != -2) return rc;
+    }
     // (the launch that carries stage 4's shortcut with fp16 planes of its weights: ConvArgs::sc_planes)
     if (a.planes == 2 && a.half && a.sc_in && a.sc_planes && conv_shortcut_planes_layer(a, a.sc_cin / a.groups) && !a.residual &&
         a.sc_stride >= 1 && a.sc_xscale > 0.0f && (a.sc_H - 1) / a.sc_stride + 1 == a.Ho && (a.sc_W - 1) / a.sc_stride + 1 == a.Wo &&

@@ -511,7 +511,7 @@ __global__ __launch_bounds__(256) void split_shortcut_kernel(const float* __rest
 
 // second convolutions whose fused 1x1 shortcut can run as fp16x2 products: conv_rw_kernel's stride-1 layer with a shortcut of 32
 // input channels per group (stage 3 of WR-ResNet-22-4: one K = 32 fragment), and the stride-1 layer of 128 -> 128 channels per
-// group with a shortcut of 64 (stage 4: conv_bf3flat_kernel, where the map is small enough for the flattened tiling)
+// group with a shortcut of 64 (stage 4: conv_flat16_kernel / conv_bf3flat_kernel, where the map is small enough for the flattened tiling)
 bool conv_shortcut_planes_layer(const ConvArgs& second, int sc_cin_g) {
   if (conv_rw_kind(second) == 1) return sc_cin_g == 32;
   return second.ksize == 3 && second.stride == 1 && second.groups >= 1 && second.Cin == second.Cout &&

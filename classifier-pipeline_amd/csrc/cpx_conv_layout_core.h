@@ -25,8 +25,8 @@ ConvShape conv_shape_of(const Args& a) {
 //   Stride2Rw  3x3 stride 2, 32 -> 64: conv_rw_kernel in fp16x2, conv_bf3_kernel<2, 2, 2, 16, 512> otherwise (stage 3)
 //   C8         3x3 stride 1, 8 -> 32: the tap-paired form of conv_bf3_kernel, and conv_block32_kernel<true>
 //   Wide       3x3 stride 1, 32 or 64 -> 32 or 64: the 16x16x32 form (conv_bf3w_kernel; 64 -> 64 in fp16x2: conv_rw_kernel)
-//   Flat       3x3, input channels in sixteens, stride 1 with 128 columns (stage 4: conv_bf3flat_kernel where the map is
-//              small, the rectangular bands otherwise) or stride 2 with 64 columns
+//   Flat       3x3, input channels in sixteens, stride 1 with 128 columns (stage 4: where the map is small the flattened bands --
+//              conv_flat16_kernel in fp16x2, conv_bf3flat_kernel otherwise --, the rectangular bands on larger maps) or stride 2 with 64 columns
 //   Plain      3x3 stride 1, input channels in sixteens, 32 or 64 columns: three bf16 planes in every math mode
 enum class ConvClass { Unsupported, Plain, Flat, Wide, C8, Stride2Rw, Rw3 };
 

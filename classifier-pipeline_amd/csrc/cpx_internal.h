@@ -86,7 +86,8 @@ struct cpx_handle {
   int cnn_math = CPX_CNN_MATH_FP16X2;    // cpx_set_cnn_math / CPX_CNN_MATH (the default: include/cpx.h)
   bool fuse_shortcut = true;             // CPX_CNN_FUSE_SHORTCUT=0 keeps the 1x1 shortcuts as launches of their own
   bool shortcut_fp16 = true;             // CPX_CNN_SHORTCUT_FP16=0 keeps the fused shortcuts' products on the float32 matrix instruction
-  DeviceBuffer bf3_scratch;              // split weights of a cpx_conv2d call that brought none
+  bool flat16 = true;                    // CPX_CNN_FLAT16=0 keeps stage 4's stride-1 fp16x2 launches on conv_bf3flat_kernel (32x32x16 products)
+  DeviceBuffer bf3_scratch;             // split weights of a cpx_conv2d call that brought none
   // activation buffers of cpx_cnn_forward (act0 | act1 | mid | sc), grown to the largest call seen and shared by every
   // network of the handle: forwards on one handle are serialised on its stream, and a second network (another model, another
   // leg of a run) must not bring 54 GB of its own (2,048 samples at frame size 32)

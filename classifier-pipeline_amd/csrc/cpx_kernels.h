@@ -225,7 +225,11 @@ struct ConvArgs {
   // staging is a copy)
   int out_planes, in_planes;
   float out_act_scale;
+  // fp16x2: the stride-1 Flat launches may go to conv_flat16_kernel (cpx_cnn_flat.hip; the handle's CPX_CNN_FLAT16).  Read on
+  // the host only; it takes the struct's tail padding, so no kernel argument moves
+  int flat16;
 };
+static_assert(sizeof(ConvArgs) == 264, "the argument layout the convolution kernels were tuned with");
 struct HeadArgs {
   int N, HW, C, L;
   int n_hidden, activation;  // hidden Dense(relu) layers; CPX_HEAD_SIGMOID / CPX_HEAD_SOFTMAX
@@ -261,6 +265,9 @@ int launch_conv_block32s(const ConvArgs& a, const ConvArgs& b, const void* wa, c
 int conv_rw_kind(const ConvArgs& a);
 bool conv_rw_layer(const ConvArgs& a);  // kind 1
 int launch_conv_rw(const ConvArgs& a, const void* wimg, hipStream_t s);
+// fp16x2, stage 4's stride-1 layer on flattened bands with 16x16x32 products (cpx_cnn_flat.hip): `wimg` = the layer's `half`
+// image in 16-channel chunks; -2 = not a launch it takes (a.flat16 clear, another mode, the guarded rerun, a float32 shortcut)
+int launch_conv_flat16(const ConvArgs& a, const void* wimg, hipStream_t s);
 // the fused 1x1 shortcut as fp16x2 products (ConvArgs::sc_planes): which second convolutions can take it (by layer shape and
 // the shortcut's input channels per group), the bytes of its weight image [g][chunk of 32][plane][quarter][cout_g] of 16-byte
 // entries, and the kernel that builds it: fp16 planes of sc_w[g][k][c] * w_scale[c] * factor
