@@ -388,89 +388,39 @@ class DeviceFileBatch:
 
 
 def inflate_files_on_device(engine, blobs, names=None):
-    """The bytes of whole .cptv files -> frames on the device, without the host touching their content: upload,
-    cpx_cptv_inflate (one wavefront per file: gzip + DEFLATE + section walk), cpx_cptv_gather_index,
-    cpx_cptv_unpack.  A file that fails is reported in ``errors`` and leaves the others alone."""
-    from ._lib import CPTV_FILE_DTYPE, CPTV_HEADER_BYTES, CPTV_RESULT_DTYPE, CPTV_SLOT_DTYPE, CPTV_STATUS
+    """The bytes of whole .cptv files -> frames on the device, without the host touching their content: the file-fed
+    path's own staging, launch, result and unpack functions (cpx/track/bulk.py: upload, cpx_cptv_inflate -- one
+    wavefront per file: gzip + DEFLATE + section walk --, cpx_cptv_gather_index, cpx_cptv_unpack) driven for ONE
+    engine: a file of another resolution, which that path would decode as a group of its own, is an error here.  A file
+    that fails is reported in ``errors`` and leaves the others alone -- one whose header the host parser refuses
+    included, and one whose gzip trailer claims more than bulk.MAX_INFLATED (it gets no device buffer).
+    (bulk.py imports this module's header parser inside its functions, and this function imports bulk.py here: neither
+    module needs the other to load.)"""
+    from .track.bulk import inflate_launch, inflate_results, stage_blobs, unpack_group
 
-    t = engine.torch
-    dev = engine.device
     n = len(blobs)
     out = DeviceFileBatch()
     if n == 0:
         return out
-    P = engine.width * engine.height
-    min_frame = 4 + (P - 1 + 7) // 8 + 8      # payload at one bit per delta + the smallest field list
-    files = np.zeros(n, CPTV_FILE_DTYPE)
-    sizes = np.array([len(b) for b in blobs], np.int64)
-    in_off = np.zeros(n + 1, np.int64)
-    np.cumsum((sizes + 15) & ~15, out=in_off[1:])
-    isize = np.zeros(n, np.int64)
-    for i, b in enumerate(blobs):
-        if len(b) >= 18:
-            isize[i] = int.from_bytes(bytes(b[-4:]), "little")
-            # DEFLATE cannot expand by more than 1032 : 1; a trailer beyond that is not one (a truncated file's last
-            # bytes): no capacity -> the file fails with "output" / "input exhausted" instead of reserving gigabytes
-            if isize[i] > 1032 * len(b) + 64:
-                isize[i] = 0
-    files["in_offset"], files["in_bytes"] = in_off[:-1], sizes
-    cap = (isize + 15) & ~15
-    out_off = np.zeros(n + 1, np.int64)
-    np.cumsum(cap + 16, out=out_off[1:])
-    files["out_offset"], files["out_capacity"] = out_off[:-1], isize
-    slot_cap = isize // min_frame + 1
-    slot_off = np.zeros(n + 1, np.int64)
-    np.cumsum(slot_cap, out=slot_off[1:])
-    files["slot_offset"], files["slot_capacity"] = slot_off[:-1], slot_cap
-    stage = t.empty(int(in_off[-1]) + 16, dtype=t.uint8, pin_memory=True)
-    sv = stage.numpy()
-    for i, b in enumerate(blobs):
-        sv[in_off[i]:in_off[i] + sizes[i]] = np.frombuffer(b, np.uint8)
-    in_dev = stage.to(dev, non_blocking=True)
-    files_dev = engine._to_dev(files)
-    out_dev = t.empty(int(out_off[-1]) + 16, dtype=t.uint8, device=dev)
-    slots_dev = t.empty(max(int(slot_off[-1]), 1) * 8, dtype=t.int32, device=dev)
-    header_dev = t.empty((n, CPTV_HEADER_BYTES), dtype=t.uint8, device=dev)
-    results_dev = t.zeros(n * 10, dtype=t.int32, device=dev)
-    engine.sync_inputs()
-    engine.call("cpx_cptv_inflate", in_dev, files_dev, n, out_dev, slots_dev, header_dev, results_dev)
-    engine.synchronize()
-    res = results_dev.cpu().numpy().view(CPTV_RESULT_DTYPE).reshape(-1)
-    out.results = res
-    hdr = header_dev.cpu().numpy()
+    staged = stage_blobs(engine.torch, blobs)
+    staged.paths = list(names) if names else ["file %d" % i for i in range(n)]
+    ctx = inflate_launch(engine, staged, min_pixels=engine.width * engine.height)
+    decoded, headers = inflate_results(staged, ctx)
+    res = out.results = decoded.results
+    out.errors = decoded.errors
+    out.inflated_dev = ctx["out_dev"]   # kept for tests (the inflated bytes, file i at files["out_offset"][i])
+    out.files = ctx["files"]
+    out.clip_offsets = np.zeros(1, np.int32)
     for i in range(n):
-        st = int(res["status"][i])
-        name = names[i] if names else "file %d" % i
-        if st != 0:
-            out.errors[i] = "%s: %s" % (name, CPTV_STATUS.get(st, "status %d" % st))
-        elif (int(res["width"][i]), int(res["height"][i])) != (engine.width, engine.height):
+        if i in staged.errors or int(res["status"][i]) != 0:
+            continue
+        # (said before any complaint about the header section, as this function always did)
+        if (int(res["width"][i]), int(res["height"][i])) != (engine.width, engine.height):
             out.errors[i] = "%s is %dx%d, the engine was created for %dx%d" % (
-                name, res["width"][i], res["height"][i], engine.width, engine.height)
-        elif int(res["header_bytes"][i]) > CPTV_HEADER_BYTES:
-            out.errors[i] = "%s: header section of %d bytes" % (name, res["header_bytes"][i])
-        else:
+                staged.paths[i], res["width"][i], res["height"][i], engine.width, engine.height)
+        elif i in headers:
             out.ok.append(i)
-    out.inflated_dev = out_dev          # kept for tests (the inflated bytes, file i at files["out_offset"][i])
-    out.files = files
-    if not out.ok:
-        out.clip_offsets = np.zeros(1, np.int32)
-        return out
-    ok = np.asarray(out.ok)
-    out.headers = [parse_header_bytes(hdr[i].tobytes()) for i in out.ok]
-    offs = np.zeros(len(ok) + 1, np.int32)
-    np.cumsum(res["n_frames"][ok], out=offs[1:])
-    total = int(offs[-1])
-    out.clip_offsets = offs
-    offs_dev = t.from_numpy(offs).to(dev)
-    so_dev = t.from_numpy(np.ascontiguousarray(slot_off[:-1][ok])).to(dev)
-    fo_dev = t.empty(total, dtype=t.int64, device=dev)
-    bw_dev = t.empty(total, dtype=t.int32, device=dev)
-    dense_dev = t.empty(total * 8, dtype=t.int32, device=dev)
-    frames_dev = t.empty((total, engine.height, engine.width), dtype=t.int16, device=dev)
-    engine.sync_inputs()
-    engine.call("cpx_cptv_gather_index", slots_dev, so_dev, offs_dev, len(ok), fo_dev, bw_dev, dense_dev)
-    engine.call("cpx_cptv_unpack", out_dev, fo_dev, bw_dev, offs_dev, len(ok), frames_dev)
-    engine.synchronize()
-    out.slots = dense_dev.cpu().numpy().view(CPTV_SLOT_DTYPE).reshape(-1)
-    out.frames_dev = frames_dev
+    if out.ok:
+        group = unpack_group(engine, (engine.width, engine.height, None), out.ok, headers, res, ctx)
+        out.headers, out.clip_offsets, out.slots, out.frames_dev = group.headers, group.offs, group.slots, group.frames_dev
     return out

@@ -22,9 +22,12 @@ import ctypes as C
 import json
 import logging
 import os
+import sys
 import threading
 import time
+from collections import namedtuple
 from concurrent.futures import ThreadPoolExecutor
+from contextlib import contextmanager
 from datetime import datetime, timedelta
 
 import numpy as np
@@ -44,6 +47,54 @@ class StagedFiles:
 
     def __init__(self, paths, stage, in_off, sizes, isize, errors):
         self.paths, self.stage, self.in_off, self.sizes, self.isize, self.errors = paths, stage, in_off, sizes, isize, errors
+
+
+MAX_INFLATED = 1 << 30  # bytes one recording may inflate to on the batched path (a ten-minute 160 x 120 clip is ~0.2 GB)
+
+
+def isize_limit(size):
+    """The largest gzip ISIZE believed of a file of `size` bytes (an integer or an array): a file shorter than the
+    smallest gzip member (18 bytes) has no trailer, and DEFLATE cannot expand by more than 1032 : 1 -- a larger figure
+    is not a trailer (a truncated file's last bytes)."""
+    return (size >= 18) * (1032 * size + 64)
+
+
+def trusted_isize(size, claim):
+    """The inflated size a file of `size` bytes is given room for, from `claim`, its last four bytes read as a gzip
+    trailer's ISIZE: 0 beyond isize_limit -- no capacity, so the file fails with "output" / "input exhausted" instead
+    of reserving gigabytes."""
+    return claim if claim <= isize_limit(size) else 0
+
+
+def staged_offsets(sizes):
+    """int64 [n + 1]: where each file starts in the staged input, 16-byte aligned (the buffer holds in_off[-1] + 16)."""
+    in_off = np.zeros(len(sizes) + 1, np.int64)
+    np.cumsum((sizes + 15) & ~15, out=in_off[1:])
+    return in_off
+
+
+def file_table(sizes, in_off, isize, in_error, min_pixels):
+    """The cpx_cptv_file table of one inflate launch -> (files CPTV_FILE_DTYPE [n], out_off [n + 1], slot_off [n + 1],
+    refused indices).  sizes / in_off / isize: StagedFiles'; in_error: indices of files that already failed.  A file in
+    error or refused gets no input and no capacity.  Refused: ISIZE is the last four bytes of an untrusted file -- a
+    claim beyond MAX_INFLATED (or beyond isize_limit) does not size device buffers; that recording goes to the
+    one-file reader, which needs no size up front (the caller words the message from its paths)."""
+    n = len(sizes)
+    min_frame = 4 + (min_pixels - 1 + 7) // 8 + 8      # payload at one bit per delta + the smallest field list
+    sizes = np.where(np.isin(np.arange(n), list(in_error)), 0, sizes)
+    isize = np.where(sizes > 0, isize, 0)
+    refused = (isize > MAX_INFLATED) | (isize > isize_limit(sizes))
+    sizes, isize = np.where(refused, 0, sizes), np.where(refused, 0, isize)
+    files = np.zeros(n, CPTV_FILE_DTYPE)
+    files["in_offset"], files["in_bytes"] = in_off[:-1], sizes
+    out_off = np.zeros(n + 1, np.int64)
+    np.cumsum(((isize + 15) & ~15) + 16, out=out_off[1:])
+    files["out_offset"], files["out_capacity"] = out_off[:-1], isize
+    slot_cap = isize // min_frame + 1
+    slot_off = np.zeros(n + 1, np.int64)
+    np.cumsum(slot_cap, out=slot_off[1:])
+    files["slot_offset"], files["slot_capacity"] = slot_off[:-1], slot_cap
+    return files, out_off, slot_off, [int(i) for i in np.nonzero(refused)[0]]
 
 
 class FileStager:
@@ -78,8 +129,7 @@ class FileStager:
                 sizes[i] = os.path.getsize(p)
             except OSError as e:
                 errors[i] = "%s: %s" % (p, e)
-        in_off = np.zeros(n + 1, np.int64)
-        np.cumsum((sizes + 15) & ~15, out=in_off[1:])
+        in_off = staged_offsets(sizes)
         need = int(in_off[-1]) + 16
         buf = self.buffers[slot]
         if buf is None or buf.numel() < need:
@@ -97,10 +147,8 @@ class FileStager:
                 if got != sizes[i]:
                     errors[i] = "%s: short read (%d of %d bytes)" % (paths[i], got, sizes[i])
                     return
-                if sizes[i] >= 18:
-                    v = int.from_bytes(view[in_off[i] + sizes[i] - 4:in_off[i] + sizes[i]], "little")
-                    # DEFLATE cannot expand by more than 1032 : 1: a larger figure is not a gzip trailer
-                    isize[i] = v if v <= 1032 * sizes[i] + 64 else 0
+                end = int(in_off[i] + sizes[i])
+                isize[i] = trusted_isize(int(sizes[i]), int.from_bytes(view[max(end - 4, 0):end], "little"))
             except OSError as e:
                 errors[i] = "%s: %s" % (paths[i], e)
 
@@ -112,17 +160,14 @@ def stage_blobs(torch, blobs):
     """The same staging for byte strings already in memory (bench.py from_files, tests)."""
     n = len(blobs)
     sizes = np.array([len(b) for b in blobs], np.int64)
-    in_off = np.zeros(n + 1, np.int64)
-    np.cumsum((sizes + 15) & ~15, out=in_off[1:])
+    in_off = staged_offsets(sizes)
     buf = torch.empty(int(in_off[-1]) + 16, dtype=torch.uint8, pin_memory=True)
     view = buf.numpy()
     isize = np.zeros(n, np.int64)
     def copy(i):
         b = blobs[i]
         view[in_off[i]:in_off[i] + sizes[i]] = np.frombuffer(b, np.uint8)   # (NumPy releases the GIL for the copy)
-        if sizes[i] >= 18:
-            v = int.from_bytes(bytes(b[-4:]), "little")
-            isize[i] = v if v <= 1032 * sizes[i] + 64 else 0
+        isize[i] = trusted_isize(len(b), int.from_bytes(bytes(b[-4:]), "little"))
 
     if n >= 64:
         with ThreadPoolExecutor(max_workers=8) as pool:
@@ -195,43 +240,22 @@ def plan_decode_batches(sizes, batch_files, max_bytes):
     return runs
 
 
-MAX_INFLATED = 1 << 30  # bytes one recording may inflate to on the batched path (a ten-minute 160 x 120 clip is ~0.2 GB)
-
-
-def decode_staged(eng, staged, min_pixels=160 * 120, unpack_engine=None):
+def decode_staged(eng, staged, min_pixels=160 * 120):
     """cpx_cptv_inflate over a staged batch, then per (resolution, camera model) group gather + unpack.  `eng`: any
     engine on the device (the inflate kernel does not depend on its geometry; the unpack of a group runs on an engine
     of that group's resolution, created on demand)."""
-    return inflate_finish(eng, staged, inflate_launch(eng, staged, min_pixels), unpack_engine)
+    return inflate_finish(eng, staged, inflate_launch(eng, staged, min_pixels))
 
 
 def inflate_launch(eng, staged, min_pixels=160 * 120):
-    """First half of decode_staged: output / slot layout, device buffers and the cpx_cptv_inflate launch on `eng`'s
+    """First half of decode_staged: file table (file_table), device buffers and the cpx_cptv_inflate launch on `eng`'s
     stream -- no wait.  -> the context inflate_finish takes (an event marks the launch's end, so a further launch
     enqueued behind it on the same stream does not delay the wait)."""
     t, dev = eng.torch, eng.device
     n = len(staged.sizes)
-    min_frame = 4 + (min_pixels - 1 + 7) // 8 + 8
-    files = np.zeros(n, CPTV_FILE_DTYPE)
-    sizes = np.where(np.isin(np.arange(n), list(staged.errors)), 0, staged.sizes)
-    files["in_offset"], files["in_bytes"] = staged.in_off[:-1], sizes
-    isize = np.where(sizes > 0, staged.isize, 0)
-    # ISIZE is the last four bytes of an untrusted file: a claim beyond MAX_INFLATED (or beyond what DEFLATE can expand
-    # the file to, 1032 x) does not size device buffers -- that recording goes to the one-file reader, which needs no
-    # size up front
-    absurd = (isize > MAX_INFLATED) | (isize > 1032 * np.maximum(sizes, 1) + 64)
-    for i in np.nonzero(absurd)[0]:
-        staged.errors.setdefault(int(i), "%s: gzip trailer claims %d inflated bytes" % (staged.paths[i], int(isize[i])))
-    sizes = np.where(absurd, 0, sizes)
-    isize = np.where(absurd, 0, isize)
-    files["in_bytes"] = sizes
-    out_off = np.zeros(n + 1, np.int64)
-    np.cumsum(((isize + 15) & ~15) + 16, out=out_off[1:])
-    files["out_offset"], files["out_capacity"] = out_off[:-1], isize
-    slot_cap = isize // min_frame + 1
-    slot_off = np.zeros(n + 1, np.int64)
-    np.cumsum(slot_cap, out=slot_off[1:])
-    files["slot_offset"], files["slot_capacity"] = slot_off[:-1], slot_cap
+    files, out_off, slot_off, refused = file_table(staged.sizes, staged.in_off, staged.isize, staged.errors, min_pixels)
+    for i in refused:
+        staged.errors.setdefault(i, "%s: gzip trailer claims %d inflated bytes" % (staged.paths[i], int(staged.isize[i])))
     n_in = int(staged.in_off[-1]) + 16
     in_dev = getattr(staged, "in_dev", None)
     if in_dev is not None:     # uploaded ahead (run_files_bulk's staging thread, a stream of its own)
@@ -247,28 +271,22 @@ def inflate_launch(eng, staged, min_pixels=160 * 120):
     eng.call("cpx_cptv_inflate", in_dev, files_dev, n, out_dev, slots_dev, header_dev, results_dev)
     done = t.cuda.Event()
     done.record(eng.torch_stream())
-    return dict(n=n, slot_off=slot_off, in_dev=in_dev, files_dev=files_dev, out_dev=out_dev, slots_dev=slots_dev,
-                header_dev=header_dev, results_dev=results_dev, done=done)
+    return dict(n=n, files=files, slot_off=slot_off, in_dev=in_dev, files_dev=files_dev, out_dev=out_dev,
+                slots_dev=slots_dev, header_dev=header_dev, results_dev=results_dev, done=done)
 
 
-def inflate_finish(eng, staged, ctx, unpack_engine=None):
-    """Second half: wait for the launch, read the per-file results, group the files that decoded by (resolution, camera
-    model) and run gather + unpack per group -- on `unpack_engine`'s stream when given (run_files_bulk: the NEXT batch's
-    inflate is already running on `eng`'s)."""
+def inflate_results(staged, ctx):
+    """Wait for the launch and read the per-file results -> (DecodedBatch with errors and results, no group yet;
+    {file index: CptvHeader} of the files that decoded)."""
     from ..cptv import parse_header_bytes
 
-    t, dev = eng.torch, eng.device
-    n, slot_off = ctx["n"], ctx["slot_off"]
-    out_dev, slots_dev, header_dev, results_dev = ctx["out_dev"], ctx["slots_dev"], ctx["header_dev"], ctx["results_dev"]
     out = DecodedBatch()
     out.errors.update(staged.errors)
     ctx["done"].synchronize()
-    res = results_dev.cpu().numpy().view(CPTV_RESULT_DTYPE).reshape(-1)
-    out.results = res
-    hdr = header_dev.cpu().numpy()
-    groups = {}
+    res = out.results = ctx["results_dev"].cpu().numpy().view(CPTV_RESULT_DTYPE).reshape(-1)
+    hdr = ctx["header_dev"].cpu().numpy()
     headers = {}
-    for i in range(n):
+    for i in range(ctx["n"]):
         if i in out.errors:
             continue
         st = int(res["status"][i])
@@ -279,17 +297,26 @@ def inflate_finish(eng, staged, ctx, unpack_engine=None):
             out.errors[i] = "%s: header section of %d bytes" % (staged.paths[i], res["header_bytes"][i])
             continue
         try:
-            h = parse_header_bytes(hdr[i].tobytes())
+            headers[i] = parse_header_bytes(hdr[i].tobytes())
         except Exception as e:  # a header the host parser refuses: the file goes the slow way
             out.errors[i] = "%s: %s" % (staged.paths[i], e)
-            continue
-        headers[i] = h
+    return out, headers
+
+
+def inflate_finish(eng, staged, ctx):
+    """Second half: inflate_results, then the files that decoded grouped by (resolution, camera model) and gather +
+    unpack per group."""
+    t = eng.torch
+    out, headers = inflate_results(staged, ctx)
+    res = out.results
+    groups = {}
+    for i, h in headers.items():
         groups.setdefault((int(res["width"][i]), int(res["height"][i]), h.model if h.model else None), []).append(i)
     for key, members in groups.items():
         # a group that cannot be unpacked (a resolution no engine takes, a kernel refusal, no memory for its frames)
         # sends ITS members to the one-file path; the other groups of the batch carry on
         try:
-            out.groups.append(_unpack_group(eng, unpack_engine, key, members, headers, res, slot_off, slots_dev, out_dev))
+            out.groups.append(unpack_group(eng, key, members, headers, res, ctx))
         except Exception as e:  # noqa: BLE001 -- fault isolation
             if isinstance(e, t.cuda.OutOfMemoryError):
                 t.cuda.empty_cache()
@@ -298,7 +325,8 @@ def inflate_finish(eng, staged, ctx, unpack_engine=None):
     return out
 
 
-def _unpack_group(eng, unpack_engine, key, members, headers, res, slot_off, slots_dev, out_dev):
+def unpack_group(eng, key, members, headers, res, ctx):
+    """cpx_cptv_gather_index + cpx_cptv_unpack for the files `members` (one resolution) of an inflate launch -> DecodedGroup."""
     from .cliptrackextractor import get_engine
 
     t, dev = eng.torch, eng.device
@@ -308,18 +336,17 @@ def _unpack_group(eng, unpack_engine, key, members, headers, res, slot_off, slot
     np.cumsum(res["n_frames"][ok], out=offs[1:])
     total = int(offs[-1])
     # any engine of this resolution can unpack; the tracking engine is picked by the caller
-    base = unpack_engine or eng
-    ueng = base if (base.width, base.height) == (W, H) else get_engine(W, H, 20.0, 0.1, device=dev.index or 0)
+    ueng = eng if (eng.width, eng.height) == (W, H) else get_engine(W, H, 20.0, 0.1, device=dev.index or 0)
     offs_dev = t.from_numpy(offs).to(dev)
-    so_dev = t.from_numpy(np.ascontiguousarray(slot_off[:-1][ok])).to(dev)
+    so_dev = t.from_numpy(np.ascontiguousarray(ctx["slot_off"][:-1][ok])).to(dev)
     fo_dev = t.empty(total, dtype=t.int64, device=dev)
     bw_dev = t.empty(total, dtype=t.int32, device=dev)
     dense_dev = t.empty(total * 8, dtype=t.int32, device=dev)
     frames_dev = t.empty((total, H, W), dtype=t.int16, device=dev)
     ueng.sync_inputs()
-    rc = ueng.status("cpx_cptv_gather_index", slots_dev, so_dev, offs_dev, len(ok), fo_dev, bw_dev, dense_dev)
+    rc = ueng.status("cpx_cptv_gather_index", ctx["slots_dev"], so_dev, offs_dev, len(ok), fo_dev, bw_dev, dense_dev)
     if rc == 0:
-        rc = ueng.status("cpx_cptv_unpack", out_dev, fo_dev, bw_dev, offs_dev, len(ok), frames_dev)
+        rc = ueng.status("cpx_cptv_unpack", ctx["out_dev"], fo_dev, bw_dev, offs_dev, len(ok), frames_dev)
     ueng.check(rc)
     ueng.synchronize()
     slots = dense_dev.cpu().numpy().view(CPTV_SLOT_DTYPE).reshape(-1)
@@ -358,6 +385,71 @@ def require_device_network(interp):
                                   "one-file path (ClipClassifier.process_file / process_files)")
 
 
+def kept_tracks(summ, ntr, failed, counts):
+    """The tracks the metadata lists -> (kept [(clip, summary row)] in output order = the order of the segment plan,
+    kept_pipe: each one's index in the pipeline's arrays).  summ: TRACK_SUMMARY_DTYPE [B, max_tracks]; ntr: tracks per
+    clip; failed: the clips that go the slow way; counts: tracks the pipeline kept per clip.  Per clip the tracks that
+    were not rejected, by rank (a stable sort: equal ranks keep their order); a failed clip contributes nothing but
+    keeps its slots in the pipeline's arrays."""
+    kept, kept_pipe = [], []
+    prefix = np.concatenate([[0], np.cumsum(counts)])
+    for b in range(len(ntr)):
+        s = summ[b, : int(ntr[b])]
+        k = np.nonzero(s["reject"] == 0)[0]
+        if len(k) and b not in failed:
+            k = k[np.argsort(s["rank"][k], kind="stable")]
+            kept.extend((b, int(j)) for j in k)
+            kept_pipe.extend(int(prefix[b]) + q for q in range(len(k)))
+    return kept, kept_pipe
+
+
+def kept_region_rows(summ, kept, offs, max_active):
+    """Where the kept tracks' regions lie in the region pool ([frame, active slot] rows) -> (rows int64, tr_off int64
+    [len(kept) + 1]: track ti's regions are rows[tr_off[ti]:tr_off[ti + 1]], one per frame of the track)."""
+    rows = [np.zeros(0, np.int64)]
+    tr_off = [0]
+    for b, j in kept:
+        s = summ[b, j]
+        n = int(s["n_frames"])
+        rows.append((int(offs[b]) + int(s["start_frame"]) + np.arange(n, dtype=np.int64)) * max_active + int(s["slot"]))
+        tr_off.append(tr_off[-1] + n)
+    return np.concatenate(rows), np.asarray(tr_off, np.int64)
+
+
+def usable_region_refs(regions, kept, tr_off, proc_idx):
+    """What cpx_thumb_stats is asked for -> (usable: indices into `regions` of the regions a thumbnail may come from
+    -- not blank, with mass --, refs REGION_REF_DTYPE [len(usable)]: each one's rectangle and its frame's index in the
+    batch; proc_idx[b]: processed frame number -> index in the batch)."""
+    usable = np.nonzero(((regions["flags"] & 1) == 0) & (regions["mass"] != 0))[0]
+    refs = np.zeros(len(usable), REGION_REF_DTYPE)
+    if len(usable):
+        clip_of_reg = np.repeat(np.array([b for b, _ in kept], np.int64), np.diff(tr_off))
+        r = regions[usable]
+        fidx = np.empty(len(usable), np.int64)
+        cb = clip_of_reg[usable]
+        for b in np.unique(cb):
+            sel = cb == b
+            fidx[sel] = proc_idx[b][r["frame_number"][sel]]
+        refs["frame"], refs["x"], refs["y"], refs["width"], refs["height"] = fidx, r["x"], r["y"], r["width"], r["height"]
+    return usable, refs
+
+
+class _Laps:
+    """CPX_BULK_PROFILE=1: wall time per stage of a device phase into `prof`, with a device synchronisation at every
+    boundary; without a `prof` a lap does nothing."""
+
+    def __init__(self, prof, eng):
+        self.prof, self.eng, self.tick = prof, eng, time.time()
+
+    def __call__(self, name):
+        if self.prof is not None:
+            self.eng.synchronize()
+            self.eng.torch.cuda.synchronize(self.eng.device)
+            now = time.time()
+            self.prof[name] = self.prof.get(name, 0.0) + now - self.tick
+            self.tick = now
+
+
 class BulkTracker:
     """Tracks decoded groups and writes the metadata; one instance per TrackExtractor.extract call."""
 
@@ -372,20 +464,23 @@ class BulkTracker:
         self.tcfg = self.extractor.config
         self.lib = None
         self.decode_engine = None   # a handle (= HIP stream) of its own for the decode stage of run_files_bulk
+        # what track_group takes when its caller names no share (run_files_bulk hands every group its lane's: lane_share)
         self.cnn_chunk = 2048
         # device memory a network call may take for working memory that grows with its samples (a TFLite graph's arena,
         # N x arena_bytes_per_sample: 2,048 samples of a 160 x 160 Inception-v3 would hold several times this): such a
-        # network's chunks are cut to fit (run_files_bulk's network_bytes, shared between its device lanes)
+        # network's chunks are cut to fit
         self.network_bytes = NETWORK_BYTES
         self._algorithm_text = {}
         self.timings = {"decode_s": 0.0, "device_s": 0.0, "host_s": 0.0, "write_s": 0.0, "files": 0, "frames": 0}
 
     # ---- device ----------------------------------------------------------------------------------------------
-    def track_group(self, group, clips, classifiers=(), lane=0):
+    def track_group(self, group, clips, classifiers=(), lane=0, cnn_chunk=None, network_bytes=None, profile=False):
         """-> dict of host arrays for the group's clips (clips[k]: the Clip object of group.files[k]).
         classifiers: [(model config, interpreter)] -- every kept track's segments (cpx_plan_segments: the reference's
-        get_segments under identity draws) are cropped, tiled and run through each model's network."""
-        from ..pipeline import BatchPipeline
+        get_segments under identity draws) are cropped, tiled and run through each model's network in chunks of
+        cnn_chunk samples within network_bytes (None: this tracker's defaults).  profile: the per-stage timings of
+        _Laps into timings["device_split_s"] -- asked for by the caller (run_files_bulk passes its CPX_BULK_PROFILE);
+        the environment variable alone no longer turns them on for a direct call."""
         from .cliptrackextractor import get_engine
 
         cfg = self.tcfg
@@ -400,9 +495,11 @@ class BulkTracker:
         # so two lanes (two threads, two engines) never receive each other's blocks while the other's kernels -- which
         # torch does not know about: they are cpx launches on the handle's stream -- may still be using them
         with eng.torch.cuda.stream(eng.torch_stream()):
-            return self._track_group(eng, group, clips, classifiers, cfg, c0, W, H)
+            return self._track_group(eng, group, clips, classifiers, cfg, c0, W, H,
+                                     self.cnn_chunk if cnn_chunk is None else cnn_chunk,
+                                     self.network_bytes if network_bytes is None else network_bytes, profile)
 
-    def _track_group(self, eng, group, clips, classifiers, cfg, c0, W, H):
+    def _track_group(self, eng, group, clips, classifiers, cfg, c0, W, H, cnn_chunk, network_bytes, profile):
         from ..pipeline import BatchPipeline
 
         t, dev = eng.torch, eng.device
@@ -432,17 +529,7 @@ class BulkTracker:
         pipe = BatchPipeline(eng, None, square_width=sq, track_params=tp, filter_params=fp, want_regions=True,
                              limits_flags=lflags)
         model_out = []
-        prof = self.timings.setdefault("device_split_s", {}) if os.environ.get("CPX_BULK_PROFILE") else None
-        tick = [time.time()]
-
-        def lap(name):  # CPX_BULK_PROFILE=1: wall time per stage, with a device synchronisation at every boundary
-            if prof is not None:
-                eng.synchronize()
-                t.cuda.synchronize(dev)
-                now = time.time()
-                prof[name] = prof.get(name, 0.0) + now - tick[0]
-                tick[0] = now
-
+        lap = _Laps(self.timings.setdefault("device_split_s", {}) if profile else None, eng)
         t.cuda.current_stream(dev).synchronize()
         lap("alloc")
         with t.cuda.stream(eng.torch_stream()):
@@ -456,7 +543,7 @@ class BulkTracker:
                 fpi = interp.labels.index("false-positive") if "false-positive" in interp.labels else -1
                 mp = BatchPipeline(eng, interp._network(eng), n_labels=len(interp.labels), fp_index=fpi,
                                    frame_size=interp.params.frame_size, square_width=sq, track_params=tp,
-                                   filter_params=fp, cnn_chunk=self.cnn_chunk, network_bytes=self.network_bytes)
+                                   filter_params=fp, cnn_chunk=cnn_chunk, network_bytes=network_bytes)
                 t0 = time.time()
                 probs = None
                 if front.n_tracks and front.n_samples:
@@ -480,48 +567,20 @@ class BulkTracker:
             failed[int(b)] = "track capacity exceeded"
         # ---- kept tracks in score order; their regions gathered on the device ----
         proc_mask = info["frame_number"] >= 0
-        kept = []       # (clip, summary row) in output order = the order of the segment plan
-        kept_pipe = []  # index of the track in the pipeline's arrays (clips that failed keep their slots there)
-        prefix = np.concatenate([[0], np.cumsum(front.counts[:, 0])])
-        for b in range(B):
-            s = summ[b, : int(ntr[b])]
-            k = np.nonzero(s["reject"] == 0)[0]
-            if len(k) and b not in failed:
-                k = k[np.argsort(s["rank"][k], kind="stable")]
-                kept.extend((b, int(j)) for j in k)
-                kept_pipe.extend(int(prefix[b]) + q for q in range(len(k)))
-        rows = []
-        tr_off = [0]
-        for b, j in kept:
-            s = summ[b, j]
-            n = int(s["n_frames"])
-            rows.append((int(offs[b]) + int(s["start_frame"]) + np.arange(n, dtype=np.int64)) * ma + int(s["slot"]))
-            tr_off.append(tr_off[-1] + n)
+        kept, kept_pipe = kept_tracks(summ, ntr, failed, front.counts[:, 0])
+        rows, tr_off = kept_region_rows(summ, kept, offs, ma)
         regions = np.zeros(0, REGION_DTYPE)
-        if rows:
-            idx = t.from_numpy(np.concatenate(rows)).to(dev)
+        if len(rows):
             pool = assoc.pool_dev.view(-1, 14)
-            regions = pool[idx].cpu().numpy().view(REGION_DTYPE).reshape(-1)
+            regions = pool[t.from_numpy(rows).to(dev)].cpu().numpy().view(REGION_DTYPE).reshape(-1)
         lap("summaries_and_region_gather")
         # ---- processed-frame index per clip: frame number q -> index in the batch ----
         proc_idx = [np.nonzero(proc_mask[offs[b]:offs[b + 1]])[0] + int(offs[b]) for b in range(B)]
         # ---- thumbnails of the kept tracks: one cpx_thumb_stats over every usable region ----
-        tr_off = np.asarray(tr_off, np.int64)
         stats = np.zeros(0, THUMB_STAT_DTYPE)
-        usable = np.zeros(0, np.int64)
-        if len(regions):
-            clip_of_reg = np.repeat(np.array([b for b, _ in kept], np.int64), np.diff(tr_off))
-            usable = np.nonzero(((regions["flags"] & 1) == 0) & (regions["mass"] != 0))[0]
-            if len(usable):
-                refs = np.zeros(len(usable), REGION_REF_DTYPE)
-                r = regions[usable]
-                fidx = np.empty(len(usable), np.int64)
-                cb = clip_of_reg[usable]
-                for b in np.unique(cb):
-                    sel = cb == b
-                    fidx[sel] = proc_idx[b][r["frame_number"][sel]]
-                refs["frame"], refs["x"], refs["y"], refs["width"], refs["height"] = fidx, r["x"], r["y"], r["width"], r["height"]
-                stats = eng.thumb_stats(group.frames_dev, res, refs)
+        usable, refs = usable_region_refs(regions, kept, tr_off, proc_idx)
+        if len(usable):
+            stats = eng.thumb_stats(group.frames_dev, res, refs)
         lap("thumbnail_kernel")
         # ---- clips without a kept track: the heaviest region ever seen, else the window search ----
         kept_clips = set(b for b, _ in kept)
@@ -985,6 +1044,120 @@ def auto_batch_files(n_files):
     return int(min(2048, max(1024, (n_files // 4 + 255) // 256 * 256)))
 
 
+def decode_bound(waited, lap_s, decode_s):
+    """The lane decision, taken once, at the run's second batch: whether the run is bound by the DECODE stage and keeps
+    one device lane.  waited: how long the main thread sat waiting for that batch's decode; lap_s: the first batch's turn
+    of the main loop; decode_s: the decode's own duration.  The wait for this batch's decode alone does not tell: the
+    first batch's device phase carries the run's allocations and can hide a decode that steady batches will wait for;
+    the decode's own duration against that turn does.  Decode-bound runs keep one lane -- two lanes slow their decode
+    (8,192 noise recordings: 6.1 s against 4.7 s)."""
+    return waited > 0.2 * (lap_s + waited) or decode_s > 0.5 * lap_s
+
+
+LaneShare = namedtuple("LaneShare", "track_files track_frames cnn_chunk network_bytes")
+
+
+def lane_share(k, track_files, track_frames, network_bytes):
+    """What one of `k` device lanes gets of the run's budgets (recordings and frames per tracking group, device memory of
+    a graph network's arena) and of the 2,048 samples per network call: two lanes hold the device memory of one --
+    half-sized groups and network calls.  The share changes no result, only the memory a lane takes."""
+    return LaneShare(max(64, track_files // k), max(20000, track_frames // k), max(256, 2048 // k), network_bytes // k)
+
+
+class LaneGate:
+    """Device phases running at once: at most `limit` of the `n` lanes (groups are submitted one ahead).  `with
+    gate.lane() as lane` waits for a free one."""
+
+    def __init__(self, n):
+        self.limit = 1
+        self.busy = 0
+        self.free = list(range(n))
+        self.cond = threading.Condition()
+
+    @contextmanager
+    def lane(self):
+        with self.cond:
+            while self.busy >= self.limit:
+                self.cond.wait()
+            self.busy += 1
+            lane = self.free.pop()
+        try:
+            yield lane
+        finally:
+            with self.cond:
+                self.busy -= 1
+                self.free.append(lane)
+                self.cond.notify_all()
+
+
+class BatchRecord:
+    """One decode batch on its way to its metadata files: `paths` (recording i of the batch is the run's recording
+    base + i), the texts that are there, the recordings to retry on their own and why (the decode's refusals to begin
+    with), the metadata workers' futures, and how many of its tracking groups are still open.  No GPU, no torch."""
+
+    def __init__(self, paths, base, errors, group_files, t0=0.0):
+        self.paths, self.base, self.t0 = paths, base, t0
+        self.texts, self.retry, self.futures = {}, dict(errors), []
+        self.expected = set(i for files in group_files for i in files)   # the recordings a group answers for
+        self.n_groups, self.submitted, self.drained = len(group_files), 0, 0
+
+    def group_submitted(self):
+        self.submitted += 1
+
+    def group_drained(self):
+        """A group went through the host phase (its texts are in `texts`, or a future for them in `futures`)."""
+        self.drained += 1
+
+    def complete(self):
+        """Every group was submitted and drained: nothing more is added to the record, it can close."""
+        return self.submitted == self.drained == self.n_groups
+
+    def ready(self):
+        return all(f.done() for f in self.futures)
+
+    def unanswered(self):
+        """The recordings no worker answered for: neither a text nor a reason to retry."""
+        return [i for i in sorted(self.expected) if i not in self.texts and i not in self.retry]
+
+    def collect(self):
+        """The groups' texts from the metadata workers (waits for them) -> (frames, seconds of formatting).  A recording
+        no worker answered for is retried on its own, like any other failure."""
+        frames, secs = 0, 0.0
+        for f in self.futures:
+            try:
+                got_texts, got_retry, n, s = f.result()
+            except Exception as e:  # noqa: BLE001 -- a worker that died: its recordings go the one-file way
+                logging.warning("metadata worker failed (%s: %s)", type(e).__name__, e)
+                continue
+            self.texts.update(got_texts)
+            self.retry.update(got_retry)
+            frames += n
+            secs += s
+        if self.futures:
+            for i in self.unanswered():
+                self.retry[i] = "%s: no metadata came back" % self.paths[i]
+        return frames, secs
+
+
+def pop_ready(closing, block=False):
+    """Takes from `closing` (the complete batches, oldest first) the ones to close now, in order: with metadata workers
+    a batch's texts arrive later, and the main thread must not wait for them -- it is the one that hands the next groups
+    to the device thread -- except at the end of the run (block)."""
+    while closing and (block or closing[0].ready()):
+        yield closing.pop(0)
+
+
+class RunOptions:
+    """The run's environment switches, read once at its start."""
+
+    def __init__(self, device_lanes, env=None):
+        env = os.environ if env is None else env
+        self.lanes = max(1, int(env.get("CPX_BULK_LANES", device_lanes)))
+        self.switch_interval = float(env.get("CPX_BULK_SWITCH_INTERVAL", "0.0002"))
+        self.profile = bool(env.get("CPX_BULK_PROFILE"))       # _Laps: device phases timed per stage, synchronised
+        self.oom_debug = bool(env.get("CPX_BULK_OOM_DEBUG"))   # the allocator's summary when a group runs out of memory
+
+
 def run_files_bulk(filenames, config, to_stdout=False, save_meta=True, device=0, batch_files=None, want_text=False,
                    stager=None, tracker=None, clip_classifier=None, blobs=None, track_files=1024,
                    decode_bytes=8 << 30, track_frames=400000, meta_pool=None, device_lanes=2, network_bytes=None):
@@ -996,94 +1169,125 @@ def run_files_bulk(filenames, config, to_stdout=False, save_meta=True, device=0,
     batch_files: recordings per decode launch (and per read-ahead batch; None: auto_batch_files); track_files: recordings
     per tracking group; network_bytes: device memory for the arena of a TFLite graph network's forwards (None:
     NETWORK_BYTES) -- its sample chunks are cut to fit, which changes no result."""
-    import torch
+    return _BulkRun(filenames, config, to_stdout=to_stdout, save_meta=save_meta, device=device, batch_files=batch_files,
+                    want_text=want_text, stager=stager, tracker=tracker, clip_classifier=clip_classifier, blobs=blobs,
+                    track_files=track_files, decode_bytes=decode_bytes, track_frames=track_frames, meta_pool=meta_pool,
+                    device_lanes=device_lanes, network_bytes=network_bytes).run()
 
-    from .cliptrackextractor import default_engine
-    from .trackextractor import extract_file
 
-    filenames = [str(f) for f in filenames]
-    if not batch_files:
-        batch_files = auto_batch_files(len(filenames))
-    own_stager = stager is None and blobs is None
-    if blobs is None:
-        stager = stager or FileStager(torch)
-    tracker = tracker or BulkTracker(config, device)
-    # (from the constant, as cnn_chunk below: a tracker reused by a later call does not hand on a lane's share)
-    base_network_bytes = NETWORK_BYTES if network_bytes is None else int(network_bytes)
-    tracker.network_bytes = base_network_bytes
-    eng0 = default_engine(device)
-    indent = None if (to_stdout or (clip_classifier is not None and config.classify.meta_to_stdout)) else 4
-    classifiers, models = [], []
-    if clip_classifier is not None:
-        models = [clip_classifier.model] if clip_classifier.model else (config.classify.models or [])
-        t0 = time.time()
-        location = clip_classifier.first_location(filenames) if blobs is None else None
-        classifiers = [(m, clip_classifier.get_classifier(m, location)) for m in models]
-        tracker.timings["model_load_s"] = time.time() - t0
-    out = {}
-    # decode launches: at most batch_files recordings and decode_bytes of compressed data (inflated bytes + frames are
-    # 4-6 x that on the device, and three batches are alive at once); tracking groups: at most track_files recordings
-    # and track_frames frames -- ten-minute recordings do not take the device's memory with them
-    n_all = len(filenames)
-    if blobs is not None:
-        sizes = [len(b) for b in blobs]
-    else:
-        sizes = []
-        for f in filenames:
-            try:
-                sizes.append(os.path.getsize(f))
-            except OSError:
-                sizes.append(0)
-    runs = plan_decode_batches(sizes, batch_files, decode_bytes)
-    order = [a for a, _ in runs]
-    bounds = [b for _, b in runs]
-    batches = [filenames[a:b] for a, b in runs]
-    # Two stages in flight: a worker thread stages batch k+1 (file reads / copies into pinned memory) and decodes it on
-    # a handle of its own (its own HIP stream: upload, inflate + section index, unpack) while this thread tracks,
-    # classifies and writes batch k.  The inflate kernel is bound by scalar issue and latency, the network by the matrix
-    # pipe: the two share the chip well.
-    from ..engine import TrackEngine
+class _BulkRun:
+    """One run_files_bulk call.  Three stages in flight, on three threads: the staging and decode of batch k+1 (`worker`:
+    produce), the device phase of group g+1 (`dev_worker`: track, classify, thumbnails -- mostly waiting on the device
+    with the GIL released) and the metadata of group g (the caller's thread: run, host_phase, close_batch)."""
 
-    deng = tracker.decode_engine
-    if deng is None:
-        deng = tracker.decode_engine = TrackEngine(width=eng0.width, height=eng0.height, device=device, max_frames=45)
+    def __init__(self, filenames, config, *, to_stdout, save_meta, device, batch_files, want_text, stager, tracker,
+                 clip_classifier, blobs, track_files, decode_bytes, track_frames, meta_pool, device_lanes, network_bytes):
+        import torch
 
-    # (the staging of batch k+1 -- file reads / copies into pinned memory, host work -- runs beside the decode of batch k)
-    stage_worker = ThreadPoolExecutor(max_workers=1)
-    stage_futs = {}
-    upload_stream = torch.cuda.Stream(device=deng.device)
+        from ..engine import TrackEngine
+        from .cliptrackextractor import default_engine
 
-    def stage(bi):
-        t0 = time.time()
-        if blobs is None:
-            staged = stager.stage(batches[bi]).result()
+        self.torch = torch
+        self.opts = RunOptions(device_lanes)
+        self.config, self.device, self.blobs, self.meta_pool = config, device, blobs, meta_pool
+        self.to_stdout, self.save_meta, self.want_text, self.clip_classifier = to_stdout, save_meta, want_text, clip_classifier
+        filenames = [str(f) for f in filenames]
+        if not batch_files:
+            batch_files = auto_batch_files(len(filenames))
+        self.own_stager = stager is None and blobs is None
+        self.stager = (stager or FileStager(torch)) if blobs is None else stager
+        self.tracker = tracker = tracker or BulkTracker(config, device)
+        # (a lane's share is cut from these, never from a tracker's attributes: a tracker reused by a later call does
+        # not hand on a share)
+        self.budgets = (track_files, track_frames, NETWORK_BYTES if network_bytes is None else int(network_bytes))
+        eng0 = default_engine(device)
+        self.indent = None if (to_stdout or (clip_classifier is not None and config.classify.meta_to_stdout)) else 4
+        self.classifiers = []
+        if clip_classifier is not None:
+            models = [clip_classifier.model] if clip_classifier.model else (config.classify.models or [])
+            t0 = time.time()
+            location = clip_classifier.first_location(filenames) if blobs is None else None
+            self.classifiers = [(m, clip_classifier.get_classifier(m, location)) for m in models]
+            tracker.timings["model_load_s"] = time.time() - t0
+        self.out = {}
+        # decode launches: at most batch_files recordings and decode_bytes of compressed data (inflated bytes + frames are
+        # 4-6 x that on the device, and three batches are alive at once); tracking groups: at most track_files recordings
+        # and track_frames frames -- ten-minute recordings do not take the device's memory with them
+        if blobs is not None:
+            sizes = [len(b) for b in blobs]
         else:
-            staged = stage_blobs(torch, blobs[order[bi]:bounds[bi]])
-            staged.paths = batches[bi]
+            sizes = []
+            for f in filenames:
+                try:
+                    sizes.append(os.path.getsize(f))
+                except OSError:
+                    sizes.append(0)
+        self.runs = plan_decode_batches(sizes, batch_files, decode_bytes)
+        self.batches = [filenames[a:b] for a, b in self.runs]
+        # Two stages in flight: a worker thread stages batch k+1 (file reads / copies into pinned memory) and decodes it on
+        # a handle of its own (its own HIP stream: upload, inflate + section index, unpack) while this thread tracks,
+        # classifies and writes batch k.  The inflate kernel is bound by scalar issue and latency, the network by the matrix
+        # pipe: the two share the chip well.
+        self.deng = tracker.decode_engine
+        if self.deng is None:
+            self.deng = tracker.decode_engine = TrackEngine(width=eng0.width, height=eng0.height, device=device, max_frames=45)
+        self.upload_stream = torch.cuda.Stream(device=self.deng.device)
+        self.config_blob = None
+        if meta_pool is not None:
+            import pickle
+
+            self.config_blob = pickle.dumps(config)
+        # Device lanes: a device phase is a chain of launches with host steps between them (work counts that size the next
+        # buffers, the kept tracks' region gather, thumbnail requests): while the host does those the device has nothing
+        # of that group to run -- 24 % of the wall time with one group at a time (rocprofv3 kernel trace of 8,192 fixture
+        # recordings, scratch/gpu_busy_from_trace.py).  Two groups in flight, each on an engine (handle = stream + tracking
+        # workspace) of its own, fill each other's gaps.
+        # How many lanes the run uses is decided once, from what its second batch had to wait for (decode_bound): a run bound
+        # by the DECODE stage (large noisy recordings: this thread sits waiting for the inflate) keeps one lane -- a second
+        # one only takes device time from the inflate kernel (8,192 synthetic recordings: 462 k frames/s with one lane,
+        # 295 k with two) -- a run bound by the device phase (real recordings: many tracks and segments per frame) takes two
+        # (16,384 fixture recordings: 322 k -> 409 k).
+        self.gate = LaneGate(self.opts.lanes)
+        self.pending = []   # (batch, group, future of its device phase), oldest first: at most gate.limit of them
+        self.closing = []   # batches whose groups are all through the device, in order; closed when their texts are there
+        self.stage_futs = {}
+        # (the staging of batch k+1 -- file reads / copies into pinned memory, host work -- runs beside the decode of batch k)
+        self.stage_worker = ThreadPoolExecutor(max_workers=1)
+        self.worker = ThreadPoolExecutor(max_workers=1)
+        self.dev_worker = ThreadPoolExecutor(max_workers=self.opts.lanes)
+
+    # ---- decode thread ---------------------------------------------------------------------------------------
+    def stage(self, bi):
+        torch = self.torch
+        t0 = time.time()
+        if self.blobs is None:
+            staged = self.stager.stage(self.batches[bi]).result()
+        else:
+            staged = stage_blobs(torch, self.blobs[self.runs[bi][0]:self.runs[bi][1]])
+            staged.paths = self.batches[bi]
         # ... and so does its upload (a copy stream of its own: the DMA engine, beside the previous batch's inflate)
-        with torch.cuda.stream(upload_stream):
-            staged.in_dev = staged.stage[: int(staged.in_off[-1]) + 16].to(deng.device, non_blocking=True)
+        with torch.cuda.stream(self.upload_stream):
+            staged.in_dev = staged.stage[: int(staged.in_off[-1]) + 16].to(self.deng.device, non_blocking=True)
             staged.in_event = torch.cuda.Event()
-            staged.in_event.record(upload_stream)
+            staged.in_event.record(self.upload_stream)
         return staged, time.time() - t0
 
     # (Measured and not adopted: enqueueing the inflate of batch k+1 -- inflate_launch -- before batch k's results are
-    # read and unpacked on a second handle keeps the decode stream busy back to back, but the tracking and network
-    # kernels of the other thread then never see the chip without an inflate on it: 8,192 noisy recordings 4.41 s
-    # either way, the directory of fixture copies 2,600-2,700 files/s against 3,400.)
-    def produce(bi):
-        if bi not in stage_futs:
-            stage_futs[bi] = stage_worker.submit(stage, bi)
-        staged, stage_s = stage_futs.pop(bi).result()
-        if bi + 1 < len(batches):
-            stage_futs[bi + 1] = stage_worker.submit(stage, bi + 1)
+    # read and unpacked on a second handle: 8,192 noisy recordings 4.41 s either way, the directory of fixture copies
+    # 2,600-2,700 files/s against 3,400 -- the tracking and network kernels then never see the chip without an inflate.)
+    def produce(self, bi):
+        if bi not in self.stage_futs:
+            self.stage_futs[bi] = self.stage_worker.submit(self.stage, bi)
+        staged, stage_s = self.stage_futs.pop(bi).result()
+        if bi + 1 < len(self.batches):
+            self.stage_futs[bi + 1] = self.stage_worker.submit(self.stage, bi + 1)
         t1 = time.time()
         try:
-            decoded = decode_staged(deng, staged)
+            decoded = decode_staged(self.deng, staged)
         except Exception as e:  # noqa: BLE001 -- (device memory for the batch's buffers, a refused launch): every member
             # is retried on its own instead of the run unwinding with the open batches' metadata unwritten
-            if isinstance(e, torch.cuda.OutOfMemoryError):
-                torch.cuda.empty_cache()
+            if isinstance(e, self.torch.cuda.OutOfMemoryError):
+                self.torch.cuda.empty_cache()
             decoded = DecodedBatch()
             decoded.errors.update(staged.errors)
             why = "%s: %s" % (type(e).__name__, str(e).splitlines()[0] if str(e) else "")
@@ -1091,30 +1295,9 @@ def run_files_bulk(filenames, config, to_stdout=False, save_meta=True, device=0,
                 decoded.errors.setdefault(i, "%s: decode stage failed (%s)" % (staged.paths[i], why))
         return staged, decoded, stage_s, time.time() - t1
 
-    worker = ThreadPoolExecutor(max_workers=1)
-    # Device lanes: a device phase is a chain of launches with host steps between them (work counts that size the next
-    # buffers, the kept tracks' region gather, thumbnail requests): while the host does those the device has nothing
-    # of that group to run -- 24 % of the wall time with one group at a time (rocprofv3 kernel trace of 8,192 fixture
-    # recordings, scratch/gpu_busy_from_trace.py).  Two groups in flight, each on an engine (handle = stream + tracking
-    # workspace) of its own, fill each other's gaps.
-    # How many lanes the run uses is decided once, from what its second batch had to wait for: a run bound by the DECODE stage
-    # (large noisy recordings: this thread sits waiting for the inflate) keeps one lane -- a second one only takes device
-    # time from the inflate kernel (8,192 synthetic recordings: 462 k frames/s with one lane, 295 k with two) -- a run
-    # bound by the device phase (real recordings: many tracks and segments per frame) takes two (16,384 fixture
-    # recordings: 322 k -> 409 k).  Two lanes hold the device memory of one: half-sized groups and network calls.
-    n_lanes = max(1, int(os.environ.get("CPX_BULK_LANES", device_lanes)))
-    lanes_now = [1]
-    base_track_files, base_track_frames = track_files, track_frames
-    dev_worker = ThreadPoolExecutor(max_workers=n_lanes)
-    lane_free = list(range(n_lanes))
-    lane_cond = threading.Condition()   # device phases running at once: at most lanes_now (groups are submitted one ahead)
-    lanes_busy = [0]
-    fut = worker.submit(produce, 0) if batches else None
-
-    # Three stages in flight: the decode of batch k+1 (worker above), the device phase of group g+1 (dev_worker: track,
-    # classify, thumbnails -- mostly waiting on the device with the GIL released) and the metadata of group g (this
-    # thread).
-    def device_phase(paths, group):
+    # ---- device threads --------------------------------------------------------------------------------------
+    def device_phase(self, paths, group, share):
+        torch, tracker = self.torch, self.tracker
         td = time.time()
         clips, existing, pre_failed = [], [], {}
         for k, i in enumerate(group.files):
@@ -1129,7 +1312,7 @@ def run_files_bulk(filenames, config, to_stdout=False, save_meta=True, device=0,
                 clip.set_model(h.model if h.model else None)
                 clip.set_video_stats(datetime.fromtimestamp(h.timestamp / 1000000).astimezone(Clip.local_tz))
                 mf = os.path.splitext(paths[i])[0] + ".txt"
-                if blobs is None and os.path.exists(mf):
+                if self.blobs is None and os.path.exists(mf):
                     meta = tools.load_clip_metadata(mf)
             except Exception as e:  # noqa: BLE001 -- fault isolation
                 pre_failed[k] = "%s: %s" % (type(e).__name__, e)
@@ -1138,52 +1321,38 @@ def run_files_bulk(filenames, config, to_stdout=False, save_meta=True, device=0,
             clips.append(clip)
             existing.append(meta)
         # (lepton3 and "no model" files share thresholds but not the metadata's camera_model: grouped by model)
-        with lane_cond:
-            while lanes_busy[0] >= lanes_now[0]:
-                lane_cond.wait()
-            lanes_busy[0] += 1
-            lane = lane_free.pop()
-        try:
-            r = tracker.track_group(group, clips, classifiers, lane=lane)
-        except torch.cuda.OutOfMemoryError as e:   # (budgets too generous for this device: memory released, members retried)
-            r = RuntimeError("device out of memory for a group of %d recordings / %d frames: %s"
-                             % (len(group.files), int(group.offs[-1]), str(e).splitlines()[0]))
-            if os.environ.get("CPX_BULK_OOM_DEBUG"):
-                import sys as _sys
-                free_b, total_b = torch.cuda.mem_get_info()
-                _sys.stderr.write("OOM DEBUG: free %.1f GiB of %.1f; torch allocated %.1f reserved %.1f GiB; lanes %s\n%s\n" % (
-                    free_b / 2**30, total_b / 2**30, torch.cuda.memory_allocated() / 2**30, torch.cuda.memory_reserved() / 2**30,
-                    lanes_now[0], torch.cuda.memory_summary(abbreviated=True)))
-            torch.cuda.empty_cache()
-        except Exception as e:  # noqa: BLE001 -- the whole group failed (CpxError or anything else): every member goes the slow way
-            r = e
-        finally:
-            with lane_cond:
-                lanes_busy[0] -= 1
-                lane_free.append(lane)
-                lane_cond.notify_all()
+        with self.gate.lane() as lane:
+            try:
+                r = tracker.track_group(group, clips, self.classifiers, lane=lane, cnn_chunk=share.cnn_chunk,
+                                        network_bytes=share.network_bytes, profile=self.opts.profile)
+            except torch.cuda.OutOfMemoryError as e:   # (budgets too generous for this device: memory released, members retried)
+                r = RuntimeError("device out of memory for a group of %d recordings / %d frames: %s"
+                                 % (len(group.files), int(group.offs[-1]), str(e).splitlines()[0]))
+                if self.opts.oom_debug:
+                    free_b, total_b = torch.cuda.mem_get_info()
+                    sys.stderr.write("OOM DEBUG: free %.1f GiB of %.1f; torch allocated %.1f reserved %.1f GiB; lanes %s\n%s\n" % (
+                        free_b / 2**30, total_b / 2**30, torch.cuda.memory_allocated() / 2**30, torch.cuda.memory_reserved() / 2**30,
+                        self.gate.limit, torch.cuda.memory_summary(abbreviated=True)))
+                torch.cuda.empty_cache()
+            except Exception as e:  # noqa: BLE001 -- the whole group failed (CpxError or anything else): every member goes the slow way
+                r = e
         if not isinstance(r, Exception):
             for k, why in pre_failed.items():
                 r["failed"].setdefault(k, why)
         return clips, existing, r, time.time() - td
 
-    def host_phase(ctx, group, result):
-        paths, texts, retry = ctx["paths"], ctx["texts"], ctx["retry"]
+    # ---- main thread -----------------------------------------------------------------------------------------
+    def host_phase(self, batch, group, result):
+        tracker, paths, timings = self.tracker, batch.paths, self.tracker.timings
         clips, existing, r, dev_s = result
-        tracker.timings["device_s"] += dev_s
+        timings["device_s"] += dev_s
         if isinstance(r, Exception):
             for i in group.files:
-                retry[i] = "%s: %s" % (paths[i], r)
+                batch.retry[i] = "%s: %s" % (paths[i], r)
             return
         th = time.time()
-        offs = group.offs
-        if os.environ.get("CPX_BULK_SKIP_META"):  # experiment switch: how long the run takes without the metadata stage
-            for b, i in enumerate(group.files):
-                texts[i] = "{}"
-                tracker.timings["frames"] += int(offs[b + 1] - offs[b])
-            return
         model_meta = None
-        if classifiers:
+        if self.classifiers:
             model_meta = []
             for mo in r["model_out"]:
                 d = mo["model"].as_dict()
@@ -1192,152 +1361,127 @@ def run_files_bulk(filenames, config, to_stdout=False, save_meta=True, device=0,
         keys = ("summ", "kept", "kept_pipe", "tr_off", "regions", "usable", "stats", "failed", "best_region", "proc_idx",
                 "samples")
         job = dict(r=dict({k: r[k] for k in keys}, model_out=model_views(r["model_out"])), files=list(group.files),
-                   paths=[paths[i] for i in group.files], offs=np.asarray(offs), clips=[clip_view(c) for c in clips],
-                   existing=existing, indent=indent, classify=bool(classifiers), model_meta=model_meta,
-                   tracking_time=(time.time() - ctx["t0"]) / max(ctx["n_ok"], 1))
-        if meta_pool is not None and meta_pool.usable():   # formatted by a worker process; collected when the batch closes
-            fut = meta_pool.submit(config_blob, job)
+                   paths=[paths[i] for i in group.files], offs=np.asarray(group.offs), clips=[clip_view(c) for c in clips],
+                   existing=existing, indent=self.indent, classify=bool(self.classifiers), model_meta=model_meta,
+                   tracking_time=(time.time() - batch.t0) / max(len(batch.expected), 1))
+        pool = self.meta_pool
+        if pool is not None and pool.usable():   # formatted by a worker process; collected when the batch closes
+            fut = pool.submit(self.config_blob, job)
             if fut is not None:
-                ctx["futures"].append(fut)
-                tracker.timings["host_submit_s"] = tracker.timings.get("host_submit_s", 0.0) + time.time() - th
+                batch.futures.append(fut)
+                timings["host_submit_s"] = timings.get("host_submit_s", 0.0) + time.time() - th
                 return
         got_texts, got_retry, frames, _ = format_group(tracker, job)
-        texts.update(got_texts)
-        retry.update(got_retry)
-        tracker.timings["frames"] += frames
-        tracker.timings["host_s"] += time.time() - th
+        batch.texts.update(got_texts)
+        batch.retry.update(got_retry)
+        timings["frames"] += frames
+        timings["host_s"] += time.time() - th
 
-    def close_batch(ctx):
-        paths, texts, retry = ctx["paths"], ctx["texts"], ctx["retry"]
+    def close_batch(self, batch):
+        from .trackextractor import extract_file
+
+        paths, timings, out, cc = batch.paths, self.tracker.timings, self.out, self.clip_classifier
         tw = time.time()
-        for f in ctx["futures"]:   # the groups' texts from the metadata workers
-            try:
-                got_texts, got_retry, frames, secs = f.result()
-            except Exception as e:  # noqa: BLE001 -- a worker that died: its recordings go the one-file way
-                logging.warning("metadata worker failed (%s: %s)", type(e).__name__, e)
-                continue
-            texts.update(got_texts)
-            retry.update(got_retry)
-            tracker.timings["frames"] += frames
-            tracker.timings["host_s"] += secs
-        tracker.timings["host_collect_s"] = tracker.timings.get("host_collect_s", 0.0) + time.time() - tw
-        if ctx["futures"]:   # (a recording no worker answered for is retried on its own, like any other failure)
-            for i in range(len(paths)):
-                if i not in texts and i not in retry and i in ctx["expected"]:
-                    retry[i] = "%s: no metadata came back" % paths[i]
+        frames, secs = batch.collect()
+        timings["frames"] += frames
+        timings["host_s"] += secs
+        timings["host_collect_s"] = timings.get("host_collect_s", 0.0) + time.time() - tw
         tw = time.time()
-        for i, text in texts.items():
-            if indent is None and (to_stdout or clip_classifier is not None):
+        for i, text in batch.texts.items():
+            if self.indent is None and (self.to_stdout or cc is not None):
                 print(text)
-            elif save_meta:
+            elif self.save_meta:
                 with open(os.path.splitext(paths[i])[0] + ".txt", "w") as fh:
                     fh.write(text)
-            out[paths[i]] = text if want_text else True
-            tracker.timings["files"] += 1
-        tracker.timings["write_s"] += time.time() - tw
-        for i, why in sorted(retry.items()):
+            out[paths[i]] = text if self.want_text else True
+            timings["files"] += 1
+        timings["write_s"] += time.time() - tw
+        for i, why in sorted(batch.retry.items()):
             # a recording the batch refused goes through the one-file path: the host reader (zlib + section walk) is
             # the reference's one reader (cliptrackextractor.py:108-129) and never loses a valid file; an in-memory
             # recording is handed to it as bytes
-            blob = blobs[ctx["base"] + i] if blobs is not None else None
+            blob = self.blobs[batch.base + i] if self.blobs is not None else None
             logging.warning("batched extract: %s -- retrying the recording on its own", why)
             try:
-                if clip_classifier is not None:
-                    res = clip_classifier.process_file(paths[i], track=True, calculate_thumbnails=True, device=device,
-                                                       blob=blob)
+                if cc is not None:
+                    res = cc.process_file(paths[i], track=True, calculate_thumbnails=True, device=self.device, blob=blob)
                     if not res:
                         raise RuntimeError("process_file refused the file")
                 else:
-                    res = extract_file(paths[i], config, False, False, to_stdout, save_meta=save_meta, blob=blob)[2]
-                out[paths[i]] = (json.dumps(res, indent=indent, cls=tools.CustomJSONEncoder) if want_text else True)
+                    res = extract_file(paths[i], self.config, False, False, self.to_stdout, save_meta=self.save_meta,
+                                       blob=blob)[2]
+                out[paths[i]] = (json.dumps(res, indent=self.indent, cls=tools.CustomJSONEncoder) if self.want_text else True)
             except Exception as e:  # noqa: BLE001 -- fault isolation: one bad recording must not stop the directory
                 logging.error("could not process %s: %s", paths[i], e)
                 out[paths[i]] = "error: %s" % (e,)
 
-    config_blob = None
-    if meta_pool is not None:
-        import pickle
+    def drain(self):
+        """The oldest group's metadata, while the newer ones are on the device."""
+        if self.pending:
+            batch, group, f = self.pending.pop(0)
+            self.host_phase(batch, group, f.result())
+            batch.group_drained()
+            if batch.complete():
+                self.closing.append(batch)
+        self.close_ready()
 
-        config_blob = pickle.dumps(config)
-    pending = []   # (ctx, group, future of its device phase), oldest first: at most lanes_now of them
-    last_batch_t0 = [time.time()]
+    def close_ready(self, block=False):
+        for batch in pop_ready(self.closing, block):
+            self.close_batch(batch)
 
-    def drain():
-        if pending:
-            ctx, group, f = pending.pop(0)
-            host_phase(ctx, group, f.result())
-            ctx["open"] -= 1
-            if ctx["open"] == 0 and ctx["submitted"]:
-                closing.append(ctx)
-        close_ready()
-
-    closing = []   # batches whose groups are all through the device, in order; closed when their texts are there
-
-    def close_ready(block=False):
-        # (with metadata workers a batch's texts arrive later: this thread must not wait for them -- it is the one that
-        # hands the next groups to the device thread)
-        while closing and (block or all(f.done() for f in closing[0]["futures"])):
-            close_batch(closing.pop(0))
-
-    # Three Python threads share one interpreter lock: the metadata thread formats text (holds it), the device thread
-    # comes back from every device wait / ctypes call needing it -- and CPython makes a waiter wait a full switch interval
-    # (5 ms by default) before the holder is asked to yield.  A device phase is dozens of such returns per group: with the
-    # default interval the device thread spent more time queueing for the lock than on the device (16,384 fixture
-    # recordings: 10.2 s with the metadata stage, 5.9 s without it).  0.2 ms for the duration of the run.
-    import sys as _sys
-
-    switch_interval = _sys.getswitchinterval()
-    _sys.setswitchinterval(float(os.environ.get("CPX_BULK_SWITCH_INTERVAL", "0.0002")))
-    try:
-        for bi, paths in enumerate(batches):
-            t0 = time.time()
-            staged, decoded, stage_s, decode_s = fut.result()
-            fut = worker.submit(produce, bi + 1) if bi + 1 < len(batches) else None
-            tracker.timings["stage_s"] = tracker.timings.get("stage_s", 0.0) + stage_s
-            tracker.timings["decode_s"] += decode_s
-            waited = time.time() - t0
-            tracker.timings["wait_decode_s"] = tracker.timings.get("wait_decode_s", 0.0) + waited
-            if n_lanes > 1 and bi == 1:
-                # decided once, at the second batch (a lane's engine, network buffers and allocator pool stay behind when
-                # it is dropped again, and a lane added later allocates on top of buffers sized for one: measured, out of
-                # memory beside the bench's resident clips).  Decode-bound runs keep one lane -- two lanes slow their decode
-                # (8,192 noise recordings: 6.1 s against 4.7 s).  The wait for this batch's decode alone does not tell:
-                # the first batch's device phase carries the run's allocations and can hide a decode that steady batches
-                # will wait for; the decode's own duration against that turn does
-                lap_s = max(t0 - last_batch_t0[0], 1e-6)   # the first batch's turn of this loop
-                decode_bound = waited > 0.2 * (lap_s + waited) or decode_s > 0.5 * lap_s
-                lanes_now[0] = 1 if decode_bound else n_lanes
-                tracker.timings["device_lanes"] = lanes_now[0]
-            last_batch_t0[0] = time.time()
-            k = lanes_now[0]
-            track_files, track_frames = max(64, base_track_files // k), max(20000, base_track_frames // k)
-            tracker.cnn_chunk = max(256, 2048 // k)
-            tracker.network_bytes = base_network_bytes // k
-            groups = [sub for g in decoded.groups for sub in g.split(track_files, track_frames)]
-            ctx = dict(paths=paths, base=order[bi], texts={}, retry=dict(decoded.errors), t0=t0, open=len(groups), submitted=False,
-                       n_ok=sum(len(g.files) for g in decoded.groups), futures=[],
-                       expected=set(i for g in groups for i in g.files))
-            for gi, group in enumerate(groups):
-                f = dev_worker.submit(device_phase, paths, group)
-                ctx["submitted"] = gi + 1 == len(groups)
-                pending.append((ctx, group, f))
-                while len(pending) > lanes_now[0]:   # the oldest group's metadata, while the newer ones are on the device
-                    drain()
-            if not groups:
-                closing.append(ctx)
-                close_ready()
-            del staged, decoded
-        while pending:
-            drain()
-        close_ready(block=True)
-    finally:  # (an exception that does escape must not leave three executors running)
-        _sys.setswitchinterval(switch_interval)
-        dev_worker.shutdown(wait=True)
-        worker.shutdown(wait=True)
-        stage_worker.shutdown(wait=True)
-    if own_stager:
-        stager.close()
-    return out, tracker
+    def run(self):
+        tracker, timings, gate, batches = self.tracker, self.tracker.timings, self.gate, self.batches
+        fut = self.worker.submit(self.produce, 0) if batches else None
+        last_batch_t0 = time.time()
+        # Three Python threads share one interpreter lock: the metadata thread formats text (holds it), the device thread
+        # comes back from every device wait / ctypes call needing it -- and CPython makes a waiter wait a full switch interval
+        # (5 ms by default) before the holder is asked to yield.  A device phase is dozens of such returns per group: with the
+        # default interval the device thread spent more time queueing for the lock than on the device (16,384 fixture
+        # recordings: 10.2 s with the metadata stage, 5.9 s without it).  0.2 ms for the duration of the run.
+        switch_interval = sys.getswitchinterval()
+        sys.setswitchinterval(self.opts.switch_interval)
+        try:
+            for bi, paths in enumerate(batches):
+                t0 = time.time()
+                staged, decoded, stage_s, decode_s = fut.result()
+                fut = self.worker.submit(self.produce, bi + 1) if bi + 1 < len(batches) else None
+                timings["stage_s"] = timings.get("stage_s", 0.0) + stage_s
+                timings["decode_s"] += decode_s
+                waited = time.time() - t0
+                timings["wait_decode_s"] = timings.get("wait_decode_s", 0.0) + waited
+                if self.opts.lanes > 1 and bi == 1:
+                    # decided once, at the second batch (a lane's engine, network buffers and allocator pool stay behind
+                    # when it is dropped again, and a lane added later allocates on top of buffers sized for one: measured,
+                    # out of memory beside the bench's resident clips)
+                    lap_s = max(t0 - last_batch_t0, 1e-6)   # the first batch's turn of this loop
+                    gate.limit = 1 if decode_bound(waited, lap_s, decode_s) else self.opts.lanes
+                    timings["device_lanes"] = gate.limit
+                last_batch_t0 = time.time()
+                # the share travels with each group: one submitted before the decision runs under the share it was cut for
+                share = lane_share(gate.limit, *self.budgets)
+                groups = [sub for g in decoded.groups for sub in g.split(share.track_files, share.track_frames)]
+                batch = BatchRecord(paths, self.runs[bi][0], decoded.errors, [g.files for g in groups], t0)
+                for group in groups:
+                    f = self.dev_worker.submit(self.device_phase, paths, group, share)
+                    batch.group_submitted()
+                    self.pending.append((batch, group, f))
+                    while len(self.pending) > gate.limit:
+                        self.drain()
+                if not groups:
+                    self.closing.append(batch)
+                    self.close_ready()
+                del staged, decoded
+            while self.pending:
+                self.drain()
+            self.close_ready(block=True)
+        finally:  # (an exception that does escape must not leave three executors running)
+            sys.setswitchinterval(switch_interval)
+            self.dev_worker.shutdown(wait=True)
+            self.worker.shutdown(wait=True)
+            self.stage_worker.shutdown(wait=True)
+        if self.own_stager:
+            self.stager.close()
+        return self.out, tracker
 
 
 def extract_files_bulk(filenames, config, to_stdout=False, save_meta=True, device=0, batch_files=None,

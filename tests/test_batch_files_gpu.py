@@ -337,3 +337,45 @@ def test_metadata_worker_processes_write_the_same_text(golden_dir, tmp_path, mod
                 assert any('"all_class_confidences"' in v for v in pooled.values())
     finally:
         pool.close()
+
+
+def test_one_and_two_device_lanes_write_the_same_text(golden_dir, tmp_path, monkeypatch):
+    """The lane decision (bulk.decode_bound, taken at the second batch) forced to one lane, then to two: three batches
+    with several groups in flight each way, and every recording's text is what a run with default arguments writes.
+    (Which lane count a run takes otherwise depends on timing.)  The groups come from the batches' camera models (one
+    group per model of a batch, and groups of consecutive batches pending together), not from track_files: lane_share
+    floors a lane's recordings per group at 64, so track_files=1 splits nothing here -- group splitting is
+    test_memory_budgets_split_batches_without_changing_results' and test_bulk_plan_cpu.py's subject."""
+    import re
+
+    from cpx.classify.clipclassifier import ClipClassifier
+    from cpx.config import Config
+    from cpx.config.config import ModelConfig
+    from cpx.ml_tools import wrresnet as wr
+    from cpx.track import bulk
+
+    labels = ["bird", "cat", "false-positive", "possum", "rodent"]
+    wr.save_model(str(tmp_path / "wr"), wr.random_weights(len(labels), seed=3), labels, hyperparams={"frame_size": 32})
+    cfg = Config.get_defaults()
+    cfg.tracking["thermal"].denoise = False
+    cfg.classify.models = [ModelConfig.load({"id": 1, "name": "wr", "model_file": str(tmp_path / "wr.npz")})]
+    cfg.classify.meta_to_stdout = False
+    paths = [str(p) for p in _files(golden_dir, tmp_path)]
+    cc = ClipClassifier(cfg)
+    monkeypatch.delenv("CPX_BULK_LANES", raising=False)
+    ref, _ = bulk.run_files_bulk(paths, cfg, save_meta=False, want_text=True, clip_classifier=cc)
+    got = {}
+    for lanes, bound in ((1, True), (2, False)):
+        monkeypatch.setattr(bulk, "decode_bound", lambda waited, lap_s, decode_s, bound=bound: bound)
+        got[lanes], tr = bulk.run_files_bulk(paths, cfg, save_meta=False, want_text=True, clip_classifier=cc,
+                                             batch_files=2, track_files=1)
+        assert tr.timings["device_lanes"] == lanes and tr.timings["files"] == len(paths)
+
+    def norm(text):
+        text = re.sub(r'"(tracking_time|classify_time|predicted_time)": [^,\n]*', '"t": 0', text)
+        return re.sub(r'^    "id": \d+,', '    "id": 0,', text, flags=re.M)
+
+    assert sum('"all_class_confidences"' in ref[p] for p in paths) >= 2      # tracks with predictions
+    for p in paths:
+        assert not ref[p].startswith("error"), ref[p][:200]
+        assert norm(got[1][p]) == norm(ref[p]) == norm(got[2][p]), p
